@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- images/sec of one train step of the SCN+Attention captioner on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N=1 default.  With N>1 the script may be started either way: under ``python -m torch.distributed.run
 --nproc-per-node N`` (one rank per GPU, RANK/LOCAL_RANK/WORLD_SIZE in the environment), or bare -- then it starts
@@ -13,7 +13,12 @@ captions, 1000 tags, V=10000, fp32): ResNet-152 encoder fwd (fine-tuning layer2-
 decoder fwd -> loss -> zero_grad -> backward (+ RCCL gradient all-reduce when N>1) -> clamp +-5 -> Adam.
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line (task contract):
+A plain run sets up, warms up, times the K steps and prints the headline (`value` images/sec, `ms_per_step`).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned to its caller as .npy
+files (see dump_outputs); inputs and weights are seeded, so two builds can be compared file for file.
+--full: also everything that costs runs of its own or extra timing (per-step HIP events and the median step,
+allocator statistics, the decode step's roofline, the trunk's roofline, the reference's literal call sequence as a
+second figure, the CPU baseline), added to the same JSON line:
   roofline     -- the per-timestep decode kernel group (the "fused SCN-cell + attention step" of
                   north_star; 7 launches per step in this round): algorithmic bytes per step
                   (enc + att1 + recurrent weights) / average step duration measured with
@@ -112,6 +117,38 @@ def cpu_baseline(kind, cfg, fine_tune, batch, budget_s=20.0):
                          Bc, dt, ncores)}
 
 
+def dump_outputs(d, ts, loss, fwd, k=1 << 20):
+    """--dump-outputs D: what the last timed step handed its caller, one float32 D/<name>.npy per array.  A train step
+    returns the loss and leaves the model state it updated: each optimizer's parameters and gradients (decoder_*,
+    encoder_* when fine-tuning), taken in parameter order, row-major, as one fixed seeded sample of k elements (the
+    same positions for parameters and gradients).  --forward-only: the decoder's scores (and alphas), sampled alike.
+    At most 4 arrays of k floats: 16 MiB."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+
+    def sample(tensors):
+        flat = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+        if flat.numel() > k:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), k, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.cpu().numpy()
+
+    arrays = {}
+    if fwd is not None:
+        arrays["scores"] = sample([fwd[0]])
+        if len(fwd) == 5:                       # (scores, caps_sorted, decode_lengths, alphas, sort_ind)
+            arrays["alphas"] = sample([fwd[3]])
+    else:
+        arrays["loss"] = loss.detach().float().reshape(1).cpu().numpy()
+        for name, opt in (("decoder", ts.decoder_optimizer), ("encoder", ts.encoder_optimizer)):
+            if opt is not None:
+                arrays[name + "_params"] = sample(opt.params)
+                arrays[name + "_grads"] = sample([p.grad if p.grad is not None else torch.zeros_like(p)
+                                                  for p in opt.params])
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def warm_miopen(dev, batch, fine_tune):
     """One throw-away ResNet-152 forward/backward so that MIOpen's compiled kernels are in the on-disk
     cache before the other ranks start."""
@@ -194,7 +231,12 @@ def main():
     ap.add_argument("--decoder-only", action="store_true", help="feed a synthetic encoder_out (diagnostics)")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--max-len", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: median step, allocator, rooflines, the reference's "
+                         "literal call sequence, CPU baseline (extra steps and timing after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--ksplit", type=int, default=0)
     ap.add_argument("--with-tagger", action="store_true",
                     help="also run the frozen EncoderTagger ResNet-152 each step (the reference's real step)")
@@ -321,13 +363,14 @@ def main():
         batches = hdf5_batches(args, cfg, dev, rank, world)
 
     last_loss = [None]
+    last_fwd = [None]      # --forward-only: what the decoder returned
     # --host-lengths (experiment): hand the decoder the caption lengths as a CPU tensor too, so that its forward pass
     # needs no device synchronisation to learn its loop bounds.  Round 3, after a long warm-up: 815 vs 812 images/s with
     # 18.8 instead of 10.4 GiB reserved (the host runs a step ahead, so blocks the side stream still holds cannot be
     # reused); with the default warm-up the extra hipMallocs make it slower.  Not worth a second copy of the activations.
     caplens_host = caplens.cpu() if (args.host_lengths and batches is None) else None
 
-    step_marks = []      # one HIP event per step end (no synchronisation): per-step durations -> the median of SURVEY 8(d)
+    step_marks = []      # --full: one HIP event per step end (no synchronisation): per-step durations -> the median of SURVEY 8(d)
 
     def run(n, mark=False):
         nonlocal imgs, caps, caplens
@@ -336,7 +379,7 @@ def main():
                 imgs, caps, caplens = next(batches)
             if args.forward_only:
                 with torch.no_grad():
-                    ts.decoder(enc_in, tags, caps, caplens, prepool=pre_in) if pre_in is not None else \
+                    last_fwd[0] = ts.decoder(enc_in, tags, caps, caplens, prepool=pre_in) if pre_in is not None else \
                         ts.decoder(enc_in, tags, caps, caplens)
             else:
                 last_loss[0] = ts.step(imgs, tags, caps, caplens, enc_in, pre_in, drop_in=drop_in[0],
@@ -351,77 +394,93 @@ def main():
     dbg("built; warm-up")
     run(args.warmup)
     dbg("warm-up done")
-    SF.set_option("profile", 1)
     prof = (ctypes.c_double * 6)()
-    torch.cuda.synchronize()
-    _lib.call("scnattn_profile_collect", prof)   # drop warm-up events
+    if args.full:
+        SF.set_option("profile", 1)
+        torch.cuda.synchronize()
+        _lib.call("scnattn_profile_collect", prof)   # drop warm-up events
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
-    ms0 = torch.cuda.memory_stats(dev)
+    ms0 = torch.cuda.memory_stats(dev) if args.full else None
     t0 = time.perf_counter()
-    e_start = torch.cuda.Event(enable_timing=True)
-    e_start.record()
-    step_marks.append(e_start)
-    run(args.steps, mark=True)
+    if args.full:
+        e_start = torch.cuda.Event(enable_timing=True)
+        e_start.record()
+        step_marks.append(e_start)
+    run(args.steps, mark=args.full)
     torch.cuda.synchronize()
-    ms1 = torch.cuda.memory_stats(dev)
-    # device allocations (hipMalloc) inside the timed region: each one stalls the device
-    alloc_stats = {"segments_allocated_in_timed_region": int(ms1.get("segment.all.allocated", 0) - ms0.get("segment.all.allocated", 0)),
-                   "alloc_retries_in_timed_region": int(ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0)),
-                   "reserved_GiB": round(ms1.get("reserved_bytes.all.current", 0) / 2**30, 2)}
-    dbg("allocator: %r" % (alloc_stats,))
+    alloc_stats = None
+    if args.full:
+        ms1 = torch.cuda.memory_stats(dev)
+        # device allocations (hipMalloc) inside the timed region: each one stalls the device
+        alloc_stats = {"segments_allocated_in_timed_region": int(ms1.get("segment.all.allocated", 0) - ms0.get("segment.all.allocated", 0)),
+                       "alloc_retries_in_timed_region": int(ms1.get("num_alloc_retries", 0) - ms0.get("num_alloc_retries", 0)),
+                       "reserved_GiB": round(ms1.get("reserved_bytes.all.current", 0) / 2**30, 2)}
+        dbg("allocator: %r" % (alloc_stats,))
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     dbg("timed region done")
-    _lib.call("scnattn_profile_collect", prof)
-    # outside the timed region: per-launch HIP-event timing of the dominant single kernel (attn_context)
+
+    # outside the timed region, before any further step: the last timed step's results
+    if last_loss[0] is not None:     # the model must still be training on finite numbers
+        final_loss = float(last_loss[0].detach())
+        assert final_loss == final_loss and abs(final_loss) < 1e6, "loss diverged: %r" % final_loss
+    else:
+        final_loss = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, last_loss[0], last_fwd[0])
+        dbg("outputs written to " + args.dump_outputs)
+
     ctx_us, ctx_per_step = None, 1.0
-    if args.workload == "attention_scn" and not args.forward_only:
-        SF.set_option("profile", 2)
-        run(2)
-        torch.cuda.synchronize()
-        p2 = (ctypes.c_double * 6)()
-        _lib.call("scnattn_profile_collect", p2)
-        if p2[5] > 0 and p2[1] > 0:
-            ctx_us = 1e3 * p2[4] / p2[5]
-            ctx_per_step = p2[5] / p2[1]      # 2 with the two-chain recurrence (half the batch rows per launch)
-    SF.set_option("profile", 0)
-    # outside the timed region: the encoder's forward + backward time by HIP events (3 extra steps) -> roofline_trunk
     enc_ms = None
-    if not args.decoder_only and not args.forward_only:
-        ts.encoder_events = []
-        run(3)
-        torch.cuda.synchronize()
-        per = []
-        for ev in ts.encoder_events:
-            fwd = ev[0].elapsed_time(ev[1])
-            bwd = ev[2].elapsed_time(ev[3]) if fine_tune else 0.0
-            per.append((fwd, bwd))
-        ts.encoder_events = None
-        if per:
-            per.sort(key=lambda fb: fb[0] + fb[1])
-            enc_ms = per[len(per) // 2]
-    # second figure, outside the headline's timed region: the same K steps through the reference's literal call
-    # sequence (the pooled (B,14,14,2048) map is materialised and the decoder picks the trunk map up from the tag)
     elapsed_di = None
-    if not args.drop_in_call and not args.decoder_only and not args.forward_only and args.workload != "pure_scn":
-        drop_in[0] = True
-        run(2)
-        torch.cuda.synchronize()
-        if dist_on:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        run(args.steps)
-        torch.cuda.synchronize()
-        if dist_on:
-            dist.barrier()
-        torch.cuda.synchronize()
-        elapsed_di = time.perf_counter() - t1
-        drop_in[0] = False
+    if args.full:
+        _lib.call("scnattn_profile_collect", prof)
+        # outside the timed region: per-launch HIP-event timing of the dominant single kernel (attn_context)
+        if args.workload == "attention_scn" and not args.forward_only:
+            SF.set_option("profile", 2)
+            run(2)
+            torch.cuda.synchronize()
+            p2 = (ctypes.c_double * 6)()
+            _lib.call("scnattn_profile_collect", p2)
+            if p2[5] > 0 and p2[1] > 0:
+                ctx_us = 1e3 * p2[4] / p2[5]
+                ctx_per_step = p2[5] / p2[1]      # 2 with the two-chain recurrence (half the batch rows per launch)
+        SF.set_option("profile", 0)
+        # outside the timed region: the encoder's forward + backward time by HIP events (3 extra steps) -> roofline_trunk
+        if not args.decoder_only and not args.forward_only:
+            ts.encoder_events = []
+            run(3)
+            torch.cuda.synchronize()
+            per = []
+            for ev in ts.encoder_events:
+                fwd = ev[0].elapsed_time(ev[1])
+                bwd = ev[2].elapsed_time(ev[3]) if fine_tune else 0.0
+                per.append((fwd, bwd))
+            ts.encoder_events = None
+            if per:
+                per.sort(key=lambda fb: fb[0] + fb[1])
+                enc_ms = per[len(per) // 2]
+        # second figure, outside the headline's timed region: the same K steps through the reference's literal call
+        # sequence (the pooled (B,14,14,2048) map is materialised and the decoder picks the trunk map up from the tag)
+        if not args.drop_in_call and not args.decoder_only and not args.forward_only and args.workload != "pure_scn":
+            drop_in[0] = True
+            run(2)
+            torch.cuda.synchronize()
+            if dist_on:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            run(args.steps)
+            torch.cuda.synchronize()
+            if dist_on:
+                dist.barrier()
+            torch.cuda.synchronize()
+            elapsed_di = time.perf_counter() - t1
+            drop_in[0] = False
     if dist_on:
         tmax = torch.tensor([elapsed, elapsed_di or 0.0], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -430,27 +489,15 @@ def main():
             elapsed_di = float(tmax[1].item())
 
     dbg("reductions done")
-    if last_loss[0] is not None:     # outside the timed region: the model must still be training on finite numbers
-        final_loss = float(last_loss[0].detach())
-        assert final_loss == final_loss and abs(final_loss) < 1e6, "loss diverged: %r" % final_loss
-    else:
-        final_loss = None
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
         value = world * args.batch * args.steps / elapsed
-        durs = sorted(step_marks[i].elapsed_time(step_marks[i + 1]) for i in range(len(step_marks) - 1))
-        ms_median = durs[len(durs) // 2] if durs else None
         T = cfg["max_len"] + 1
         out = {
             "metric": "images/sec (train step, SCN+Attention, bs32/GPU)" if args.workload == "attention_scn"
             else "images/sec (train step, %s, bs%d/GPU)" % (args.workload, args.batch),
             "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
-            # SURVEY 8(d) defines the metric on the MEDIAN step; `value` / `ms_per_step` stay the whole-region figures the
-            # driver's own clock can check (K steps / wall time between two barriers), the median (rank 0's GPU timeline,
-            # HIP events at every step end) rides beside them
-            "ms_per_step_median": None if ms_median is None else round(ms_median, 3),
-            "value_at_median_step": None if not ms_median else round(world * args.batch * 1e3 / ms_median, 3),
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "loss_after_timed_steps": None if final_loss is None else round(final_loss, 4),
             "dtype": {("f32", "f32"): "f32",
@@ -473,10 +520,18 @@ def main():
                        "global_batch": world * args.batch, "parallelism": "dp%d" % world,
                        "call_sequence": "drop-in: encoder(imgs) -> decoder(encoder_out, ...)" if args.drop_in_call else
                        "harness: encoder(imgs, pooled=False) -> decoder(None, ..., prepool=trunk map)"},
-            "allocator": alloc_stats,
             "rccl_world_size": dist.get_world_size() if dist_on else 1,
             "dp_backend": (args.dp_backend if dist_on else None),
         }
+        if args.full:
+            # SURVEY 8(d) defines the metric on the MEDIAN step; `value` / `ms_per_step` stay the whole-region figures the
+            # driver's own clock can check (K steps / wall time between two barriers), the median (rank 0's GPU timeline,
+            # HIP events at every step end) rides beside them
+            durs = sorted(step_marks[i].elapsed_time(step_marks[i + 1]) for i in range(len(step_marks) - 1))
+            ms_median = durs[len(durs) // 2] if durs else None
+            out["ms_per_step_median"] = None if ms_median is None else round(ms_median, 3)
+            out["value_at_median_step"] = None if not ms_median else round(world * args.batch * 1e3 / ms_median, 3)
+            out["allocator"] = alloc_stats
         if not args.decoder_only and not args.no_fused_conv:
             from scnattn import conv as _conv
             out["config"]["trunk"] = ("stem (7x7 conv + BN + ReLU + max-pool) on csrc/stem.hip; fused Bottleneck: every convolution "
@@ -565,7 +620,7 @@ def main():
                         "2.4 GHz -- the chip sustains ~2.0 GHz under this load (csrc/cgemm.hip: 131-134 TFLOP/s at 4096^3)"
                         % ("fine-tuning layer2-4" if fine_tune else "frozen (forward only)",
                            ENC_GFLOP_PER_IMAGE[bool(fine_tune)], args.batch, "bf16" if bf else "fp32-input")}
-        if world == 1 and not args.no_cpu_baseline and not args.decoder_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.decoder_only:
             print("[bench] GPU part done: %.1f images/sec; timing the CPU oracle sample ..." % value,
                   file=sys.stderr, flush=True)
             try:

@@ -115,5 +115,37 @@ def main():
         print("%8d  %s" % (os.path.getsize(os.path.join(OUT, f)), f))
 
 
+def writer():
+    """h5lite_writer.json: the project's own writer (scnattn/h5lite.write_arrays) on the inputs of
+    tests/test_data_path.py::test_h5lite_writer_roundtrip_and_real_h5py, read back by h5py.  The test then checks
+    that the writer still produces these exact bytes, without needing h5py itself:
+
+        python3 oracle/gen_hdf5_golden.py writer        # an interpreter that has h5py"""
+    import importlib.util
+    import tempfile
+    spec = importlib.util.spec_from_file_location(
+        "h5lite", os.path.join(ROOT, "indonesian-image-captioning_amd", "scnattn", "h5lite.py"))
+    h5lite = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(h5lite)
+    rng = np.random.RandomState(5)
+    imgs = rng.randint(0, 256, size=(6, 3, 16, 16)).astype("uint8")
+    tags = rng.rand(6, 9).astype("float32")
+    res = {"h5py": h5py.__version__, "hdf5": h5py.version.hdf5_version, "file_sha256": {}}
+    with tempfile.TemporaryDirectory() as d:
+        pi, pt = os.path.join(d, "w_images.hdf5"), os.path.join(d, "w_tags.hdf5")
+        h5lite.write_arrays(pi, {"images": imgs}, {"captions_per_image": 5})
+        h5lite.write_arrays(pt, {"tags": tags, "extra": np.arange(6, dtype="int32").reshape(2, 3)}, {"tag_size": 9})
+        for p in (pi, pt):
+            with open(p, "rb") as fh:
+                res["file_sha256"][os.path.basename(p)] = hashlib.sha256(fh.read()).hexdigest()
+        with h5py.File(pi, "r") as h, h5py.File(pt, "r") as t:
+            res["h5py_read"] = [int(h.attrs["captions_per_image"]), list(h["images"].shape), str(h["images"].dtype),
+                                sha(h["images"][:]), int(t.attrs["tag_size"]), sorted(t.keys()), sha(t["tags"][:]),
+                                t["extra"][:].tolist()]
+    with open(os.path.join(OUT, "h5lite_writer.json"), "w") as j:
+        json.dump(res, j, indent=1)
+
+
 if __name__ == "__main__":
-    main()
+    import sys
+    writer() if sys.argv[1:] == ["writer"] else main()

@@ -469,6 +469,38 @@ def test_bench_starts_its_own_ranks_when_launched_bare(monkeypatch):
     assert cmd[-6:] == ["--gpus", "4", "--steps", "3", "--warmup", "1"] and cmd[-7].endswith("bench.py")
 
 
+def test_bench_dump_outputs_writes_seeded_float32_samples(tmp_path):
+    """`bench.py --dump-outputs DIR`: the loss, then each optimizer's parameters and gradients as one fixed seeded
+    sample (the same positions in both, identical from run to run), whole when smaller than the sample; with
+    --forward-only the decoder's scores and alphas."""
+    import importlib
+    import sys
+    from types import SimpleNamespace as NS
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    torch.manual_seed(0)
+    big, small = [torch.randn(300, 7), torch.randn(11)], [torch.randn(5, 3)]
+    for p in big + small:
+        p.grad = 2 * p
+    ts = NS(decoder_optimizer=NS(params=big), encoder_optimizer=NS(params=small))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ts, torch.tensor(1.5), None, k=64)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["decoder_grads.npy", "decoder_params.npy", "encoder_grads.npy", "encoder_params.npy", "loss.npy"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype == np.float32 and np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n))
+    assert got["loss"].tolist() == [1.5]
+    assert got["decoder_params"].shape == (64,) and np.array_equal(got["decoder_grads"], 2 * got["decoder_params"])
+    assert np.isin(got["decoder_params"], torch.cat([p.reshape(-1) for p in big]).numpy()).all()
+    assert np.array_equal(got["encoder_params"], small[0].reshape(-1).numpy())
+    scores, alphas = torch.randn(2, 3, 40), torch.rand(2, 3, 5)
+    bench.dump_outputs(str(tmp_path / "f"), None, None, (scores, None, [3, 3], alphas, None), k=64)
+    assert sorted(os.listdir(tmp_path / "f")) == ["alphas.npy", "scores.npy"]
+    assert np.load(tmp_path / "f" / "scores.npy").shape == (64,)
+    assert np.array_equal(np.load(tmp_path / "f" / "alphas.npy"), alphas.reshape(-1).numpy())
+
+
 def test_flat_gradient_view_is_stolen_once_and_accumulated_after():
     """ADVICE r2 (conv.py:285 / :410): a backward node that writes a weight gradient straight into the parameter's
     slice of the flat gradient buffer must (1) return a FRESH alias so that AccumulateGrad steals it instead of
