@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-#define SCNATTN_VERSION 108 /* 0.1.8: + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
+#define SCNATTN_VERSION 108 /* 0.1.8: + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
+                               _conv3x3_fwd_bn_eval; new symbols only, the version stays), + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
                                epilogues inside the GEMM launch (options cgemm_combine, cgemm_combine_max), option dec_tail;
                                0.1.7: + halo-staged 3x3 weight gradient, strided 3x3 d input, the stem (scnattn_stem_*), BatchNorm
                                finalize on load; - whole-block drivers, scnattn_stream_*, the experiment options of rounds 1-2 */
@@ -347,6 +348,29 @@ int scnattn_conv3x3_dgrad_strided(void* stream, int N, int Hi, int Wi, int Cin, 
  * kernel (needs Cin % 128 == 0). */
 int scnattn_conv3x3_wgrad(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const float* dy,
                           const float* x, float* dw, float* ws, long ws_floats, int k_slices);
+/* ---- forward convolutions of an EVAL-mode trunk with the BatchNorm folded into the epilogue (csrc/cgemm.hip, EPI 3) ------
+ * With running statistics a BatchNorm is the per-channel map z*scale + shift, scale = gamma / sqrt(var + eps),
+ * shift = beta - mean * scale; the kernel forms scale / shift per output column from the module's own parameters and
+ * buffers when it finishes a tile (nothing to precompute, nothing cached), so the pre-BatchNorm map z is never written:
+ *     y [R][Cout] = act(conv(x, w) * scale + shift (+ res)),   act = ReLU when relu != 0, identity otherwise.
+ * res (optional, NULL: none) is a [R][Cout] map with leading dimension ldres (16-byte aligned, ldres % 4 == 0,
+ * ldres >= Cout) added before the activation: the residual of a Bottleneck's last convolution.  gamma / beta / mean /
+ * var are [Cout] fp32 vectors (16-byte aligned).  Nothing is written to the running statistics.
+ * ex (may be NULL) carries only geometry -- stride / Hi / Wi / Ho / Wo of a strided 1x1 (downsample) whose input rows are
+ * gathered, as for scnattn_conv1x1_fwd -- and force_split / force_mi; a non-zero pro or epi is an error.  Split-K runs
+ * only as the in-launch combine (at most the cgemm_combine_max slices; otherwise unsplit).  Cin, Cout multiples of 16.
+ * scnattn_conv3x3_fwd_bn_eval: the 3x3 (pad 1, stride 1 or 2) forward of scnattn_conv3x3_fwd with the same epilogue,
+ * x [N*Hi*Wi][Cin], w [Cout][3][3][Cin], y / res [N*Ho*Wo][Cout], Ho = (Hi-1)/stride + 1 (odd maps allowed). */
+typedef struct scnattn_bn_eval {
+    const float* gamma; const float* beta; const float* mean; const float* var; float eps;
+    const float* res; long ldres;   /* optional residual added before the activation (NULL: none) */
+    int relu;
+} scnattn_bn_eval;
+int scnattn_conv1x1_fwd_bn_eval(void* stream, int R, int Cin, int Cout, const float* x, const float* w, float* y,
+                                const scnattn_bn_eval* bn, const scnattn_conv_extra* ex, float* ws, long ws_floats);
+int scnattn_conv3x3_fwd_bn_eval(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const float* x,
+                                const float* w, float* y, const scnattn_bn_eval* bn, const scnattn_conv_extra* ex,
+                                float* ws, long ws_floats);
 /* ---- the stem: conv1 7x7 / 2 / pad 3 (3 -> 64) -> BatchNorm -> ReLU -> MaxPool 3x3 / 2 / pad 1 (csrc/stem.hip) ----------
  * children 0..3 of the trunk behind models/encoders/caption.py:17-22; frozen in every configuration of the reference, so
  * forward only.  x is the (N,3,H,W) image batch in ANY memory format (element strides sn, sc, sh, sw), w the (64,3,7,7)

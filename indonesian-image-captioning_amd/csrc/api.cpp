@@ -179,6 +179,49 @@ int scnattn_conv3x3_fwd(void* stream, int N, int Hi, int Wi, int Cin, int Cout, 
                  nullptr, 1, 0, 0, 0, ws, ws ? ws_floats : 0, &e);
 }
 
+// eval BatchNorm epilogue (EPI 3): geometry and tuning from ex, the BatchNorm from bn; every check before the GPU is touched
+static int bn_eval_extra(const char* who, int Cin, int Cout, const scnattn_bn_eval* bn, const scnattn_conv_extra* ex,
+                         ConvExtra* e) {
+    if (!bn) { set_error("%s: invalid argument: bn is NULL", who); return -1; }
+    if (ex && (ex->pro != 0 || ex->epi != 0)) { set_error("%s: invalid argument: ex carries geometry only (pro = epi = 0)", who); return -1; }
+    if (!(bn->gamma && bn->beta && bn->mean && bn->var)) { set_error("%s: invalid argument: null BatchNorm parameter / statistic", who); return -1; }
+    if (Cin <= 0 || Cout <= 0 || Cin % 16 || Cout % 16) { set_error("%s: invalid argument: Cin and Cout must be positive multiples of 16", who); return -1; }
+    if (!(aligned16(bn->gamma) && aligned16(bn->beta) && aligned16(bn->mean) && aligned16(bn->var))) {
+        set_error("%s: invalid argument: BatchNorm vectors must be 16-byte aligned", who); return -1;
+    }
+    if (bn->res && (!aligned16(bn->res) || bn->ldres % 4 || bn->ldres < Cout)) {
+        set_error("%s: invalid argument: res must be 16-byte aligned with ldres %% 4 == 0 and ldres >= Cout", who); return -1;
+    }
+    if (ex) {
+        e->stride = ex->stride < 1 ? 1 : ex->stride; e->Hi = ex->Hi; e->Wi = ex->Wi; e->Ho = ex->Ho; e->Wo = ex->Wo;
+        e->force_split = ex->force_split; e->force_mi = ex->force_mi;
+    }
+    e->epi = 3;
+    e->egamma = bn->gamma; e->ebeta = bn->beta; e->emean = bn->mean; e->evar = bn->var; e->eeps = bn->eps;
+    e->ez = bn->res; e->ldz = bn->res ? bn->ldres : 0; e->erelu = bn->relu != 0;
+    return 0;
+}
+
+int scnattn_conv1x1_fwd_bn_eval(void* stream, int R, int Cin, int Cout, const float* x, const float* w, float* y,
+                                const scnattn_bn_eval* bn, const scnattn_conv_extra* ex, float* ws, long ws_floats) {
+    ConvExtra e;
+    SCN_TRY(bn_eval_extra("conv1x1_fwd_bn_eval", Cin, Cout, bn, ex, &e));
+    return cgemm(ST(stream), false, true, R, Cout, Cin, 1.f, x, Cin, w, Cin, 0.f, y, Cout, nullptr, nullptr, 1, 0, 0, 0,
+                 ws, ws ? ws_floats : 0, &e);
+}
+
+int scnattn_conv3x3_fwd_bn_eval(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const float* x,
+                                const float* w, float* y, const scnattn_bn_eval* bn, const scnattn_conv_extra* ex,
+                                float* ws, long ws_floats) {
+    SCN_ARG(N > 0 && Hi > 0 && Wi > 0 && (stride == 1 || stride == 2), "conv3x3_fwd_bn_eval: geometry");
+    ConvExtra e;
+    SCN_TRY(bn_eval_extra("conv3x3_fwd_bn_eval", Cin, Cout, bn, ex, &e));
+    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
+    e.c3 = 1; e.c3c = Cin; e.c3_src_rows = (long)N * Hi * Wi; e.Hi = Hi; e.Wi = Wi; e.Ho = Ho; e.Wo = Wo; e.stride = stride;
+    return cgemm(ST(stream), false, true, N * Ho * Wo, Cout, 9 * Cin, 1.f, x, Cin, w, 9L * Cin, 0.f, y, Cout, nullptr,
+                 nullptr, 1, 0, 0, 0, ws, ws ? ws_floats : 0, &e);
+}
+
 int scnattn_conv3x3_dgrad(void* stream, int N, int Hi, int Wi, int Cin, int Cout, const float* dy, const float* w,
                           float* dx, const scnattn_conv_extra* ex, float* ws, long ws_floats) {
     SCN_ARG(N > 0 && Hi > 0 && Wi > 0, "conv3x3_dgrad: geometry");

@@ -32,6 +32,8 @@
 //   * optional mask epilogue for d-input products (EPI 2; round 3: inside the launch): g = dx * [relu-mask recomputed
 //     from z], column sums of g and g*xhat (the BatchNorm backward reductions);  cstats_kernel<2> is the same as a second
 //     launch for the layouts the in-launch form does not cover;
+//   * eval BatchNorm epilogue (EPI 3; forward products of an eval-mode trunk): y = act(acc*scale[n] + shift[n] (+ res)),
+//     scale / shift formed per column from the module's gamma, beta, running mean and variance in the epilogue set-up;
 //   * C rows (and split-K slab rows) leave through a wave-private LDS transpose as 16-byte range-checked buffer stores
 //     (16 store instructions per wave instead of 64);
 //   * split-K into slabs, for shapes whose tile grid alone cannot fill 256 CUs; the slabs are summed in slab order
@@ -77,6 +79,7 @@ struct CArgs {
     int ldp;                      // leading dimension of stat_partial: cdiv(M, 64) rounded up to 4 (cgemm_stat_ld)
     const float* ez; const float* emean; const float* einvstd; const float* egamma; const float* ebeta;  // mask pass
     long ldz;
+    const float* evar; float eeps; int erelu;           // EPI 3: running variance, eps, ReLU (ez / ldz: the residual)
     int* cnt;                     // in-launch split-K combine: one arrival counter per (batch, tile), zero at rest; null -> two launches
     int comb;                     // 1: write-through (sc1) slab stores, 2: plain slab stores + agent release
 };
@@ -119,7 +122,10 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // A_MC / B_MC: operand stored with its m / n dimension contiguous ([K][M] / [K][N]); otherwise k contiguous.
 // PRO: 0 none, 1 relu(a*scale[k]+shift[k]) on a KC A operand, 2 relu(b*scale[n]+shift[n]) on a MC B operand.
 // EPI: 0 plain (alpha, beta, bias, rowmask), 1 plain store + column statistics, 2 ReLU mask of the consumer BatchNorm
-//      recomputed from its pre-activation z + the two column sums of its backward (g, g*xhat), g stored.
+//      recomputed from its pre-activation z + the two column sums of its backward (g, g*xhat), g stored; 3 eval-mode
+//      BatchNorm: y = act(acc * scale[n] + shift[n] (+ res[m][n])) with scale = gamma / sqrt(var + eps), shift = beta -
+//      mean * scale formed per column from the running statistics at set-up (no fold launch, nothing cached), res rows
+//      read like EPI 2's z rows, act = ReLU or identity (NT forward products and the 3x3 forward only).
 //      A split product (S > 1) with arrival counters (g.cnt) applies its epilogue IN THE SAME LAUNCH: every slice writes
 //      its slab, takes a ticket, and the workgroup that draws the last ticket of a tile sums the S slabs in slab order
 //      (deterministic) and finishes the tile -- no second launch, no second trip of the product through HBM.
@@ -533,15 +539,16 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
     const int mw0 = m0 + wm * 32 * RB;             // first row of this wave
 
     // ---- finishing a 32-row block in ROW layout (lane = columns c4 .. c4+3 of rows it*4 + rl, it = 0 .. 7): the in-launch
-    // split-K combine (all epilogues) and the un-split mask epilogue (EPI 2) ------------------------------------------------
+    // split-K combine (all epilogues) and the un-split mask / eval BatchNorm epilogues (EPI 2, 3) ----------------------------
     [[maybe_unused]] f32x4 kv0 = {0.f, 0.f, 0.f, 0.f}, kv1 = kv0, kv2 = kv0, kv3 = kv0;   // per-column constants of the epilogue
     const bool folded = EPI == 2 && g.pro_ss != nullptr;   // the mask of the function the forward pass evaluated: relu(fma(z, scale, shift))
     [[maybe_unused]] float fs1[4] = {0.f, 0.f, 0.f, 0.f}, fs2[4] = {0.f, 0.f, 0.f, 0.f};
-    [[maybe_unused]] f32x4 xv[8];            // EPI 0: C rows (beta != 0); EPI 2: z rows
+    [[maybe_unused]] f32x4 xv[8];            // EPI 0: C rows (beta != 0); EPI 2: z rows; EPI 3: residual rows
     [[maybe_unused]] float mk[8];
     const bool f_use_c = EPI == 0 && g.beta != 0.f, f_use_m = EPI == 0 && g.rowmask != nullptr;
     const __amdgpu_buffer_rsrc_t f_crs = make_rsrc(C, VEC ? (unsigned)(((long)(g.M - 1) * g.ldc + g.N) * 4) : 0u);
-    const __amdgpu_buffer_rsrc_t f_zrs = make_rsrc(g.ez, (VEC && EPI == 2) ? (unsigned)(((long)(g.M - 1) * g.ldz + g.N) * 4) : 0u);
+    const bool f_use_r = EPI == 2 || (EPI == 3 && g.ez != nullptr);      // z rows (EPI 2) / residual rows (EPI 3)
+    const __amdgpu_buffer_rsrc_t f_zrs = make_rsrc(g.ez, (VEC && f_use_r) ? (unsigned)(((long)(g.M - 1) * g.ldz + g.N) * 4) : 0u);
     const __amdgpu_buffer_rsrc_t f_mrs = make_rsrc(g.rowmask, f_use_m ? (unsigned)g.M * 4u : 0u);
     auto out_off = [&](int m) -> unsigned { return (m < g.M && cok) ? (unsigned)(((long)m * g.ldc + ncol) * 4) + opq : OOB_OFF; };
     auto finish_setup = [&]() {
@@ -558,6 +565,15 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
             } else {
                 kv2 = *reinterpret_cast<const f32x4*>(g.egamma + ncol);
                 kv3 = *reinterpret_cast<const f32x4*>(g.ebeta + ncol);
+            }
+        }
+        if (EPI == 3) {     // kv0 = scale, kv1 = shift of this lane's four columns
+            const f32x4 ga = *reinterpret_cast<const f32x4*>(g.egamma + ncol), be = *reinterpret_cast<const f32x4*>(g.ebeta + ncol);
+            const f32x4 mu = *reinterpret_cast<const f32x4*>(g.emean + ncol), va = *reinterpret_cast<const f32x4*>(g.evar + ncol);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                kv0[q] = ga[q] * (1.f / sqrtf(va[q] + g.eeps));
+                kv1[q] = be[q] - mu[q] * kv0[q];
             }
         }
     };
@@ -577,7 +593,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
                 mk[u] = buf_load(f_mrs, m < g.M ? (unsigned)m * 4u + opq : OOB_OFF);
             }
         }
-        if (EPI == 2) {
+        if (f_use_r) {
 #pragma unroll
             for (int u = 0; u < NV; ++u) {
                 const int m = mb + (it0 + u) * 4 + rl;
@@ -608,6 +624,13 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
                         fs2[q] = fmaf(d, d, fs2[q]);
                     }
                 }
+            } else if (EPI == 3) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float y = fmaf(v[u][q], kv0[q], kv1[q]);
+                    if (f_use_r) y += xv[u][q];
+                    v[u][q] = g.erelu ? fmaxf(y, 0.f) : y;
+                }
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -622,7 +645,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
         }
     };
     auto finish_stats = [&]() {              // column sums of this wave's rows -> one partial per 64-row block
-        if (EPI == 0) return;
+        if (EPI == 0 || EPI == 3) return;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             fs1[q] += __shfl_xor(fs1[q], 16, 64); fs1[q] += __shfl_xor(fs1[q], 32, 64);
@@ -753,7 +776,8 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
         return;
     }
 
-    if constexpr (VEC && EPI == 2) {      // un-split product feeding a BatchNorm backward: mask + sums in the epilogue
+    // un-split product feeding a BatchNorm backward (mask + sums in the epilogue) or an eval BatchNorm (EPI 3)
+    if constexpr (VEC && (EPI == 2 || EPI == 3)) {
         finish_setup();
 #pragma unroll
         for (int i = 0; i < RB; ++i) {
@@ -1115,6 +1139,8 @@ void launch_ev(hipStream_t st, dim3 grid, const CArgs& g, int kepi, bool vec) {
     dim3 block(256);
     if (kepi == 2) {       // mask epilogue: the d-input products only (host-checked)
         if constexpr (!AMC && BMC && PRO == 0 && !G) hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 2, false, true>), grid, block, 0, st, g);
+    } else if (kepi == 3) {   // eval BatchNorm epilogue: forward products without a prologue only (host-checked)
+        if constexpr (!AMC && !BMC && PRO == 0) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 3, G, true>), grid, block, 0, st, g);
     } else if (kepi == 1) hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 1, G, true>), grid, block, 0, st, g);
     else if (vec)  hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 0, G, true>), grid, block, 0, st, g);
     else           hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 0, G, false>), grid, block, 0, st, g);
@@ -1125,6 +1151,7 @@ int launch_conv3(hipStream_t st, dim3 grid, const CArgs& g, int c3, int kepi) {
     dim3 block(256);
     if (c3 == 1) {
         if (kepi == 1) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 1, false, true, 1>), grid, block, 0, st, g);
+        else if (kepi == 3) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 3, false, true, 1>), grid, block, 0, st, g);
         else           hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 0, false, true, 1>), grid, block, 0, st, g);
     } else if (c3 == 2) {
         if (kepi == 2) hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 2, false, true, 2>), grid, block, 0, st, g);
@@ -1158,7 +1185,8 @@ int launch_layout(hipStream_t st, dim3 grid, const CArgs& g, bool tA, bool tB, i
 
 }  // namespace
 
-// pro: 0 none, 1 A prologue (needs !tA), 2 B prologue (needs tA && !tB);  epi: 0 plain, 1 stats, 2 mask + BN-backward sums.
+// pro: 0 none, 1 A prologue (needs !tA), 2 B prologue (needs tA && !tB);  epi: 0 plain, 1 stats, 2 mask + BN-backward sums,
+// 3 eval BatchNorm (+ residual, ReLU; NT without prologue, or the 3x3 forward).
 int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, const float* A, long lda, const float* B,
           long ldb, float beta, float* C, long ldc, const float* bias, const float* rowmask, int batch, long sA, long sB,
           long sC, float* ws, long ws_floats, const ConvExtra* ex) {
@@ -1180,7 +1208,14 @@ int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, co
         SCN_ARG(ex->c3_src_rows * (c3 == 3 ? ldb : lda) * 4 < 0x7fffffffL, "cgemm: 3x3 source map exceeds the descriptor range");
     }
     SCN_ARG(pro == 0 || (pro == 1 && !tA) || (pro == 2 && !tB && tA), "cgemm: prologue / layout mismatch");
-    SCN_ARG(epi == 0 || (batch == 1 && beta == 0.f && !bias && !rowmask && ex->stat_partial), "cgemm: statistics epilogue needs a plain product");
+    SCN_ARG(epi == 0 || (batch == 1 && beta == 0.f && !bias && !rowmask && (epi == 3 || ex->stat_partial)),
+            "cgemm: statistics epilogue needs a plain product");
+    SCN_ARG(epi != 3 || (!tA && tB && pro == 0 && (c3 == 0 || c3 == 1)), "cgemm: eval BatchNorm epilogue: forward products only");
+    SCN_ARG(epi != 3 || (ex->egamma && ex->ebeta && ex->emean && ex->evar && aligned16(ex->egamma) && aligned16(ex->ebeta) &&
+                         aligned16(ex->emean) && aligned16(ex->evar) &&
+                         (!ex->ez || (aligned16(ex->ez) && ex->ldz % 4 == 0 && ex->ldz >= N &&
+                                      ((long)(M - 1) * ex->ldz + N) * 4 < 0x7fffffffL))),
+            "cgemm: eval BatchNorm epilogue arguments");
     SCN_ARG(epi != 2 || (ex->ez && ex->emean && ex->einvstd && (ex->pro_ss || (ex->egamma && ex->ebeta)) && ex->ldz % 4 == 0),
             "cgemm: mask epilogue arguments");
     SCN_ARG(pro == 0 || ex->pro_ss, "cgemm: prologue table");
@@ -1241,6 +1276,13 @@ int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, co
         S = ex->force_split;
         SCN_ARG(S == 1 || (ws && (long)S * batch * M * N <= ws_floats && S <= CG_MAX_SPLIT), "cgemm: forced split does not fit");
     }
+    // EPI 3 has no second-launch form (creduce applies the plain epilogue only): a split product takes the in-launch
+    // combine, so S is clamped to what the last arriver sums alone (g_cgemm_combine_max) and drops to 1 when the combine
+    // is not available (option off, no counters -- e.g. inside a stream capture -- or a slab stack beyond 2 GiB).
+    if (epi == 3 && S > 1) {
+        if (S > g_cgemm_combine_max) S = g_cgemm_combine_max;
+        if (!(g_cgemm_combine && S > 1 && vec && tiles <= CNT_N && (long)S * M * N * 4 < 0x7fffffffL && stream_counters(st))) S = 1;
+    }
     int kper = cdiv(K, S);
     kper = (kper + TK - 1) / TK * TK;
     S = cdiv(K, kper);
@@ -1255,6 +1297,7 @@ int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, co
         g.pro_ss = ex->pro_ss;
         g.stat_partial = ex->stat_partial; g.stat_shift = ex->stat_shift; g.ldp = cgemm_stat_ld(M);
         g.ez = ex->ez; g.emean = ex->emean; g.einvstd = ex->einvstd; g.egamma = ex->egamma; g.ebeta = ex->ebeta; g.ldz = ex->ldz;
+        g.evar = ex->evar; g.eeps = ex->eeps; g.erelu = ex->erelu;
     }
     dim3 grid(mt * nt, c3 == 4 ? 4 : batch * S), block(256);
     // The epilogue runs inside the launch: from the accumulators of an un-split product, or -- split product -- by the
@@ -1266,6 +1309,7 @@ int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, co
         (long)S * M * N * 4 < 0x7fffffffL)
         cnt = stream_counters(st);
     g.cnt = cnt; g.comb = g_cgemm_combine;
+    SCN_ARG(epi != 3 || S == 1 || cnt, "cgemm: eval BatchNorm epilogue of a split product needs the in-launch combine");
     const int kepi = (S > 1 && !cnt) ? 0 : (epi_in ? epi : 0);
     if (c3) {
         SCN_ARG(vec, "cgemm: 3x3 mode needs 16-byte row stores");

@@ -34,6 +34,9 @@ struct ConvExtra {
     int c3 = 0;               // 3x3 convolution as an implicit GEMM: 1 forward, 2 dgrad (stride 1), 3 wgrad, 4 dgrad (stride 2)
     int c3c = 0;              // channels per tap of the gathered operand
     long c3_src_rows = 0;     // rows of the gathered map
+    // epi 3 (eval BatchNorm): y = act(acc * scale[n] + shift[n] (+ ez[m][n])), scale = egamma / sqrt(evar + eeps),
+    // shift = ebeta - emean * scale; ez / ldz is the optional residual, erelu selects the ReLU
+    const float* evar = nullptr; float eeps = 0.f; int erelu = 0;
 };
 bool cgemm_supported(bool tA, bool tB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
                      long sA, long sB);

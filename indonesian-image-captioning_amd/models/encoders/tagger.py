@@ -3,8 +3,8 @@
 (B,3,H,W) images -> ResNet-152 trunk INCLUDING the global average pool -> (B,2048) -> Dropout(0.15) ->
 Linear(2048, semantic_size) -> Sigmoid = tag probabilities (B, semantic_size), which the train step feeds
 to the decoder as `semantic_input` (trains/attention_scn.py:214).  Same module tree / state_dict keys as
-the reference (`resnet.<idx>...`, `linear.{weight,bias}`); the trunk is scnattn.resnet (MIOpen convolutions +
-the fused BatchNorm kernels), the Linear runs on the MFMA sgemm."""
+the reference (`resnet.<idx>...`, `linear.{weight,bias}`); the trunk is scnattn.resnet (the hand-written
+convolution kernels with the BatchNorm fused into them, in training and in eval mode), the Linear runs on the MFMA sgemm."""
 import torch
 from torch import nn
 

@@ -53,6 +53,11 @@ class ConvExtra(C.Structure):      # scnattn_conv_extra
                 ("force_split", C.c_int), ("force_mi", C.c_int)]
 
 
+class BnEval(C.Structure):         # scnattn_bn_eval
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p), ("eps", C.c_float),
+                ("res", C.c_void_p), ("ldres", C.c_long), ("relu", C.c_int)]
+
+
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
@@ -77,6 +82,9 @@ _SIGS = {
     "scnattn_conv3x3_dgrad": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(ConvExtra), vp, i64], i32),
     "scnattn_conv3x3_wgrad": ([vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, i32], i32),
     "scnattn_conv3x3_dgrad_strided": ([vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64], i32),
+    "scnattn_conv1x1_fwd_bn_eval": ([vp, i32, i32, i32, vp, vp, vp, C.POINTER(BnEval), C.POINTER(ConvExtra), vp, i64], i32),
+    "scnattn_conv3x3_fwd_bn_eval": ([vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(BnEval), C.POINTER(ConvExtra),
+                                     vp, i64], i32),
     "scnattn_cgemm_stat_ld": ([i32], i32),
     "scnattn_bn_finalize": ([vp, i64, i32, vp, i32, i32, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp], i32),
     "scnattn_bn_apply_fin": ([vp, i64, i32, vp, vp, i32, vp, i32, i32, vp, f32, f32, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),

@@ -22,9 +22,10 @@ d weight -- runs on the hand-written kernels of csrc/cgemm.hip / csrc/conv3.hip,
 The strided 1x1 downsample convolution gathers its input rows inside the kernel.  No library (MIOpen / rocBLAS) kernel
 runs in a block; `SCNATTN_CONV3=miopen` swaps conv2 back to MIOpen for A/B measurements only.
 
-`Bottleneck.forward` (scnattn/resnet.py) calls `bottleneck()` for fp32 CUDA inputs in training mode and
-scnattn/conv16.py's mixed-precision twin for bf16 ones; everything else (eval mode, CPU structure tests) takes the
-unfused module path."""
+`Bottleneck.forward` (scnattn/resnet.py) calls `bottleneck()` for fp32 CUDA inputs in training mode,
+scnattn/conv_eval.py's eval block (BatchNorm with running statistics folded into the convolution epilogues) for fp32
+CUDA inputs in eval mode and scnattn/conv16.py's mixed-precision twin for bf16 ones; everything else (CPU structure
+tests, fp32 under autocast, widths the kernels do not address) takes the unfused module path."""
 import ctypes as C
 import os
 

@@ -1,0 +1,180 @@
+"""Eval-mode Bottleneck of the ResNet-152 trunk on the hand-written kernels (fp32, channels-last maps).
+
+With running statistics a BatchNorm is the fixed per-channel map z*scale + shift (scale = gamma / sqrt(var + eps),
+shift = beta - mean * scale), so it folds into the epilogue of the convolution that produces z (csrc/cgemm.hip, EPI 3):
+the pre-BatchNorm maps z1, z2, z3 are never written, and a block is three launches, four with a downsample:
+
+    a1  = relu(bn1(conv1(x)))                       scnattn_conv1x1_fwd_bn_eval
+    a2  = relu(bn2(conv2(a1)))     (3x3, stride s)   scnattn_conv3x3_fwd_bn_eval
+    idn = bnd(convd(x))  | x       (rows gathered at stride s)
+    out = relu(bn3(conv3(a2)) + idn)
+
+scale / shift are formed by the kernel from the module's own weight, bias and running buffers at every call, so a
+training step that moves the running statistics in place (through raw pointers, which does not bump `_version`) is
+seen by the next eval call; nothing is cached.  Running statistics and `num_batches_tracked` are never touched.
+
+Autograd: the reference's inference.py runs the encoder in eval mode WITH grad enabled (layer2-4 require grad), so the
+fused forward is one autograd node that saves only its input and, in backward, recomputes the block through the
+unchanged module-path ops (`Bottleneck.module_forward`) and returns their gradients -- backward keeps today's kernels.
+
+`Bottleneck.forward` (scnattn/resnet.py) takes this path when `eval_reason` returns None; every other case (bf16
+autocast, widths that are not multiples of 16, CPU tensors, `conv.ENABLED = False`) keeps the module path."""
+import ctypes as C
+
+import torch
+
+from . import conv as _conv
+from ._lib import BnEval, ConvExtra
+
+
+def _bns(mod):
+    return (mod.bn1, mod.bn2, mod.bn3) + ((mod.downsample[1],) if mod.downsample is not None else ())
+
+
+def eval_reason(mod, x):
+    """None when the fused eval block applies to `mod` (a scnattn.resnet.Bottleneck) on input `x`, else why not."""
+    if not _conv.ENABLED:
+        return "fused kernels disabled (scnattn.conv.ENABLED is False)"
+    if mod.training:
+        return "module is in training mode"
+    if torch.is_autocast_enabled():
+        return "autocast is enabled"
+    if not x.is_cuda:
+        return "input is not a GPU tensor"
+    if x.dtype != torch.float32 or x.dim() != 4:
+        return "input is not an fp32 (N, C, H, W) map"
+    for bn in _bns(mod):
+        if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+            return "a BatchNorm has no running statistics"
+        if bn.weight is None or bn.bias is None:
+            return "a BatchNorm is not affine"
+        if any(t.dtype != torch.float32 or t.device != x.device for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+            return "a BatchNorm parameter / statistic is not fp32 on the input's device"
+    c1, c2, c3 = mod.conv1, mod.conv2, mod.conv3
+    for cv in (c1, c2, c3):
+        if cv.bias is not None or cv.groups != 1 or cv.dilation != (1, 1) or cv.weight.dtype != torch.float32 \
+                or cv.weight.device != x.device:
+            return "a convolution has a bias, groups, dilation or a non-fp32 weight"
+    if c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.padding != (0, 0) \
+            or c3.kernel_size != (1, 1) or c3.stride != (1, 1) or c3.padding != (0, 0):
+        return "conv1 / conv3 are not 1x1 at stride 1"
+    s = mod.stride
+    if c2.kernel_size != (3, 3) or c2.padding != (1, 1) or s not in (1, 2) or c2.stride != (s, s):
+        return "conv2 is not 3x3 / padding 1 at stride 1 or 2"
+    p, cin, c4 = c1.weight.shape[0], c1.weight.shape[1], c3.weight.shape[0]
+    if p % 16 or cin % 16 or c4 % 16:
+        return "widths (%d, %d, %d) are not multiples of 16" % (cin, p, c4)
+    if x.shape[1] != cin:
+        return "input has %d channels, conv1 takes %d" % (x.shape[1], cin)
+    if mod.downsample is not None:
+        d0 = mod.downsample[0]
+        if len(mod.downsample) != 2 or not isinstance(d0, torch.nn.Conv2d) or d0.kernel_size != (1, 1) \
+                or d0.stride != (s, s) or d0.padding != (0, 0) or d0.bias is not None or d0.groups != 1 \
+                or d0.weight.dtype != torch.float32 or d0.weight.shape[0] != c4:
+            return "downsample is not a 1x1 convolution at the block's stride + BatchNorm"
+    elif s != 1 or cin != c4:
+        return "no downsample, but the identity does not match the output"
+    return None
+
+
+def _vec(t):
+    """A [C] fp32 vector the kernel can read 16 bytes at a time (parameters and buffers already are: no copy)."""
+    if not t.is_contiguous() or t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def _w2d(w, rows, cols):
+    w = w.reshape(rows, cols)
+    return w if w.is_contiguous() and w.data_ptr() % 16 == 0 else w.contiguous().clone()
+
+
+def _bn_eval(bn, relu, res=None, ldres=0):
+    keep = (_vec(bn.weight), _vec(bn.bias), _vec(bn.running_mean), _vec(bn.running_var))
+    b = BnEval(gamma=keep[0].data_ptr(), beta=keep[1].data_ptr(), mean=keep[2].data_ptr(), var=keep[3].data_ptr(),
+               eps=float(bn.eps), res=None if res is None else res.data_ptr(), ldres=ldres, relu=1 if relu else 0)
+    return b, keep
+
+
+def _forward(mod, x):
+    """The fused eval block on the caller's stream; returns the (N, C4, Ho, Wo) channels-last output."""
+    h, raw_stream = _conv._fns()
+    dev = x.device
+    st = raw_stream(dev.index)
+    ws = _conv._buffers(dev)[0]
+    if not x.is_contiguous(memory_format=torch.channels_last):
+        x = x.contiguous(memory_format=torch.channels_last)
+    N, Cin, Hi, Wi = x.shape
+    w1, w3 = mod.conv1.weight, mod.conv3.weight
+    p, C4, s = w1.shape[0], w3.shape[0], mod.stride
+    Ho, Wo = (Hi - 1) // s + 1, (Wi - 1) // s + 1
+    Rin, Rout = N * Hi * Wi, N * Ho * Wo
+    x2 = _conv._as2d(x)
+    f32 = dict(device=dev, dtype=torch.float32)
+    with torch.no_grad():
+        # conv2's weight as [Cout][3][3][Cin]: a transient channels-last copy when the module is not channels-last (never
+        # cached -- an optimizer may rewrite the weights in place through raw pointers)
+        w2 = mod.conv2.weight.detach().contiguous(memory_format=torch.channels_last)
+        a1 = torch.empty((Rin, p), **f32)
+        bn, keep1 = _bn_eval(mod.bn1, True)
+        _conv._chk(h.scnattn_conv1x1_fwd_bn_eval(st, Rin, Cin, p, x2.data_ptr(), _w2d(w1.detach(), p, Cin).data_ptr(),
+                                                 a1.data_ptr(), C.byref(bn), None, ws.data_ptr(), ws.numel()),
+                   "scnattn_conv1x1_fwd_bn_eval")
+        a2 = torch.empty((Rout, p), **f32)
+        bn, keep2 = _bn_eval(mod.bn2, True)
+        _conv._chk(h.scnattn_conv3x3_fwd_bn_eval(st, N, Hi, Wi, p, p, s, a1.data_ptr(), w2.data_ptr(), a2.data_ptr(),
+                                                 C.byref(bn), None, ws.data_ptr(), ws.numel()),
+                   "scnattn_conv3x3_fwd_bn_eval")
+        if mod.downsample is not None:
+            idn = torch.empty((Rout, C4), **f32)
+            bn, keepd = _bn_eval(mod.downsample[1], False)
+            ex = ConvExtra(stride=s, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo)
+            _conv._chk(h.scnattn_conv1x1_fwd_bn_eval(st, Rout, Cin, C4, x2.data_ptr(),
+                                                     _w2d(mod.downsample[0].weight.detach(), C4, Cin).data_ptr(),
+                                                     idn.data_ptr(), C.byref(bn), C.byref(ex), ws.data_ptr(), ws.numel()),
+                       "scnattn_conv1x1_fwd_bn_eval")
+        else:
+            idn = x2
+        out = torch.empty((Rout, C4), **f32)
+        bn, keep3 = _bn_eval(mod.bn3, True, idn, C4)
+        _conv._chk(h.scnattn_conv1x1_fwd_bn_eval(st, Rout, p, C4, a2.data_ptr(), _w2d(w3.detach(), C4, p).data_ptr(),
+                                                 out.data_ptr(), C.byref(bn), None, ws.data_ptr(), ws.numel()),
+                   "scnattn_conv1x1_fwd_bn_eval")
+    return _conv._as4d(out, N, Ho, Wo)
+
+
+def _params(mod):
+    d = mod.downsample
+    return (mod.conv1.weight, mod.bn1.weight, mod.bn1.bias, mod.conv2.weight, mod.bn2.weight, mod.bn2.bias,
+            mod.conv3.weight, mod.bn3.weight, mod.bn3.bias,
+            d[0].weight if d is not None else None, d[1].weight if d is not None else None,
+            d[1].bias if d is not None else None)
+
+
+class _EvalBottleneckFn(torch.autograd.Function):
+    """Fused eval forward; backward recomputes the block through the module-path ops and returns their gradients."""
+
+    @staticmethod
+    def forward(ctx, mod, x, *params):
+        ctx.mod = mod
+        ctx.save_for_backward(x, *params)
+        return _forward(mod, x)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, *params = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:]          # (x, *params)
+        with torch.enable_grad():
+            xr = x.detach().requires_grad_(need[0])
+            y = ctx.mod.module_forward(xr)
+            leaves = [t for t, n in zip([xr] + list(params), need) if n]
+            got = iter(torch.autograd.grad(y, leaves, dout, allow_unused=True)) if leaves else iter(())
+        return (None,) + tuple(next(got) if n else None for n in need)
+
+
+def bottleneck_eval(mod, x):
+    """Eval-mode forward of `mod` on the fused kernels (caller checked `eval_reason(mod, x) is None`)."""
+    params = _params(mod)
+    if torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in params)):
+        return _EvalBottleneckFn.apply(mod, x, *params)
+    return _forward(mod, x)

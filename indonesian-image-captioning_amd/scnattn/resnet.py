@@ -5,9 +5,12 @@ the module tree -- and therefore every state_dict key -- equals
 
 torchvision is not installed in this image (nor on the GPU box), and the reference's
 ``pretrained=True`` needs a download, so weights are random-init by torchvision's own recipe
-(kaiming-normal fan-out convs, BN gamma=1 beta=0) unless a state_dict is loaded.  On MI355X the
-convolutions run on MIOpen's MFMA kernels through PyTorch-ROCm; channels-last memory format is used so
-the 1x1 convolutions are plain GEMMs over contiguous channels."""
+(kaiming-normal fan-out convs, BN gamma=1 beta=0) unless a state_dict is loaded.  On MI355X every
+Bottleneck of fp32 maps runs on the hand-written kernels: training mode through scnattn/conv.py (one autograd
+node per block, BatchNorm statistics fused into the convolutions), eval mode through scnattn/conv_eval.py (the
+running-statistics BatchNorm folded into each convolution's epilogue), bf16 maps through scnattn/conv16.py.
+What none of them covers (CPU tensors, fp32 under autocast, widths that are not multiples of 16) takes the
+module path: nn.Conv2d (MIOpen) + the fused BatchNorm kernels."""
 import os
 
 import torch
@@ -67,10 +70,18 @@ class Bottleneck(nn.Module):
         from . import conv as _conv
         if _conv.usable(self, x):
             return _conv.bottleneck(self, x)
+        # fp32 eval-mode maps on the GPU: three (four) launches with the BatchNorm folded into the epilogues (scnattn/conv_eval.py)
+        from . import conv_eval as _ce
+        if _ce.eval_reason(self, x) is None:
+            return _ce.bottleneck_eval(self, x)
         if x.dtype == torch.bfloat16:        # the mixed-precision trunk (bf16 maps from scnattn/stem.py under bf16 autocast)
             from . import conv16 as _c16
             if _c16.usable(self, x):
                 return _c16.bottleneck(self, x)
+        return self.module_forward(x)
+
+    def module_forward(self, x):
+        """The unfused module path: nn.Conv2d + FusedBatchNorm2d (also what the eval block's backward recomputes)."""
         identity = x if self.downsample is None else self.downsample(x)
         out = self.bn1(self.conv1(x), relu=True)
         out = self.bn2(self.conv2(out), relu=True)
