@@ -22,16 +22,15 @@ d weight -- runs on the hand-written kernels of csrc/cgemm.hip / csrc/conv3.hip,
 The strided 1x1 downsample convolution gathers its input rows inside the kernel.  No library (MIOpen / rocBLAS) kernel
 runs in a block; `SCNATTN_CONV3=miopen` swaps conv2 back to MIOpen for A/B measurements only.
 
-`Bottleneck.forward` (scnattn/resnet.py) calls `bottleneck()` for fp32 CUDA inputs in training mode,
-scnattn/conv_eval.py's eval block (BatchNorm with running statistics folded into the convolution epilogues) for fp32
-CUDA inputs in eval mode and scnattn/conv16.py's mixed-precision twin for bf16 ones; everything else (CPU structure
-tests, fp32 under autocast, widths the kernels do not address) takes the unfused module path."""
+`Bottleneck.forward` (scnattn/resnet.py) calls `bottleneck()` when `train_reason` returns None; scnattn/block.py holds
+what this path shares with the eval block (scnattn/conv_eval.py) and the bf16 one (scnattn/conv16.py)."""
 import ctypes as C
 import os
 
 import torch
 
 from . import _lib
+from . import block as B
 from ._lib import ConvExtra
 
 ENABLED = True          # class-wide switch: tests / A-B runs compare against the unfused path
@@ -45,16 +44,17 @@ W3_SLICES = int(os.environ.get("SCNATTN_W3_SLICES", "0"))   # tuning: K slices o
 _bufs = {}
 
 
-def _buffers(dev):
-    """Scratch per (device, current stream), reused in stream order: split-K slabs of the GEMMs and the statistics
-    partials.  Per stream because two trunks may run at once (the frozen tagger beside the caption encoder)."""
-    key = (dev, torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device()))
-    b = _bufs.get(key)
+def _launch(dev):
+    """What a block call needs: the library, the current stream of `dev` and the scratch of that (device, stream), reused
+    in stream order: split-K slabs of the GEMMs and the statistics partials `part`, `bnpart`.  Per stream because two
+    trunks may run at once (the frozen tagger beside the caption encoder)."""
+    st = torch._C._cuda_getCurrentRawStream(dev.index if dev.index is not None else torch.cuda.current_device())
+    b = _bufs.get((dev, st))
     if b is None:
-        b = _bufs[key] = (torch.empty(16 << 20, device=dev, dtype=torch.float32),     # 64 MiB split-K slabs
-                          torch.empty(2 << 20, device=dev, dtype=torch.float32),      # [64-row blocks][2][C] partials
-                          torch.empty(2 << 20, device=dev, dtype=torch.float32))      # BN chunk partials (bn_stats)
-    return b
+        b = _bufs[(dev, st)] = (torch.empty(16 << 20, device=dev, dtype=torch.float32),     # 64 MiB split-K slabs
+                                torch.empty(B.PART_FLOATS, device=dev, dtype=torch.float32),    # [2][C][stat_ld] partials
+                                torch.empty(B.PART_FLOATS, device=dev, dtype=torch.float32))    # BN chunk partials (bn_stats)
+    return (_lib.lib(), st) + b
 
 
 def _concurrent_stream(dev, attempts=8, beside=()):
@@ -184,17 +184,6 @@ def join_side_streams():
         sd.join()
 
 
-_fn = None
-
-
-def _fns():
-    global _fn
-    if _fn is None:
-        h = _lib.lib()
-        _fn = (h, torch._C._cuda_getCurrentRawStream)
-    return _fn
-
-
 def _chk(rc, what):
     if rc:
         _lib.check(rc, what)
@@ -229,6 +218,10 @@ def _shift(bn):
     return s
 
 
+def _set_shift(bn, mean):
+    bn._scn_shift = mean
+
+
 def _finalize(h, st, R, Cn, part, bn_mod, shift, gamma, beta, want_ss):
     """Statistics only (the consumer normalises on load): mean / invstd / running statistics / folded {scale, shift}."""
     dev = part.device
@@ -239,7 +232,7 @@ def _finalize(h, st, R, Cn, part, bn_mod, shift, gamma, beta, want_ss):
                                bn_mod.running_mean.data_ptr(), bn_mod.running_var.data_ptr(),
                                gamma.data_ptr() if want_ss else None, beta.data_ptr() if want_ss else None,
                                ss.data_ptr() if want_ss else None), "scnattn_bn_finalize")
-    bn_mod._scn_shift = stats[0]
+    _set_shift(bn_mod, stats[0])
     return stats, ss
 
 
@@ -253,7 +246,7 @@ def _apply_fin(h, st, R, Cn, z, res, part, bn_mod, shift, gamma, beta, relu):
                                 bn_mod.momentum, gamma.data_ptr(), beta.data_ptr(), 1 if relu else 0, y.data_ptr(),
                                 stats[0].data_ptr(), stats[1].data_ptr(), bn_mod.running_mean.data_ptr(),
                                 bn_mod.running_var.data_ptr(), None), "scnattn_bn_apply_fin")
-    bn_mod._scn_shift = stats[0]
+    _set_shift(bn_mod, stats[0])
     return y, stats
 
 
@@ -307,18 +300,10 @@ def _wt(h, st, w, cout, cin):
 class _BottleneckFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd):
-        h, raw_stream = _fns()
         dev = x.device
-        st = raw_stream(dev.index)
-        ws, part, bnpart = _buffers(dev)
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        N, Cin, Hi, Wi = x.shape
-        p = w1.shape[0]
-        C4 = w3.shape[0]
-        s = mod.stride
-        Ho, Wo = (Hi - 1) // s + 1, (Wi - 1) // s + 1
-        Rin, Rout = N * Hi * Wi, N * Ho * Wo
+        h, st, ws, part, bnpart = _launch(dev)
+        x = B.channels_last(x)
+        N, Cin, Hi, Wi, p, C4, s, Ho, Wo, Rin, Rout = g = B.geometry(mod, x)
         x2 = _as2d(x)
         bn1, bn2, bn3 = mod.bn1, mod.bn2, mod.bn3
         # conv1 (+ bn1 statistics) -> bn1 apply + relu with the finalize inside
@@ -372,27 +357,20 @@ class _BottleneckFn(torch.autograd.Function):
             _chk(h.scnattn_transpose2d(sw, p, Cin, w1.data_ptr(), Cin, wt.data_ptr(), p), "scnattn_transpose2d")
             wt_ev = torch.cuda.Event()
             wt_ev.record(sd.stream)
-        ctx.wt, ctx.wt_ev = wt, wt_ev
-        ctx.geom = (N, Cin, Hi, Wi, p, C4, s, Ho, Wo)
-        ctx.has_down = wd is not None
+        ctx.wt, ctx.wt_ev, ctx.geom = wt, wt_ev, g
         ctx.save_for_backward(x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd, z1, a1, z2, z3, out, zd, st1, st2, ss2,
                               st3, std)
         return _as4d(out, N, Ho, Wo)
 
     @staticmethod
     def backward(ctx, dout):
-        h, raw_stream = _fns()
         (x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd, z1, a1, z2, z3, out, zd, st1, st2, ss2, st3,
          std) = ctx.saved_tensors
-        N, Cin, Hi, Wi, p, C4, s, Ho, Wo = ctx.geom
+        N, Cin, Hi, Wi, p, C4, s, Ho, Wo, Rin, Rout = ctx.geom
         dev = x.device
-        st = raw_stream(dev.index)
-        ws, part, bnpart = _buffers(dev)
-        Rin, Rout = N * Hi * Wi, N * Ho * Wo
+        h, st, ws, part, bnpart = _launch(dev)
         need = ctx.needs_input_grad      # (mod, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd)
-        if dout.dtype != torch.float32 or not dout.is_contiguous(memory_format=torch.channels_last):
-            dout = dout.float().contiguous(memory_format=torch.channels_last)
-        dout2 = _as2d(dout)
+        dout2 = _as2d(B.channels_last(dout.float()))
         x2 = _as2d(x)
         f32 = dict(device=dev, dtype=torch.float32)
         ld_out, nc_out = h.scnattn_cgemm_stat_ld(Rout), h.scnattn_cgemm_row_tiles(Rout)
@@ -471,7 +449,7 @@ class _BottleneckFn(torch.autograd.Function):
                 main.wait_event(ctx.wt_ev)
         dwd = dgbd = None
         dx = None
-        if ctx.has_down:
+        if wd is not None:
             _, nch = _bwd_reduce(h, st, Rout, C4, dres, None, zd, std, False, bnpart, False)
             dzd = torch.empty((Rout, C4), **f32)
             dgbd = _bwd_dx_fin(h, st, Rout, C4, dres, zd, std, gd, bnpart, (nch + 3) & ~3, nch, dzd)
@@ -498,48 +476,31 @@ class _BottleneckFn(torch.autograd.Function):
         if side:
             side.mark()      # joined by the first reader of the weight gradients (FlatBuffer.gather)
         dx4 = _as4d(dx, N, Hi, Wi) if dx is not None else None
-        return (None, dx4, dw1, dgb1[1] if need[3] else None, dgb1[0] if need[4] else None,
-                dw2 if need[5] else None, dgb2[1] if need[6] else None, dgb2[0] if need[7] else None,
-                dw3, dgb3[1] if need[9] else None, dgb3[0] if need[10] else None,
-                dwd, (dgbd[1] if need[12] else None) if dgbd is not None else None,
-                (dgbd[0] if need[13] else None) if dgbd is not None else None)
+        return B.grads(need, dx4, (dw1, dw2, dw3, dwd), (dgb1, dgb2, dgb3, dgbd))
+
+
+def train_reason(mod, x):
+    """None when the fused training block covers `mod` (a scnattn.resnet.Bottleneck) on input `x`, else why not: fp32 CUDA
+    maps outside autocast, widths the 3x3 kernels' tiles address, a channels-last conv2 weight, partials within the scratch."""
+    r = B.reason(mod, x, ENABLED, True, torch.float32)
+    if r:
+        return r
+    g = B.geometry(mod, x)
+    # the 3x3 kernels: 32-channel blocks (stride 1), 128-channel column tiles and even maps (stride 2)
+    if CONV3 == "hip" and (g.p % 32 if g.s == 1 else g.p % 128 or g.Hi % 2 or g.Wi % 2):
+        return "conv2's width / map parity is not one the 3x3 kernels address"
+    if not mod.conv2.weight.is_contiguous(memory_format=torch.channels_last):
+        return "conv2's weight is not channels-last"
+    if B.part_floats(g) > B.PART_FLOATS:
+        return "statistics partials exceed the scratch"
+    return None
 
 
 def usable(mod, x):
-    """The fused path covers what the train step runs: fp32 CUDA maps, BatchNorm in training mode with running
-    statistics and affine parameters, widths that the 16-byte LDS-DMA granules can address."""
-    if not (ENABLED and x.is_cuda and x.dtype == torch.float32 and mod.training and not torch.is_autocast_enabled()):
-        return False
-    for bn in (mod.bn1, mod.bn2, mod.bn3):
-        if bn.weight is None or not bn.track_running_stats or bn.momentum is None or bn.weight.dtype != torch.float32:
-            return False
-    p, cin = mod.conv1.weight.shape[0], mod.conv1.weight.shape[1]
-    if p % 16 or cin % 16 or mod.conv2.groups != 1 or mod.conv2.dilation != (1, 1):
-        return False
-    if mod.conv2.kernel_size != (3, 3) or mod.conv2.padding != (1, 1) or mod.stride not in (1, 2) \
-            or not mod.conv2.weight.is_contiguous(memory_format=torch.channels_last):
-        return False
-    if CONV3 == "hip":      # what the 3x3 kernels address: 32-channel blocks (stride 1), 128-channel
-        H, W = x.shape[2], x.shape[3]      # column tiles and even maps (stride 2)
-        if mod.stride == 1 and p % 32:
-            return False
-        if mod.stride == 2 and (p % 128 or H % 2 or W % 2):
-            return False
-    if mod.downsample is not None:
-        d0, d1 = mod.downsample[0], mod.downsample[1]
-        if d0.kernel_size != (1, 1) or d0.stride != (mod.stride, mod.stride) or d1.weight is None or d1.momentum is None:
-            return False
-    return True
+    return train_reason(mod, x) is None
 
 
 def bottleneck(mod, x):
     """One fused forward of `mod` (a scnattn.resnet.Bottleneck); autograd gets a single node."""
-    for bn in (mod.bn1, mod.bn2, mod.bn3) + ((mod.downsample[1],) if mod.downsample is not None else ()):
-        if not bn.counter_managed and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-    if mod.downsample is not None:
-        wd, gd, bd = mod.downsample[0].weight, mod.downsample[1].weight, mod.downsample[1].bias
-    else:
-        wd = gd = bd = None
-    return _BottleneckFn.apply(mod, x, mod.conv1.weight, mod.bn1.weight, mod.bn1.bias, mod.conv2.weight, mod.bn2.weight,
-                               mod.bn2.bias, mod.conv3.weight, mod.bn3.weight, mod.bn3.bias, wd, gd, bd)
+    B.bump_counters(B.bns(mod))
+    return _BottleneckFn.apply(mod, x, *B.params(mod))

@@ -13,15 +13,15 @@ but every feature map and every gradient map is bf16 in HBM and every convolutio
   * a2 = relu(bn2(z2)) is materialised here (in fp32 it is recomputed on load by conv3's prologue): at 2 bytes per element
     the extra map costs less than a prologue pass in a kernel whose matrix work is 8x shorter.
 
-`Bottleneck.forward` (scnattn/resnet.py) calls `bottleneck()` when its input is a bf16 CUDA map in training mode; the
-trunk produces one when it runs under `torch.autocast("cuda", dtype=torch.bfloat16)` (scnattn/stem.py)."""
+`Bottleneck.forward` (scnattn/resnet.py) calls `bottleneck()` when `bf16_reason` returns None: bf16 CUDA maps in training
+mode, which the trunk produces under `torch.autocast("cuda", dtype=torch.bfloat16)` (scnattn/stem.py)."""
 import ctypes as C
 import os
 
-import numpy as np
 import torch
 
 from . import _lib
+from . import block as B
 from . import conv as _conv
 from ._lib import ConvExtra
 
@@ -45,29 +45,27 @@ class _Weights:
         self.buf = torch.empty(n, device=dev, dtype=BF)
         self.buf_t = torch.empty(n, device=dev, dtype=BF)
         self.ptrs = None
-        off = 0
-        for m in self.convs:
-            co, ci, kh, kw = m.weight.shape
-            k = m.weight.numel()
-            m._w16 = self.buf[off:off + k].view(co, kh * kw * ci)           # [Cout][taps][Cin]
-            m._w16t = self.buf_t[off:off + k].view(ci, kh * kw * co)        # [Cin][taps][Cout]
-            off += k
 
     def _table(self, dev):
-        descs = (_WeightDesc * len(self.convs))()
-        prefix = np.zeros(len(self.convs) + 1, dtype=np.int32)
-        for i, m in enumerate(self.convs):
+        """A copy for each weight the kernel reads as [Cout][taps][Cin]; a 3x3 weight that is not channels-last gets none
+        (no `_w16`: its block takes the module path).  Each conv keeps its slot in the buffers."""
+        descs, prefix, off = [], [0], 0
+        for m in self.convs:
             w = m.weight
             co, ci, kh, kw = w.shape
             taps = kh * kw
-            if taps > 1 and not w.is_contiguous(memory_format=torch.channels_last):
-                raise RuntimeError("conv16: 3x3 weights must be channels-last ([Cout][3][3][Cin] in memory)")
-            descs[i] = _WeightDesc(w.data_ptr(), m._w16.data_ptr(), m._w16t.data_ptr(), co, taps, ci, 0)
-            prefix[i + 1] = prefix[i] + taps * (co // 32) * (ci // 32)
-        raw = np.frombuffer(bytes(descs), dtype=np.uint8).copy()
-        self.desc = torch.from_numpy(raw).to(dev)
-        self.prefix = torch.from_numpy(prefix).to(dev)
-        self.total = int(prefix[-1])
+            if taps == 1 or w.is_contiguous(memory_format=torch.channels_last):
+                m._w16 = self.buf[off:off + w.numel()].view(co, taps * ci)           # [Cout][taps][Cin]
+                m._w16t = self.buf_t[off:off + w.numel()].view(ci, taps * co)        # [Cin][taps][Cout]
+                descs.append(_WeightDesc(w.data_ptr(), m._w16.data_ptr(), m._w16t.data_ptr(), co, taps, ci, 0))
+                prefix.append(prefix[-1] + taps * (co // 32) * (ci // 32))
+            else:
+                m.__dict__.pop("_w16", None)
+                m.__dict__.pop("_w16t", None)
+            off += w.numel()
+        self.n, self.total = len(descs), prefix[-1]
+        self.desc = torch.tensor(list(b"".join(bytes(d) for d in descs)), dtype=torch.uint8, device=dev)
+        self.prefix = torch.tensor(prefix, dtype=torch.int32, device=dev)
         self.ptrs = [m.weight.data_ptr() for m in self.convs]
 
     def refresh(self, dev):
@@ -75,8 +73,8 @@ class _Weights:
         if self.ptrs is None or any(m.weight.data_ptr() != p for m, p in zip(self.convs, self.ptrs)):
             self._table(dev)
         st = torch._C._cuda_getCurrentRawStream(dev.index)
-        _conv._chk(_lib.lib().scnattn_bf16_weights(st, len(self.convs), self.desc.data_ptr(), self.prefix.data_ptr(),
-                                                   self.total), "scnattn_bf16_weights")
+        _conv._chk(_lib.lib().scnattn_bf16_weights(st, self.n, self.desc.data_ptr(), self.prefix.data_ptr(), self.total),
+                   "scnattn_bf16_weights")
 
 
 def refresh_weights(trunk):
@@ -90,24 +88,26 @@ def refresh_weights(trunk):
     w.refresh(dev)
 
 
+def bf16_reason(mod, x):
+    """None when the bf16 block covers `mod` (a scnattn.resnet.Bottleneck) on input `x`, else why not: bf16 CUDA maps in
+    training mode, widths in whole 64-channel tiles, bf16 weight copies (`refresh_weights`), partials within the scratch."""
+    r = B.reason(mod, x, _conv.ENABLED, True, BF)
+    if r:
+        return r
+    g = B.geometry(mod, x)
+    if g.p % 64 or g.Cin % 64:
+        return "widths are not multiples of 64"
+    if g.s == 2 and (g.Hi % 2 or g.Wi % 2):
+        return "a stride-2 block needs an even map"
+    if not all(hasattr(cv, "_w16") for cv in B.convs(mod)):
+        return "a convolution has no bf16 weight copy"
+    if B.part_floats(g) > B.PART_FLOATS:
+        return "statistics partials exceed the scratch"
+    return None
+
+
 def usable(mod, x):
-    if not (_conv.ENABLED and x.is_cuda and x.dtype == BF and mod.training and hasattr(mod.conv1, "_w16")):
-        return False
-    for bn in (mod.bn1, mod.bn2, mod.bn3):
-        if bn.weight is None or not bn.track_running_stats or bn.momentum is None or bn.weight.dtype != torch.float32:
-            return False
-    p, cin = mod.conv1.weight.shape[0], mod.conv1.weight.shape[1]
-    if p % 64 or cin % 64 or mod.conv2.groups != 1 or mod.conv2.dilation != (1, 1) or mod.conv2.kernel_size != (3, 3) \
-            or mod.conv2.padding != (1, 1) or mod.stride not in (1, 2):
-        return False
-    if mod.stride == 2 and (x.shape[2] % 2 or x.shape[3] % 2):
-        return False
-    if mod.downsample is not None:
-        d0, d1 = mod.downsample[0], mod.downsample[1]
-        if d0.kernel_size != (1, 1) or d0.stride != (mod.stride, mod.stride) or d1.weight is None or d1.momentum is None \
-                or not hasattr(d0, "_w16"):
-            return False
-    return True
+    return bf16_reason(mod, x) is None
 
 
 def _mm(h, st, M, N, K, a, lda, b, ldb, out, ldc, ws, ex=None, beta=0.0):
@@ -120,16 +120,10 @@ def _mm(h, st, M, N, K, a, lda, b, ldb, out, ldc, ws, ex=None, beta=0.0):
 class _Bottleneck16Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd):
-        h, raw_stream = _conv._fns()
         dev = x.device
-        st = raw_stream(dev.index)
-        ws, part, bnpart = _conv._buffers(dev)
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
-        N, Cin, Hi, Wi = x.shape
-        p, C4, s = w1.shape[0], w3.shape[0], mod.stride
-        Ho, Wo = (Hi - 1) // s + 1, (Wi - 1) // s + 1
-        Rin, Rout = N * Hi * Wi, N * Ho * Wo
+        h, st, ws, part, bnpart = _conv._launch(dev)
+        x = B.channels_last(x)
+        N, Cin, Hi, Wi, p, C4, s, Ho, Wo, Rin, Rout = g = B.geometry(mod, x)
         x2 = _conv._as2d(x)
         bn1, bn2, bn3 = mod.bn1, mod.bn2, mod.bn3
         bf = dict(device=dev, dtype=BF)
@@ -162,26 +156,19 @@ class _Bottleneck16Fn(torch.autograd.Function):
         else:
             idn = x2
         out, st3 = _conv._apply_fin(h, st, Rout, C4, z3, idn, part, bn3, sh3, g3, b3, True)
-        ctx.mod = mod
-        ctx.geom = (N, Cin, Hi, Wi, p, C4, s, Ho, Wo)
-        ctx.has_down = wd is not None
+        ctx.mod, ctx.geom = mod, g
         ctx.save_for_backward(x, w1, g1, w2, g2, w3, g3, wd, gd, z1, a1, z2, a2, z3, out, zd, st1, st2, st3, std)
         return _conv._as4d(out, N, Ho, Wo)
 
     @staticmethod
     def backward(ctx, dout):
-        h, raw_stream = _conv._fns()
         (x, w1, g1, w2, g2, w3, g3, wd, gd, z1, a1, z2, a2, z3, out, zd, st1, st2, st3, std) = ctx.saved_tensors
         mod = ctx.mod
-        N, Cin, Hi, Wi, p, C4, s, Ho, Wo = ctx.geom
+        N, Cin, Hi, Wi, p, C4, s, Ho, Wo, Rin, Rout = ctx.geom
         dev = x.device
-        st = raw_stream(dev.index)
-        ws, part, bnpart = _conv._buffers(dev)
-        Rin, Rout = N * Hi * Wi, N * Ho * Wo
+        h, st, ws, part, bnpart = _conv._launch(dev)
         need = ctx.needs_input_grad      # (mod, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd)
-        if dout.dtype != BF or not dout.is_contiguous(memory_format=torch.channels_last):
-            dout = dout.to(BF).contiguous(memory_format=torch.channels_last)
-        dout2, x2 = _conv._as2d(dout), _conv._as2d(x)
+        dout2, x2 = _conv._as2d(B.channels_last(dout.to(BF))), _conv._as2d(x)
         bf = dict(device=dev, dtype=BF)
         _chk, _red, _dx = _conv._chk, _conv._bwd_reduce, _conv._bwd_dx_fin
         main = torch.cuda.current_stream(dev)
@@ -241,7 +228,7 @@ class _Bottleneck16Fn(torch.autograd.Function):
         # ---- identity branch and d x -----------------------------------------------------------------------------------------
         need_dx = need[1]
         dwd = dgbd = dx = None
-        if ctx.has_down:
+        if wd is not None:
             _, nch = _red(h, st, Rout, C4, dres, None, zd, std, False, bnpart, False)
             dzd = torch.empty((Rout, C4), **bf)
             dgbd = _dx(h, st, Rout, C4, dres, zd, std, gd, bnpart, (nch + 3) & ~3, nch, dzd)
@@ -262,11 +249,7 @@ class _Bottleneck16Fn(torch.autograd.Function):
         if side:
             side.mark()
         dx4 = _conv._as4d(dx, N, Hi, Wi) if dx is not None else None
-        return (None, dx4, dw1, dgb1[1] if need[3] else None, dgb1[0] if need[4] else None,
-                dw2 if need[5] else None, dgb2[1] if need[6] else None, dgb2[0] if need[7] else None,
-                dw3, dgb3[1] if need[9] else None, dgb3[0] if need[10] else None,
-                dwd, (dgbd[1] if need[12] else None) if dgbd is not None else None,
-                (dgbd[0] if need[13] else None) if dgbd is not None else None)
+        return B.grads(need, dx4, (dw1, dw2, dw3, dwd), (dgb1, dgb2, dgb3, dgbd))
 
 
 class _Block16(C.Structure):      # scnattn_block16 (include/scnattn.h)
@@ -282,22 +265,15 @@ class _Block16(C.Structure):      # scnattn_block16 (include/scnattn.h)
 
 
 class _Plan:
-    """Per (module, input geometry): the filled scnattn_block16 and the sizes of the three buffers the calls need."""
+    """Per (module, input geometry): the geometry, a scnattn_block16 with only its sizes set, the sizes of the buffers."""
 
     def __init__(self, mod, x, h):
-        N, Cin, Hi, Wi = x.shape
-        b = _Block16()
-        b.N, b.Cin, b.Hi, b.Wi, b.p, b.stride = N, Cin, Hi, Wi, mod.conv1.weight.shape[0], mod.stride
-        b.has_down = 1 if mod.downsample is not None else 0
+        self.g = g = B.geometry(mod, x)
+        self.b = b = _Block16(g.N, g.Cin, g.Hi, g.Wi, g.p, g.s, 1 if mod.downsample is not None else 0)
         sz = [C.c_long(0) for _ in range(5)]
         _conv._chk(h.scnattn_block16_sizes(C.byref(b), *[C.byref(v) for v in sz]), "scnattn_block16_sizes")
-        self.b = b
         self.save_elems, self.out_off, self.stats_floats, self.tmp_elems, self.dgb_floats = (v.value for v in sz)
-        self.key = (N, Cin, Hi, Wi, x.device)
-        self.bns = (mod.bn1, mod.bn2, mod.bn3) + ((mod.downsample[1],) if mod.downsample is not None else ())
-        self.convs = (mod.conv1, mod.conv2, mod.conv3) + ((mod.downsample[0],) if mod.downsample is not None else ())
-        self.C4 = 4 * b.p
-        self.Ho, self.Wo = (Hi - 1) // mod.stride + 1, (Wi - 1) // mod.stride + 1
+        self.key = (g.N, g.Cin, g.Hi, g.Wi, x.device)
 
 
 def _plan(mod, x, h):
@@ -308,113 +284,90 @@ def _plan(mod, x, h):
     return pl
 
 
+def _fill(pl, mod, x, save, stats, scratch):
+    """A fresh scnattn_block16 for one forward call: a copy of the plan's sized struct with every pointer and scalar of
+    the block's modules, the scratch and the call's buffers filled in."""
+    b = _Block16.from_buffer_copy(pl.b)
+    for i, bn in enumerate(B.bns(mod)):
+        b.gamma[i], b.beta[i] = bn.weight.data_ptr(), bn.bias.data_ptr()
+        b.run_mean[i], b.run_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        b.shift[i] = _conv._shift(bn).data_ptr()
+        b.eps[i], b.momentum[i] = bn.eps, bn.momentum
+    for i, cv in enumerate(B.convs(mod)):
+        b.w[i], b.wt[i] = cv._w16.data_ptr(), cv._w16t.data_ptr()
+    ws, part, bnpart = scratch
+    b.ws, b.ws_floats, b.part, b.bnpart, b.bnpart_floats = ws.data_ptr(), ws.numel(), part.data_ptr(), bnpart.data_ptr(), bnpart.numel()
+    b.x, b.save, b.stats = x.data_ptr(), save.data_ptr(), stats.data_ptr()
+    return b
+
+
 class _Bottleneck16DriverFn(torch.autograd.Function):
     """The same block as _Bottleneck16Fn with ONE library call per direction (csrc/block16.cpp): identical kernels on
     identical operands in the identical order (bit-identical by test); what changes is the host's cost, ~105 -> ~35 us
-    per block forward and ~300 -> ~70 us backward, which is what bounds the bf16 step."""
+    per block forward and ~300 -> ~70 us backward, which is what bounds the bf16 step.  Each call has its own struct: the
+    forward's from `_fill`, the backward's a copy of it (the backward runs on the forward's stream) plus its own fields."""
 
     @staticmethod
     def forward(ctx, mod, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd):
-        h, raw_stream = _conv._fns()
         dev = x.device
-        st = raw_stream(dev.index)
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            x = x.contiguous(memory_format=torch.channels_last)
+        h, st, *scratch = _conv._launch(dev)
+        x = B.channels_last(x)
         pl = _plan(mod, x, h)
-        b = pl.b
-        ws, part, bnpart = _conv._buffers(dev)
         save = torch.empty(pl.save_elems, device=dev, dtype=BF)
         stats = torch.empty(pl.stats_floats, device=dev, dtype=torch.float32)
-        for i, bn in enumerate(pl.bns):
-            b.gamma[i], b.beta[i] = bn.weight.data_ptr(), bn.bias.data_ptr()
-            b.run_mean[i], b.run_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-            b.shift[i] = _conv._shift(bn).data_ptr()
-            b.eps[i], b.momentum[i] = bn.eps, bn.momentum
-        for i, cv in enumerate(pl.convs):
-            b.w[i], b.wt[i] = cv._w16.data_ptr(), cv._w16t.data_ptr()
-        b.ws, b.ws_floats, b.part, b.bnpart, b.bnpart_floats = ws.data_ptr(), ws.numel(), part.data_ptr(), bnpart.data_ptr(), bnpart.numel()
-        b.x, b.save, b.stats = x.data_ptr(), save.data_ptr(), stats.data_ptr()
+        b = _fill(pl, mod, x, save, stats, scratch)
         _conv._chk(h.scnattn_block16_fwd(st, C.byref(b)), "scnattn_block16_fwd")
-        C4 = pl.C4
-        for i, bn in enumerate(pl.bns):       # next step's conditioning shift: this step's batch mean
-            bn._scn_shift = stats[2 * i * C4:2 * i * C4 + bn.num_features]
-        Rout = x.shape[0] * pl.Ho * pl.Wo
+        N, Cin, Hi, Wi, p, C4, s, Ho, Wo, Rin, Rout = pl.g
+        for i, bn in enumerate(B.bns(mod)):       # next step's conditioning shift: this step's batch mean
+            _conv._set_shift(bn, stats[2 * i * C4:2 * i * C4 + bn.num_features])
         out = save[pl.out_off:pl.out_off + Rout * C4].view(Rout, C4)
-        ctx.mod, ctx.pl = mod, pl
+        ctx.pl, ctx.b = pl, b
         ctx.save_for_backward(x, save, stats, w1, w2, w3, wd)
-        return _conv._as4d(out, x.shape[0], pl.Ho, pl.Wo)
+        return _conv._as4d(out, N, Ho, Wo)
 
     @staticmethod
     def backward(ctx, dout):
-        h, raw_stream = _conv._fns()
+        h = _lib.lib()
         x, save, stats, w1, w2, w3, wd = ctx.saved_tensors
-        mod, pl = ctx.mod, ctx.pl
-        b = pl.b
+        pl = ctx.pl
+        N, Cin, Hi, Wi, p, C4, s, Ho, Wo, Rin, Rout = pl.g
+        b = _Block16.from_buffer_copy(ctx.b)
         dev = x.device
-        st = raw_stream(dev.index)
+        st = torch._C._cuda_getCurrentRawStream(dev.index)
         need = ctx.needs_input_grad      # (mod, x, w1, g1, b1, w2, g2, b2, w3, g3, b3, wd, gd, bd)
-        if dout.dtype != BF or not dout.is_contiguous(memory_format=torch.channels_last):
-            dout = dout.to(BF).contiguous(memory_format=torch.channels_last)
-        ws, part, bnpart = _conv._buffers(dev)
+        dout = B.channels_last(dout.to(BF))
         tmp = torch.empty(pl.tmp_elems, device=dev, dtype=BF)
         dgb = torch.empty(pl.dgb_floats, device=dev, dtype=torch.float32)
-        main = torch.cuda.current_stream(dev)
         side = _conv._side(dev) if _conv.side_ok(w1, w2, w3, wd) else None
         dws = [(_conv._grad_out(w) if (w is not None and need[k]) else None) for w, k in ((w1, 2), (w2, 5), (w3, 8), (wd, 11))]
-        for i, bn in enumerate(pl.bns):       # the forward call of ANOTHER input may have re-pointed the plan since
-            b.gamma[i] = bn.weight.data_ptr()
-        for i, cv in enumerate(pl.convs):
-            b.w[i], b.wt[i] = cv._w16.data_ptr(), cv._w16t.data_ptr()
-        b.ws, b.ws_floats, b.part, b.bnpart, b.bnpart_floats = ws.data_ptr(), ws.numel(), part.data_ptr(), bnpart.data_ptr(), bnpart.numel()
-        b.x, b.save, b.stats = x.data_ptr(), save.data_ptr(), stats.data_ptr()
         b.dout, b.tmp, b.dgb = dout.data_ptr(), tmp.data_ptr(), dgb.data_ptr()
-        for i in range(4):
-            b.dw[i] = dws[i].data_ptr() if dws[i] is not None else None
+        b.dw[:] = [d.data_ptr() if d is not None else None for d in dws]
         b.need_dx = 1 if need[1] else 0
         if side is not None:
             b.side_stream, b.side_ws, b.side_ws_floats = side.stream.cuda_stream, side.ws.data_ptr(), side.ws.numel()
             for t in (x, save, tmp) + tuple(d for d in dws if d is not None):
                 t.record_stream(side.stream)
-        else:
-            b.side_stream, b.side_ws, b.side_ws_floats = None, None, 0
         dxp, dxdp = C.c_void_p(0), C.c_void_p(0)
         _conv._chk(h.scnattn_block16_bwd(st, C.byref(b), C.byref(dxp), C.byref(dxdp)), "scnattn_block16_bwd")
         if side is not None:
             side.mark()
-        N, Cin, Hi, Wi = x.shape
         dx4 = None
         if need[1]:
             off = (dxp.value - tmp.data_ptr()) // 2
-            dx = tmp[off:off + N * Hi * Wi * Cin].view(N * Hi * Wi, Cin)
+            dx = tmp[off:off + Rin * Cin].view(Rin, Cin)
             if dxdp.value:
                 offd = (dxdp.value - tmp.data_ptr()) // 2
-                s = mod.stride
-                dxd = tmp[offd:offd + N * pl.Ho * pl.Wo * Cin]
-                dx.view(N, Hi, Wi, Cin)[:, ::s, ::s].add_(dxd.view(N, pl.Ho, pl.Wo, Cin))
+                dxd = tmp[offd:offd + Rout * Cin]
+                dx.view(N, Hi, Wi, Cin)[:, ::s, ::s].add_(dxd.view(N, Ho, Wo, Cin))
             dx4 = _conv._as4d(dx, N, Hi, Wi)
-        C4 = pl.C4
-
-        def gb(i, which, k, n):          # which: 0 d beta, 1 d gamma
-            return dgb[(2 * i + which) * C4:(2 * i + which) * C4 + n] if need[k] else None
-        p = b.p
-        has_down = wd is not None
-        return (None, dx4, dws[0], gb(0, 1, 3, p), gb(0, 0, 4, p), dws[1], gb(1, 1, 6, p), gb(1, 0, 7, p),
-                dws[2], gb(2, 1, 9, C4), gb(2, 0, 10, C4),
-                dws[3], gb(3, 1, 12, C4) if has_down else None, gb(3, 0, 13, C4) if has_down else None)
+        d = dgb[:8 * C4].view(4, 2, C4)          # [BatchNorm][d beta, d gamma][channel]
+        return B.grads(need, dx4, dws, (d[0, :, :p], d[1, :, :p], d[2], d[3] if wd is not None else None))
 
 
 BLOCK16 = os.environ.get("SCNATTN_BLOCK16", "c")     # "c": one library call per block and direction; "py": the per-launch path
 
 
-
 def bottleneck(mod, x):
-    for bn in (mod.bn1, mod.bn2, mod.bn3) + ((mod.downsample[1],) if mod.downsample is not None else ()):
-        if not bn.counter_managed and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
-    if mod.downsample is not None:
-        wd, gd, bd = mod.downsample[0].weight, mod.downsample[1].weight, mod.downsample[1].bias
-    else:
-        wd = gd = bd = None
+    B.bump_counters(B.bns(mod))
     fn = _Bottleneck16DriverFn if BLOCK16 == "c" else _Bottleneck16Fn
-    return fn.apply(mod, x, mod.conv1.weight, mod.bn1.weight, mod.bn1.bias, mod.conv2.weight, mod.bn2.weight,
-                    mod.bn2.bias, mod.conv3.weight, mod.bn3.weight, mod.bn3.bias, wd, gd, bd)
+    return fn.apply(mod, x, *B.params(mod))

@@ -23,58 +23,18 @@ import ctypes as C
 
 import torch
 
+from . import block as B
 from . import conv as _conv
 from ._lib import BnEval, ConvExtra
 
 
-def _bns(mod):
-    return (mod.bn1, mod.bn2, mod.bn3) + ((mod.downsample[1],) if mod.downsample is not None else ())
-
-
 def eval_reason(mod, x):
     """None when the fused eval block applies to `mod` (a scnattn.resnet.Bottleneck) on input `x`, else why not."""
-    if not _conv.ENABLED:
-        return "fused kernels disabled (scnattn.conv.ENABLED is False)"
-    if mod.training:
-        return "module is in training mode"
-    if torch.is_autocast_enabled():
-        return "autocast is enabled"
-    if not x.is_cuda:
-        return "input is not a GPU tensor"
-    if x.dtype != torch.float32 or x.dim() != 4:
-        return "input is not an fp32 (N, C, H, W) map"
-    for bn in _bns(mod):
-        if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
-            return "a BatchNorm has no running statistics"
-        if bn.weight is None or bn.bias is None:
-            return "a BatchNorm is not affine"
-        if any(t.dtype != torch.float32 or t.device != x.device for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
-            return "a BatchNorm parameter / statistic is not fp32 on the input's device"
-    c1, c2, c3 = mod.conv1, mod.conv2, mod.conv3
-    for cv in (c1, c2, c3):
-        if cv.bias is not None or cv.groups != 1 or cv.dilation != (1, 1) or cv.weight.dtype != torch.float32 \
-                or cv.weight.device != x.device:
-            return "a convolution has a bias, groups, dilation or a non-fp32 weight"
-    if c1.kernel_size != (1, 1) or c1.stride != (1, 1) or c1.padding != (0, 0) \
-            or c3.kernel_size != (1, 1) or c3.stride != (1, 1) or c3.padding != (0, 0):
-        return "conv1 / conv3 are not 1x1 at stride 1"
-    s = mod.stride
-    if c2.kernel_size != (3, 3) or c2.padding != (1, 1) or s not in (1, 2) or c2.stride != (s, s):
-        return "conv2 is not 3x3 / padding 1 at stride 1 or 2"
-    p, cin, c4 = c1.weight.shape[0], c1.weight.shape[1], c3.weight.shape[0]
-    if p % 16 or cin % 16 or c4 % 16:
-        return "widths (%d, %d, %d) are not multiples of 16" % (cin, p, c4)
-    if x.shape[1] != cin:
-        return "input has %d channels, conv1 takes %d" % (x.shape[1], cin)
-    if mod.downsample is not None:
-        d0 = mod.downsample[0]
-        if len(mod.downsample) != 2 or not isinstance(d0, torch.nn.Conv2d) or d0.kernel_size != (1, 1) \
-                or d0.stride != (s, s) or d0.padding != (0, 0) or d0.bias is not None or d0.groups != 1 \
-                or d0.weight.dtype != torch.float32 or d0.weight.shape[0] != c4:
-            return "downsample is not a 1x1 convolution at the block's stride + BatchNorm"
-    elif s != 1 or cin != c4:
-        return "no downsample, but the identity does not match the output"
-    return None
+    r = B.reason(mod, x, _conv.ENABLED, False, torch.float32)
+    if r is None and any(t.dtype != torch.float32 or t.device != x.device for t in [cv.weight for cv in B.convs(mod)] +
+                         [t for bn in B.bns(mod) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)]):
+        return "a parameter / statistic is not fp32 on the input's device"
+    return r
 
 
 def _vec(t):
@@ -98,17 +58,11 @@ def _bn_eval(bn, relu, res=None, ldres=0):
 
 def _forward(mod, x):
     """The fused eval block on the caller's stream; returns the (N, C4, Ho, Wo) channels-last output."""
-    h, raw_stream = _conv._fns()
     dev = x.device
-    st = raw_stream(dev.index)
-    ws = _conv._buffers(dev)[0]
-    if not x.is_contiguous(memory_format=torch.channels_last):
-        x = x.contiguous(memory_format=torch.channels_last)
-    N, Cin, Hi, Wi = x.shape
+    h, st, ws = _conv._launch(dev)[:3]
+    x = B.channels_last(x)
+    N, Cin, Hi, Wi, p, C4, s, Ho, Wo, Rin, Rout = B.geometry(mod, x)
     w1, w3 = mod.conv1.weight, mod.conv3.weight
-    p, C4, s = w1.shape[0], w3.shape[0], mod.stride
-    Ho, Wo = (Hi - 1) // s + 1, (Wi - 1) // s + 1
-    Rin, Rout = N * Hi * Wi, N * Ho * Wo
     x2 = _conv._as2d(x)
     f32 = dict(device=dev, dtype=torch.float32)
     with torch.no_grad():
@@ -143,14 +97,6 @@ def _forward(mod, x):
     return _conv._as4d(out, N, Ho, Wo)
 
 
-def _params(mod):
-    d = mod.downsample
-    return (mod.conv1.weight, mod.bn1.weight, mod.bn1.bias, mod.conv2.weight, mod.bn2.weight, mod.bn2.bias,
-            mod.conv3.weight, mod.bn3.weight, mod.bn3.bias,
-            d[0].weight if d is not None else None, d[1].weight if d is not None else None,
-            d[1].bias if d is not None else None)
-
-
 class _EvalBottleneckFn(torch.autograd.Function):
     """Fused eval forward; backward recomputes the block through the module-path ops and returns their gradients."""
 
@@ -174,7 +120,7 @@ class _EvalBottleneckFn(torch.autograd.Function):
 
 def bottleneck_eval(mod, x):
     """Eval-mode forward of `mod` on the fused kernels (caller checked `eval_reason(mod, x) is None`)."""
-    params = _params(mod)
+    params = B.params(mod)
     if torch.is_grad_enabled() and (x.requires_grad or any(t is not None and t.requires_grad for t in params)):
         return _EvalBottleneckFn.apply(mod, x, *params)
     return _forward(mod, x)

@@ -6,15 +6,15 @@ the module tree -- and therefore every state_dict key -- equals
 torchvision is not installed in this image (nor on the GPU box), and the reference's
 ``pretrained=True`` needs a download, so weights are random-init by torchvision's own recipe
 (kaiming-normal fan-out convs, BN gamma=1 beta=0) unless a state_dict is loaded.  On MI355X every
-Bottleneck of fp32 maps runs on the hand-written kernels: training mode through scnattn/conv.py (one autograd
-node per block, BatchNorm statistics fused into the convolutions), eval mode through scnattn/conv_eval.py (the
-running-statistics BatchNorm folded into each convolution's epilogue), bf16 maps through scnattn/conv16.py.
-What none of them covers (CPU tensors, fp32 under autocast, widths that are not multiples of 16) takes the
-module path: nn.Conv2d (MIOpen) + the fused BatchNorm kernels."""
+Bottleneck runs on the hand-written kernels of one of the three paths of scnattn/block.py (fp32 training, fp32
+eval, bf16 training); what none of them covers (CPU tensors, fp32 under autocast, widths that are not multiples
+of 16) takes the module path: nn.Conv2d (MIOpen) + the fused BatchNorm kernels."""
 import os
 
 import torch
 from torch import nn
+
+from . import block as B
 
 
 def configure_miopen():
@@ -43,8 +43,8 @@ class FusedBatchNorm2d(nn.BatchNorm2d):
                 y = y + residual
             return torch.relu(y) if relu else y
         from . import functional as SF
-        if self.training and not self.counter_managed and self.num_batches_tracked is not None:
-            self.num_batches_tracked.add_(1)
+        if self.training:
+            B.bump_counters((self,))
         return SF.bn_act(x, residual, self.weight, self.bias, self.running_mean, self.running_var, self.training,
                          self.momentum, self.eps, relu)
 
@@ -65,19 +65,15 @@ class Bottleneck(nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        # fp32 training-mode maps on the GPU: the whole block as ONE autograd node on the hand-written 1x1-convolution
-        # kernels with the BatchNorm statistics / normalisation fused into them (scnattn/conv.py)
-        from . import conv as _conv
+        # the hand-written paths of scnattn/block.py in this order: fp32 training (scnattn/conv.py: one autograd node, the
+        # BatchNorm fused into the convolutions), fp32 eval (scnattn/conv_eval.py), bf16 training (scnattn/conv16.py)
+        from . import conv as _conv, conv_eval as _ce, conv16 as _c16
         if _conv.usable(self, x):
             return _conv.bottleneck(self, x)
-        # fp32 eval-mode maps on the GPU: three (four) launches with the BatchNorm folded into the epilogues (scnattn/conv_eval.py)
-        from . import conv_eval as _ce
         if _ce.eval_reason(self, x) is None:
             return _ce.bottleneck_eval(self, x)
-        if x.dtype == torch.bfloat16:        # the mixed-precision trunk (bf16 maps from scnattn/stem.py under bf16 autocast)
-            from . import conv16 as _c16
-            if _c16.usable(self, x):
-                return _c16.bottleneck(self, x)
+        if _c16.usable(self, x):
+            return _c16.bottleneck(self, x)
         return self.module_forward(x)
 
     def module_forward(self, x):

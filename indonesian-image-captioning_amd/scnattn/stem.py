@@ -10,33 +10,37 @@ The image batch is read in whatever memory format it arrives in (strides are pas
 import torch
 
 from . import _lib
+from . import block as B
 from . import conv as _conv
 
 
-def usable(trunk, x):
+def stem_reason(trunk, x):
+    """None when the fused stem applies to the first four children of `trunk` on images `x`, else why not."""
     if not (_conv.ENABLED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
-        return False
+        return "not an fp32 (N, C, H, W) GPU batch, or fused kernels disabled"
     if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") != torch.bfloat16:
-        return False
+        return "autocast to a dtype other than bf16"
     if len(trunk) < 4:
-        return False
+        return "fewer than four children"
     c1, bn, pool = trunk[0], trunk[1], trunk[3]
     if not (isinstance(c1, torch.nn.Conv2d) and isinstance(bn, torch.nn.BatchNorm2d) and isinstance(pool, torch.nn.MaxPool2d)):
-        return False
+        return "children are not conv, BatchNorm, _, max-pool"
     if c1.weight.shape != (64, 3, 7, 7) or c1.stride != (2, 2) or c1.padding != (3, 3) or c1.dilation != (1, 1) \
             or c1.bias is not None or c1.groups != 1 or c1.weight.dtype != torch.float32 or x.shape[1] != 3:
-        return False
+        return "conv1 is not the 7x7 / 2 convolution of 3 fp32 channels to 64"
     if bn.weight is None or bn.running_mean is None or (bn.training and bn.momentum is None):
-        return False
-    ks = pool.kernel_size if isinstance(pool.kernel_size, tuple) else (pool.kernel_size,) * 2
-    sd = pool.stride if isinstance(pool.stride, tuple) else (pool.stride,) * 2
-    pd = pool.padding if isinstance(pool.padding, tuple) else (pool.padding,) * 2
+        return "bn1 is not affine with running statistics"
+    ks, sd, pd = (v if isinstance(v, tuple) else (v, v) for v in (pool.kernel_size, pool.stride, pool.padding))
     if ks != (3, 3) or sd != (2, 2) or pd != (1, 1) or pool.dilation not in (1, (1, 1)) or pool.ceil_mode:
-        return False
+        return "the pool is not the 3x3 / 2 max-pool"
     # forward-only kernels: nothing here may need a gradient
     if torch.is_grad_enabled() and (x.requires_grad or c1.weight.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
-        return False
-    return True
+        return "the stem needs a gradient"
+    return None
+
+
+def usable(trunk, x):
+    return stem_reason(trunk, x) is None
 
 
 def stem(trunk, x, bf16=False):
@@ -54,8 +58,7 @@ def stem(trunk, x, bf16=False):
     z = torch.empty((N * Hz * Wz, 64), device=dev, dtype=torch.float32)
     ss = torch.empty((64, 2), device=dev, dtype=torch.float32)
     if bn.training:
-        if not getattr(bn, "counter_managed", False) and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked.add_(1)
+        B.bump_counters((bn,))
         nt = h.scnattn_stem_tiles(N, H, W)
         ldp = (nt + 3) & ~3
         part = torch.empty((2, 64, ldp), device=dev, dtype=torch.float32)     # channel-major partials, one entry per workgroup
@@ -67,7 +70,7 @@ def stem(trunk, x, bf16=False):
                                          bn.momentum, stats[0].data_ptr(), stats[1].data_ptr(),
                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(), bn.weight.data_ptr(),
                                          bn.bias.data_ptr(), ss.data_ptr()), "scnattn_bn_finalize")
-        bn._scn_shift = stats[0]
+        _conv._set_shift(bn, stats[0])
     else:
         _conv._chk(h.scnattn_stem_conv7(st, N, H, W, x.data_ptr(), *x.stride(), w.data_ptr(), *w.stride(), z.data_ptr(),
                                         None, None), "scnattn_stem_conv7")
@@ -81,12 +84,14 @@ def stem(trunk, x, bf16=False):
 
 
 def run_trunk(trunk, x):
-    """`trunk(x)` with the four stem children on the fused kernels when they qualify."""
-    if usable(trunk, x):
-        bf16 = torch.is_autocast_enabled()          # bf16 autocast = the mixed-precision trunk (scnattn/conv16.py)
-        if bf16:
-            from . import conv16 as _c16
-            _c16.refresh_weights(trunk)              # fp32 master weights -> bf16 operand copies, one launch
+    """`trunk(x)` with the four stem children on the fused kernels when they qualify.  Under bf16 autocast the blocks'
+    bf16 weight copies (scnattn/conv16.py) are refreshed first: when the stem qualifies, or the trunk already has copies."""
+    fused = usable(trunk, x)
+    bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
+    if bf16 and (fused or getattr(trunk, "_scn_w16", None) is not None):
+        from . import conv16 as _c16
+        _c16.refresh_weights(trunk)
+    if fused:
         y = stem(trunk, x, bf16)
         for child in list(trunk.children())[4:]:
             y = child(y)
