@@ -632,6 +632,7 @@ int mean_pixels(hipStream_t st, int rows, int P, int E, const float* enc, float*
     SCN_ARG(enc && out && P > 0 && E > 0, "mean_pixels: bad argument");
     dim3 grid(cdiv(E, 256), rows), block(512);
     const size_t lds = (8 * 256 + 16 + P) * sizeof(float);
+    SCN_ARG(lds <= 64 * 1024, "mean_pixels: num_pixels too large for the LDS staging");
     Slabs none{nullptr, 0, 0, 0};
     if (E % 4 == 0 && aligned16(enc))
         hipLaunchKernelGGL((attn_context_kernel<true, 1, 8, false>), grid, block, lds, st, rows, P, E, enc, (const float*)nullptr,

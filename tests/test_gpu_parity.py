@@ -760,6 +760,8 @@ def test_argument_errors_surface_as_runtime_errors(dev):
     x = torch.zeros(8, device=dev)
     with pytest.raises(RuntimeError, match="attention_dim too large"):
         call("scnattn_attn_scores", stream_of(x), 1, 4, 1 << 16, ptr(x), ptr(x), 1, 0, 1 << 16, None, ptr(x), None, ptr(x), None)
+    with pytest.raises(RuntimeError, match="mean_pixels: num_pixels too large"):   # refused on the host, never launched
+        call("scnattn_mean_pixels", stream_of(x), 1, 1 << 14, 4, ptr(x), ptr(x))
     with pytest.raises(RuntimeError, match="K must be >= 1"):
         call("scnattn_sgemm", stream_of(x), 0, 0, 2, 2, 0, 1.0, ptr(x), 2, ptr(x), 2, 0.0, ptr(x), 2, None, None, 1, 0, 0, 0)
     from models.decoders.attention_scn import AttentionSCN
@@ -992,7 +994,9 @@ def test_full_length_batch_never_reads_unwritten_workspace(dev, kind):
     _ok(out2[0], runs[0][0], 1e-6, "predictions under an explicit permutation")
 
 
-@pytest.mark.parametrize("B,lens,hin", [(6, [8, 8, 6, 5, 3, 2], 8), (4, [5, 5, 5, 5], 8), (3, [7, 4, 4], 7)])
+@pytest.mark.parametrize("B,lens,hin", [(6, [8, 8, 6, 5, 3, 2], 8), (4, [5, 5, 5, 5], 8), (3, [7, 4, 4], 7),
+                                        (3, [6, 6, 2], 14),     # Q = P: the pool is the identity, one tap everywhere
+                                        (5, [9, 4, 4, 3, 1], 3)])   # Q = 9: long qtap rows (up to 36 pooled pixels per source)
 def test_pooled_attention_path_equals_dense_path(dev, B, lens, hin):
     """Attention on the trunk's un-pooled map (scnattn_pool: att1 = pool(x.We^T)+be, context / d alpha over the Q
     source pixels, d x produced directly) against the dense path fed with the materialised AdaptiveAvgPool2d(14)
