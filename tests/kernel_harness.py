@@ -1,0 +1,111 @@
+"""What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_gemm_kernels.py): guarded
+buffers, the C-ABI call, the per-element sum judge and the parity-report fixture.  How a case is judged: DESIGN.md 3.
+A plain module (tests/ is on sys.path, like decoder_kernel_refs); a test module imports `_write_report` by name to get
+its own table in the run's parity report."""
+import ctypes as C
+
+import pytest
+import torch
+
+U = 2.0 ** -24
+SENT = 0x7FC5A5A5          # a quiet-NaN bit pattern: a kernel that reads its own output margin poisons its result too
+NAN = float("nan")
+
+
+# ---- report -------------------------------------------------------------------------------------------------------------
+_STATS = {}     # (kernel, result) -> [worst ratio, kind, worst yardstick, cases]
+
+
+def _note(kernel, name, ratio, kind, yard=0.0):
+    s = _STATS.setdefault((kernel, name), [0.0, kind, 0.0, 0])
+    s[0], s[2], s[3] = max(s[0], ratio), max(s[2], yard), s[3] + 1
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_report(request):
+    """Module-scoped: a test module imports it by name; its REPORT_TITLE heads the table (the decode-step title otherwise)."""
+    _STATS.clear()
+    yield
+    if not _STATS:
+        return
+    from test_gpu_parity import _report
+    w = max([18] + [len(k[0]) for k in _STATS])
+    fmt = "%%-%ds %%-10s %%-9s %%-6s %%s" % w
+    lines = [fmt % ("kernel", "result", "err/bound", "cases", "bound")]
+    for (kern, name), (ratio, kind, yard, n) in sorted(_STATS.items()):
+        how = "(n+8)*2^-24*sum|terms|" if kind == "sum" else \
+            "min(4 x CPU-fp32 worst element error [worst seen %.3e], %s x row max)" % (yard, kind)
+        lines.append(fmt.replace("%-9s %-6s", "%-9.3f %-6d") % (kern, name, ratio, n, how))
+    _report(lines, getattr(request.module, "REPORT_TITLE",
+                           "decode-step primitives vs fp64: worst |got - ref| / bound over all cases"))
+    _STATS.clear()
+
+
+# ---- guarded buffers ----------------------------------------------------------------------------------------------------
+class GBuf:
+    """A strided window `shape` / `strides` (elements) inside a flat allocation: 16 floats (+ `mis`) in front, `tail` behind.
+    Inputs: NaN everywhere outside the window.  Outputs (out=True): the sentinel everywhere (window included unless `vals`
+    is given: accumulators), checked by read().  mis = 1 offsets the base by one float (not 16-byte aligned)."""
+
+    def __init__(self, dev, shape, strides=None, vals=None, out=False, mis=0, tail=64):
+        shape = tuple(int(n) for n in shape)
+        if strides is None:                                   # dense
+            strides, acc = [], 1
+            for n in reversed(shape):
+                strides.insert(0, acc)
+                acc *= n
+        self.base = 16 + mis
+        span = 1 + sum((n - 1) * int(s) for n, s in zip(shape, strides))
+        total = self.base + span + int(tail)
+        if out:
+            host = torch.full((total,), SENT, dtype=torch.int32).view(torch.float32).clone()
+        else:
+            host = torch.full((total,), NAN, dtype=torch.float32)
+        pos = torch.zeros((), dtype=torch.long) + self.base
+        for n, s in zip(shape, strides):
+            pos = pos.unsqueeze(-1) + torch.arange(n) * int(s)
+        assert pos.numel() == pos.unique().numel(), "overlapping window"
+        self.pos, self.out = pos, out
+        if vals is not None:
+            host[pos] = vals.to(torch.float32).expand(shape)
+        self.flat = host.to(dev)
+        assert self.flat.data_ptr() % 64 == 0
+        self.ptr = C.c_void_p(self.flat.data_ptr() + 4 * self.base)
+
+    def read(self, what):
+        host = self.flat.cpu()
+        guard = torch.ones(host.numel(), dtype=torch.bool)
+        guard[self.pos.reshape(-1)] = False
+        bad = (host.view(torch.int32)[guard] != SENT).nonzero().reshape(-1)
+        assert bad.numel() == 0, "%s: %d guard words overwritten (first at window offset %d)" % (
+            what, bad.numel(), int(guard.nonzero().reshape(-1)[bad[0]]) - self.base)
+        return host[self.pos]
+
+
+def _call(name, dev, *args):
+    from scnattn._lib import call
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    call(name, st, *args)
+    torch.cuda.synchronize()
+
+
+# ---- judging ------------------------------------------------------------------------------------------------------------
+def _sum_ok(kernel, name, got, ref):
+    """|got - ref| <= (n + 8) * 2^-24 * S per element"""
+    want, bound = ref[name].double(), (ref[name + "_n"] + 8) * U * ref[name + "_abs"].double()
+    got = got.double().reshape(want.shape)
+    err = (got - want).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), (err > 0).double() * 1e30)
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    print("%s %s: worst err/bound %.3f (n = %d)" % (kernel, name, worst, ref[name + "_n"]))
+    assert bool((err <= bound).all()), "%s %s: worst err/bound %.3f at %d, %d NaN" % (
+        kernel, name, worst, int(ratio.reshape(-1).nan_to_num(1e30).argmax()), int(got.isnan().sum()))
+    _note(kernel, name, worst, "sum")
+
+
+def _slab_buf(dev, vals, extra_ld=3, extra_stride=5):
+    """vals [n, rows, W] -> window with ld = W + extra_ld, slab stride = rows * ld + extra_stride, one NaN slab behind"""
+    n, rows, W = vals.shape
+    ld = W + extra_ld
+    stride = rows * ld + extra_stride
+    return GBuf(dev, vals.shape, (stride, ld, 1), vals, tail=stride + 64), stride, ld
