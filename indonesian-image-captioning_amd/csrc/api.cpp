@@ -169,13 +169,21 @@ int scnattn_conv1x1_wgrad(void* stream, int R, int Cin, int Cout, const float* d
                  ws, ws ? ws_floats : 0, ex ? &e : nullptr);
 }
 
+// 3x3 convolution as an implicit GEMM (ConvExtra::c3): `c` channels per tap of the gathered map.  The output map is
+// Ho x Wo = ceil(Hi / stride) x ceil(Wi / stride); mode 4 (d-input, stride 2) gathers from that map, every other mode from
+// the Hi x Wi one.
+static void set_c3(ConvExtra& e, int mode, int c, int N, int Hi, int Wi, int stride) {
+    e.c3 = mode; e.c3c = c;
+    e.Hi = Hi; e.Wi = Wi; e.Ho = (Hi - 1) / stride + 1; e.Wo = (Wi - 1) / stride + 1; e.stride = stride;
+    e.c3_src_rows = mode == 4 ? (long)N * e.Ho * e.Wo : (long)N * Hi * Wi;
+}
+
 int scnattn_conv3x3_fwd(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const float* x,
                         const float* w, float* y, const scnattn_conv_extra* ex, float* ws, long ws_floats) {
     SCN_ARG(N > 0 && Hi > 0 && Wi > 0 && stride >= 1, "conv3x3_fwd: geometry");
     ConvExtra e = to_extra(ex);
-    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    e.c3 = 1; e.c3c = Cin; e.c3_src_rows = (long)N * Hi * Wi; e.Hi = Hi; e.Wi = Wi; e.Ho = Ho; e.Wo = Wo; e.stride = stride;
-    return cgemm(ST(stream), false, true, N * Ho * Wo, Cout, 9 * Cin, 1.f, x, Cin, w, 9L * Cin, 0.f, y, Cout, nullptr,
+    set_c3(e, 1, Cin, N, Hi, Wi, stride);
+    return cgemm(ST(stream), false, true, N * e.Ho * e.Wo, Cout, 9 * Cin, 1.f, x, Cin, w, 9L * Cin, 0.f, y, Cout, nullptr,
                  nullptr, 1, 0, 0, 0, ws, ws ? ws_floats : 0, &e);
 }
 
@@ -216,9 +224,8 @@ int scnattn_conv3x3_fwd_bn_eval(void* stream, int N, int Hi, int Wi, int Cin, in
     SCN_ARG(N > 0 && Hi > 0 && Wi > 0 && (stride == 1 || stride == 2), "conv3x3_fwd_bn_eval: geometry");
     ConvExtra e;
     SCN_TRY(bn_eval_extra("conv3x3_fwd_bn_eval", Cin, Cout, bn, ex, &e));
-    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    e.c3 = 1; e.c3c = Cin; e.c3_src_rows = (long)N * Hi * Wi; e.Hi = Hi; e.Wi = Wi; e.Ho = Ho; e.Wo = Wo; e.stride = stride;
-    return cgemm(ST(stream), false, true, N * Ho * Wo, Cout, 9 * Cin, 1.f, x, Cin, w, 9L * Cin, 0.f, y, Cout, nullptr,
+    set_c3(e, 1, Cin, N, Hi, Wi, stride);
+    return cgemm(ST(stream), false, true, N * e.Ho * e.Wo, Cout, 9 * Cin, 1.f, x, Cin, w, 9L * Cin, 0.f, y, Cout, nullptr,
                  nullptr, 1, 0, 0, 0, ws, ws ? ws_floats : 0, &e);
 }
 
@@ -227,7 +234,7 @@ int scnattn_conv3x3_dgrad(void* stream, int N, int Hi, int Wi, int Cin, int Cout
     SCN_ARG(N > 0 && Hi > 0 && Wi > 0, "conv3x3_dgrad: geometry");
     ConvExtra e = to_extra(ex);
     // stride 1: dy and dx maps have the same extent; the gathered (source) map is dy
-    e.c3 = 2; e.c3c = Cout; e.c3_src_rows = (long)N * Hi * Wi; e.Hi = Hi; e.Wi = Wi; e.Ho = Hi; e.Wo = Wi; e.stride = 1;
+    set_c3(e, 2, Cout, N, Hi, Wi, 1);
     return cgemm(ST(stream), false, false, N * Hi * Wi, Cin, 9 * Cout, 1.f, dy, Cout, w, 9L * Cin, 0.f, dx, Cin, nullptr,
                  nullptr, 1, 0, 0, 0, ws, ws ? ws_floats : 0, &e);
 }
@@ -236,10 +243,9 @@ int scnattn_conv3x3_dgrad_strided(void* stream, int N, int Hi, int Wi, int Cin, 
                                   const float* w, float* dx, float* ws, long ws_floats) {
     SCN_ARG(N > 0 && Hi > 0 && Wi > 0 && stride == 2 && Hi % 2 == 0 && Wi % 2 == 0, "conv3x3_dgrad_strided: stride 2, even map");
     ConvExtra e;
-    const int Ho = Hi / 2, Wo = Wi / 2;
     // one launch, four parity classes of d-input pixels (grid.y), each a product over the taps that reach it
-    e.c3 = 4; e.c3c = Cout; e.c3_src_rows = (long)N * Ho * Wo; e.Hi = Hi; e.Wi = Wi; e.Ho = Ho; e.Wo = Wo; e.stride = 2;
-    return cgemm(ST(stream), false, false, N * Ho * Wo, Cin, 9 * Cout, 1.f, dy, Cout, w, 9L * Cin, 0.f, dx, Cin, nullptr,
+    set_c3(e, 4, Cout, N, Hi, Wi, 2);
+    return cgemm(ST(stream), false, false, N * e.Ho * e.Wo, Cin, 9 * Cout, 1.f, dy, Cout, w, 9L * Cin, 0.f, dx, Cin, nullptr,
                  nullptr, 1, 0, 0, 0, ws, ws ? ws_floats : 0, &e);
 }
 
@@ -250,9 +256,8 @@ int scnattn_conv3x3_wgrad(void* stream, int N, int Hi, int Wi, int Cin, int Cout
     if (stride == 1 && k_slices >= 0 && conv3x3_wgrad_halo_ok(N, Hi, Wi, Cin, Cout, dy, x, dw))
         return conv3x3_wgrad_halo(ST(stream), N, Hi, Wi, Cin, Cout, dy, x, dw, ws, ws ? ws_floats : 0, k_slices);
     ConvExtra e;
-    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    e.c3 = 3; e.c3c = Cin; e.c3_src_rows = (long)N * Hi * Wi; e.Hi = Hi; e.Wi = Wi; e.Ho = Ho; e.Wo = Wo; e.stride = stride;
-    return cgemm(ST(stream), true, false, Cout, 9 * Cin, N * Ho * Wo, 1.f, dy, Cout, x, Cin, 0.f, dw, 9L * Cin, nullptr,
+    set_c3(e, 3, Cin, N, Hi, Wi, stride);
+    return cgemm(ST(stream), true, false, Cout, 9 * Cin, N * e.Ho * e.Wo, 1.f, dy, Cout, x, Cin, 0.f, dw, 9L * Cin, nullptr,
                  nullptr, 1, 0, 0, 0, ws, ws ? ws_floats : 0, &e);
 }
 
@@ -307,9 +312,8 @@ int scnattn_conv3x3_fwd16(void* stream, int N, int Hi, int Wi, int Cin, int Cout
                           void* y, const scnattn_conv_extra* ex, float* ws, long ws_floats) {
     SCN_ARG(N > 0 && Hi > 0 && Wi > 0 && stride >= 1, "conv3x3_fwd16: geometry");
     ConvExtra e = to_extra(ex);
-    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    e.c3 = 1; e.c3c = Cin; e.c3_src_rows = (long)N * Hi * Wi; e.Hi = Hi; e.Wi = Wi; e.Ho = Ho; e.Wo = Wo; e.stride = stride;
-    return cgemm16(ST(stream), N * Ho * Wo, Cout, 9 * Cin, x, Cin, w, 9L * Cin, 0.f, y, Cout, 1, ws, ws ? ws_floats : 0, &e, 0);
+    set_c3(e, 1, Cin, N, Hi, Wi, stride);
+    return cgemm16(ST(stream), N * e.Ho * e.Wo, Cout, 9 * Cin, x, Cin, w, 9L * Cin, 0.f, y, Cout, 1, ws, ws ? ws_floats : 0, &e, 0);
 }
 
 // wt: the TRANSPOSED bf16 weight copy [Cin][3][3][Cout] (scnattn_bf16_weights).  stride 1: a forward convolution of dy with
@@ -320,12 +324,11 @@ int scnattn_conv3x3_dgrad16(void* stream, int N, int Hi, int Wi, int Cin, int Co
     ConvExtra e = to_extra(ex);
     SCN_ARG(stride == 1 || e.epi == 0, "conv3x3_dgrad16: the mask epilogue serves the stride-1 form only");
     if (stride == 1) {
-        e.c3 = 1; e.c3c = Cout; e.c3_src_rows = (long)N * Hi * Wi; e.Hi = Hi; e.Wi = Wi; e.Ho = Hi; e.Wo = Wi; e.stride = 1;
+        set_c3(e, 1, Cout, N, Hi, Wi, 1);
         return cgemm16(ST(stream), N * Hi * Wi, Cin, 9 * Cout, dy, Cout, wt, 9L * Cout, 0.f, dx, Cin, 1, ws, ws ? ws_floats : 0, &e, 1);
     }
-    const int Ho = Hi / 2, Wo = Wi / 2;
-    e.c3 = 4; e.c3c = Cout; e.c3_src_rows = (long)N * Ho * Wo; e.Hi = Hi; e.Wi = Wi; e.Ho = Ho; e.Wo = Wo; e.stride = 2;
-    return cgemm16(ST(stream), N * Ho * Wo, Cin, 9 * Cout, dy, Cout, wt, 9L * Cout, 0.f, dx, Cin, 1, ws, ws ? ws_floats : 0, &e, 0);
+    set_c3(e, 4, Cout, N, Hi, Wi, 2);
+    return cgemm16(ST(stream), N * e.Ho * e.Wo, Cin, 9 * Cout, dy, Cout, wt, 9L * Cout, 0.f, dx, Cin, 1, ws, ws ? ws_floats : 0, &e, 0);
 }
 
 int scnattn_wgrad16_3x3(void* stream, int N, int H, int W, int Cin, int Cout, const void* dy, const void* x, float* dw,
@@ -351,28 +354,30 @@ int scnattn_bn_stats_fold(void* stream, int R, int C, const void* x, float eps, 
     return bn_stats(ST(stream), R, C, x, 0, eps, momentum, partial, mean, invstd, run_mean, run_var, gamma, beta, ss_out);
 }
 
+// wbf: 0 fp32 W; 1 bf16 W; 2 bf16 W and the bf16 matrix instruction (kernels.h)
+static int skinny_entry(void* stream, int rows, int N, int K, int groups, const float* X, long ldx, long xg, const void* W,
+                        long ldw, long wg, float* Y, long ldy, long yg, long yslab, int ksplit, int* ksplit_out, int wbf) {
+    if (ksplit <= 0) ksplit = skinny_pick_ksplit(rows, N, K, groups);
+    if (ksplit_out) *ksplit_out = ksplit;
+    return skinny_gemm(ST(stream), rows, N, K, groups, X, ldx, xg, W, ldw, wg, Y, ldy, yg, yslab, ksplit, wbf);
+}
+
 int scnattn_skinny_gemm(void* stream, int rows, int N, int K, int groups, const float* X, long ldx, long xg,
                         const float* W, long ldw, long wg, float* Y, long ldy, long yg, long yslab,
                         int ksplit, int* ksplit_out) {
-    if (ksplit <= 0) ksplit = skinny_pick_ksplit(rows, N, K, groups);
-    if (ksplit_out) *ksplit_out = ksplit;
-    return skinny_gemm(ST(stream), rows, N, K, groups, X, ldx, xg, W, ldw, wg, Y, ldy, yg, yslab, ksplit);
+    return skinny_entry(stream, rows, N, K, groups, X, ldx, xg, W, ldw, wg, Y, ldy, yg, yslab, ksplit, ksplit_out, 0);
 }
 
 int scnattn_skinny_gemm_bf16w(void* stream, int rows, int N, int K, int groups, const float* X, long ldx, long xg,
                               const void* W_bf16, long ldw, long wg, float* Y, long ldy, long yg, long yslab,
                               int ksplit, int* ksplit_out) {
-    if (ksplit <= 0) ksplit = skinny_pick_ksplit(rows, N, K, groups);
-    if (ksplit_out) *ksplit_out = ksplit;
-    return skinny_gemm(ST(stream), rows, N, K, groups, X, ldx, xg, W_bf16, ldw, wg, Y, ldy, yg, yslab, ksplit, 1);
+    return skinny_entry(stream, rows, N, K, groups, X, ldx, xg, W_bf16, ldw, wg, Y, ldy, yg, yslab, ksplit, ksplit_out, 1);
 }
 
 int scnattn_skinny_gemm_bf16(void* stream, int rows, int N, int K, int groups, const float* X, long ldx, long xg,
                              const void* W_bf16, long ldw, long wg, float* Y, long ldy, long yg, long yslab,
                              int ksplit, int* ksplit_out) {
-    if (ksplit <= 0) ksplit = skinny_pick_ksplit(rows, N, K, groups);
-    if (ksplit_out) *ksplit_out = ksplit;
-    return skinny_gemm(ST(stream), rows, N, K, groups, X, ldx, xg, W_bf16, ldw, wg, Y, ldy, yg, yslab, ksplit, 2);
+    return skinny_entry(stream, rows, N, K, groups, X, ldx, xg, W_bf16, ldw, wg, Y, ldy, yg, yslab, ksplit, ksplit_out, 2);
 }
 
 int scnattn_f32_to_bf16(void* stream, long n, const float* in, void* out) { return f32_to_bf16(ST(stream), n, in, out); }

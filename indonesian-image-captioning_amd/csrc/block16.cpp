@@ -137,7 +137,6 @@ int scnattn_block16_bwd(void* st, const scnattn_block16* b, void** dx_out, void*
     auto istd = [&](int i) { return b->stats + (2L * i + 1) * C4; };
     auto dbeta = [&](int i) { return b->dgb + (2L * i) * C4; };
     auto dgamma = [&](int i) { return b->dgb + (2L * i + 1) * C4; };
-    const int cap = (int)(b->bnpart_floats / (2L * C4));       // chunk capacity of the backward partials at the widest map
     // weight gradients: their own stream when the caller gave one, forked once the operands exist
     auto wstream = [&](void** ws_out, long* wsn) -> void* {
         if (b->side_stream) { *ws_out = b->side_ws; *wsn = b->side_ws_floats; return b->side_stream; }
@@ -151,7 +150,6 @@ int scnattn_block16_bwd(void* st, const scnattn_block16* b, void** dx_out, void*
         return scnattn_bn_bwd_dx_fin(st, R, Cn, g, z, 1, mean(i), istd(i), b->gamma[i], b->bnpart, (nch + 3) & ~3, nch, dbeta(i),
                                      dgamma(i), dz);
     };
-    (void)cap;
     int nch = 0;
     void* wsw = nullptr; long wsn = 0; void* sw = nullptr;
     // ---- bn3 (+ identity + relu): dres = dout * [out > 0] = d identity; dz3 -------------------------------------------------

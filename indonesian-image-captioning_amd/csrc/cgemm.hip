@@ -58,8 +58,6 @@ constexpr int AUX_F = 4 * 64;                   // per-wave {scale, shift} pairs
 constexpr int STAGE_F = 2 * TILE_F + AUX_F;     // 17 KiB per stage -> 51 KiB per workgroup, 3 workgroups per CU
 constexpr int SROWS = 64;                       // rows per statistics partial
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
 struct CArgs {
     const float* A; const float* B; float* C;
     const float* bias; const float* rowmask;
@@ -83,37 +81,6 @@ struct CArgs {
     int* cnt;                     // in-launch split-K combine: one arrival counter per (batch, tile), zero at rest; null -> two launches
     int comb;                     // 1: write-through (sc1) slab stores, 2: plain slab stores + agent release
 };
-
-// output row (n, ho, wo) of a strided 1x1 convolution -> input row (n, ho*s, wo*s)
-__device__ __forceinline__ long gather_row(const CArgs& g, int r) {
-    if (g.gs == 0) return r;
-    const int hw = g.gHo * g.gWo;
-    const int n = r / hw, rem = r - n * hw;
-    const int ho = rem / g.gWo, wo = rem - ho * g.gWo;
-    return (long)n * g.gHi * g.gWi + (long)(ho * g.gs) * g.gWi + wo * g.gs;
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, float* lds_wave_base, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_wave_base, 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ void dma4(__amdgpu_buffer_rsrc_t rs, float* lds_wave_base, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_wave_base, 4, voff, 0, 0, 0);
-}
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_off, 0, 0);
-}
-
-__device__ __forceinline__ void buf_store4_sc1(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {   // write-through
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_off, 0, 16);
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else static_assert(N < 0, "unsupported count");
-}
 
 // MI: 32-row MFMA tiles per wave along m (block tile = 64*MI x 128, waves 2 x 2).
 // MI = 4 is a different WAVE LAYOUT, not a bigger register block: the four waves stack along m (4 x 1), each owning

@@ -33,7 +33,6 @@ constexpr int TILE_F = 128 * 16;                 // floats reserved per operand 
 constexpr int STAGE_F = 2 * TILE_F;              // 16 KiB per stage -> 48 KiB per workgroup
 constexpr int SROWS = 64;
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct HArgs {
@@ -53,32 +52,10 @@ struct HArgs {
     const bf16_t* ez; long ldz; const float* emean; const float* einvstd; const float* egamma; const float* ebeta;   // EPI 2
 };
 
-__device__ __forceinline__ long gather_row(const HArgs& g, int r) {
-    if (g.gs == 0) return r;
-    const int hw = g.gHo * g.gWo;
-    const int n = r / hw, rem = r - n * hw;
-    const int ho = rem / g.gWo, wo = rem - ho * g.gWo;
-    return (long)n * g.gHi * g.gWi + (long)(ho * g.gs) * g.gWi + wo * g.gs;
-}
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, float* lds_wave_base, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_wave_base, 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_off, 0, 0);
-}
-__device__ __forceinline__ void buf_store2(__amdgpu_buffer_rsrc_t r, unsigned byte_off, u32x2 v) {
-    __builtin_amdgcn_raw_buffer_store_b64(v, r, byte_off, 0, 0);
-}
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {       // round to nearest even, NaN stays NaN (v_cvt_pk_bf16_f32)
     typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     const bf16x2 p = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(unsigned, p);
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else static_assert(N < 0, "unsupported count");
 }
 
 // MI: 32-row MFMA tiles per wave along m (block tile 64*MI x 128, waves 2 x 2).  EPI 1: + column statistics.

@@ -112,6 +112,39 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned by
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
 }
 
+__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_off, 0, 0);
+}
+__device__ __forceinline__ void buf_store4_sc1(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {   // write-through
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_off, 0, 16);
+}
+__device__ __forceinline__ void buf_store2(__amdgpu_buffer_rsrc_t r, unsigned byte_off, u32x2 v) {
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, byte_off, 0, 0);
+}
+
+// ---- buffer -> LDS DMA: each lane's 16 / 4 bytes at `voff` land behind the wave's LDS base, in lane order ------------
+typedef __attribute__((address_space(3))) void* lds_ptr;
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, void* lds_wave_base, unsigned voff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_wave_base, 16, voff, 0, 0, 0);
+}
+__device__ __forceinline__ void dma4(__amdgpu_buffer_rsrc_t rs, void* lds_wave_base, unsigned voff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_wave_base, 4, voff, 0, 0, 0);
+}
+// wait until at most N of this wave's vector-memory operations (the DMAs included) are still in flight
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+    static_assert(N >= 0 && N < 64, "unsupported count");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// output row (n, ho, wo) of a strided 1x1 convolution -> input row (n, ho*s, wo*s); Args: the kernel's argument struct
+template <class Args> __device__ __forceinline__ long gather_row(const Args& g, int r) {
+    if (g.gs == 0) return r;
+    const int hw = g.gHo * g.gWo;
+    const int n = r / hw, rem = r - n * hw;
+    const int ho = rem / g.gWo, wo = rem - ho * g.gWo;
+    return (long)n * g.gHi * g.gWi + (long)(ho * g.gs) * g.gWi + wo * g.gs;
+}
+
 // row (0..31) of accumulator register r of lane l in a 32x32 f32 MFMA C/D tile; column is l & 31.
 __device__ __forceinline__ int mfma32_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 

@@ -33,8 +33,6 @@ int cgemm_reduce(hipStream_t st, const float* ws, int S, int M, int N, float* C,
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-
 struct W3Args {
     const float* dy;      // [N*H*W][Co]
     const float* x;       // [N*H*W][C]
@@ -45,17 +43,6 @@ struct W3Args {
     int S;                // K slices at workgroup level (each is split again over the 4 waves)
     int tci, ntiles;      // ci tiles, (Co/32) * (C/32)
 };
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, float* lds_wave_base, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_wave_base, 16, voff, 0, 0, 0);
-}
-
-template <int N> __device__ __forceinline__ void wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else static_assert(N < 0, "unsupported count");
-}
 
 template <int SEG>
 __global__ __launch_bounds__(256, 2) void conv3_wgrad_kernel(W3Args g) {
@@ -131,9 +118,9 @@ __global__ __launch_bounds__(256, 2) void conv3_wgrad_kernel(W3Args g) {
         if (q + 1 < q1 && h + 1 < g.H) {       // next line continues the strip: ONE new activation line + its dY line
             issue_x(n, cs, h + 2);
             issue_y(n, cs, h + 1, (q + 1) & 1);
-            wait_vm<NX + NY>();
+            wait_vmcnt<NX + NY>();
         } else {
-            wait_vm<0>();
+            wait_vmcnt<0>();
         }
         const float* yb = yring + (q & 1) * YSLOT + hh * 32 + l31;
         const float* xb0 = xring + ((h + 0) & 3) * XSLOT + hh * 32 + l31;

@@ -225,10 +225,6 @@ int check_pool(const scnattn_dims* d, const scnattn_pool* p, PoolDesc& out) {
 inline bool bf16_mode(const scnattn_dims& d) {
     return g_dec_bf16 && d.D % 4 == 0 && d.F % 4 == 0 && d.E % 4 == 0 && (!d.has_att || d.A % 4 == 0);
 }
-// element offset into a buffer that holds fp32 or bf16 elements
-inline const void* eoff(const void* base, long elems, bool bf) {
-    return reinterpret_cast<const char*>(base) + elems * (bf ? 2 : 4);
-}
 
 inline int pick(int rows, int N, int K, int groups) {
     if (g_ksplit_scale > 0) {
@@ -241,16 +237,27 @@ inline int pick(int rows, int N, int K, int groups) {
     return skinny_pick_ksplit(rows, N, K, groups);
 }
 
-}  // namespace
+// Split-K workspace of the big GEMMs: pointer and size travel together.
+struct GemmWs { float* p; long floats; };
 
-// The recurrence bodies are written as a function of (stream, first row, row count).  Round 1 ran them as two
-// independent half-batch chains on two streams (no kernel of the loop mixes batch rows); bit-identical but SLOWER (52.8
-// vs 47.8 us per step: the step kernels are latency-bound, a half-batch launch takes as long as a full one), so since
-// round 3 there is one chain on the caller's stream and the machinery is gone (DESIGN.md 6 keeps the numbers).
-namespace {
+// C = op(A) . op(B) + beta * C (+ bias; rows with rowmask == 0 written as zeros): the un-batched sgemm_ws with alpha = 1
+int gemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
+         float beta, float* C, long ldc, GemmWs ws, const float* bias = nullptr, const float* rowmask = nullptr) {
+    return sgemm_ws(st, tA, tB, M, N, K, 1.f, A, lda, B, ldb, beta, C, ldc, bias, rowmask, 1, 0, 0, 0, ws.p, ws.floats);
+}
 
-template <class Body>   // body(stream, first_row, max_rows) -> 0 or error code
-int run_chains(hipStream_t st, int /*kind*/, int B, Body&& body) { return body(st, 0, B); }
+// What the step kernels stream, the same selection in both drivers: the fp32 originals, or in bf16 mode the copies of
+// att1 and of the map the context is summed over that the forward pass makes once per call.
+struct Streamed {
+    bool bf;                    // bf16 storage mode
+    int bfm;                    // skinny_gemm's wbf: 0 fp32 weights, 1 bf16 weights, 2 + the bf16 matrix instruction
+    const void *att1, *enc;
+};
+Streamed streamed(const scnattn_dims& d, const Saved& s, const float* enc) {
+    const bool bf = bf16_mode(d), copies = bf && d.has_att;
+    return Streamed{bf, bf ? (g_dec_bf16 >= 2 ? 2 : 1) : 0, copies ? (const void*)s.att1h : s.att1,
+                    copies ? (const void*)s.ench : enc};
+}
 
 }  // namespace
 
@@ -286,6 +293,10 @@ int seq_fwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, con
     FwdScratch f;
     carve_saved(d, Q, saved, s);
     carve_fwd(d, Q, scratch, f);
+    const GemmWs gws{f.gws, GEMM_WS_FLOATS};
+    const Streamed sm = streamed(d, s, enc);
+    const bool bf = sm.bf;
+    const int bfm = sm.bfm;
 
     // ---- weight re-layout: every per-step contraction streams a row-major [K][N] matrix ----------
     if (d.has_att) {
@@ -299,8 +310,6 @@ int seq_fwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, con
         SCN_TRY(transpose2d(st, D, F, w->decode_step_weight_hc + g * F, F4, wd + (long)F * D, D));  // Hc_g^T
     }
 
-    const bool bf = bf16_mode(d);
-    const int bfm = bf ? (g_dec_bf16 >= 2 ? 2 : 1) : 0;     // 2: the skinny products on the bf16 matrix instruction
     if (bf) {
         SCN_TRY(f32_to_bf16(st, sz(D, NA), f.WcatA, f.WcatAh));
         SCN_TRY(f32_to_bf16(st, sz(4, 2 * F, D), f.WD, f.WDh));
@@ -313,113 +322,82 @@ int seq_fwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, con
     // ---- time-invariant pieces -----------------------------------------------------------------
     if (d.has_att && Q > 0) {
         // att1 = pool(x) . We^T + be = pool(x . We^T) + be: the projection runs on Q rows per image, not P
-        SCN_TRY(sgemm_ws(st, false, true, B * Q, A, E, 1.f, enc, E, w->attention_encoder_att_weight, E, 0.f, f.y, A,
-                      nullptr, nullptr, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
+        SCN_TRY(gemm(st, false, true, B * Q, A, E, enc, E, w->attention_encoder_att_weight, E, 0.f, f.y, A, gws));
         SCN_TRY(pool_expand(st, B, P, A, pd, f.y, w->attention_encoder_att_bias, s.att1));
     } else if (d.has_att) {
-        SCN_TRY(sgemm_ws(st, false, true, B * P, A, E, 1.f, enc, E, w->attention_encoder_att_weight, E, 0.f, s.att1, A,
-                      w->attention_encoder_att_bias, nullptr, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
+        SCN_TRY(gemm(st, false, true, B * P, A, E, enc, E, w->attention_encoder_att_weight, E, 0.f, s.att1, A, gws,
+                     w->attention_encoder_att_bias));
     }
     if (bf && d.has_att) {     // what the step kernels stream: bf16 copies of att1 and of the map the context is summed over
         SCN_TRY(f32_to_bf16(st, sz(B, P, A), s.att1, s.att1h));
         SCN_TRY(f32_to_bf16(st, sz(B, Q > 0 ? Q : P, E), enc, s.ench));
     }
-    const void* att1_s = (bf && d.has_att) ? (const void*)s.att1h : s.att1;
-    const void* enc_s = (bf && d.has_att) ? (const void*)s.ench : enc;
-    SCN_TRY(sgemm_ws(st, false, false, B, F4, d.S, 1.f, tags, d.S, w->decode_step_weight_ib, F4, 0.f, s.qx, F4, nullptr,
-                  nullptr, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
-    SCN_TRY(sgemm_ws(st, false, false, B, F4, d.S, 1.f, tags, d.S, w->decode_step_weight_hb, F4, 0.f, s.qh, F4, nullptr,
-                  nullptr, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
+    SCN_TRY(gemm(st, false, false, B, F4, d.S, tags, d.S, w->decode_step_weight_ib, F4, 0.f, s.qx, F4, gws));
+    SCN_TRY(gemm(st, false, false, B, F4, d.S, tags, d.S, w->decode_step_weight_hb, F4, 0.f, s.qh, F4, gws));
     SCN_TRY(gather_rows_tm(st, B, T, d.L, M, (const long long*)caps, w->embedding_weight, d.V, s.emb_tm));
-    SCN_TRY(sgemm_ws(st, false, false, T * B, F4, M, 1.f, s.emb_tm, M, w->decode_step_weight_ia, F4, 0.f, s.ex, F4,
-                  nullptr, nullptr, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
+    SCN_TRY(gemm(st, false, false, T * B, F4, M, s.emb_tm, M, w->decode_step_weight_ia, F4, 0.f, s.ex, F4, gws));
     if (Q > 0) SCN_TRY(weighted_rows(st, B, Q, E, enc, pd.col_w, s.mean_enc));
     else SCN_TRY(mean_pixels(st, B, P, E, enc, s.mean_enc));
-    SCN_TRY(sgemm_ws(st, false, true, B, D, E, 1.f, s.mean_enc, E, w->init_h_weight, E, 0.f, s.Hs, D, w->init_h_bias,
-                  nullptr, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
-    SCN_TRY(sgemm_ws(st, false, true, B, D, E, 1.f, s.mean_enc, E, w->init_c_weight, E, 0.f, s.Cs, D, w->init_c_bias,
-                  nullptr, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
+    SCN_TRY(gemm(st, false, true, B, D, E, s.mean_enc, E, w->init_h_weight, E, 0.f, s.Hs, D, gws, w->init_h_bias));
+    SCN_TRY(gemm(st, false, true, B, D, E, s.mean_enc, E, w->init_c_weight, E, 0.f, s.Cs, D, gws, w->init_c_bias));
 
     // ---- the recurrence --------------------------------------------------------------------------
     const long BD = (long)B * D;
     hipEvent_t ev0 = prof_begin(st);
-    SCN_TRY(run_chains(st, 0, B, [&](hipStream_t cs, int r0, int rmax) -> int {
-        const void* enc_c = eoff(enc_s, (long)r0 * (Q > 0 ? Q : P) * E, bf && d.has_att);
-        const void* att1_c = d.has_att ? eoff(att1_s, (long)r0 * P * A, bf) : nullptr;
-        float* slabA = f.slabA + (long)r0 * NA;
-        float* slabC = d.has_att ? f.slabC + (long)r0 * F4 : nullptr;
-        float* slabD = f.slabD + (long)r0 * D;
-        float* e_c = d.has_att ? f.e + (long)r0 * P : nullptr;
-        float* xcat = f.xcat + (long)r0 * 8 * F;
-        const float* qx = s.qx + (long)r0 * F4;
-        const float* qh = s.qh + (long)r0 * F4;
-        for (int t = 0; t < T; ++t) {
-            const int bt_ = (bt[t] - r0 < rmax) ? bt[t] - r0 : rmax;   // rows of this chain still decoding
-            if (bt_ <= 0) break;                                       // bt is non-increasing
-            const long rowT = (long)t * B + r0;                        // first row of this chain in [T][B][.] buffers
-            const float* h = s.Hs + rowT * D;
-            const float* c = s.Cs + rowT * D;
-            const int ksA = pick(bt_, NA, D, 1);
-            SCN_TRY(skinny_gemm(cs, bt_, NA, D, 1, h, D, 0, WcatA, NA, 0, slabA, NA, 0, (long)B * NA, ksA, bfm));
-            Slabs pz{nullptr, 0, 0, 0};
-            bool mixed = false;
-            if (d.has_att) {
-                float* alpha_out = alphas + (long)r0 * T * P + (long)t * P;
-                if (Q > 0) {
-                    SCN_TRY(attn_scores(cs, bt_, P, A, att1_c, Slabs{slabA, ksA, (long)B * NA, NA},
-                                        w->attention_decoder_att_bias, w->attention_full_att_weight,
-                                        w->attention_full_att_bias, e_c, s.att2_all + rowT * A, bf));
-                    hipEvent_t evc = g_profile >= 2 ? prof_begin(cs) : nullptr;
-                    SCN_TRY(attn_context_pooled(cs, bt_, P, E, enc_c, pd, e_c, Slabs{slabA + A, ksA, (long)B * NA, NA},
-                                                w->f_beta_bias, alpha_out, (long)T * P, s.alpha_tm + rowT * P,
-                                                s.alphaq_tm + rowT * Q, s.awe_all + rowT * E, s.gate_all + rowT * E,
-                                                s.z_all + rowT * E, bf));
-                    prof_end(cs, evc, 2, 1);
-                } else {
-                    SCN_TRY(attn_scores(cs, bt_, P, A, att1_c, Slabs{slabA, ksA, (long)B * NA, NA},
-                                        w->attention_decoder_att_bias, w->attention_full_att_weight,
-                                        w->attention_full_att_bias, e_c, s.att2_all + rowT * A, bf));
-                    hipEvent_t evc = g_profile >= 2 ? prof_begin(cs) : nullptr;   // per-launch timing of the dominant kernel
-                    SCN_TRY(attn_context(cs, bt_, P, E, enc_c, e_c, Slabs{slabA + A, ksA, (long)B * NA, NA},
-                                         w->f_beta_bias, alpha_out, (long)T * P, s.alpha_tm + rowT * P,
-                                         s.awe_all + rowT * E, s.gate_all + rowT * E, s.z_all + rowT * E, bf));
-                    prof_end(cs, evc, 2, 1);
-                }
-                // z . Wa[M:], and -- inside the same launch, by the workgroup that arrives last at each 32-column unit --
-                // the SCN mix that consumes it (scn_cell.py:73-86); stand-alone kernel when the launch cannot take it
-                const int ksC = pick(bt_, F4, E, 1);
-                SkinnyTail mix{2, bt_, 0, F4, {s.ex + rowT * F4, qx, qh, nullptr},
-                               {s.pa_all + rowT * F4, s.ph_all + rowT * F4, xcat, nullptr}, 0,
-                               Slabs{slabA + colph, ksA, (long)B * NA, NA}};
-                SCN_TRY(skinny_gemm(cs, bt_, F4, E, 1, s.z_all + rowT * E, E, 0, WaM, F4, 0, slabC, F4, 0, (long)B * F4, ksC,
-                                    bfm, &mix, &mixed));
-                pz = Slabs{slabC, ksC, (long)B * F4, F4};
-            }
-            if (!mixed)
-                SCN_TRY(scn_mix_fwd(cs, bt_, F4, pz, s.ex + rowT * F4, Slabs{slabA + colph, ksA, (long)B * NA, NA}, qx, qh,
-                                    s.pa_all + rowT * F4, s.ph_all + rowT * F4, xcat));
-            // [mx | mh] . [Wc; Hc] for the four gates, and the LSTM update of the units each 32-column tile feeds
-            const int ksD = pick(bt_, D, 2 * F, 4);
-            SkinnyTail cell{1, bt_, 0, D, {w->decode_step_bias_ih, w->decode_step_bias_hh, c, nullptr},
-                            {s.gates_all + rowT * 4 * D, s.Cs + (rowT + B) * D, s.Hs + (rowT + B) * D, s.tanhc_all + rowT * D}, 0,
-                            Slabs{nullptr, 0, 0, 0}};
-            bool celled = false;
-            SCN_TRY(skinny_gemm(cs, bt_, D, 2 * F, 4, xcat, 8 * F, 2 * F, WD, D, (long)2 * F * D, slabD, D, BD, 4 * BD,
-                                ksD, bfm, &cell, &celled));
-            if (!celled)
-                SCN_TRY(lstm_fwd(cs, bt_, D, Slabs{slabD, ksD, 4 * BD, D}, BD, w->decode_step_bias_ih,
-                                 w->decode_step_bias_hh, c, s.gates_all + rowT * 4 * D, s.Cs + (rowT + B) * D,
-                                 s.Hs + (rowT + B) * D, s.tanhc_all + rowT * D));
+    for (int t = 0; t < T; ++t) {
+        const int rows = bt[t];                                    // captions still decoding (check_bt: 1 <= rows <= B)
+        const long rowT = (long)t * B;                             // first row of this step in [T][B][.] buffers
+        const float *h = s.Hs + rowT * D, *c = s.Cs + rowT * D, *ex = s.ex + rowT * F4;
+        float *h_new = s.Hs + (rowT + B) * D, *c_new = s.Cs + (rowT + B) * D;
+        float *pa = s.pa_all + rowT * F4, *phs = s.ph_all + rowT * F4;
+        float *gates = s.gates_all + rowT * 4 * D, *tanhc = s.tanhc_all + rowT * D;
+        // h . [Wd^T | Wbeta^T | Ha]: att2, the gate's pre-activation and ph, as column ranges of one split-K result
+        const int ksA = pick(rows, NA, D, 1);
+        SCN_TRY(skinny_gemm(st, rows, NA, D, 1, h, D, 0, WcatA, NA, 0, f.slabA, NA, 0, (long)B * NA, ksA, bfm));
+        const Slabs ph{f.slabA + colph, ksA, (long)B * NA, NA};
+        Slabs pz{nullptr, 0, 0, 0};
+        bool mixed = false;
+        if (d.has_att) {
+            const Slabs att2{f.slabA, ksA, (long)B * NA, NA}, gpre{f.slabA + A, ksA, (long)B * NA, NA};
+            float* alpha_out = alphas + (long)t * P;
+            SCN_TRY(attn_scores(st, rows, P, A, sm.att1, att2, w->attention_decoder_att_bias, w->attention_full_att_weight,
+                                w->attention_full_att_bias, f.e, s.att2_all + rowT * A, bf));
+            hipEvent_t evc = g_profile >= 2 ? prof_begin(st) : nullptr;   // per-launch timing of the dominant kernel
+            if (Q > 0)
+                SCN_TRY(attn_context_pooled(st, rows, P, E, sm.enc, pd, f.e, gpre, w->f_beta_bias, alpha_out, (long)T * P,
+                                            s.alpha_tm + rowT * P, s.alphaq_tm + rowT * Q, s.awe_all + rowT * E,
+                                            s.gate_all + rowT * E, s.z_all + rowT * E, bf));
+            else
+                SCN_TRY(attn_context(st, rows, P, E, sm.enc, f.e, gpre, w->f_beta_bias, alpha_out, (long)T * P,
+                                     s.alpha_tm + rowT * P, s.awe_all + rowT * E, s.gate_all + rowT * E, s.z_all + rowT * E,
+                                     bf));
+            prof_end(st, evc, 2, 1);
+            // z . Wa[M:], and -- inside the same launch, by the workgroup that arrives last at each 32-column unit --
+            // the SCN mix that consumes it (scn_cell.py:73-86); stand-alone kernel when the launch cannot take it
+            const int ksC = pick(rows, F4, E, 1);
+            SkinnyTail mix{2, rows, 0, F4, {ex, s.qx, s.qh, nullptr}, {pa, phs, f.xcat, nullptr}, 0, ph};
+            SCN_TRY(skinny_gemm(st, rows, F4, E, 1, s.z_all + rowT * E, E, 0, WaM, F4, 0, f.slabC, F4, 0, (long)B * F4, ksC,
+                                bfm, &mix, &mixed));
+            pz = Slabs{f.slabC, ksC, (long)B * F4, F4};
         }
-        return 0;
-    }));
-
+        if (!mixed) SCN_TRY(scn_mix_fwd(st, rows, F4, pz, ex, ph, s.qx, s.qh, pa, phs, f.xcat));
+        // [mx | mh] . [Wc; Hc] for the four gates, and the LSTM update of the units each 32-column tile feeds
+        const int ksD = pick(rows, D, 2 * F, 4);
+        SkinnyTail cell{1, rows, 0, D, {w->decode_step_bias_ih, w->decode_step_bias_hh, c, nullptr},
+                        {gates, c_new, h_new, tanhc}, 0, Slabs{nullptr, 0, 0, 0}};
+        bool celled = false;
+        SCN_TRY(skinny_gemm(st, rows, D, 2 * F, 4, f.xcat, 8 * F, 2 * F, WD, D, (long)2 * F * D, f.slabD, D, BD, 4 * BD, ksD,
+                            bfm, &cell, &celled));
+        if (!celled)
+            SCN_TRY(lstm_fwd(st, rows, D, Slabs{f.slabD, ksD, 4 * BD, D}, BD, w->decode_step_bias_ih,
+                             w->decode_step_bias_hh, c, gates, c_new, h_new, tanhc));
+    }
     prof_end(st, ev0, 0, T);
 
     // ---- dropout + fc over all (b,t) rows at once ------------------------------------------------
     SCN_TRY(hidden_to_bm(st, B, T, D, dl_dev, s.Hs + BD, drop_mask, s.Hd_bm, s.rowmask));
-    SCN_TRY(sgemm_ws(st, false, true, B * T, d.V, D, 1.f, s.Hd_bm, D, w->fc_weight, D, 0.f, preds, d.V, w->fc_bias,
-                  s.rowmask, 1, 0, 0, 0, f.gws, GEMM_WS_FLOATS));
+    SCN_TRY(gemm(st, false, true, B * T, d.V, D, s.Hd_bm, D, w->fc_weight, D, 0.f, preds, d.V, gws, w->fc_bias,
+                 s.rowmask));
     return 0;
 }
 
@@ -447,9 +425,15 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     BwdScratch k;
     carve_saved(d, Q, const_cast<float*>(saved), s);
     carve_bwd(d, Q, scratch, k);
+    const GemmWs gws{k.gws, GEMM_WS_FLOATS};
+    const Streamed sm = streamed(d, s, enc);    // the copies the forward pass streamed
+    const bool bf = sm.bf;
+    const int bfm = sm.bfm;
+    const int R = Q > 0 ? Q : P;                // pixels per image of the map `enc` holds
+    const float* dproj = Q > 0 ? k.dy : k.datt1;    // d (enc . We^T) on those pixels: d y (pooled) or d att1
     const bool two = wst && wst != st;
     hipStream_t ws = two ? wst : st;            // stream of the weight gradients
-    float* wgws = two ? k.gws2 : k.gws;         // ... and its split-K workspace
+    const GemmWs wgws = two ? GemmWs{k.gws2, GEMM_WS_FLOATS} : gws;    // ... and its split-K workspace
     // ws_after_main(): everything enqueued on `st` so far happens-before what is enqueued on `ws` next
     auto ws_after_main = [&]() -> int {
         if (!two) return 0;
@@ -465,12 +449,10 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     // ---- fc / dropout ----------------------------------------------------------------------------
     SCN_TRY(ws_after_main());
     if (g->fc_weight)
-        SCN_TRY(sgemm_ws(ws, true, false, V, D, B * T, 1.f, dpreds, V, s.Hd_bm, D, 0.f, g->fc_weight, D, nullptr, nullptr,
-                      1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+        SCN_TRY(gemm(ws, true, false, V, D, B * T, dpreds, V, s.Hd_bm, D, 0.f, g->fc_weight, D, wgws));
     if (g->fc_bias)  // only rows that were decoded carry the bias
         SCN_TRY(colsum_masked(ws, B * T, V, dpreds, V, s.rowmask, g->fc_bias, 0.f));
-    SCN_TRY(sgemm_ws(st, false, false, B * T, D, V, 1.f, dpreds, V, w->fc_weight, D, 0.f, k.dHd_bm, D, nullptr, nullptr, 1,
-                  0, 0, 0, k.gws, GEMM_WS_FLOATS));
+    SCN_TRY(gemm(st, false, false, B * T, D, V, dpreds, V, w->fc_weight, D, 0.f, k.dHd_bm, D, gws));
     SCN_TRY(hidden_from_bm(st, B, T, D, dl_dev, k.dHd_bm, drop_mask, k.dhfc_tm));
 
     // ---- transposed weight layouts for the backward contractions ------------------------------------
@@ -485,8 +467,6 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
         SCN_TRY(copy2d(st, E, D, w->f_beta_weight, D, k.WcatT + (long)F4 * D, D));
         SCN_TRY(copy2d(st, A, D, w->attention_decoder_att_weight, D, k.WcatT + (long)(F4 + E) * D, D));
     }
-    const bool bf = bf16_mode(d);
-    const int bfm = bf ? (g_dec_bf16 >= 2 ? 2 : 1) : 0;     // 2: the skinny products on the bf16 matrix instruction
     if (bf) {
         SCN_TRY(f32_to_bf16(st, sz(4, D, 2 * F), k.WDb, k.WDbh));
         SCN_TRY(f32_to_bf16(st, sz(NC, D), k.WcatT, k.WcatTh));
@@ -495,93 +475,75 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     const void* WDb = bf ? (const void*)k.WDbh : k.WDb;
     const void* WcatT = bf ? (const void*)k.WcatTh : k.WcatT;
     const void* WaTz = bf ? (const void*)k.WaTzh : k.WaTz;
-    const void* att1_s = (bf && d.has_att) ? (const void*)s.att1h : s.att1;     // the copies the forward pass streamed
-    const void* enc_s = (bf && d.has_att) ? (const void*)s.ench : enc;
     SCN_HIP(hipMemsetAsync(k.dc, 0, sizeof(float) * BD, st));
     SCN_HIP(hipMemsetAsync(k.dqx_acc, 0, sizeof(float) * B * F4, st));
     SCN_HIP(hipMemsetAsync(k.dqh_acc, 0, sizeof(float) * B * F4, st));
 
     // ---- reverse recurrence ----------------------------------------------------------------------
     hipEvent_t ev0 = prof_begin(st);
-    SCN_TRY(run_chains(st, 1, B, [&](hipStream_t cs, int r0, int rmax) -> int {
-        const void* enc_c = eoff(enc_s, (long)r0 * (Q > 0 ? Q : P) * E, bf && d.has_att);
-        const void* att1_c = d.has_att ? eoff(att1_s, (long)r0 * P * A, bf) : nullptr;
-        float* sDb = k.sDb + (long)r0 * 2 * F;
-        float* sZ = d.has_att ? k.sZ + (long)r0 * E : nullptr;
-        float* sH = k.sH + (long)r0 * D;
-        float* dalpha = d.has_att ? k.dalpha + (long)r0 * P : nullptr;
-        float* dc = k.dc + (long)r0 * D;
-        const float* qx = s.qx + (long)r0 * F4;
-        const float* qh = s.qh + (long)r0 * F4;
-        float* dqx_acc = k.dqx_acc + (long)r0 * F4;
-        float* dqh_acc = k.dqh_acc + (long)r0 * F4;
-        auto rows_at = [&](int t) { const int n = bt[t] - r0; return n < 0 ? 0 : (n < rmax ? n : rmax); };
-        int ksH = 0, tlast = -1;
-        bool lstm_done = false;
-        for (int t = T - 1; t >= 0; --t) {
-            const int bt_ = rows_at(t);
-            if (bt_ <= 0) continue;                                    // this chain starts decoding later (shorter rows)
-            const int btn = (t + 1 < T) ? rows_at(t + 1) : 0;
-            const long rowT = (long)t * B + r0;
-            float* dr = k.dr_all + rowT * 4 * D;
-            float* dcat = k.dcat_all + rowT * NC;
-            float* dpx = k.dpx_all + rowT * F4;
-            // the LSTM backward of this step ran inside the previous iteration's last product (below) unless that launch
-            // could not take it, or this is the first iteration
-            if (!lstm_done)
-                SCN_TRY(lstm_bwd(cs, bt_, btn, D, k.dhfc_tm + rowT * D,
-                                 btn > 0 ? Slabs{sH, ksH, BD, D} : Slabs{nullptr, 0, 0, 0}, dc, s.gates_all + rowT * 4 * D,
-                                 s.Cs + rowT * D, s.tanhc_all + rowT * D, dr));
-            lstm_done = false;
-            const int ksDb = pick(bt_, 2 * F, D, 4);
-            SkinnyTail mixb{3, bt_, 0, F4, {qx, qh, s.pa_all + rowT * F4, s.ph_all + rowT * F4}, {dpx, dcat, dqx_acc, dqh_acc}, NC,
-                            Slabs{nullptr, 0, 0, 0}};
-            bool mixed = false;
-            SCN_TRY(skinny_gemm(cs, bt_, 2 * F, D, 4, dr, 4 * D, D, WDb, 2 * F, (long)D * 2 * F, sDb, 2 * F,
-                                (long)B * 2 * F, (long)4 * B * 2 * F, ksDb, bfm, &mixb, &mixed));
-            if (!mixed)
-                SCN_TRY(scn_mix_bwd(cs, bt_, F4, Slabs{sDb, ksDb, (long)4 * B * 2 * F, 2 * F}, (long)B * 2 * F, qx, qh,
-                                    s.pa_all + rowT * F4, s.ph_all + rowT * F4, dpx, dcat, NC, dqx_acc, dqh_acc));
-            if (d.has_att) {
-                const int ksZ = pick(bt_, E, F4, 1);
-                float* dawe = k.dawe_all + rowT * E;
-                SkinnyTail gateb{4, bt_, 0, E, {s.awe_all + rowT * E, s.gate_all + rowT * E, nullptr, nullptr},
-                                 {dawe, dcat + F4, nullptr, nullptr}, NC, Slabs{nullptr, 0, 0, 0}};
-                bool gated = false;
-                SCN_TRY(skinny_gemm(cs, bt_, E, F4, 1, dpx, F4, 0, WaTz, E, 0, sZ, E, 0, (long)B * E, ksZ, bfm, &gateb, &gated));
-                if (!gated)
-                    SCN_TRY(gate_bwd(cs, bt_, E, Slabs{sZ, ksZ, (long)B * E, E}, s.awe_all + rowT * E,
-                                     s.gate_all + rowT * E, dawe, dcat + F4, NC));
-                const float* din = dalphas ? dalphas + (long)r0 * T * P + (long)t * P : nullptr;
-                if (Q > 0) {
-                    // Q dot products per image against x, folded onto the P pooled pixels inside softmax_bwd
-                    float* dalphaq = k.dalphaq + (long)r0 * Q;
-                    SCN_TRY(attn_dalpha(cs, bt_, Q, E, enc_c, dawe, nullptr, 0, dalphaq, bf));
-                    SCN_TRY(attn_softmax_bwd_pooled(cs, bt_, P, A, att1_c, s.att2_all + rowT * A,
-                                                    w->attention_full_att_weight, s.alpha_tm + rowT * P, pd, dalphaq, din,
-                                                    (long)T * P, k.de_all + rowT * P, dcat + F4 + E, NC, bf));
-                } else {
-                    SCN_TRY(attn_dalpha(cs, bt_, P, E, enc_c, dawe, din, (long)T * P, dalpha, bf));
-                    SCN_TRY(attn_softmax_bwd(cs, bt_, P, A, att1_c, s.att2_all + rowT * A, w->attention_full_att_weight,
-                                             s.alpha_tm + rowT * P, dalpha, k.de_all + rowT * P, dcat + F4 + E, NC, bf));
-                }
+    int ksH = 0;
+    bool lstm_done = false;
+    for (int t = T - 1; t >= 0; --t) {
+        const int rows = bt[t];                                    // check_bt: 1 <= rows <= B, non-increasing in t
+        const int rows_next = (t + 1 < T) ? bt[t + 1] : 0;
+        const long rowT = (long)t * B;
+        float* dr = k.dr_all + rowT * 4 * D;
+        float* dcat = k.dcat_all + rowT * NC;
+        float* dpx = k.dpx_all + rowT * F4;
+        const float *pa = s.pa_all + rowT * F4, *phs = s.ph_all + rowT * F4;
+        // the LSTM backward of this step ran inside the previous iteration's last product (below) unless that launch
+        // could not take it, or this is the first iteration
+        if (!lstm_done)
+            SCN_TRY(lstm_bwd(st, rows, rows_next, D, k.dhfc_tm + rowT * D,
+                             rows_next > 0 ? Slabs{k.sH, ksH, BD, D} : Slabs{nullptr, 0, 0, 0}, k.dc,
+                             s.gates_all + rowT * 4 * D, s.Cs + rowT * D, s.tanhc_all + rowT * D, dr));
+        lstm_done = false;
+        const int ksDb = pick(rows, 2 * F, D, 4);
+        SkinnyTail mixb{3, rows, 0, F4, {s.qx, s.qh, pa, phs}, {dpx, dcat, k.dqx_acc, k.dqh_acc}, NC,
+                        Slabs{nullptr, 0, 0, 0}};
+        bool mixed = false;
+        SCN_TRY(skinny_gemm(st, rows, 2 * F, D, 4, dr, 4 * D, D, WDb, 2 * F, (long)D * 2 * F, k.sDb, 2 * F, (long)B * 2 * F,
+                            (long)4 * B * 2 * F, ksDb, bfm, &mixb, &mixed));
+        if (!mixed)
+            SCN_TRY(scn_mix_bwd(st, rows, F4, Slabs{k.sDb, ksDb, (long)4 * B * 2 * F, 2 * F}, (long)B * 2 * F, s.qx, s.qh,
+                                pa, phs, dpx, dcat, NC, k.dqx_acc, k.dqh_acc));
+        if (d.has_att) {
+            const int ksZ = pick(rows, E, F4, 1);
+            float* dawe = k.dawe_all + rowT * E;
+            const float *awe = s.awe_all + rowT * E, *gate = s.gate_all + rowT * E;
+            SkinnyTail gateb{4, rows, 0, E, {awe, gate, nullptr, nullptr}, {dawe, dcat + F4, nullptr, nullptr}, NC,
+                             Slabs{nullptr, 0, 0, 0}};
+            bool gated = false;
+            SCN_TRY(skinny_gemm(st, rows, E, F4, 1, dpx, F4, 0, WaTz, E, 0, k.sZ, E, 0, (long)B * E, ksZ, bfm, &gateb,
+                                &gated));
+            if (!gated)
+                SCN_TRY(gate_bwd(st, rows, E, Slabs{k.sZ, ksZ, (long)B * E, E}, awe, gate, dawe, dcat + F4, NC));
+            const float* din = dalphas ? dalphas + (long)t * P : nullptr;
+            if (Q > 0) {
+                // Q dot products per image against x, folded onto the P pooled pixels inside softmax_bwd
+                SCN_TRY(attn_dalpha(st, rows, Q, E, sm.enc, dawe, nullptr, 0, k.dalphaq, bf));
+                SCN_TRY(attn_softmax_bwd_pooled(st, rows, P, A, sm.att1, s.att2_all + rowT * A, w->attention_full_att_weight,
+                                                s.alpha_tm + rowT * P, pd, k.dalphaq, din, (long)T * P, k.de_all + rowT * P,
+                                                dcat + F4 + E, NC, bf));
+            } else {
+                SCN_TRY(attn_dalpha(st, rows, P, E, sm.enc, dawe, din, (long)T * P, k.dalpha, bf));
+                SCN_TRY(attn_softmax_bwd(st, rows, P, A, sm.att1, s.att2_all + rowT * A, w->attention_full_att_weight,
+                                         s.alpha_tm + rowT * P, k.dalpha, k.de_all + rowT * P, dcat + F4 + E, NC, bf));
             }
-            ksH = pick(bt_, D, NC, 1);
-            // d cat . Wcat^T = this step's d h, and with it -- same launch -- the LSTM backward of step t-1, whose only
-            // missing input it is (scn_cell.py:134-152 transposed)
-            SkinnyTail cellb{5, t > 0 ? rows_at(t - 1) : 0, bt_, D,
-                             {t > 0 ? k.dhfc_tm + (rowT - B) * D : nullptr, t > 0 ? s.gates_all + (rowT - B) * 4 * D : nullptr,
-                              t > 0 ? s.Cs + (rowT - B) * D : nullptr, t > 0 ? s.tanhc_all + (rowT - B) * D : nullptr},
-                             {dc, t > 0 ? k.dr_all + (rowT - B) * 4 * D : nullptr, nullptr, nullptr}, 0, Slabs{nullptr, 0, 0, 0}};
-            SCN_TRY(skinny_gemm(cs, bt_, D, NC, 1, dcat, NC, 0, WcatT, D, 0, sH, D, 0, BD, ksH, bfm, t > 0 ? &cellb : nullptr,
-                                &lstm_done));
-            tlast = t;
         }
-        // d loss / d h0 for this chain's rows (d/d c0 is k.dc); every row decodes at t = 0
-        SCN_ARG(tlast == 0, "internal: chain without a step at t = 0");
-        SCN_TRY(reduce_slabs(cs, rmax, D, Slabs{sH, ksH, BD, D}, k.dh0 + (long)r0 * D));
-        return 0;
-    }));
+        ksH = pick(rows, D, NC, 1);
+        // d cat . Wcat^T = this step's d h, and with it -- same launch -- the LSTM backward of step t-1, whose only
+        // missing input it is (scn_cell.py:134-152 transposed)
+        SkinnyTail cellb{5, t > 0 ? bt[t - 1] : 0, rows, D,
+                         {t > 0 ? k.dhfc_tm + (rowT - B) * D : nullptr, t > 0 ? s.gates_all + (rowT - B) * 4 * D : nullptr,
+                          t > 0 ? s.Cs + (rowT - B) * D : nullptr, t > 0 ? s.tanhc_all + (rowT - B) * D : nullptr},
+                         {k.dc, t > 0 ? k.dr_all + (rowT - B) * 4 * D : nullptr, nullptr, nullptr}, 0,
+                         Slabs{nullptr, 0, 0, 0}};
+        SCN_TRY(skinny_gemm(st, rows, D, NC, 1, dcat, NC, 0, WcatT, D, 0, k.sH, D, 0, BD, ksH, bfm, t > 0 ? &cellb : nullptr,
+                            &lstm_done));
+    }
+    // d loss / d h0 (d/d c0 is k.dc): the last product ran at t = 0, where every row decodes
+    SCN_TRY(reduce_slabs(st, B, D, Slabs{k.sH, ksH, BD, D}, k.dh0));
     prof_end(st, ev0, 1, T);
 
     // ---- after the loop: two strands ------------------------------------------------------------------
@@ -607,71 +569,61 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     auto wgrad_loop = [&]() -> int {      // everything whose operands the reverse recurrence produced
         SCN_TRY(ws_wait(&ev_loop));
         if (g->decode_step_weight_ia) {
-            SCN_TRY(sgemm_ws(ws, true, false, M, F4, TB, 1.f, s.emb_tm, M, k.dpx_all, F4, 0.f, g->decode_step_weight_ia, F4,
-                          nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(ws, true, false, M, F4, TB, s.emb_tm, M, k.dpx_all, F4, 0.f, g->decode_step_weight_ia, F4,
+                         wgws));
             if (d.has_att)
-                SCN_TRY(sgemm_ws(ws, true, false, E, F4, TB, 1.f, s.z_all, E, k.dpx_all, F4, 0.f,
-                              g->decode_step_weight_ia + (long)M * F4, F4, nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+                SCN_TRY(gemm(ws, true, false, E, F4, TB, s.z_all, E, k.dpx_all, F4, 0.f,
+                             g->decode_step_weight_ia + (long)M * F4, F4, wgws));
         }
         if (g->embedding_weight) {
-            SCN_TRY(sgemm_ws(ws, false, true, TB, M, F4, 1.f, k.dpx_all, F4, w->decode_step_weight_ia, F4, 0.f, k.demb_tm, M,
-                          nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(ws, false, true, TB, M, F4, k.dpx_all, F4, w->decode_step_weight_ia, F4, 0.f, k.demb_tm, M,
+                         wgws));
             SCN_TRY(scatter_add_rows_tm(ws, B, T, d.L, M, (const long long*)caps, dl_dev, k.demb_tm, V,
                                         g->embedding_weight, reinterpret_cast<int*>(k.present)));
         }
         if (g->decode_step_weight_ic) {
             SCN_TRY(mul_bcast(ws, T, B, F4, s.pa_all, s.qx, k.mx_all));
             SCN_TRY(sgemm_ws(ws, true, false, D, F, TB, 1.f, k.dr_all, 4 * D, k.mx_all, F4, 0.f, g->decode_step_weight_ic, F4,
-                          nullptr, nullptr, 4, D, F, F, wgws, GEMM_WS_FLOATS));
+                             nullptr, nullptr, 4, D, F, F, wgws.p, wgws.floats));
         }
         if (g->decode_step_weight_hc) {
             SCN_TRY(mul_bcast(ws, T, B, F4, s.ph_all, s.qh, k.mx_all));
             SCN_TRY(sgemm_ws(ws, true, false, D, F, TB, 1.f, k.dr_all, 4 * D, k.mx_all, F4, 0.f, g->decode_step_weight_hc, F4,
-                          nullptr, nullptr, 4, D, F, F, wgws, GEMM_WS_FLOATS));
+                             nullptr, nullptr, 4, D, F, F, wgws.p, wgws.floats));
         }
         if (g->decode_step_weight_ha)
-            SCN_TRY(sgemm_ws(ws, true, false, D, F4, TB, 1.f, s.Hs, D, k.dcat_all, NC, 0.f, g->decode_step_weight_ha, F4,
-                          nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(ws, true, false, D, F4, TB, s.Hs, D, k.dcat_all, NC, 0.f, g->decode_step_weight_ha, F4, wgws));
         if (g->decode_step_weight_ib)
-            SCN_TRY(sgemm_ws(ws, true, false, d.S, F4, B, 1.f, tags, d.S, k.dqx_acc, F4, 0.f, g->decode_step_weight_ib, F4,
-                          nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(ws, true, false, d.S, F4, B, tags, d.S, k.dqx_acc, F4, 0.f, g->decode_step_weight_ib, F4,
+                         wgws));
         if (g->decode_step_weight_hb)
-            SCN_TRY(sgemm_ws(ws, true, false, d.S, F4, B, 1.f, tags, d.S, k.dqh_acc, F4, 0.f, g->decode_step_weight_hb, F4,
-                          nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(ws, true, false, d.S, F4, B, tags, d.S, k.dqh_acc, F4, 0.f, g->decode_step_weight_hb, F4,
+                         wgws));
         if (g->decode_step_bias_ih) SCN_TRY(colsum(ws, TB, 4 * D, k.dr_all, 4 * D, g->decode_step_bias_ih, 0.f));
         if (g->decode_step_bias_hh) SCN_TRY(colsum(ws, TB, 4 * D, k.dr_all, 4 * D, g->decode_step_bias_hh, 0.f));
         if (d.has_att) {
             if (g->f_beta_weight)
-                SCN_TRY(sgemm_ws(ws, true, false, E, D, TB, 1.f, k.dcat_all + F4, NC, s.Hs, D, 0.f, g->f_beta_weight, D,
-                              nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+                SCN_TRY(gemm(ws, true, false, E, D, TB, k.dcat_all + F4, NC, s.Hs, D, 0.f, g->f_beta_weight, D, wgws));
             if (g->f_beta_bias) SCN_TRY(colsum(ws, TB, E, k.dcat_all + F4, NC, g->f_beta_bias, 0.f));
             if (g->attention_decoder_att_weight)
-                SCN_TRY(sgemm_ws(ws, true, false, A, D, TB, 1.f, k.dcat_all + F4 + E, NC, s.Hs, D, 0.f,
-                              g->attention_decoder_att_weight, D, nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+                SCN_TRY(gemm(ws, true, false, A, D, TB, k.dcat_all + F4 + E, NC, s.Hs, D, 0.f,
+                             g->attention_decoder_att_weight, D, wgws));
             if (g->attention_decoder_att_bias)
                 SCN_TRY(colsum(ws, TB, A, k.dcat_all + F4 + E, NC, g->attention_decoder_att_bias, 0.f));
         }
         if (g->init_h_weight)
-            SCN_TRY(sgemm_ws(ws, true, false, D, E, B, 1.f, k.dh0, D, s.mean_enc, E, 0.f, g->init_h_weight, E, nullptr,
-                          nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(ws, true, false, D, E, B, k.dh0, D, s.mean_enc, E, 0.f, g->init_h_weight, E, wgws));
         if (g->init_h_bias) SCN_TRY(colsum(ws, B, D, k.dh0, D, g->init_h_bias, 0.f));
         if (g->init_c_weight)
-            SCN_TRY(sgemm_ws(ws, true, false, D, E, B, 1.f, k.dc, D, s.mean_enc, E, 0.f, g->init_c_weight, E, nullptr, nullptr,
-                          1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(ws, true, false, D, E, B, k.dc, D, s.mean_enc, E, 0.f, g->init_c_weight, E, wgws));
         if (g->init_c_bias) SCN_TRY(colsum(ws, B, D, k.dc, D, g->init_c_bias, 0.f));
         return 0;
     };
     auto wgrad_att = [&]() -> int {       // d encoder_att: needs d att1 (/ d y)
         SCN_TRY(ws_wait(&ev_att));
         if (!d.has_att) return 0;
-        if (g->attention_encoder_att_weight) {
-            if (Q > 0)
-                SCN_TRY(sgemm_ws(ws, true, false, A, E, B * Q, 1.f, k.dy, A, enc, E, 0.f, g->attention_encoder_att_weight,
-                              E, nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
-            else
-                SCN_TRY(sgemm_ws(ws, true, false, A, E, B * P, 1.f, k.datt1, A, enc, E, 0.f,
-                              g->attention_encoder_att_weight, E, nullptr, nullptr, 1, 0, 0, 0, wgws, GEMM_WS_FLOATS));
-        }
+        if (g->attention_encoder_att_weight)
+            SCN_TRY(gemm(ws, true, false, A, E, B * R, dproj, A, enc, E, 0.f, g->attention_encoder_att_weight, E, wgws));
         if (g->attention_encoder_att_bias)
             SCN_TRY(colsum(ws, B * P, A, k.datt1, A, g->attention_encoder_att_bias, 0.f));
         return 0;
@@ -679,14 +631,12 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     SCN_TRY(mark(&ev_loop));
     if (!two) SCN_TRY(wgrad_loop());
     if (dtags) {
-        SCN_TRY(sgemm_ws(st, false, true, B, d.S, F4, 1.f, k.dqx_acc, F4, w->decode_step_weight_ib, F4, 0.f, dtags, d.S,
-                      nullptr, nullptr, 1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
-        SCN_TRY(sgemm_ws(st, false, true, B, d.S, F4, 1.f, k.dqh_acc, F4, w->decode_step_weight_hb, F4, 1.f, dtags, d.S,
-                      nullptr, nullptr, 1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
+        SCN_TRY(gemm(st, false, true, B, d.S, F4, k.dqx_acc, F4, w->decode_step_weight_ib, F4, 0.f, dtags, d.S, gws));
+        SCN_TRY(gemm(st, false, true, B, d.S, F4, k.dqh_acc, F4, w->decode_step_weight_hb, F4, 1.f, dtags, d.S, gws));
     }
     if (d.has_att) {
         int nblk = 0;
-        SCN_TRY(attn_datt1_post(st, B, P, A, T, dl_dev, att1_s, s.att2_all, k.de_all, w->attention_full_att_weight,
+        SCN_TRY(attn_datt1_post(st, B, P, A, T, dl_dev, sm.att1, s.att2_all, k.de_all, w->attention_full_att_weight,
                                 k.datt1, k.dwpart, &nblk, bf));
         SCN_TRY(colsum(st, nblk, A + 1, k.dwpart, A + 1, k.dwtmp, 0.f));
         if (g->attention_full_att_weight)
@@ -699,36 +649,21 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     if (!two) SCN_TRY(wgrad_att());
 
     // ---- d loss / d encoder_out (only when the encoder is fine-tuned) -------------------------------
-    if (denc && Q > 0) {
-        // d x = d y . We  +  sum_t alphaq_t (x) dawe_t  +  col_w (x) d mean      (all on the Q source pixels)
+    if (denc) {
+        // pooled: d x = d y . We  +  sum_t alphaq_t (x) dawe_t  +  col_w (x) d mean      (all on the Q source pixels)
+        // dense:  d enc = d att1 . We  +  sum_t alpha_t (x) dawe_t  +  d mean / P           (on the P pixels)
         if (d.has_att) {
-            SCN_TRY(sgemm_ws(st, false, false, B * Q, E, A, 1.f, k.dy, A, w->attention_encoder_att_weight, E, 0.f, denc,
-                          E, nullptr, nullptr, 1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
-            SCN_TRY(sgemm_ws(st, true, false, Q, E, T, 1.f, s.alphaq_tm, (long)B * Q, k.dawe_all, (long)B * E, 1.f, denc,
-                          E, nullptr, nullptr, B, Q, E, (long)Q * E, k.gws, GEMM_WS_FLOATS));
+            SCN_TRY(gemm(st, false, false, B * R, E, A, dproj, A, w->attention_encoder_att_weight, E, 0.f, denc, E, gws));
+            // denc[b] += alpha_b^T (R x T) . dawe_b (T x E), batched over b
+            SCN_TRY(sgemm_ws(st, true, false, R, E, T, 1.f, Q > 0 ? s.alphaq_tm : s.alpha_tm, (long)B * R, k.dawe_all,
+                             (long)B * E, 1.f, denc, E, nullptr, nullptr, B, R, E, (long)R * E, gws.p, gws.floats));
         } else {
-            SCN_HIP(hipMemsetAsync(denc, 0, sizeof(float) * B * Q * E, st));
+            SCN_HIP(hipMemsetAsync(denc, 0, sizeof(float) * B * R * E, st));
         }
-        SCN_TRY(sgemm_ws(st, false, false, B, E, D, 1.f, k.dh0, D, w->init_h_weight, E, 0.f, k.dmean, E, nullptr, nullptr,
-                      1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
-        SCN_TRY(sgemm_ws(st, false, false, B, E, D, 1.f, k.dc, D, w->init_c_weight, E, 1.f, k.dmean, E, nullptr, nullptr,
-                      1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
-        SCN_TRY(add_bcast_rows_w(st, B, Q, E, pd.col_w, k.dmean, denc));
-    } else if (denc) {
-        if (d.has_att) {
-            SCN_TRY(sgemm_ws(st, false, false, B * P, E, A, 1.f, k.datt1, A, w->attention_encoder_att_weight, E, 0.f,
-                          denc, E, nullptr, nullptr, 1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
-            // denc[b] += alpha_b^T (P x T) . dawe_b (T x E), batched over b
-            SCN_TRY(sgemm_ws(st, true, false, P, E, T, 1.f, s.alpha_tm, (long)B * P, k.dawe_all, (long)B * E, 1.f, denc, E,
-                          nullptr, nullptr, B, P, E, (long)P * E, k.gws, GEMM_WS_FLOATS));
-        } else {
-            SCN_HIP(hipMemsetAsync(denc, 0, sizeof(float) * B * P * E, st));
-        }
-        SCN_TRY(sgemm_ws(st, false, false, B, E, D, 1.f, k.dh0, D, w->init_h_weight, E, 0.f, k.dmean, E, nullptr, nullptr,
-                      1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
-        SCN_TRY(sgemm_ws(st, false, false, B, E, D, 1.f, k.dc, D, w->init_c_weight, E, 1.f, k.dmean, E, nullptr, nullptr,
-                      1, 0, 0, 0, k.gws, GEMM_WS_FLOATS));
-        SCN_TRY(add_bcast_rows(st, B, P, E, k.dmean, 1.f / (float)P, denc));
+        SCN_TRY(gemm(st, false, false, B, E, D, k.dh0, D, w->init_h_weight, E, 0.f, k.dmean, E, gws));
+        SCN_TRY(gemm(st, false, false, B, E, D, k.dc, D, w->init_c_weight, E, 1.f, k.dmean, E, gws));
+        if (Q > 0) SCN_TRY(add_bcast_rows_w(st, B, Q, E, pd.col_w, k.dmean, denc));
+        else SCN_TRY(add_bcast_rows(st, B, P, E, k.dmean, 1.f / (float)P, denc));
     }
     if (two) {
         SCN_TRY(wgrad_loop());

@@ -25,14 +25,10 @@ int cgemm_reduce(hipStream_t st, const float* ws, int S, int M, int N, float* C,
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short v8i16 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, char* lds_wave_base, unsigned voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr)lds_wave_base, 16, voff, 0, 0, 0);
-}
 // 8 consecutive k (rows of the LDS image, `rs` bytes apart) of this lane's column as one MFMA operand: two transposing
 // reads of 4 rows each.  `p` = this lane's address for the first: row (k0 + q), columns 4p' .. 4p'+3 of its 16-column block.
 __device__ __forceinline__ bf16x8 tr_frag(const char* p, int rs) {
@@ -41,12 +37,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* p, int rs) {
     const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(p + 4 * rs));
     const v8i16 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
-}
-template <int N> __device__ __forceinline__ void wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else static_assert(N < 0, "unsupported count");
 }
 
 struct W16Args {
@@ -137,9 +127,9 @@ __global__ __launch_bounds__(256, 2) void wgrad16_w9_kernel(W16Args g) {
         if (q + 1 < q1 && h + 1 < g.H) {
             issue_x(n, cs, h + 2);
             issue_y(n, cs, h + 1, (q + 1) & 1);
-            wait_vm<3>();
+            wait_vmcnt<3>();
         } else {
-            wait_vm<0>();
+            wait_vmcnt<0>();
         }
         const bf16x8 a = tr_frag(yring + (q & 1) * YSLOT + fo, 64);
 #pragma unroll
@@ -261,9 +251,9 @@ __global__ __launch_bounds__(256, 2) void wgrad16_w1_kernel(W16Args g) {
         if (q == q0) issue(q, q & 1);
         if (q + 1 < q1) {
             issue(q + 1, (q + 1) & 1);
-            wait_vm<4>();
+            wait_vmcnt<4>();
         } else {
-            wait_vm<0>();
+            wait_vmcnt<0>();
         }
         const char* yb = yring + (q & 1) * SLOT;
         const char* xb = xring + (q & 1) * SLOT;
