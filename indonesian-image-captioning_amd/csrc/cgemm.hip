@@ -39,8 +39,9 @@
 //   * split-K into slabs, for shapes whose tile grid alone cannot fill 256 CUs; the slabs are summed in slab order
 //     (deterministic) by the workgroup that arrives last at a tile, inside the launch, epilogue included (round 3; S <= 8),
 //     or by a second launch (deeper splits, scalar stores).
-#include "common.h"
-#include "kernels.h"
+// Block order, the convolution geometry (ConvGeom, row -> pixel, row gather, class-row scatter), the BatchNorm mask term and
+// the slab reducers' column-sum tail are csrc/tile.h, shared with the bf16 twin (csrc/cgemm16.hip).
+#include "tile.h"
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -67,11 +68,7 @@ struct CArgs {
     int S, kper;                  // split-K
     float* ws;
     int mt, nt;                   // tile grid
-    // conv extras
-    int gHi, gWi, gHo, gWo, gs;   // row gather (strided 1x1 convolution); gs == 0: none.  3x3: source / destination maps
-    int c3c;                      // 3x3 modes: channels per tap of the gathered operand (Cin forward / wgrad, Cout dgrad)
-    long src_rows;                // 3x3 modes: rows of the gathered map (N * gHi * gWi)
-    int dHi, dWi;                 // mode 4: extent of the d-input map the rows are scattered into
+    ConvGeom geo;                 // conv extras: row gather of a strided 1x1 convolution, 3x3 source / destination maps
     const float* pro_ss;          // interleaved {scale, shift} per channel: PRO 1 per k (A), PRO 2 per n (B)
     float* stat_partial; const float* stat_shift;       // [2][N][ldp]: channel-major, one entry per 64-row block (chunk)
     int ldp;                      // leading dimension of stat_partial: cdiv(M, 64) rounded up to 4 (cgemm_stat_ld)
@@ -121,13 +118,8 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
     const int wm = W41 ? wave : wave >> 1, wn = W41 ? 0 : wave & 1;
     const int hh = lane >> 5, l31 = lane & 31;
 
-    // ---- XCD-aware tile order (speed only): blocks b, b+8, b+16 ... share an XCD ---------------------------
     const int ntiles = g.mt * g.nt;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles >> 3, r = ntiles & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_order(blockIdx.x, ntiles);
     const int tm = bid / g.nt, tn = bid - tm * g.nt;
     const int m0 = tm * TM, n0 = tn * (W41 ? 64 : TN);      // 4 x 1 layout: 64-column tiles
     const int cls = C3 == 4 ? 3 - (int)blockIdx.y : 0, ph = cls >> 1, pw = cls & 1, ntw = 1 + pw;   // mode 4: parity class, the 4-tap one dispatched first
@@ -135,15 +127,15 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
     const float* A = g.A + (long)zb * g.sA;
     const float* B = g.B + (long)zb * g.sB;
     float* C = g.C + (long)zb * g.sC;
-    const int kbeg = sp * g.kper, Kend = C3 == 4 ? (1 + ph) * ntw * g.c3c : min(g.K, kbeg + g.kper);
+    const int kbeg = sp * g.kper, Kend = C3 == 4 ? (1 + ph) * ntw * g.geo.c3c : min(g.K, kbeg + g.kper);
     const int nk = (Kend - kbeg + TK - 1) / TK;
 
-    const long a_elems = (C3 == 1 || C3 == 2 || C3 == 4) ? g.src_rows * g.lda
+    const long a_elems = (C3 == 1 || C3 == 2 || C3 == 4) ? g.geo.src_rows * g.lda
                          : A_MC ? ((long)(g.K - 1) * g.lda + g.M)
-                                : (GATHER ? (gather_row(g, g.M - 1) * g.lda + g.K) : ((long)(g.M - 1) * g.lda + g.K));
-    const long b_elems = C3 == 3 ? g.src_rows * g.ldb
+                                : (GATHER ? (gather_row(g.geo, g.M - 1) * g.lda + g.K) : ((long)(g.M - 1) * g.lda + g.K));
+    const long b_elems = C3 == 3 ? g.geo.src_rows * g.ldb
                          : (C3 == 2 || C3 == 4) ? (long)(g.K / 9) * g.ldb
-                         : B_MC ? ((GATHER && A_MC ? gather_row(g, g.K - 1) : (long)(g.K - 1)) * g.ldb + g.N)
+                         : B_MC ? ((GATHER && A_MC ? gather_row(g.geo, g.K - 1) : (long)(g.K - 1)) * g.ldb + g.N)
                                 : ((long)(g.N - 1) * g.ldb + g.K);
     const __amdgpu_buffer_rsrc_t ars = make_rsrc(A, (unsigned)(a_elems * 4));
     const __amdgpu_buffer_rsrc_t brs = make_rsrc(B, (unsigned)(b_elems * 4));
@@ -162,17 +154,16 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
             const int row = chunk * 16 + (lane >> 2), gsrc = (lane & 3) ^ ((row >> 2) & 3);
             const int grow = m0 + row;
             a_ok[c] = grow < g.M;
-            const int r = a_ok[c] ? grow : 0, hw = g.gHo * g.gWo;
-            const int n = r / hw, rem = r - n * hw, hd = rem / g.gWo, wd = rem - hd * g.gWo;
-            a_nb[c] = n * g.gHi * g.gWi;
-            a_h0[c] = C3 == 4 ? hd : hd * g.gs - 1;
-            a_w0[c] = C3 == 4 ? wd : wd * g.gs - 1;
+            const Pixel p = pixel_of(a_ok[c] ? grow : 0, g.geo.Ho, g.geo.Wo);
+            a_nb[c] = p.n * g.geo.Hi * g.geo.Wi;
+            a_h0[c] = C3 == 4 ? p.h : p.h * g.geo.s - 1;
+            a_w0[c] = C3 == 4 ? p.w : p.w * g.geo.s - 1;
             a_off[c] = (unsigned)(gsrc * 16);
         } else if (!A_MC) {
             const int row = chunk * 16 + (lane >> 2), gsrc = (lane & 3) ^ ((row >> 2) & 3);
             const int grow = m0 + row;
             a_ok[c] = grow < g.M;
-            const long src = (GATHER ? gather_row(g, a_ok[c] ? grow : 0) : (long)grow) * g.lda + gsrc * 4;
+            const long src = (GATHER ? gather_row(g.geo, a_ok[c] ? grow : 0) : (long)grow) * g.lda + gsrc * 4;
             a_off[c] = (unsigned)(src * 4);
         } else if (TM == 128) {
             const int col = m0 + 4 * (lane & 31);
@@ -211,17 +202,17 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
             const int chunk = wave * ACH + c;
             unsigned va;
             if (C3 == 4) {                  // class tap t = (th, tw): source pixel (ho' + oh, wo' + ow)
-                const int t = k0 / g.c3c, c0 = k0 - t * g.c3c, th = t / ntw, tw = t - th * ntw;
+                const int t = k0 / g.geo.c3c, c0 = k0 - t * g.geo.c3c, th = t / ntw, tw = t - th * ntw;
                 const int hi = a_h0[c] + ((ph && th == 0) ? 1 : 0), wi = a_w0[c] + ((pw && tw == 0) ? 1 : 0);
-                const bool ok = a_ok[c] && k0 < Kend && hi < g.gHi && wi < g.gWi;
-                va = ok ? (unsigned)(((long)(a_nb[c] + hi * g.gWi + wi) * g.lda + c0) * 4) + a_off[c] : OOB_OFF;
+                const bool ok = a_ok[c] && k0 < Kend && hi < g.geo.Hi && wi < g.geo.Wi;
+                va = ok ? (unsigned)(((long)(a_nb[c] + hi * g.geo.Wi + wi) * g.lda + c0) * 4) + a_off[c] : OOB_OFF;
             } else if (C3 == 1 || C3 == 2) {       // k-step -> one tap (c3c % 16 == 0), channels c0 .. c0+15 of it
-                const int tap = k0 / g.c3c, c0 = k0 - tap * g.c3c;
+                const int tap = k0 / g.geo.c3c, c0 = k0 - tap * g.geo.c3c;
                 int dh = tap / 3, dw = tap - 3 * dh;
                 if (C3 == 2) { dh = 2 - dh; dw = 2 - dw; }
                 const int hi = a_h0[c] + dh, wi = a_w0[c] + dw;
-                const bool ok = a_ok[c] && k0 < Kend && (unsigned)hi < (unsigned)g.gHi && (unsigned)wi < (unsigned)g.gWi;
-                va = ok ? (unsigned)(((long)(a_nb[c] + hi * g.gWi + wi) * g.lda + c0) * 4) + a_off[c] : OOB_OFF;
+                const bool ok = a_ok[c] && k0 < Kend && (unsigned)hi < (unsigned)g.geo.Hi && (unsigned)wi < (unsigned)g.geo.Wi;
+                va = ok ? (unsigned)(((long)(a_nb[c] + hi * g.geo.Wi + wi) * g.lda + c0) * 4) + a_off[c] : OOB_OFF;
             } else if (!A_MC) {
                 const int kk = k0 + 4 * ((lane & 3) ^ (((chunk * 16 + (lane >> 2)) >> 2) & 3));
                 va = (a_ok[c] && kk < Kend) ? a_off[c] + (unsigned)k0 * 4u : OOB_OFF;
@@ -241,21 +232,20 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
             } else {
                 const int kr = k0 + chunk * 2 + (lane >> 5);
                 if (C3 == 4) {            // B row k = (class tap t, co): the weight tap is (dh, dw) = (ph ? 2*th : 1, pw ? 2*tw : 1)
-                    const int t = k0 / g.c3c, co = kr - t * g.c3c, th = t / ntw, tw = t - th * ntw;
+                    const int t = k0 / g.geo.c3c, co = kr - t * g.geo.c3c, th = t / ntw, tw = t - th * ntw;
                     const int tap = (ph ? 2 * th : 1) * 3 + (pw ? 2 * tw : 1);
                     vb = (b_ok[c] && kr < Kend) ? (unsigned)(((long)co * g.ldb + (long)tap * g.N + n0 + 4 * (lane & 31)) * 4) : OOB_OFF;
                 } else if (C3 == 2) {            // B row k = (tap, co) of W[co][tap][ci]: co*ldb + tap*Cin + ci
-                    const int tap = k0 / g.c3c, co = kr - tap * g.c3c;
+                    const int tap = k0 / g.geo.c3c, co = kr - tap * g.geo.c3c;
                     vb = (b_ok[c] && kr < Kend) ? (unsigned)(((long)co * g.ldb + (long)tap * g.N + n0 + 4 * (lane & 31)) * 4) : OOB_OFF;
                 } else if (C3 == 3) {     // B k-row r = output pixel; the column tile fixes the tap (c3c % 128 == 0)
-                    const int tap = n0 / g.c3c, ci0 = n0 - tap * g.c3c, dh = tap / 3, dw = tap - 3 * dh;
-                    const int r = kr < Kend ? kr : 0, hw = g.gHo * g.gWo;
-                    const int n = r / hw, rem = r - n * hw, ho = rem / g.gWo, wo = rem - ho * g.gWo;
-                    const int hi = ho * g.gs + dh - 1, wi = wo * g.gs + dw - 1;
-                    const bool ok = b_ok[c] && kr < Kend && (unsigned)hi < (unsigned)g.gHi && (unsigned)wi < (unsigned)g.gWi;
-                    vb = ok ? (unsigned)(((long)(n * g.gHi * g.gWi + hi * g.gWi + wi) * g.ldb + ci0 + 4 * (lane & 31)) * 4) : OOB_OFF;
+                    const int tap = n0 / g.geo.c3c, ci0 = n0 - tap * g.geo.c3c, dh = tap / 3, dw = tap - 3 * dh;
+                    const Pixel p = pixel_of(kr < Kend ? kr : 0, g.geo.Ho, g.geo.Wo);
+                    const int n = p.n, hi = p.h * g.geo.s + dh - 1, wi = p.w * g.geo.s + dw - 1;
+                    const bool ok = b_ok[c] && kr < Kend && (unsigned)hi < (unsigned)g.geo.Hi && (unsigned)wi < (unsigned)g.geo.Wi;
+                    vb = ok ? (unsigned)(((long)(n * g.geo.Hi * g.geo.Wi + hi * g.geo.Wi + wi) * g.ldb + ci0 + 4 * (lane & 31)) * 4) : OOB_OFF;
                 } else if (GATHER && A_MC) {     // wgrad of a strided convolution: k-rows of B = gathered rows of the input map
-                    const long src = gather_row(g, kr < Kend ? kr : 0) * g.ldb + n0 + 4 * (lane & 31);
+                    const long src = gather_row(g.geo, kr < Kend ? kr : 0) * g.ldb + n0 + 4 * (lane & 31);
                     vb = (b_ok[c] && kr < Kend) ? (unsigned)(src * 4) : OOB_OFF;
                 } else {
                     vb = (b_ok[c] && kr < Kend) ? b_off[c] + (unsigned)((long)k0 * g.ldb * 4) : OOB_OFF;
@@ -487,11 +477,7 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
     const __amdgpu_buffer_rsrc_t ors = make_rsrc(c_base, VEC ? (unsigned)(((long)((C3 == 4 ? 4 * g.M : g.M) - 1) * c_ld + g.N) * 4) : 0u);
     auto row_off = [&](int m) -> unsigned {
         if (!(m < g.M && cok)) return OOB_OFF;
-        long rr = m;
-        if (C3 == 4) {      // class row (n, ho', wo') -> d-input row (n, 2 ho' + ph, 2 wo' + pw)
-            const int hw = g.gHo * g.gWo, n = m / hw, rem = m - n * hw, hd = rem / g.gWo, wd = rem - hd * g.gWo;
-            rr = ((long)n * g.dHi + 2 * hd + ph) * g.dWi + 2 * wd + pw;
-        }
+        const long rr = C3 == 4 ? class_row_scatter(g.geo, m, ph, pw) : m;
         return (unsigned)((rr * c_ld + ncol) * 4) + opq;
     };
     // one 32-row block of this wave from the accumulators into the transpose region
@@ -601,8 +587,8 @@ __global__ __launch_bounds__(256, MI == 2 ? 2 : 3) void cgemm_kernel(CArgs g) {
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const float z = xv[u][q], xh = (z - kv0[q]) * kv1[q];
-                    const bool on = fmaf(folded ? z : xh, kv2[q], kv3[q]) > 0.f;
+                    float xh;
+                    const bool on = bn_relu_on(xv[u][q], kv0[q], kv1[q], kv2[q], kv3[q], folded, xh);
                     v[u][q] = on ? v[u][q] : 0.f;
                     fs1[q] += v[u][q];
                     fs2[q] = fmaf(v[u][q], xh, fs2[q]);
@@ -1018,9 +1004,8 @@ __global__ __launch_bounds__(256) void cstats_kernel(CArgs g) {
             if (MODE == 2) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float xh = (zz[u][k] - mu[k]) * is[k];
-                    const bool on = folded ? (fmaf(zz[u][k], ga[k], be[k]) > 0.f) : (fmaf(xh, ga[k], be[k]) > 0.f);
-                    if (!on) v[u][k] = 0.f;
+                    float xh;
+                    if (!bn_relu_on(zz[u][k], mu[k], is[k], ga[k], be[k], folded, xh)) v[u][k] = 0.f;
                     s1[k] += v[u][k];
                     s2[k] = fmaf(v[u][k], xh, s2[k]);
                 }
@@ -1035,21 +1020,7 @@ __global__ __launch_bounds__(256) void cstats_kernel(CArgs g) {
             *reinterpret_cast<f32x4*>(g.C + (long)r * g.ldc + c) = v[u];
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        red[rl][0][cl * 4 + k] = s1[k];
-        red[rl][1][cl * 4 + k] = s2[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        const int which = threadIdx.x >> 6, cc = threadIdx.x & 63;
-        if (blockIdx.x * 64 + cc < g.N) {
-            float t = red[0][which][cc];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) t += red[i][which][cc];
-            g.stat_partial[((long)which * g.N + blockIdx.x * 64 + cc) * g.ldp + blockIdx.y] = t;
-        }
-    }
+    slab_colsum_tail(g, red, s1, s2);
 }
 
 }  // namespace
@@ -1258,9 +1229,7 @@ int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, co
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = sA; g.sB = sB; g.sC = sC;
     g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.S = S; g.kper = kper; g.ws = ws; g.mt = mt; g.nt = nt;
     if (ex) {
-        g.gHi = ex->Hi; g.gWi = ex->Wi; g.gHo = ex->Ho; g.gWo = ex->Wo; g.gs = (gather || c3) ? ex->stride : 0;
-        g.c3c = ex->c3c; g.src_rows = ex->c3_src_rows;
-        if (c3 == 4) { g.gHi = ex->Ho; g.gWi = ex->Wo; g.dHi = ex->Hi; g.dWi = ex->Wi; }   // gathered map = dY (Ho x Wo)
+        g.geo = conv_geom(*ex);
         g.pro_ss = ex->pro_ss;
         g.stat_partial = ex->stat_partial; g.stat_shift = ex->stat_shift; g.ldp = cgemm_stat_ld(M);
         g.ez = ex->ez; g.emean = ex->emean; g.einvstd = ex->einvstd; g.egamma = ex->egamma; g.ebeta = ex->ebeta; g.ldz = ex->ldz;

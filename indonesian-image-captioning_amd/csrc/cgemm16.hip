@@ -12,15 +12,16 @@
 //             in csrc/cgemm.hip);
 // so the m/n-contiguous LDS image and its transposed reads are needed only by the weight gradients (csrc/wgrad16.hip).
 //
-// Structure = csrc/cgemm.hip's: 128 x 128 (or 64 x 128) block tile, 4 waves as 2 x 2, LDS-DMA 3-stage ring with ONE raw
+// Structure = csrc/cgemm.hip's; block order, the convolution geometry, the BatchNorm mask term and the slab reducer's
+// column-sum tail are the same code (csrc/tile.h), the rest is this file's own:
+// 128 x 128 (or 64 x 128) block tile, 4 waves as 2 x 2, LDS-DMA 3-stage ring with ONE raw
 // s_barrier per k-step and a counted vmcnt, XCD-aware tile order, [row][64-byte] LDS image with the 16-byte granules
 // XOR-swizzled on the SOURCE address.  A k-step is 32 bf16 = the same 64 bytes per row, so every address computation is
 // the fp32 kernel's in bytes; the fragment of v_mfma_f32_32x32x16_bf16 (lane (r, h): k = 8h .. 8h+7) is ONE 16-byte granule,
 // one conflict-free ds_read_b128 per 32-row block and 16 k.  The matrix work per k-step is 8x shorter than in fp32 (8
 // instructions of 32 cycles against 32 of 64), so this kernel is bound by its fill / epilogue / launch, not by the matrix
 // pipes: what it buys is half the bytes of every map.
-#include "common.h"
-#include "kernels.h"
+#include "tile.h"
 
 namespace scn {
 
@@ -43,10 +44,7 @@ struct HArgs {
     int S, kper;
     float* ws;
     int mt, nt;
-    int gHi, gWi, gHo, gWo, gs;   // row gather (strided 1x1) / 3x3 source and destination maps
-    int c3c;                      // 3x3 modes: channels per tap of the gathered operand
-    long src_rows;
-    int dHi, dWi;                 // mode 4: extent of the d-input map the rows are scattered into
+    ConvGeom geo;                 // row gather (strided 1x1) / 3x3 source and destination maps
     int flip;                     // mode 1: weight tap = 8 - t (a stride-1 d input as a forward convolution of dY)
     float* stat_partial; const float* stat_shift; int ldp;
     const bf16_t* ez; long ldz; const float* emean; const float* einvstd; const float* egamma; const float* ebeta;   // EPI 2
@@ -74,21 +72,17 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
     const int hh = lane >> 5, l31 = lane & 31;
 
     const int ntiles = g.mt * g.nt;
-    int bid = blockIdx.x;
-    {
-        const int q = ntiles >> 3, r = ntiles & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_order(blockIdx.x, ntiles);
     const int tm = bid / g.nt, tn = bid - tm * g.nt;
     const int m0 = tm * TM, n0 = tn * TN;
     const int cls = C3 == 4 ? 3 - (int)blockIdx.y : 0, ph = cls >> 1, pw = cls & 1, ntw = 1 + pw;
     const int sp = C3 == 4 ? 0 : blockIdx.y;
-    const int kbeg = sp * g.kper, Kend = C3 == 4 ? (1 + ph) * ntw * g.c3c : min(g.K, kbeg + g.kper);
+    const int kbeg = sp * g.kper, Kend = C3 == 4 ? (1 + ph) * ntw * g.geo.c3c : min(g.K, kbeg + g.kper);
     const int nk = (Kend - kbeg + TKE - 1) / TKE;
 
-    const long a_elems = (C3 == 1 || C3 == 4) ? g.src_rows * g.lda
-                         : (GATHER ? (gather_row(g, g.M - 1) * g.lda + g.K) : ((long)(g.M - 1) * g.lda + g.K));
-    const long b_elems = (long)(g.N - 1) * g.ldb + (C3 ? 9L * g.c3c : g.K);
+    const long a_elems = (C3 == 1 || C3 == 4) ? g.geo.src_rows * g.lda
+                         : (GATHER ? (gather_row(g.geo, g.M - 1) * g.lda + g.K) : ((long)(g.M - 1) * g.lda + g.K));
+    const long b_elems = (long)(g.N - 1) * g.ldb + (C3 ? 9L * g.geo.c3c : g.K);
     const __amdgpu_buffer_rsrc_t ars = make_rsrc(g.A, (unsigned)(a_elems * 2));
     const __amdgpu_buffer_rsrc_t brs = make_rsrc(g.B, (unsigned)(b_elems * 2));
 
@@ -104,14 +98,13 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
         a_ok[c] = grow < g.M;
         a_g[c] = gsrc;
         if (C3 == 1 || C3 == 4) {
-            const int r = a_ok[c] ? grow : 0, hw = g.gHo * g.gWo;
-            const int n = r / hw, rem = r - n * hw, hd = rem / g.gWo, wd = rem - hd * g.gWo;
-            a_nb[c] = n * g.gHi * g.gWi;
-            a_h0[c] = C3 == 4 ? hd : hd * g.gs - 1;
-            a_w0[c] = C3 == 4 ? wd : wd * g.gs - 1;
+            const Pixel p = pixel_of(a_ok[c] ? grow : 0, g.geo.Ho, g.geo.Wo);
+            a_nb[c] = p.n * g.geo.Hi * g.geo.Wi;
+            a_h0[c] = C3 == 4 ? p.h : p.h * g.geo.s - 1;
+            a_w0[c] = C3 == 4 ? p.w : p.w * g.geo.s - 1;
             a_off[c] = (unsigned)(gsrc * 16);
         } else {
-            const long src = (GATHER ? gather_row(g, a_ok[c] ? grow : 0) : (long)grow) * g.lda * 2 + gsrc * 16;
+            const long src = (GATHER ? gather_row(g.geo, a_ok[c] ? grow : 0) : (long)grow) * g.lda * 2 + gsrc * 16;
             a_off[c] = (unsigned)src;
         }
     }
@@ -132,11 +125,11 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
         // 3x3 modes: a k-step is 32 channels of ONE tap (c3c % 32 == 0)
         int t = 0, c0 = 0, wt = 0, oh = 0, ow = 0;
         if (C3 == 1) {
-            t = k0 / g.c3c; c0 = k0 - t * g.c3c;
+            t = k0 / g.geo.c3c; c0 = k0 - t * g.geo.c3c;
             oh = t / 3; ow = t - 3 * oh;                   // source pixel offset (oh - 1, ow - 1) from a_h0 / a_w0
             wt = g.flip ? 8 - t : t;
         } else if (C3 == 4) {
-            t = k0 / g.c3c; c0 = k0 - t * g.c3c;
+            t = k0 / g.geo.c3c; c0 = k0 - t * g.geo.c3c;
             const int th = t / ntw, tw = t - th * ntw;
             oh = (ph && th == 0) ? 1 : 0; ow = (pw && tw == 0) ? 1 : 0;
             wt = (ph ? 2 * th : 1) * 3 + (pw ? 2 * tw : 1);
@@ -147,8 +140,8 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
             unsigned va;
             if (C3 == 1 || C3 == 4) {
                 const int hi = a_h0[c] + oh, wi = a_w0[c] + ow;
-                const bool ok = a_ok[c] && k0 < Kend && (unsigned)hi < (unsigned)g.gHi && (unsigned)wi < (unsigned)g.gWi;
-                va = ok ? (unsigned)(((long)(a_nb[c] + hi * g.gWi + wi) * g.lda + c0) * 2) + a_off[c] : OOB_OFF;
+                const bool ok = a_ok[c] && k0 < Kend && (unsigned)hi < (unsigned)g.geo.Hi && (unsigned)wi < (unsigned)g.geo.Wi;
+                va = ok ? (unsigned)(((long)(a_nb[c] + hi * g.geo.Wi + wi) * g.lda + c0) * 2) + a_off[c] : OOB_OFF;
             } else {
                 va = (a_ok[c] && k0 + 8 * a_g[c] < Kend) ? a_off[c] + (unsigned)k0 * 2u : OOB_OFF;
             }
@@ -158,7 +151,7 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
         for (int c = 0; c < 2; ++c) {
             const int chunk = wave * 2 + c;
             unsigned vb;
-            if (C3) vb = (b_ok[c] && k0 < Kend) ? b_off[c] + (unsigned)((wt * g.c3c + c0) * 2) : OOB_OFF;
+            if (C3) vb = (b_ok[c] && k0 < Kend) ? b_off[c] + (unsigned)((wt * g.geo.c3c + c0) * 2) : OOB_OFF;
             else    vb = (b_ok[c] && k0 + 8 * b_g[c] < Kend) ? b_off[c] + (unsigned)k0 * 2u : OOB_OFF;
             dma16(brs, sb + chunk * 256, vb);
         }
@@ -218,11 +211,7 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
     float* const colsum = lds + 4 * 2048;          // [wm][2][TN] (MI = 1 only)
     const long c_ld = g.S > 1 ? (long)g.N : g.ldc;
     const long out_rows = C3 == 4 ? 4L * g.M : g.M;
-    auto row_of = [&](int m) -> long {
-        if (C3 != 4) return m;
-        const int hw = g.gHo * g.gWo, n = m / hw, rem = m - n * hw, hd = rem / g.gWo, wd = rem - hd * g.gWo;
-        return ((long)n * g.dHi + 2 * hd + ph) * g.dWi + 2 * wd + pw;
-    };
+    auto row_of = [&](int m) -> long { return C3 == 4 ? class_row_scatter(g.geo, m, ph, pw) : m; };
     auto dump_half = [&](int i) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -343,8 +332,9 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
                     for (int q = 0; q < 8; ++q) {
                         const unsigned w = zv[it][q >> 1];
                         const float z = bf16_to_f32((q & 1) ? (w >> 16) : (w & 0xffffu));
-                        const float xh = (z - mu[q]) * is[q];
-                        const bool on = m < g.M && fmaf(xh, ga[q], be[q]) > 0.f;     // the forward pass's expression (csrc/batchnorm.hip)
+                        float xh;
+                        const bool pos = bn_relu_on(z, mu[q], is[q], ga[q], be[q], false, xh);     // the forward pass's expression (csrc/batchnorm.hip)
+                        const bool on = m < g.M && pos;
                         // the sums are taken of the bf16 rounding of g: what the consumers will read
                         vv[q] = on ? bf16_to_f32(pack2(vv[q], 0.f) & 0xffffu) : 0.f;
                         s1[q] += vv[q];
@@ -484,22 +474,7 @@ __global__ __launch_bounds__(256) void creduce16_kernel(HArgs g) {
             }
         }
     }
-    if (!STATS) return;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        red[rl][0][cl * 4 + k] = s1[k];
-        red[rl][1][cl * 4 + k] = s2[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 128) {
-        const int which = threadIdx.x >> 6, cc = threadIdx.x & 63;
-        if (blockIdx.x * 64 + cc < g.N) {
-            float t = red[0][which][cc];
-#pragma unroll
-            for (int i = 1; i < 16; ++i) t += red[i][which][cc];
-            g.stat_partial[((long)which * g.N + blockIdx.x * 64 + cc) * g.ldp + blockIdx.y] = t;
-        }
-    }
+    if (STATS) slab_colsum_tail(g, red, s1, s2);
 }
 
 template <int MI, int C3>
@@ -570,9 +545,7 @@ int cgemm16(hipStream_t st, int M, int N, int K, const void* A, long lda, const 
     g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.M = M; g.N = N; g.K = K; g.beta = beta; g.S = S; g.kper = kper; g.ws = ws; g.mt = mt; g.nt = nt; g.flip = flip;
     if (ex) {
-        g.gHi = ex->Hi; g.gWi = ex->Wi; g.gHo = ex->Ho; g.gWo = ex->Wo; g.gs = (gather || c3) ? ex->stride : 0;
-        g.c3c = ex->c3c; g.src_rows = ex->c3_src_rows;
-        if (c3 == 4) { g.gHi = ex->Ho; g.gWi = ex->Wo; g.dHi = ex->Hi; g.dWi = ex->Wi; }
+        g.geo = conv_geom(*ex);
         g.stat_partial = ex->stat_partial; g.stat_shift = ex->stat_shift; g.ldp = cgemm_stat_ld(M);
         g.ez = (const bf16_t*)ex->ez; g.ldz = ex->ldz; g.emean = ex->emean; g.einvstd = ex->einvstd; g.egamma = ex->egamma; g.ebeta = ex->ebeta;
     }

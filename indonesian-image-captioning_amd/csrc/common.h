@@ -136,15 +136,6 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// output row (n, ho, wo) of a strided 1x1 convolution -> input row (n, ho*s, wo*s); Args: the kernel's argument struct
-template <class Args> __device__ __forceinline__ long gather_row(const Args& g, int r) {
-    if (g.gs == 0) return r;
-    const int hw = g.gHo * g.gWo;
-    const int n = r / hw, rem = r - n * hw;
-    const int ho = rem / g.gWo, wo = rem - ho * g.gWo;
-    return (long)n * g.gHi * g.gWi + (long)(ho * g.gs) * g.gWi + wo * g.gs;
-}
-
 // row (0..31) of accumulator register r of lane l in a 32x32 f32 MFMA C/D tile; column is l & 31.
 __device__ __forceinline__ int mfma32_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 

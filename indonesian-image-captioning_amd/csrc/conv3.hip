@@ -22,10 +22,10 @@
 //   * a 32 x 32 x 9 block per workgroup means many small tiles: (Cout/32) x (Cin/32) = 16 / 64 / 256 of them for layer2 /
 //     3 / 4, so a 512-workgroup grid needs only 32 / 8 / 2 K-slices whose slabs are 19 MB in all (the 128 x 128 tiling
 //     needed ~50 MB), reduced by the same slab-order pass the GEMMs use.  layer4 can run with no slabs at all.
+// Block order and the split policy are shared with the bf16 twin (csrc/wgrad16.hip) through csrc/tile.h.
 // LDS: 53 KB (SEG 16) / 29 KB (SEG 8) per workgroup, ~170 VGPRs -> two workgroups per CU, or one beside a cgemm workgroup
 // of the main stream.
-#include "common.h"
-#include "kernels.h"
+#include "tile.h"
 
 namespace scn {
 
@@ -58,11 +58,7 @@ __global__ __launch_bounds__(256, 2) void conv3_wgrad_kernel(W3Args g) {
     // XCD-aware order (speed only): an XCD owns contiguous virtual ids = whole K slices, so a slice's dY / X lines are
     // fetched into ONE L2 and shared there by every (co, ci) tile
     const int total = g.ntiles * g.S;
-    int v;
-    {
-        const int bid = blockIdx.x, q = total >> 3, r = total & 7, xcd = bid & 7, idx = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int v = xcd_order(blockIdx.x, total);
     const int ks = v / g.ntiles, tile = v - ks * g.ntiles;
     const int tco = tile / g.tci, tci = tile - tco * g.tci;
     const int co0 = tco * 32, ci0 = tci * 32;
@@ -191,12 +187,7 @@ int conv3x3_wgrad_halo(hipStream_t st, int N, int H, int W, int C, int Co, const
     g.Q = N * g.nseg * H;
     g.tci = C / 32;
     g.ntiles = (Co / 32) * g.tci;
-    int S = force_split > 0 ? force_split : (g_w3_target + g.ntiles / 2) / g.ntiles;
-    const int smax = g.Q / 16 > 0 ? g.Q / 16 : 1;       // at least 4 lines per wave
-    if (S > smax) S = smax;
-    if (S < 1) S = 1;
-    const long mn = (long)Co * 9 * C;
-    while (S > 1 && (!ws || (long)S * mn > ws_floats)) --S;
+    const int S = wgrad_split(g.ntiles, g.Q, g_w3_target, (long)Co * 9 * C, ws, ws_floats, force_split);
     SCN_ARG(force_split <= 0 || S == force_split, "conv3x3_wgrad_halo: forced split does not fit the workspace / the map");
     g.S = S;
     g.out = S > 1 ? ws : dw;

@@ -8,7 +8,8 @@
 // load ds_read_b64_tr_b16 (a 4-row x 16-column block per 16 lanes, delivered column-major): the maps are staged as they
 // lie in memory -- one LDS-DMA instruction moves 16 pixels x 32 channels -- and no transposed copy of any map exists.
 //
-// Structure = csrc/conv3.hip's (fp32 halo-staged weight gradient): a wave owns a block of dW, walks its share of the
+// Structure = csrc/conv3.hip's (fp32 halo-staged weight gradient; block order, the row -> pixel decode and the host's
+// split policy are the same code, csrc/tile.h): a wave owns a block of dW, walks its share of the
 // pixels line by line (16 pixels = ONE matrix instruction per tap) with wave-private LDS rings and NO s_barrier in the
 // loop; the four waves of a workgroup own the same block, split K and meet in LDS at the end (fixed order).
 //   w9: stride-1 3x3: 32(co) x 32(ci) x 9 taps per wave, activation lines staged once with their halo and read at nine
@@ -16,8 +17,7 @@
 //   w1: everything else: a 64 x 64 block of one [Cout][Cin] slice over rows that may be GATHERED -- plain 1x1 weight
 //       gradients, the strided 1x1 downsample, and a stride-2 3x3 (layerN.0) as nine launches, one per tap, whose source
 //       pixel (2 ho + dh - 1, 2 wo + dw - 1) is a per-lane row index (out-of-image = out-of-range = zeros).
-#include "common.h"
-#include "kernels.h"
+#include "tile.h"
 
 namespace scn {
 
@@ -66,11 +66,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_w9_kernel(W16Args g) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31;
     const int total = g.ntiles * g.S;
-    int v;
-    {
-        const int bid = blockIdx.x, q = total >> 3, r = total & 7, xcd = bid & 7, idx = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int v = xcd_order(blockIdx.x, total);
     const int ks = v / g.ntiles, tile = v - ks * g.ntiles;
     const int tco = tile / g.tci, tci = tile - tco * g.tci;
     const int co0 = tco * 32, ci0 = tci * 32;
@@ -182,11 +178,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_w1_kernel(W16Args g) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31;
     const int total = g.ntiles * g.S;
-    int v;
-    {
-        const int bid = blockIdx.x, q = total >> 3, r = total & 7, xcd = bid & 7, idx = bid >> 3;
-        v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int v = xcd_order(blockIdx.x, total);
     const int ks = v / g.ntiles, tile = v - ks * g.ntiles;
     const int tco = tile / g.tci, tci = tile - tco * g.tci;
     const int co0 = tco * 64, ci0 = tci * 64;
@@ -215,11 +207,10 @@ __global__ __launch_bounds__(256, 2) void wgrad16_w1_kernel(W16Args g) {
             long src = r;
             bool sok = ok;
             if (g.gs > 0 && ok) {
-                const int hw = g.gHo * g.gWo;
-                const int n = (int)(r / hw), rem = (int)(r - (long)n * hw), ho = rem / g.gWo, wo = rem - ho * g.gWo;
-                const int hi = ho * g.gs + g.goh, wi = wo * g.gs + g.gow;
+                const Pixel p = pixel_of(r, g.gHo, g.gWo);
+                const int hi = p.h * g.gs + g.goh, wi = p.w * g.gs + g.gow;
                 sok = (unsigned)hi < (unsigned)g.gHi && (unsigned)wi < (unsigned)g.gWi;
-                src = ((long)n * g.gHi + hi) * g.gWi + wi;
+                src = ((long)p.n * g.gHi + hi) * g.gWi + wi;
             }
             dma16(yrs, yd + j * 1024, ok ? (unsigned)((r * g.Co + co0 + 8 * gs_) * 2) : OOB_OFF);
             dma16(xrs, xd + j * 1024, sok ? (unsigned)((src * g.C + ci0 + 8 * gs_) * 2) : OOB_OFF);
@@ -310,12 +301,8 @@ int wgrad16_3x3(hipStream_t st, int N, int H, int W, int C, int Co, const void* 
     g.Q = N * g.nseg * H;
     g.tci = C / 32;
     g.ntiles = (Co / 32) * g.tci;
-    int S = force_split > 0 ? force_split : (512 + g.ntiles / 2) / g.ntiles;
-    const int smax = g.Q / 16 > 0 ? g.Q / 16 : 1;
-    if (S > smax) S = smax;
-    if (S < 1) S = 1;
     const long mn = (long)Co * 9 * C;
-    while (S > 1 && (!ws || (long)S * mn > ws_floats)) --S;
+    const int S = wgrad_split(g.ntiles, g.Q, 512, mn, ws, ws_floats, force_split);
     SCN_ARG(force_split <= 0 || S == force_split, "wgrad16_3x3: forced split does not fit");
     g.S = S; g.ldo = 9L * C; g.slab_ld = 9L * C; g.slab_stride = mn;
     g.out = S > 1 ? ws : dw;
@@ -339,12 +326,8 @@ int wgrad16_rows(hipStream_t st, int R, int C, int Co, const void* dy, const voi
     g.Q = (R + 15) / 16;
     g.tci = C / 64;
     g.ntiles = (Co / 64) * g.tci;
-    int S = force_split > 0 ? force_split : (512 + g.ntiles / 2) / g.ntiles;
-    const int smax = g.Q / 16 > 0 ? g.Q / 16 : 1;       // at least 4 lines per wave
-    if (S > smax) S = smax;
-    if (S < 1) S = 1;
     const long mn = (long)Co * C;
-    while (S > 1 && (!ws || (long)S * mn > ws_floats)) --S;
+    const int S = wgrad_split(g.ntiles, g.Q, 512, mn, ws, ws_floats, force_split);
     SCN_ARG(force_split <= 0 || S == force_split, "wgrad16_rows: forced split does not fit");
     g.S = S; g.ldo = ldo; g.slab_ld = C; g.slab_stride = mn;
     g.out = S > 1 ? ws : dw;

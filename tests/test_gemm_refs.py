@@ -54,7 +54,7 @@ def mirror_skinny(r):
 
 
 def cgemm_supported(r, L):
-    """csrc/cgemm.hip:1122-1133"""
+    """csrc/cgemm.hip:1060-1071"""
     if L["misA"] or L["misB"] or L["lda"] % 4 or L["ldb"] % 4 or L["sA"] % 4 or L["sB"] % 4:
         return False
     if (r.M if r.ta else r.K) % 4 or (r.K if r.tb else r.N) % 4:
@@ -63,7 +63,7 @@ def cgemm_supported(r, L):
 
 
 def mirror_dense(r):
-    """csrc/sgemm.hip:220-273 sgemm_ws and csrc/cgemm.hip:1190-1336 cgemm (plain epilogue, no prologue / gather / 3x3)"""
+    """csrc/sgemm.hip:220-273 sgemm_ws and csrc/cgemm.hip:1128-1272 cgemm (plain epilogue, no prologue / gather / 3x3)"""
     L = T.dg_layout(r)
     ws_floats = T.dg_ws_floats(r)
     o = dict(T.OPTION_DEFAULTS)

@@ -24,17 +24,17 @@ row's `inst` is what the host code picks and that every instance below is reache
                              matrix instruction: whole 16-k blocks, nb even); :271 XVEC = X 16-byte aligned, ldx % 4 == 0,
                              xg % 4 == 0, K % 4 == 0, K >= 4; :273 grid = (ceil(N/32) * groups, ksplit, ceil(rows/32));
                              :294-311 <NB, XVEC, WBF, BFM>.  inst = "nb<NB> c<chunks> v<XVEC> e<empty slices> z<grid.z>"
-  sgemm_ws (csrc/sgemm.hip)  :226 cgemm when use_cgemm and cgemm_supported (csrc/cgemm.hip:1122-1133: A, B 16-byte aligned,
+  sgemm_ws (csrc/sgemm.hip)  :226 cgemm when use_cgemm and cgemm_supported (csrc/cgemm.hip:1060-1071: A, B 16-byte aligned,
                              lda, ldb, sA, sB % 4 == 0, the contiguous extents % 4 == 0); :238-251 S (tiles < 256 and
                              K >= 2 * kmin, kmin = 128 for <= 16 tiles else 256; target 512 workgroups; at most K / kmin, 16,
                              and what fits ws), kper in whole 16s; :255-256 VEC; :269 splitk_reduce_kernel when S > 1.
                              inst = "sgemm v<VEC> S<S>"
-  cgemm (csrc/cgemm.hip)     :1223 vector C store = N % 4 == 0, ldc % 4 == 0, sC % 4 == 0, C 16-byte aligned; :1227-1234 row
+  cgemm (csrc/cgemm.hip)     :1161 vector C store = N % 4 == 0, ldc % 4 == 0, sC % 4 == 0, C 16-byte aligned; :1165-1172 row
                              tile mi (2: 128 rows; 1: 64 rows when the 128-row grid has < 256 tiles and M > 64; 4: 128 x 64
-                             when N <= 64 and M >= 128; option cgemm_mi, ex->force_mi); :1240-1256 S (tiles < 224 and
-                             K >= 256: 512 / tiles, at most K / 128 and what fits ws), :1275-1278 ex->force_split,
-                             :1286-1288 kper in whole 16s; :1308-1310 in-launch combine (finish_block) when S <= 8, vector
-                             store and option cgemm_combine, else :1323-1326 creduce_kernel<vector store>.
+                             when N <= 64 and M >= 128; option cgemm_mi, ex->force_mi); :1178-1194 S (tiles < 224 and
+                             K >= 256: 512 / tiles, at most K / 128 and what fits ws), :1213-1216 ex->force_split,
+                             :1224-1226 kper in whole 16s; :1244-1246 in-launch combine (finish_block) when S <= 8, vector
+                             store and option cgemm_combine, else :1259-1262 creduce_kernel<vector store>.
                              inst = "cgemm mi<mi> S<S> <-|comb|red> <vst|sst>"
 Picking: every value the sizes can take at an edge appears at least once and every instance; sizes and options are otherwise
 paired round-robin instead of as a cross product.  Each row's `why` names the instance or edge it is there for.
