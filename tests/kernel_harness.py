@@ -33,8 +33,8 @@ def _write_report(request):
     fmt = "%%-%ds %%-10s %%-9s %%-6s %%s" % w
     lines = [fmt % ("kernel", "result", "err/bound", "cases", "bound")]
     for (kern, name), (ratio, kind, yard, n) in sorted(_STATS.items()):
-        how = "(n+8)*2^-24*sum|terms|" if kind == "sum" else \
-            "min(4 x CPU-fp32 worst element error [worst seen %.3e], %s x row max)" % (yard, kind)
+        how = "(n+8)*2^-24*sum|terms|" if kind == "sum" else "(n+16)*2^-24*(sum|terms|*|scale|+|mean*scale|+|beta|+|res|)" \
+            if kind == "eval" else "min(4 x CPU-fp32 worst element error [worst seen %.3e], %s x row max)" % (yard, kind)
         lines.append(fmt.replace("%-9s %-6s", "%-9.3f %-6d") % (kern, name, ratio, n, how))
     _report(lines, getattr(request.module, "REPORT_TITLE",
                            "decode-step primitives vs fp64: worst |got - ref| / bound over all cases"))
@@ -101,6 +101,20 @@ def _sum_ok(kernel, name, got, ref):
     assert bool((err <= bound).all()), "%s %s: worst err/bound %.3f at %d, %d NaN" % (
         kernel, name, worst, int(ratio.reshape(-1).nan_to_num(1e30).argmax()), int(got.isnan().sum()))
     _note(kernel, name, worst, "sum")
+
+
+def _bound_ok(kernel, name, got, want, bound, kind="sum"):
+    """|got - want| <= bound per element, for a bound the caller derived (per-slot partials, per-tap n, the eval epilogue);
+    an element whose bound is 0 must be equal, a NaN (an output word never written) fails"""
+    want, bound = want.double(), bound.double().expand(want.shape)
+    got = got.double().reshape(want.shape)
+    err = (got - want).abs()
+    ratio = torch.where(bound > 0, err / bound.clamp_min(1e-300), (err > 0).double() * 1e30)
+    worst = float(ratio.nan_to_num(1e30).max()) if ratio.numel() else 0.0
+    print("%s %s: worst err/bound %.3f" % (kernel, name, worst))
+    assert bool((err <= bound).all()), "%s %s: worst err/bound %.3f at %d, %d NaN" % (
+        kernel, name, worst, int(ratio.reshape(-1).nan_to_num(1e30).argmax()), int(got.isnan().sum()))
+    _note(kernel, name, worst, kind)
 
 
 def _slab_buf(dev, vals, extra_ld=3, extra_stride=5):

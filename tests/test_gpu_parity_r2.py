@@ -598,7 +598,9 @@ def test_cgemm_variants_vs_fp64(dev):
     """csrc/cgemm.hip through the C ABI (scnattn_cgemm): every layout (NT forward, NN dgrad, TN wgrad, TT), both row
     tiles, split-K, the BatchNorm prologues (A per k, B per n), the statistics epilogue, the mask + reduction pass,
     beta accumulation and the strided row gather, on ResNet-152 1x1 shapes and on an odd shape, against fp64 torch:
-    products 3e-6 (1e-5 for the K = rows weight gradients), column statistics 2e-5."""
+    products 3e-6 (1e-5 for the K = rows weight gradients), column statistics 2e-5.
+    A whole-tensor metric at production sizes; the same entry points per element, per partial slot and with the ReLU mask
+    decided exactly, on guarded windows at the smallest shapes: tests/test_gpu_conv_kernels.py."""
     import importlib.util
     import os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
