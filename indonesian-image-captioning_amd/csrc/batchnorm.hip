@@ -11,8 +11,9 @@
 //   backward: bn_bwd_reduce : dbeta = sum g, dgamma = sum g*xhat with g = dy*[y>0]
 //             bn_bwd_dx     : dz = gamma/std * (g - dbeta/R - xhat*dgamma/R),  dresidual = g
 // All are HBM-bound streaming kernels (16-byte loads along C, 4 independent row loads in flight).
-#include "common.h"
-#include "kernels.h"
+#include "tile.h"
+#include <climits>
+#include <type_traits>
 
 namespace scn {
 
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(long n4, int C, const T* 
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float t = fmaf((v[k] - mu[k]) * is[k], ga[k], be[k]);
+            float t = bn_norm(v[k], mu[k], is[k], ga[k], be[k]);
             if (RES) t += rr[k];
             if (RELU) t = fmaxf(t, 0.f);
             o[k] = t;
@@ -176,12 +177,13 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(long n4, int C, const T* 
 }
 
 // partial[chunk][2][C]: sum g, sum g*xhat, g = dy * [y > 0] (RELU) or dy.
-// MASKZ: the ReLU mask is recomputed from z with the forward's own expression, fma((z-mean)*invstd, gamma, beta) > 0,
+// MASKZ: the ReLU mask is recomputed from z with the forward's own expression, bn_norm(z, ...) > 0 (bn_relu_on, tile.h),
 // instead of being read back from y -- valid when no residual was added before the ReLU (bn1/bn2 of a bottleneck);
 // the backward pass then never touches y (one 4-byte read per element less in each of its two passes).
 // GOUT: the masked gradient g is also WRITTEN (it is the gradient of the residual branch, an output of the backward pass
 // anyway): the element-wise second pass then reads g and z only -- not dy and y again -- and writes dz only: 7 map
 // transfers per BatchNorm(+residual)+ReLU backward instead of 8.
+// gout may be dy (in place; kernels.h): each thread reads an element before it writes it.
 template <typename T, bool RELU, bool MASKZ, bool GOUT = false>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(int R, int C, int rows_per_chunk, const T* __restrict__ dy,
                                                             const T* __restrict__ y, const T* __restrict__ z,
@@ -220,9 +222,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(int R, int C, int ro
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     float gv = g[j][k];
-                    const float xh = (zz[j][k] - mu[k]) * is[k];
+                    float xh = bn_xhat(zz[j][k], mu[k], is[k]);
                     if (RELU) {
-                        const bool on = MASKZ ? (fmaf(xh, ga[k], be[k]) > 0.f) : (yy[j][k] > 0.f);
+                        const bool on = MASKZ ? bn_relu_on(zz[j][k], mu[k], is[k], ga[k], be[k], false, xh) : (yy[j][k] > 0.f);
                         if (!on) gv = 0.f;
                     }
                     if (!ok[j]) gv = 0.f;
@@ -354,7 +356,7 @@ __global__ __launch_bounds__(256) void bn_apply_fin_kernel(long R, int C, int ro
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                float t = fmaf((v[j][k] - mu[k]) * is[k], ga[k], be[k]);      // the expression every mask recomputation uses
+                float t = bn_norm(v[j][k], mu[k], is[k], ga[k], be[k]);
                 if (RES) t += rr[j][k];
                 if (RELU) t = fmaxf(t, 0.f);
                 o[j][k] = t;
@@ -440,8 +442,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_fin_kernel(long R, int C, int r
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float xh = (zz[j][k] - mu[k]) * is[k];
-                o[j][k] = ga[k] * is[k] * (gg[j][k] - db[k] * inv_n - xh * dg[k] * inv_n);
+                o[j][k] = bn_dz(gg[j][k], bn_xhat(zz[j][k], mu[k], is[k]), ga[k], is[k], db[k], dg[k], inv_n);
             }
         const long rn = r + 64;
         if (rn < r1) {
@@ -494,8 +495,10 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(long n4, int R, int C, c
         if (RELU && MASKZ) {
             const f32x4 be = *reinterpret_cast<const f32x4*>(beta + c);
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (!(fmaf((zz[k] - mu[k]) * is[k], ga[k], be[k]) > 0.f)) g[k] = 0.f;
+            for (int k = 0; k < 4; ++k) {
+                float xh;
+                if (!bn_relu_on(zz[k], mu[k], is[k], ga[k], be[k], false, xh)) g[k] = 0.f;
+            }
         } else if (RELU) {
             const f32x4 yy = IO<T>::ld(y + i * 4);
 #pragma unroll
@@ -507,10 +510,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(long n4, int R, int C, c
             const f32x4 db = *reinterpret_cast<const f32x4*>(dbeta + c);
             const f32x4 dg = *reinterpret_cast<const f32x4*>(dgamma + c);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xh = (zz[k] - mu[k]) * is[k];
-                o[k] = ga[k] * is[k] * (g[k] - db[k] * inv_n - xh * dg[k] * inv_n);
-            }
+            for (int k = 0; k < 4; ++k) o[k] = bn_dz(g[k], bn_xhat(zz[k], mu[k], is[k]), ga[k], is[k], db[k], dg[k], inv_n);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) o[k] = ga[k] * is[k] * g[k];
@@ -523,18 +523,23 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(long n4, int R, int C, c
 }  // namespace
 namespace {
 
-inline int pick_chunks(int R, int C, int* rows_per_chunk) {
-    const int colgroups = cdiv(C, 64);
-    int nchunk = 2048 / colgroups;           // ~8 workgroups per CU in total
-    const int maxchunk = cdiv(R, 64);        // at least 64 rows per chunk
-    if (nchunk > maxchunk) nchunk = maxchunk;
-    if (nchunk < 1) nchunk = 1;
-    if (nchunk > 256) nchunk = 256;
-    int rpc = cdiv(R, nchunk);
-    rpc = (rpc + 15) & ~15;
-    *rows_per_chunk = rpc;
-    return cdiv(R, rpc);
+// Row chunks of an [R, C] map for a grid (64-column blocks, chunks): aim at `wg_aim` workgroups in all, with at least
+// `min_rows` rows per chunk and at most `max_chunks` chunks; the rows of a chunk are a multiple of 16.
+inline int row_chunks(long R, int C, int wg_aim, int min_rows, int max_chunks, int* rows_per_chunk) {
+    long n = wg_aim / cdiv(C, 64);
+    const long most = (R + min_rows - 1) / min_rows;
+    if (n > most) n = most;
+    if (n < 1) n = 1;
+    if (n > max_chunks) n = max_chunks;
+    long rpc = (R + n - 1) / n;
+    rpc = (rpc + 15) & ~15L;
+    *rows_per_chunk = (int)rpc;
+    return (int)((R + rpc - 1) / rpc);
 }
+// the reductions: ~8 workgroups per CU in total, no more chunks than the chunk-major workspace holds (bn_max_chunks)
+inline int pick_chunks(int R, int C, int* rows_per_chunk) { return row_chunks(R, C, 2048, 64, 256, rows_per_chunk); }
+// the finalize-on-load element-wise kernels: their finalize prologue is paid once per workgroup
+inline int ew_chunks(long R, int C, int* rows_per_chunk) { return row_chunks(R, C, 1024, 128, INT_MAX, rows_per_chunk); }
 
 inline unsigned ew_blocks(long n4) {
     long b = (n4 + 255) / 256;
@@ -542,22 +547,18 @@ inline unsigned ew_blocks(long n4) {
     return (unsigned)b;
 }
 
+// A run-time flag as a template argument: f(yes) or f(no); FLAG() is the compile-time bool inside f.
+constexpr std::true_type yes{};
+constexpr std::false_type no{};
+template <class F> inline void on_flag(bool flag, F f) {
+    if (flag) f(yes);
+    else f(no);
+}
+template <bool BF16> using MapT = std::conditional_t<BF16, __bf16, float>;     // element type of the maps for the ABI's bf16 flag
+
 }  // namespace
 
 int bn_max_chunks() { return 256; }
-
-template <typename T>
-static int bn_stats_t(hipStream_t st, int R, int C, const T* x, float eps, float momentum, float* partial, float* mean,
-                      float* invstd, float* run_mean, float* run_var, const float* gamma, const float* beta, float* ss_out) {
-    int rpc;
-    const int nchunk = pick_chunks(R, C, &rpc);
-    hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(cdiv(C, 64), nchunk), dim3(256), 0, st, R, C, rpc, x, partial);
-    SCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_finalize_kernel<T>, dim3(cdiv(C, 16)), dim3(256), 0, st, R, C, nchunk, x, partial, eps,
-                       momentum, mean, invstd, run_mean, run_var, gamma, beta, ss_out);
-    SCN_LAUNCH_CHECK();
-    return 0;
-}
 
 int bn_stats(hipStream_t st, int R, int C, const void* x, int bf16, float eps, float momentum, float* partial,
              float* mean, float* invstd, float* run_mean, float* run_var, const float* gamma, const float* beta,
@@ -565,22 +566,14 @@ int bn_stats(hipStream_t st, int R, int C, const void* x, int bf16, float eps, f
     SCN_ARG(R > 0 && C > 0 && C % 4 == 0 && x && partial && mean && invstd, "bn_stats: bad argument");
     SCN_ARG((reinterpret_cast<uintptr_t>(x) & (bf16 ? 7u : 15u)) == 0, "bn_stats: x is not vector aligned");
     SCN_ARG(!ss_out || (gamma && beta), "bn_stats: folded scale/shift need gamma and beta");
-    if (bf16) return bn_stats_t<__bf16>(st, R, C, (const __bf16*)x, eps, momentum, partial, mean, invstd, run_mean, run_var, gamma, beta, ss_out);
-    return bn_stats_t<float>(st, R, C, (const float*)x, eps, momentum, partial, mean, invstd, run_mean, run_var, gamma, beta, ss_out);
-}
-
-template <typename T>
-static int bn_apply_t(hipStream_t st, int R, int C, const T* z, const T* res, const float* mean, const float* invstd,
-                      const float* gamma, const float* beta, int relu, T* y) {
-    const long n4 = (long)R * C / 4;
-    dim3 grid(ew_blocks(n4)), block(256);
-#define SCN_BN_APPLY(RELU_, RES_) \
-    hipLaunchKernelGGL((bn_apply_kernel<T, RELU_, RES_>), grid, block, 0, st, n4, C, z, res, mean, invstd, gamma, beta, y)
-    if (relu && res) SCN_BN_APPLY(true, true);
-    else if (relu) SCN_BN_APPLY(true, false);
-    else if (res) SCN_BN_APPLY(false, true);
-    else SCN_BN_APPLY(false, false);
-#undef SCN_BN_APPLY
+    int rpc;
+    const int nchunk = pick_chunks(R, C, &rpc);
+    on_flag(bf16, [&](auto BF) {
+        using T = MapT<BF()>;
+        hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(cdiv(C, 64), nchunk), dim3(256), 0, st, R, C, rpc, (const T*)x, partial);
+        hipLaunchKernelGGL(bn_finalize_kernel<T>, dim3(cdiv(C, 16)), dim3(256), 0, st, R, C, nchunk, (const T*)x, partial, eps,
+                           momentum, mean, invstd, run_mean, run_var, gamma, beta, ss_out);
+    });
     SCN_LAUNCH_CHECK();
     return 0;
 }
@@ -588,8 +581,14 @@ static int bn_apply_t(hipStream_t st, int R, int C, const T* z, const T* res, co
 int bn_apply(hipStream_t st, int R, int C, const void* z, const void* res, int bf16, const float* mean,
              const float* invstd, const float* gamma, const float* beta, int relu, void* y) {
     SCN_ARG(R > 0 && C > 0 && C % 4 == 0 && z && mean && invstd && gamma && beta && y, "bn_apply: bad argument");
-    if (bf16) return bn_apply_t<__bf16>(st, R, C, (const __bf16*)z, (const __bf16*)res, mean, invstd, gamma, beta, relu, (__bf16*)y);
-    return bn_apply_t<float>(st, R, C, (const float*)z, (const float*)res, mean, invstd, gamma, beta, relu, (float*)y);
+    const long n4 = (long)R * C / 4;
+    on_flag(bf16, [&](auto BF) { on_flag(relu, [&](auto RELU) { on_flag(res, [&](auto RES) {
+        using T = MapT<BF()>;
+        hipLaunchKernelGGL((bn_apply_kernel<T, RELU(), RES()>), dim3(ew_blocks(n4)), dim3(256), 0, st, n4, C, (const T*)z,
+                           (const T*)res, mean, invstd, gamma, beta, (T*)y);
+    }); }); });
+    SCN_LAUNCH_CHECK();
+    return 0;
 }
 
 template <typename T>
@@ -603,49 +602,36 @@ static int bn_bwd_t(hipStream_t st, int R, int C, const T* dy, const T* y, const
     // fp32 maps with a residual branch: the reduction pass writes g = dy * [y > 0] as d residual, the second pass reads it
     // (bf16 maps keep the old form: their dz is computed from the unrounded g)
     const bool gfirst = relu && !maskz && dres && dz && sizeof(T) == 4;
-    if (maskz)     hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, true>), rgrid, block, 0, st, R, C, rpc, dy, y, z, mean, invstd, gamma, beta, partial);
-    else if (relu && gfirst) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, false, true>), rgrid, block, 0, st, R, C, rpc, dy, y, z, mean, invstd, gamma, beta, partial, dres);
-    else if (relu) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true, false>), rgrid, block, 0, st, R, C, rpc, dy, y, z, mean, invstd, gamma, beta, partial);
-    else           hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false, false>), rgrid, block, 0, st, R, C, rpc, dy, y, z, mean, invstd, gamma, beta, partial);
+    auto reduce = [&](auto RELU, auto MASKZ, auto GOUT) {
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, RELU(), MASKZ(), GOUT()>), rgrid, block, 0, st, R, C, rpc, dy, y, z, mean, invstd,
+                           gamma, beta, partial, GOUT() ? dres : (T*)nullptr, 0);
+    };
+    if (maskz) reduce(yes, yes, no);
+    else if (relu) on_flag(gfirst, [&](auto GOUT) { reduce(yes, no, GOUT); });
+    else reduce(no, no, no);
     SCN_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(C, 16)), block, 0, st, C, nchunk, partial, dbeta, dgamma);
     SCN_LAUNCH_CHECK();
     if (dz || dres) {
         const long n4 = (long)R * C / 4;
         dim3 grid(ew_blocks(n4));
-#define SCN_BN_DX(RELU_, TRAIN_, MASKZ_)                                                                                  \
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<T, RELU_, TRAIN_, MASKZ_>), grid, block, 0, st, n4, R, C, dy, y, z, mean, invstd, \
-                       gamma, beta, dbeta, dgamma, dz, dres)
-        if (gfirst) {
-            if (train) hipLaunchKernelGGL((bn_bwd_dx_kernel<T, false, true, false>), grid, block, 0, st, n4, R, C, dres, y, z, mean,
-                                          invstd, gamma, beta, dbeta, dgamma, dz, (T*)nullptr);
-            else       hipLaunchKernelGGL((bn_bwd_dx_kernel<T, false, false, false>), grid, block, 0, st, n4, R, C, dres, y, z, mean,
-                                          invstd, gamma, beta, dbeta, dgamma, dz, (T*)nullptr);
-        } else if (maskz && train) SCN_BN_DX(true, true, true);
-        else if (maskz) SCN_BN_DX(true, false, true);
-        else if (relu && train) SCN_BN_DX(true, true, false);
-        else if (relu) SCN_BN_DX(true, false, false);
-        else if (train) SCN_BN_DX(false, true, false);
-        else SCN_BN_DX(false, false, false);
-#undef SCN_BN_DX
+        // after a g-first reduce dres holds the masked g: it takes dy's place, needs no mask and is not written again
+        const T* g = gfirst ? dres : dy;
+        T* dres2 = gfirst ? nullptr : dres;
+        on_flag(train, [&](auto TRAIN) {
+            auto dx = [&](auto RELU, auto MASKZ) {
+                hipLaunchKernelGGL((bn_bwd_dx_kernel<T, RELU(), TRAIN(), MASKZ()>), grid, block, 0, st, n4, R, C, g, y, z, mean, invstd,
+                                   gamma, beta, dbeta, dgamma, dz, dres2);
+            };
+            if (maskz) dx(yes, yes);
+            else on_flag(relu && !gfirst, [&](auto RELU) { dx(RELU, no); });
+        });
         SCN_LAUNCH_CHECK();
     }
     return 0;
 }
 
-// ---- finalize-on-load entry points (fp32 maps, channel-major partials) -----------------------------------------------------
-static inline int ew_chunks(long R, int C, int* rows_per_chunk) {       // ~1024 workgroups, >= 128 rows each: the finalize
-    const int colgroups = cdiv(C, 64);                                    // prologue is paid once per workgroup
-    long n = 1024 / colgroups;
-    const long maxn = (R + 127) / 128;
-    if (n > maxn) n = maxn;
-    if (n < 1) n = 1;
-    long rpc = (R + n - 1) / n;
-    rpc = (rpc + 15) & ~15L;
-    *rows_per_chunk = (int)rpc;
-    return (int)((R + rpc - 1) / rpc);
-}
-
+// ---- finalize-on-load entry points (channel-major partials) ----------------------------------------------------------------
 int bn_apply_fin(hipStream_t st, long R, int C, const void* z, const void* res, int bf16, const float* partial, int ldp, int nchunk,
                  const float* shift, float eps, float momentum, const float* gamma, const float* beta, int relu, void* y,
                  float* mean, float* invstd, float* run_mean, float* run_var, float* ss_out) {
@@ -658,14 +644,11 @@ int bn_apply_fin(hipStream_t st, long R, int C, const void* z, const void* res, 
     BnFin f{partial, ldp, nchunk, shift, eps, momentum, mean, invstd, run_mean, run_var, ss_out};
     int rpc;
     const int nch = ew_chunks(R, C, &rpc);
-    dim3 grid(cdiv(C, 64), nch), block(256);
-#define SCN_AF(T_, RELU_, RES_) hipLaunchKernelGGL((bn_apply_fin_kernel<T_, RELU_, RES_>), grid, block, 0, st, R, C, rpc, (const T_*)z, (const T_*)res, gamma, beta, (T_*)y, f)
-    if (bf16) {
-        if (relu && res) SCN_AF(__bf16, true, true); else if (relu) SCN_AF(__bf16, true, false); else if (res) SCN_AF(__bf16, false, true); else SCN_AF(__bf16, false, false);
-    } else {
-        if (relu && res) SCN_AF(float, true, true); else if (relu) SCN_AF(float, true, false); else if (res) SCN_AF(float, false, true); else SCN_AF(float, false, false);
-    }
-#undef SCN_AF
+    on_flag(bf16, [&](auto BF) { on_flag(relu, [&](auto RELU) { on_flag(res, [&](auto RES) {
+        using T = MapT<BF()>;
+        hipLaunchKernelGGL((bn_apply_fin_kernel<T, RELU(), RES()>), dim3(cdiv(C, 64), nch), dim3(256), 0, st, R, C, rpc, (const T*)z,
+                           (const T*)res, gamma, beta, (T*)y, f);
+    }); }); });
     SCN_LAUNCH_CHECK();
     return 0;
 }
@@ -692,12 +675,16 @@ int bn_bwd_reduce_t(hipStream_t st, int R, int C, const void* dy, const void* y,
     const int nchunk = pick_chunks(R, C, &rpc);
     const int ldp = (nchunk + 3) & ~3;
     SCN_ARG(ldp <= ldp_cap, "bn_bwd_reduce_t: partial buffer too small");
-    dim3 grid(cdiv(C, 64), nchunk), block(256);
     const float* nf = nullptr;
-#define SCN_BR(T_, RELU_, GOUT_) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T_, RELU_, false, GOUT_>), grid, block, 0, st, R, C, rpc, (const T_*)dy, (const T_*)y, (const T_*)z, mean, invstd, nf, nf, partial, (T_*)gout, ldp)
-    if (bf16) { if (relu && gout) SCN_BR(__bf16, true, true); else if (relu) SCN_BR(__bf16, true, false); else SCN_BR(__bf16, false, false); }
-    else      { if (relu && gout) SCN_BR(float, true, true); else if (relu) SCN_BR(float, true, false); else SCN_BR(float, false, false); }
-#undef SCN_BR
+    on_flag(bf16, [&](auto BF) {
+        using T = MapT<BF()>;
+        auto reduce = [&](auto RELU, auto GOUT) {
+            hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, RELU(), false, GOUT()>), dim3(cdiv(C, 64), nchunk), dim3(256), 0, st, R, C, rpc,
+                               (const T*)dy, (const T*)y, (const T*)z, mean, invstd, nf, nf, partial, (T*)gout, ldp);
+        };
+        if (relu) on_flag(gout, [&](auto GOUT) { reduce(yes, GOUT); });
+        else reduce(no, no);
+    });
     SCN_LAUNCH_CHECK();
     if (nchunk_out) *nchunk_out = nchunk;
     return 0;
@@ -712,10 +699,11 @@ int bn_bwd_dx_fin(hipStream_t st, long R, int C, const void* g, const void* z, i
     SCN_ARG(2L * C * ldp * 4 < 0x7fffffffL, "bn_bwd_dx_fin: partial too large");
     int rpc;
     const int nch = ew_chunks(R, C, &rpc);
-    if (bf16) hipLaunchKernelGGL(bn_bwd_dx_fin_kernel<__bf16>, dim3(cdiv(C, 64), nch), dim3(256), 0, st, R, C, rpc, (const __bf16*)g, (const __bf16*)z,
-                                 mean, invstd, gamma, partial, ldp, nchunk, dbeta, dgamma, (__bf16*)dz);
-    else      hipLaunchKernelGGL(bn_bwd_dx_fin_kernel<float>, dim3(cdiv(C, 64), nch), dim3(256), 0, st, R, C, rpc, (const float*)g, (const float*)z,
-                                 mean, invstd, gamma, partial, ldp, nchunk, dbeta, dgamma, (float*)dz);
+    on_flag(bf16, [&](auto BF) {
+        using T = MapT<BF()>;
+        hipLaunchKernelGGL(bn_bwd_dx_fin_kernel<T>, dim3(cdiv(C, 64), nch), dim3(256), 0, st, R, C, rpc, (const T*)g, (const T*)z, mean,
+                           invstd, gamma, partial, ldp, nchunk, dbeta, dgamma, (T*)dz);
+    });
     SCN_LAUNCH_CHECK();
     return 0;
 }

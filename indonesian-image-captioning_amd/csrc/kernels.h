@@ -200,8 +200,13 @@ int bn_finalize_t(hipStream_t st, long R, int C, const float* partial, int ldp, 
 int bn_apply_fin(hipStream_t st, long R, int C, const void* z, const void* res, int bf16, const float* partial, int ldp, int nchunk,
                  const float* shift, float eps, float momentum, const float* gamma, const float* beta, int relu, void* y,
                  float* mean, float* invstd, float* run_mean, float* run_var, float* ss_out);
+// Aliasing: gout may BE dy (the masked gradient replaces dy in place; csrc/block16.cpp does that); it must not overlap
+// y or z, nor dy in any other way.
 int bn_bwd_reduce_t(hipStream_t st, int R, int C, const void* dy, const void* y, const void* z, int bf16, const float* mean,
                     const float* invstd, int relu, float* partial, int ldp_cap, void* gout, int* nchunk_out);
+// Aliasing: dz may BE g (dz replaces the masked gradient in place; scnattn/conv.py and csrc/block16.cpp do that); it must
+// not overlap z, nor g in any other way.  In both entries a thread reads an element before the same thread writes it; the
+// kernels rely on that order, not on their __restrict__ qualifiers, which these two pairs do not honour.
 int bn_bwd_dx_fin(hipStream_t st, long R, int C, const void* g, const void* z, int bf16, const float* mean, const float* invstd,
                   const float* gamma, const float* partial, int ldp, int nchunk, float* dbeta, float* dgamma, void* dz);
 

@@ -1,7 +1,8 @@
-// Tile machinery shared by the trunk's convolution kernels and their bf16 twins (internal; gfx950 only):
+// Tile machinery shared by the trunk's convolution kernels and their bf16 twins, and the BatchNorm expressions they share
+// with csrc/batchnorm.hip (internal; gfx950 only):
 // csrc/cgemm.hip + csrc/cgemm16.hip (GEMM / implicit 3x3) and csrc/conv3.hip + csrc/wgrad16.hip (wave-split weight
 // gradients).  Everything here is force-inlined into its caller: block order, convolution geometry, the BatchNorm
-// ReLU-mask term, the slab reducers' column-sum tail and the weight gradients' split policy, each written once.
+// forward / backward expressions and ReLU-mask term, the slab reducers' column-sum tail and the weight gradients' split policy, each written once.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -49,15 +50,27 @@ __device__ __forceinline__ long class_row_scatter(const ConvGeom& g, int m, int 
     return ((long)p.n * g.dHi + 2 * p.h + ph) * g.dWi + 2 * p.w + pw;
 }
 
-// ---- BatchNorm pieces of the epilogues; Args: the kernel's argument struct (stat_partial, ldp, N) ---------------------
+// ---- BatchNorm pieces of csrc/batchnorm.hip and of the GEMM epilogues, each expression written once ----------------------
+__device__ __forceinline__ float bn_xhat(float z, float mean, float invstd) { return (z - mean) * invstd; }
+// The forward expression.  Every ReLU mask that the backward pass recomputes from z is right only while it is THIS
+// expression bit for bit, so the forward kernels and the masks all come through here.
+__device__ __forceinline__ float bn_norm(float z, float mean, float invstd, float gamma, float beta) {
+    return fmaf(bn_xhat(z, mean, invstd), gamma, beta);
+}
 // ReLU mask of a BatchNorm recomputed from its pre-activation z: the function the forward pass evaluated was
-// relu(fma(xhat, gamma, beta)), or -- folded -- relu(fma(z, scale, shift)); (a, b) is that pair.  xhat is handed back for
-// the g * xhat sum.
+// relu(bn_norm(z, ...)), or -- folded -- relu(fma(z, scale, shift)); (a, b) is that pair.  xhat is handed back for
+// the g * xhat sum.  Not folded, this IS bn_norm(z, mean, invstd, a, b) > 0: the same fma of the same bn_xhat; it selects
+// the operand and not the result, so that a run-time `folded` costs one fma.
 __device__ __forceinline__ bool bn_relu_on(float z, float mean, float invstd, float a, float b, bool folded, float& xhat) {
-    xhat = (z - mean) * invstd;
+    xhat = bn_xhat(z, mean, invstd);
     return fmaf(folded ? z : xhat, a, b) > 0.f;
 }
+// The backward expression (batch statistics): dz from the masked gradient g, dbeta = sum g, dgamma = sum g * xhat, 1 / R.
+__device__ __forceinline__ float bn_dz(float g, float xhat, float gamma, float invstd, float dbeta, float dgamma, float inv_n) {
+    return gamma * invstd * (g - dbeta * inv_n - xhat * dgamma * inv_n);
+}
 
+// Args: the kernel's argument struct (stat_partial, ldp, N).
 // Tail of the 64 x 64 slab reducers (256 threads; thread (rl, cl) holds the sums of 4 columns over its 4 rows): the 16 row
 // groups meet in LDS and are added in row-group order, one partial per (column, 64-row block blockIdx.y).
 template <class Args>
