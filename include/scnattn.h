@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SCNATTN_VERSION 108 /* 0.1.8: + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
+#define SCNATTN_VERSION 108 /* 0.1.8: + batched beam search (scnattn_beam_*; new symbols only, the version stays), + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
                                _conv3x3_fwd_bn_eval; new symbols only, the version stays), + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
                                epilogues inside the GEMM launch (options cgemm_combine, cgemm_combine_max), option dec_tail;
                                0.1.7: + halo-staged 3x3 weight gradient, strided 3x3 d input, the stem (scnattn_stem_*), BatchNorm
@@ -158,6 +158,56 @@ int scnattn_seq_bwd_streams(void* stream, void* wgrad_stream, const scnattn_dims
                             const int32_t* bt_host, const float* drop_mask, const float* saved, float* scratch,
                             const float* dpreds, const float* dalphas, const scnattn_params* g, float* denc,
                             float* dtags, const scnattn_pool* pool);
+
+/* ---- batched beam search: the reference's sample() (models/decoders/attention_scn.py:160-296, pure_scn.py:142-249,
+ * pure_attention.py:153-281), which eval_caption.py:96-131 calls once per image, for N images at once ---------------------
+ * dims: B = N images; T and L are ignored (max_steps is passed explicitly; the reference stops after 51).  K = beam_size
+ * slots per image, 1 <= K <= 8 <= V; rows of every per-step buffer are n*K + j and nothing shrinks: per image `nsrc` live
+ * source beams (1 at the first step: the reference selects from scores[0]) and `kk` beams still to fill.  Each step
+ * takes the top kk of the nsrc x V candidates score[j] + log_softmax(fc(h_j))[v], ordered by (value descending, flat
+ * index j*V + v ascending -- the TIE RULE, which the reference leaves to topk); <end> picks are recorded as completed (the
+ * running best replaced only on a strictly greater score), the others compacted to slots 0.. in rank order.  Sequences
+ * and attention maps are not copied per step: token[t][row] / parent[t][row] / alpha[t][row][P] are recorded and the
+ * caller follows the parent chain.  The k rows of an image read att1[n] / enc[n] once (csrc/beam.hip).
+ * fp32 only: option "decoder_bf16" is ignored here.  Dense encoder_out only (no scnattn_pool).
+ *   enc [N,P,E], tags [N,S] (NOT expanded per beam); ws: scnattn_beam_workspace bytes, 16-byte aligned, owned by the caller
+ *   scnattn_beam_init   set-up (weight re-layout, att1 once per image, tag factors, initial state, <start> embeddings)
+ *   scnattn_beam_steps  enqueues steps t0 .. t0+n_steps-1 (0-based, clipped to max_steps); steps on a finished batch are
+ *                       no-ops, so the host may enqueue chunks and read `open_images` (one int) in between
+ *   scnattn_beam_layout offsets (in 4-byte elements from ws) of the results, in this order:
+ *       0 open_images int[1]   1 nsrc int[N]   2 kk int[N]   3 ncomp int[N]   4 best_idx int[N] (-1: none completed)
+ *       5 best_score f32[N]    6 scores f32[N*K] (open slots)   7 comp_score f32[N*K]   8 comp_step int[N*K] (0-based)
+ *       9 comp_parent int[N*K] (source slot that picked <end>)  10 token int[max_steps][N*K]   11 parent int[max_steps][N*K]
+ *       12 alpha f32[max_steps][N*K][P] (-1 without attention), alpha[t][row] belonging to SOURCE slot `row` of step t
+ *     completed beams of image n sit at n*K .. n*K+ncomp[n]-1 in completion order (by step, within a step by rank). */
+#define SCNATTN_BEAM_NOFF 13
+int scnattn_beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes);
+int scnattn_beam_layout(const scnattn_dims* d, int K, int max_steps, long* offsets);
+int scnattn_beam_init(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
+                      const float* tags, int start_token, float* ws);
+int scnattn_beam_steps(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
+                       int end_token, int t0, int n_steps, float* ws);
+/* The kernels of a step (csrc/beam.hip), one launch each; nsrc int[N] on the device.
+ *   _attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0 for j < nsrc[n] (other rows untouched)
+ *   _attn_context  alpha_out [N*K][P], awe [N*K][E] (either may be NULL), z = sigmoid(gpre + gate_bias) * awe (gpre NULL: awe)
+ *   _row_topk      outv / outi [N*K][K]: per live row the top K of scores[row] + logits[row][v] - logsumexp(logits[row]);
+ *                  force_passes != 0 reads the row from global memory in every pass (the path of a V beyond the LDS)
+ *   _merge         one step's selection for every image, on the state arrays a scnattn_beam_layout describes (state:
+ *                  pointers in that order, entries 0..11); t = 0-based step whose token / parent rows are written
+ *   _advance       hd / cd [N*K][D] = hs / cs [n*K + parent_t[row]], emb [N*K][M] = table[token_t[row]] */
+int scnattn_beam_attn_scores(void* stream, int N, int K, int P, int A, const float* att1, const float* att2, int nslab,
+                             long slab_stride, long att2_ld, const float* dec_bias, const float* w, const float* b0,
+                             const int32_t* nsrc, float* e);
+int scnattn_beam_attn_context(void* stream, int N, int K, int P, int E, const float* enc, const float* e, const float* gpre,
+                              int nslab, long slab_stride, long gpre_ld, const float* gate_bias, const int32_t* nsrc,
+                              float* alpha_out, float* awe, float* z);
+int scnattn_beam_row_topk(void* stream, int N, int K, int V, const float* logits, long ld, const float* scores,
+                          const int32_t* nsrc, float* outv, int32_t* outi, int force_passes);
+int scnattn_beam_merge(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
+                       void* const* state);
+int scnattn_beam_advance(void* stream, int N, int K, int D, int M, int V, const float* hs, const float* cs,
+                         const int32_t* parent_t, const int32_t* token_t, const float* table, float* hd, float* cd,
+                         float* emb);
 
 /* ---- primitives (each = one kernel launch); used by the stand-alone modules and the tests ------- */
 /* C = alpha*op(A).op(B) + beta*C + bias[n]; rows with rowmask[m]==0 written as 0.  Replaces the

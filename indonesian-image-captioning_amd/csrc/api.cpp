@@ -33,6 +33,12 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* d, const scnatt
             const float* tags, const int64_t* caps, const int32_t* dl_dev, const int32_t* bt, const float* drop_mask,
             const float* saved, float* scratch, const float* dpreds, const float* dalphas, const scnattn_params* g,
             float* denc, float* dtags, const scnattn_pool* pool);
+int beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes);
+int beam_layout(const scnattn_dims* d, int K, int max_steps, long* off);
+int beam_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
+              const float* tags, int start_token, float* ws);
+int beam_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
+               int end_token, int t0, int n_steps, float* ws);
 
 }  // namespace scn
 
@@ -74,6 +80,50 @@ int scnattn_set_option(const char* name, int value) {
 int scnattn_profile_collect(double* out6) {
     if (!out6) { set_error("scnattn_profile_collect: NULL"); return -1; }
     return profile_collect(out6);
+}
+
+int scnattn_beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes) {
+    return beam_workspace(d, K, max_steps, bytes);
+}
+int scnattn_beam_layout(const scnattn_dims* d, int K, int max_steps, long* offsets) {
+    return beam_layout(d, K, max_steps, offsets);
+}
+int scnattn_beam_init(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
+                      const float* tags, int start_token, float* ws) {
+    return beam_init(ST(stream), d, K, max_steps, w, enc, tags, start_token, ws);
+}
+int scnattn_beam_steps(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
+                       int end_token, int t0, int n_steps, float* ws) {
+    return beam_steps(ST(stream), d, K, max_steps, w, enc, end_token, t0, n_steps, ws);
+}
+int scnattn_beam_attn_scores(void* stream, int N, int K, int P, int A, const float* att1, const float* att2, int nslab,
+                             long slab_stride, long att2_ld, const float* dec_bias, const float* w, const float* b0,
+                             const int32_t* nsrc, float* e) {
+    return beam_attn_scores(ST(stream), N, K, P, A, att1, Slabs{att2, nslab, slab_stride, att2_ld}, dec_bias, w, b0, nsrc, e);
+}
+int scnattn_beam_attn_context(void* stream, int N, int K, int P, int E, const float* enc, const float* e, const float* gpre,
+                              int nslab, long slab_stride, long gpre_ld, const float* gate_bias, const int32_t* nsrc,
+                              float* alpha_out, float* awe, float* z) {
+    return beam_attn_context(ST(stream), N, K, P, E, enc, e, Slabs{gpre, nslab, slab_stride, gpre_ld}, gate_bias, nsrc,
+                             alpha_out, awe, z);
+}
+int scnattn_beam_row_topk(void* stream, int N, int K, int V, const float* logits, long ld, const float* scores,
+                          const int32_t* nsrc, float* outv, int32_t* outi, int force_passes) {
+    return beam_row_topk(ST(stream), N, K, V, logits, ld, scores, nsrc, outv, outi, force_passes);
+}
+int scnattn_beam_merge(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
+                       void* const* state) {
+    if (!state) { set_error("scnattn_beam_merge: state is NULL"); return -1; }
+    if (N <= 0 || K < 1 || K > SCN_MAX_BEAM) { set_error("scnattn_beam_merge: bad N / beam size"); return -1; }
+    const BeamState s{N * K, (float*)state[6], (int*)state[1], (int*)state[2], (int*)state[3], (int*)state[4],
+                      (float*)state[5], (int*)state[0], (float*)state[7], (int*)state[8], (int*)state[9], (int*)state[10],
+                      (int*)state[11]};
+    return beam_merge(ST(stream), N, K, V, end_token, t, candv, candi, s);
+}
+int scnattn_beam_advance(void* stream, int N, int K, int D, int M, int V, const float* hs, const float* cs,
+                         const int32_t* parent_t, const int32_t* token_t, const float* table, float* hd, float* cd,
+                         float* emb) {
+    return beam_advance(ST(stream), N, K, D, M, V, hs, cs, parent_t, token_t, table, hd, cd, emb);
 }
 
 int scnattn_seq_workspace(const scnattn_dims* d, const scnattn_pool* pool, size_t* saved_bytes, size_t* scratch_bytes) {

@@ -1,0 +1,482 @@
+// Batched beam search (models/decoders/_common.py:beam_search_batched; the reference's sample(), attention_scn.py:160-296,
+// for N images at once).  K = beam_size slots per image, rows of every per-step buffer are n*K + j, nothing shrinks:
+//   nsrc[n]  live source beams of image n (slots 0 .. nsrc-1); kk[n] beams still to fill (0: the image is finished)
+// The k rows of one image attend over the SAME att1[n] / enc[n]; the two attention kernels here read that map once per
+// image and feed K accumulators from every loaded fragment, where the per-image search keeps k materialised copies:
+//   beam_attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0      (attn_scores_kernel's pixel-row layout)
+//   beam_attn_context  K softmaxes over P, awe / z for the K rows from one pass over enc[n] (attn_context_kernel's tiles)
+//   beam_row_topk      per live row: log-softmax statistics and the row's top K of  score + logit - lse
+//   beam_merge         per image: the top kk of the nsrc x K row candidates, <end> picks recorded, the rest compacted
+//   beam_advance       h / c gathered from the parent slot, next input embedding gathered from the table
+// ORDER (the tie rule): candidates are ranked by (value descending, flat index j*V + v ascending), values compared as the
+// fp32 numbers the kernel computes.  Dead slots (j >= nsrc) are never read as candidates and never written by the first
+// three kernels; beam_merge / beam_advance fill them with a copy of slot 0 (or zeros), so every row stays finite.
+// Plain vector stores only; no kernel waits for another workgroup.
+#include <climits>
+#include "common.h"
+#include "kernels.h"
+
+namespace scn {
+
+namespace {
+
+constexpr int PC = 16;      // pixel rows per workgroup of beam_attn_scores (4 waves x 4 rows)
+constexpr int CU = 4;       // encoder rows per wave per load batch of beam_attn_context
+
+template <int KT, bool VEC>
+__global__ __launch_bounds__(256) void beam_attn_scores_kernel(int P, int A, const float* __restrict__ att1, Slabs att2,
+                                                               const float* __restrict__ bd, const float* __restrict__ w,
+                                                               const float* __restrict__ b0, const int* __restrict__ nsrc,
+                                                               float* __restrict__ e) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int A4 = (A + 3) & ~3;
+    float* ws = sm;             // [A4]
+    float* att2s = sm + A4;     // [KT][A4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = blockIdx.y, p0 = blockIdx.x * PC;
+    const int live = min(nsrc[n], KT);
+    if (live <= 0) return;      // a finished image: uniform over the workgroup
+    const float* rowp[4];
+    bool ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int p = p0 + wave * 4 + j;
+        ok[j] = p < P;
+        rowp[j] = att1 + ((long)n * P + (ok[j] ? p : P - 1)) * A;
+    }
+    for (int a = tid; a < A4; a += 256) {
+        const bool in = a < A;
+        ws[a] = in ? w[a] : 0.f;
+        const float bda = (in && bd) ? bd[a] : 0.f;
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            att2s[k * A4 + a] = (in && k < live) ? slab_sum(att2.p, (long)(n * KT + k) * att2.ld + a, att2.n, att2.stride) + bda : 0.f;
+    }
+    __syncthreads();
+    float acc[4][KT];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < KT; ++k) acc[j][k] = 0.f;
+    if (VEC) {
+        for (int a = lane * 4; a < A; a += 256) {
+            const f32x4 ww = *reinterpret_cast<const f32x4*>(ws + a);
+            f32x4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = ld4(rowp[j] + a);
+#pragma unroll
+            for (int k = 0; k < KT; ++k) {
+                const f32x4 s2 = *reinterpret_cast<const f32x4*>(att2s + k * A4 + a);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc[j][k] = fmaf(fmaxf(v[j][c] + s2[c], 0.f), ww[c], acc[j][k]);
+            }
+        }
+    } else {
+        for (int a = lane; a < A; a += 64) {
+            const float ww = ws[a];
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = rowp[j][a];
+#pragma unroll
+            for (int k = 0; k < KT; ++k) {
+                const float s2 = att2s[k * A4 + a];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j][k] = fmaf(fmaxf(v[j] + s2, 0.f), ww, acc[j][k]);
+            }
+        }
+    }
+    const float bias0 = b0 ? b0[0] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const float s = wave_sum(acc[j][k]);
+            if (lane == 0 && ok[j] && k < live) e[((long)n * KT + k) * P + p0 + wave * 4 + j] = s + bias0;
+        }
+}
+
+template <int KT, bool VEC>
+__global__ __launch_bounds__(512) void beam_attn_context_kernel(int P, int E, const float* __restrict__ enc,
+                                                                const float* __restrict__ e, Slabs gpre,
+                                                                const float* __restrict__ bbeta, const int* __restrict__ nsrc,
+                                                                float* __restrict__ alpha_out, float* __restrict__ awe,
+                                                                float* __restrict__ z) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* part = sm;               // [8][256]
+    float* alph = sm + 8 * 256;     // [KT][P]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = blockIdx.y, e0 = blockIdx.x * 256;
+    const int live = min(nsrc[n], KT);
+    if (live <= 0) return;
+    // wave k: the softmax of slot k (KT <= 8 waves), wave reductions only
+    if (wave < KT) {
+        float* al = alph + wave * P;
+        if (wave < live) {
+            const long row = (long)n * KT + wave;
+            const float* er = e + row * P;
+            float m = -INFINITY;
+            for (int p = lane; p < P; p += 64) m = fmaxf(m, er[p]);
+            m = wave_max(m);
+            float s = 0.f;
+            for (int p = lane; p < P; p += 64) {
+                const float ex = expf(er[p] - m);
+                al[p] = ex;
+                s += ex;
+            }
+            s = wave_sum(s);
+            for (int p = lane; p < P; p += 64) {
+                const float a = al[p] / s;
+                al[p] = a;
+                if (blockIdx.x == 0 && alpha_out) alpha_out[row * P + p] = a;
+            }
+        } else {
+            for (int p = lane; p < P; p += 64) al[p] = 0.f;
+        }
+    }
+    __syncthreads();
+    const int col = e0 + lane * 4;
+    const float* base = enc + (long)n * P * E;
+    float acc[KT][4];
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[k][c] = 0.f;
+    if (VEC) {
+        const int cc = min(col, E - 4);     // columns past E repeat the last fragment; their sums are never stored
+        for (int p = wave; p < P; p += 8 * CU) {
+            f32x4 v[CU];
+#pragma unroll
+            for (int j = 0; j < CU; ++j) v[j] = ld4(base + (long)min(p + 8 * j, P - 1) * E + cc);
+#pragma unroll
+            for (int j = 0; j < CU; ++j) {
+                const int pp = p + 8 * j;
+#pragma unroll
+                for (int k = 0; k < KT; ++k) {
+                    const float a = pp < P ? alph[k * P + min(pp, P - 1)] : 0.f;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) acc[k][c] = fmaf(a, v[j][c], acc[k][c]);
+                }
+            }
+        }
+    } else {
+        for (int p = wave; p < P; p += 8) {
+            float x[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) x[c] = col + c < E ? base[(long)p * E + col + c] : 0.f;
+#pragma unroll
+            for (int k = 0; k < KT; ++k) {
+                const float a = alph[k * P + p];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[k][c] = fmaf(a, x[c], acc[k][c]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        if (k < live) {             // uniform over the workgroup
+#pragma unroll
+            for (int c = 0; c < 4; ++c) part[wave * 256 + lane * 4 + c] = acc[k][c];
+            __syncthreads();
+            const int c = e0 + tid;
+            if (tid < 256 && c < E) {
+                float a = part[tid];
+#pragma unroll
+                for (int w8 = 1; w8 < 8; ++w8) a += part[w8 * 256 + tid];
+                const long row = (long)n * KT + k;
+                if (awe) awe[row * E + c] = a;
+                if (gpre.p) {
+                    const float gp = slab_sum(gpre.p, row * gpre.ld + c, gpre.n, gpre.stride) + (bbeta ? bbeta[c] : 0.f);
+                    z[row * E + c] = sigmoidf_(gp) * a;
+                } else {
+                    z[row * E + c] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// (value, index) pairs under the search order: larger value first, lower index among equal values
+__device__ __forceinline__ bool before(float v, int i, float ov, int oi) { return v > ov || (v == ov && i < oi); }
+
+__device__ __forceinline__ void block_best(float& v, int& i, float* redv, int* redi) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (before(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    __syncthreads();
+    if (lane == 0) { redv[wave] = v; redi[wave] = i; }
+    __syncthreads();
+    v = redv[0]; i = redi[0];
+    for (int k = 1; k < nw; ++k)
+        if (before(redv[k], redi[k], v, i)) { v = redv[k]; i = redi[k]; }
+}
+
+__device__ __forceinline__ float block_sum_max(float v, float* red, bool is_max) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    v = is_max ? wave_max(v) : wave_sum(v);
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    float r = red[0];
+    for (int k = 1; k < nw; ++k) r = is_max ? fmaxf(r, red[k]) : r + red[k];
+    return r;
+}
+
+// One workgroup per row.  STAGED: the row's V logits sit in LDS after the first pass; otherwise every pass re-reads them
+// from global memory.  Round r takes the best candidate that comes strictly after round r-1's pick in the search order,
+// which is the knock-out without a store (and exact on ties: equal values leave in index order).
+template <bool STAGED>
+__global__ __launch_bounds__(256) void beam_row_topk_kernel(int K, int V, const float* __restrict__ logits, long ld,
+                                                            const float* __restrict__ scores, const int* __restrict__ nsrc,
+                                                            float* __restrict__ outv, int* __restrict__ outi) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* redv = sm;                               // [4]
+    int* redi = reinterpret_cast<int*>(sm + 8);     // [4]
+    float* buf = sm + 16;                           // [V] when STAGED
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    const int n = (int)(row / K), j = (int)(row - (long)n * K);
+    if (j >= nsrc[n]) return;
+    const float* g = logits + row * ld;
+    float m = -INFINITY;
+    for (int v = tid; v < V; v += 256) {
+        const float x = g[v];
+        if (STAGED) buf[v] = x;
+        m = fmaxf(m, x);
+    }
+    m = block_sum_max(m, redv, true);               // its barriers also publish buf
+    const float* src = STAGED ? buf : g;
+    float s = 0.f;
+    for (int v = tid; v < V; v += 256) s += expf(src[v] - m);
+    s = block_sum_max(s, redv, false);
+    const float lse = m + logf(s), sc = scores[row];
+    float pv = INFINITY;
+    int pi = -1;
+    for (int r = 0; r < K; ++r) {
+        float bv = -INFINITY;
+        int bi = INT_MAX;
+        for (int v = tid; v < V; v += 256) {
+            const float val = sc + (src[v] - lse);
+            if (before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
+        }
+        block_best(bv, bi, redv, redi);
+        if (tid == 0) {
+            outv[row * K + r] = bv;
+            outi[row * K + r] = bi;
+        }
+        pv = bv;
+        pi = bi;
+    }
+}
+
+__global__ __launch_bounds__(64) void beam_merge_kernel(int K, int V, int end_tok, int t, const float* __restrict__ candv,
+                                                        const int* __restrict__ candi, BeamState s) {
+    __shared__ float sv[8];
+    __shared__ int sj[8], sw[8];
+    const int n = blockIdx.x, lane = threadIdx.x;
+    const int ns = s.nsrc[n], k = s.kk[n];
+    if (k <= 0) return;         // finished image: a no-op
+    const int j = lane / K, r = lane - j * K;
+    const bool valid = j < ns;  // ns <= K, so lane < K * K
+    const long ci = ((long)n * K + (valid ? j : 0)) * K + r;
+    const float v = valid ? candv[ci] : -INFINITY;
+    const int w = valid ? candi[ci] : 0;
+    const int flat = valid ? j * V + w : INT_MAX;
+    int rank = 0;
+    for (int l = 0; l < 64; ++l) {
+        const float ov = __shfl(v, l, 64);
+        const int of = __shfl(flat, l, 64);
+        if (of != INT_MAX && before(ov, of, v, flat)) ++rank;
+    }
+    if (valid && rank < k) { sv[rank] = v; sj[rank] = j; sw[rank] = w; }
+    __syncthreads();
+    if (lane != 0) return;
+    // picks in rank order: <end> picks are recorded as completed, the rest compacted to slots 0 .. nopen-1
+    int nopen = 0, nc = s.ncomp[n], bi = s.best_idx[n];
+    float bs = s.best_score[n];
+    int tok0 = 0, par0 = 0;
+    const long r0 = (long)n * K;
+    int* token_t = s.token + (long)t * s.R;
+    int* parent_t = s.parent + (long)t * s.R;
+    for (int q = 0; q < k; ++q) {
+        if (sw[q] == end_tok) {
+            if (nc < K) {
+                s.comp_score[r0 + nc] = sv[q];
+                s.comp_step[r0 + nc] = t;
+                s.comp_parent[r0 + nc] = sj[q];
+                if (bi < 0 || sv[q] > bs) { bs = sv[q]; bi = nc; }     // strictly greater: index(max(...))
+                ++nc;
+            }
+        } else {
+            if (nopen == 0) { tok0 = sw[q]; par0 = sj[q]; }
+            token_t[r0 + nopen] = sw[q];
+            parent_t[r0 + nopen] = sj[q];
+            s.scores[r0 + nopen] = sv[q];
+            ++nopen;
+        }
+    }
+    for (int d = nopen; d < K; ++d) {       // dead slots: a copy of slot 0 (zeros when nothing is open)
+        token_t[r0 + d] = tok0;
+        parent_t[r0 + d] = par0;
+        s.scores[r0 + d] = 0.f;
+    }
+    s.ncomp[n] = nc;
+    s.best_idx[n] = bi;
+    s.best_score[n] = bs;
+    s.nsrc[n] = nopen;
+    s.kk[n] = nopen;
+    if (nopen == 0) atomicAdd(s.open_images, -1);
+}
+
+__global__ __launch_bounds__(256) void beam_advance_kernel(int K, int D, int M, int V, const float* __restrict__ hs,
+                                                           const float* __restrict__ cs, const int* __restrict__ parent_t,
+                                                           const int* __restrict__ token_t, const float* __restrict__ table,
+                                                           float* __restrict__ hd, float* __restrict__ cd,
+                                                           float* __restrict__ emb) {
+    const long row = blockIdx.x;
+    const long n = row / K;
+    const long src = n * K + min(max(parent_t[row], 0), K - 1);     // an index outside the image's slots cannot leave them
+    const long tok = min(max(token_t[row], 0), V - 1);
+    for (int d = threadIdx.x; d < D; d += 256) {
+        hd[row * D + d] = hs[src * D + d];
+        cd[row * D + d] = cs[src * D + d];
+    }
+    for (int m = threadIdx.x; m < M; m += 256) emb[row * M + m] = table[tok * M + m];
+}
+
+// out[n*K + j][:] = in[n][:]
+__global__ __launch_bounds__(256) void beam_expand_rows_kernel(long total, int K, int W, const float* __restrict__ in,
+                                                               float* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long row = i / W;
+    out[i] = in[(row / K) * W + (i - row * W)];
+}
+
+__global__ __launch_bounds__(256) void beam_state_init_kernel(int N, int K, BeamState s) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < s.R) {
+        s.scores[i] = 0.f;
+        s.comp_score[i] = 0.f;
+        s.comp_step[i] = -1;
+        s.comp_parent[i] = 0;
+    }
+    if (i < N) {
+        s.nsrc[i] = 1;          // the reference selects from scores[0] only at step 1
+        s.kk[i] = K;
+        s.ncomp[i] = 0;
+        s.best_idx[i] = -1;
+        s.best_score[i] = 0.f;
+    }
+    if (i == 0) s.open_images[0] = N;
+}
+
+inline bool vec_ok(const float* p, int W) { return W % 4 == 0 && W >= 4 && aligned16(p); }
+
+}  // namespace
+
+#define SCN_BEAM_K_SWITCH(LAUNCH)                                                                             \
+    switch (K) {                                                                                              \
+        case 1: LAUNCH(1) break; case 2: LAUNCH(2) break; case 3: LAUNCH(3) break; case 4: LAUNCH(4) break;   \
+        case 5: LAUNCH(5) break; case 6: LAUNCH(6) break; case 7: LAUNCH(7) break; default: LAUNCH(8) break;  \
+    }
+
+int beam_attn_scores(hipStream_t st, int N, int K, int P, int A, const float* att1, Slabs att2, const float* bd,
+                     const float* w, const float* b0, const int* nsrc, float* e) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM, "beam_attn_scores: beam size out of range");
+    SCN_ARG(att1 && att2.p && w && nsrc && e && P > 0 && A > 0, "beam_attn_scores: bad argument");
+    const size_t lds = (size_t)(K + 1) * ((A + 3) & ~3) * sizeof(float);
+    SCN_ARG(lds <= 64 * 1024, "beam_attn_scores: attention_dim too large for the LDS staging");
+    dim3 grid(cdiv(P, PC), N), block(256);
+    const bool vec = vec_ok(att1, A);
+#define L(KT)                                                                                                        \
+    if (vec) hipLaunchKernelGGL((beam_attn_scores_kernel<KT, true>), grid, block, lds, st, P, A, att1, att2, bd, w, b0, nsrc, e);  \
+    else     hipLaunchKernelGGL((beam_attn_scores_kernel<KT, false>), grid, block, lds, st, P, A, att1, att2, bd, w, b0, nsrc, e);
+    SCN_BEAM_K_SWITCH(L)
+#undef L
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_attn_context(hipStream_t st, int N, int K, int P, int E, const float* enc, const float* e, Slabs gpre,
+                      const float* bbeta, const int* nsrc, float* alpha_out, float* awe, float* z) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM, "beam_attn_context: beam size out of range");
+    SCN_ARG(enc && e && nsrc && z && P > 0 && E > 0, "beam_attn_context: bad argument");
+    const size_t lds = (size_t)(8 * 256 + (long)K * P) * sizeof(float);
+    SCN_ARG(lds <= 64 * 1024, "beam_attn_context: num_pixels too large for the LDS staging");
+    dim3 grid(cdiv(E, 256), N), block(512);
+    const bool vec = vec_ok(enc, E);
+#define L(KT)                                                                                                                    \
+    if (vec) hipLaunchKernelGGL((beam_attn_context_kernel<KT, true>), grid, block, lds, st, P, E, enc, e, gpre, bbeta, nsrc, alpha_out, awe, z);  \
+    else     hipLaunchKernelGGL((beam_attn_context_kernel<KT, false>), grid, block, lds, st, P, E, enc, e, gpre, bbeta, nsrc, alpha_out, awe, z);
+    SCN_BEAM_K_SWITCH(L)
+#undef L
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
+                  float* outv, int* outi, int force_passes) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk: need 1 <= beam size <= 8 and vocab_size >= beam size");
+    SCN_ARG(logits && scores && nsrc && outv && outi && ld >= V, "beam_row_topk: bad argument");
+    const size_t staged = (size_t)(16 + V) * sizeof(float);
+    dim3 grid(N * K), block(256);
+    if (staged <= 64 * 1024 && !force_passes)
+        hipLaunchKernelGGL(beam_row_topk_kernel<true>, grid, block, staged, st, K, V, logits, ld, scores, nsrc, outv, outi);
+    else
+        hipLaunchKernelGGL(beam_row_topk_kernel<false>, grid, block, 16 * sizeof(float), st, K, V, logits, ld, scores, nsrc,
+                           outv, outi);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
+               const BeamState& s) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K && t >= 0, "beam_merge: bad beam size / step");
+    SCN_ARG((long)K * V < INT_MAX, "beam_merge: beam size x vocab_size overflows the flat index");
+    SCN_ARG(candv && candi && s.R == N * K && s.scores && s.nsrc && s.kk && s.ncomp && s.best_idx && s.best_score &&
+                s.open_images && s.comp_score && s.comp_step && s.comp_parent && s.token && s.parent,
+            "beam_merge: bad argument");
+    hipLaunchKernelGGL(beam_merge_kernel, dim3(N), dim3(64), 0, st, K, V, end_tok, t, candv, candi, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,
+                 const int* token_t, const float* table, float* hd, float* cd, float* emb) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && D > 0 && M > 0 && V > 0, "beam_advance: bad dims");
+    SCN_ARG(hs && cs && parent_t && token_t && table && hd && cd && emb, "beam_advance: null operand");
+    hipLaunchKernelGGL(beam_advance_kernel, dim3(N * K), dim3(256), 0, st, K, D, M, V, hs, cs, parent_t, token_t, table, hd,
+                       cd, emb);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_expand_rows(hipStream_t st, int N, int K, int W, const float* in, float* out) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && W > 0 && in && out, "beam_expand_rows: bad argument");
+    const long total = (long)N * K * W;
+    hipLaunchKernelGGL(beam_expand_rows_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, total, K, W, in, out);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_state_init(hipStream_t st, int N, int K, const BeamState& s) {
+    SCN_ARG(N > 0 && K >= 1 && K <= SCN_MAX_BEAM && s.R == N * K, "beam_state_init: bad argument");
+    hipLaunchKernelGGL(beam_state_init_kernel, dim3(cdiv(s.R > N ? s.R : N, 256)), dim3(256), 0, st, N, K, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace scn

@@ -133,6 +133,41 @@ int attn_datt1_post(hipStream_t st, int B, int P, int A, int T, const int* dl, c
                     float* dwpart, int* nblocks_out, bool bf = false);
 int attn_datt1_post_blocks(int B, int P);
 
+// ---- beam.hip: batched beam search, K slots per image, rows n*K + j (the semantics are at the top of that file) ------
+#define SCN_MAX_BEAM 8
+// The search state of N images (R = N*K rows); every array lives in the caller's workspace.
+struct BeamState {
+    int R;
+    float* scores;          // [R]    running score of each open slot
+    int* nsrc;              // [N]    live source beams
+    int* kk;                // [N]    beams still to fill (0: finished)
+    int* ncomp;             // [N]    completed beams so far (<= K)
+    int* best_idx;          // [N]    index of the best completed beam in comp_* (-1: none), replaced on strictly greater
+    float* best_score;      // [N]
+    int* open_images;       // [1]    images with kk > 0
+    float* comp_score;      // [R]    completed beams of image n in completion order at n*K ..
+    int* comp_step;         // [R]    step (0-based) at which <end> was picked
+    int* comp_parent;       // [R]    source slot that picked it
+    int* token;             // [steps][R]  word of the beam that sits in this slot AFTER the step
+    int* parent;            // [steps][R]  slot it came from
+};
+// e[n*K+j][p] for j < nsrc[n]; att2 = sum(slabs) + bd over rows n*K+j; rows of dead slots are left untouched
+int beam_attn_scores(hipStream_t st, int N, int K, int P, int A, const float* att1, Slabs att2, const float* bd,
+                     const float* w, const float* b0, const int* nsrc, float* e);
+// alpha_out [N*K][P] (may be NULL), awe [N*K][E] (may be NULL), z = sigmoid(gpre + bbeta) * awe (gpre.p == nullptr: z = awe)
+int beam_attn_context(hipStream_t st, int N, int K, int P, int E, const float* enc, const float* e, Slabs gpre,
+                      const float* bbeta, const int* nsrc, float* alpha_out, float* awe, float* z);
+// outv / outi [N*K][K]: per live row the top K of scores[row] + logits[row][v] - lse(row), best first.
+// force_passes != 0 (tests): read the row from global memory in every pass even when it fits the LDS.
+int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
+                  float* outv, int* outi, int force_passes);
+int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
+               const BeamState& s);
+int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,
+                 const int* token_t, const float* table, float* hd, float* cd, float* emb);
+int beam_expand_rows(hipStream_t st, int N, int K, int W, const float* in, float* out);
+int beam_state_init(hipStream_t st, int N, int K, const BeamState& s);
+
 // ---- scn_cell.hip ----------------------------------------------------------------------------
 int scn_mix_fwd(hipStream_t st, int rows, int F4, Slabs pz, const float* ex, Slabs ph, const float* qx,
                 const float* qh, float* pa, float* phs, float* xcat);

@@ -18,6 +18,7 @@
 #include "../../include/scnattn.h"
 #include "common.h"
 #include "kernels.h"
+#include "driver.h"
 
 namespace scn {
 
@@ -71,17 +72,6 @@ int profile_collect(double* out) {
 
 namespace {
 
-struct Carver {
-    float* base;
-    size_t off = 0;  // in floats
-    explicit Carver(float* b) : base(b) {}
-    float* take(size_t n) {
-        float* p = base ? base + off : nullptr;
-        off += (n + 63) & ~size_t(63);  // 256-byte granules keep every buffer 16-byte aligned
-        return p;
-    }
-};
-
 struct Saved {
     float *att1, *qx, *qh, *ex, *emb_tm, *mean_enc, *Hs, *Cs, *att2_all, *alpha_tm, *awe_all, *gate_all, *z_all,
         *pa_all, *ph_all, *gates_all, *tanhc_all, *Hd_bm, *rowmask, *alphaq_tm;
@@ -100,8 +90,6 @@ struct BwdScratch {
         *dqx_acc, *dqh_acc, *sDb, *sZ, *sH, *datt1, *dwpart, *dwtmp, *demb_tm, *dmean, *dh0, *mx_all, *gws, *present,
         *dalphaq, *dy, *gws2, *WDbh, *WaTzh, *WcatTh;
 };
-
-inline size_t sz(long a, long b = 1, long c = 1, long d = 1) { return (size_t)a * b * c * d; }
 
 // Q > 0: pooled path (encoder_out given as its un-pooled source map x [B][Q][E])
 size_t carve_saved(const scnattn_dims& d, int Q, float* base, Saved& s) {
@@ -131,8 +119,6 @@ size_t carve_saved(const scnattn_dims& d, int Q, float* base, Saved& s) {
     s.ench = d.has_att ? c.take((sz(B, Q > 0 ? Q : P, E) + 1) / 2) : nullptr;
     return c.off * sizeof(float);
 }
-
-inline int ncatA(const scnattn_dims& d) { return d.has_att ? d.A + d.E + 4 * d.F : 4 * d.F; }
 
 size_t carve_fwd(const scnattn_dims& d, int Q, float* base, FwdScratch& s) {
     Carver c(base);
@@ -226,26 +212,6 @@ inline bool bf16_mode(const scnattn_dims& d) {
     return g_dec_bf16 && d.D % 4 == 0 && d.F % 4 == 0 && d.E % 4 == 0 && (!d.has_att || d.A % 4 == 0);
 }
 
-inline int pick(int rows, int N, int K, int groups) {
-    if (g_ksplit_scale > 0) {
-        int ks = g_ksplit_scale;
-        const int kmax = K / 8 > 0 ? K / 8 : 1;
-        if (ks > kmax) ks = kmax;
-        if (ks > SCN_MAX_KSPLIT) ks = SCN_MAX_KSPLIT;
-        return ks;
-    }
-    return skinny_pick_ksplit(rows, N, K, groups);
-}
-
-// Split-K workspace of the big GEMMs: pointer and size travel together.
-struct GemmWs { float* p; long floats; };
-
-// C = op(A) . op(B) + beta * C (+ bias; rows with rowmask == 0 written as zeros): the un-batched sgemm_ws with alpha = 1
-int gemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
-         float beta, float* C, long ldc, GemmWs ws, const float* bias = nullptr, const float* rowmask = nullptr) {
-    return sgemm_ws(st, tA, tB, M, N, K, 1.f, A, lda, B, ldb, beta, C, ldc, bias, rowmask, 1, 0, 0, 0, ws.p, ws.floats);
-}
-
 // What the step kernels stream, the same selection in both drivers: the fp32 originals, or in bf16 mode the copies of
 // att1 and of the map the context is summed over that the forward pass makes once per call.
 struct Streamed {
@@ -298,17 +264,8 @@ int seq_fwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, con
     const bool bf = sm.bf;
     const int bfm = sm.bfm;
 
-    // ---- weight re-layout: every per-step contraction streams a row-major [K][N] matrix ----------
-    if (d.has_att) {
-        SCN_TRY(transpose2d(st, A, D, w->attention_decoder_att_weight, D, f.WcatA, NA));       // Wd^T
-        SCN_TRY(transpose2d(st, E, D, w->f_beta_weight, D, f.WcatA + A, NA));                  // Wbeta^T
-    }
-    SCN_TRY(copy2d(st, D, F4, w->decode_step_weight_ha, F4, f.WcatA + colph, NA));             // Ha
-    for (int g = 0; g < 4; ++g) {
-        float* wd = f.WD + (long)g * 2 * F * D;
-        SCN_TRY(transpose2d(st, D, F, w->decode_step_weight_ic + g * F, F4, wd, D));           // Wc_g^T
-        SCN_TRY(transpose2d(st, D, F, w->decode_step_weight_hc + g * F, F4, wd + (long)F * D, D));  // Hc_g^T
-    }
+    // ---- weight re-layout (driver.h) -------------------------------------------------------------
+    SCN_TRY(step_weight_layout(st, d, w, f.WcatA, f.WD));
 
     if (bf) {
         SCN_TRY(f32_to_bf16(st, sz(D, NA), f.WcatA, f.WcatAh));

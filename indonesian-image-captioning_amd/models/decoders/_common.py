@@ -173,3 +173,79 @@ def beam_search(decoder, beam_size, word_map, encoder_out, tag_out, use_attentio
     if return_all:
         return out, list(zip(complete_seqs, complete_seqs_scores))
     return out
+
+
+def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_attention, use_tags, return_all=False):
+    """``beam_search`` for N images at once, the search itself on the device (csrc/beam_search.cpp): encoder_out
+    (N, h, w, E), tag_out (N, S).  Returns a list of N results, each what ``beam_search`` returns for that image --
+    the leading <start>, the all-ones first alpha map and this build's fallback to the best open beam included; with
+    ``return_all`` each result is paired with the image's completed (sequence, score) list in completion order (by
+    step, within a step by rank).
+    K = beam_size slots per image; a step takes the top candidates of score + log_softmax ordered by (value
+    descending, flat index beam * vocab_size + word ascending): among EQUAL values the lower flat index wins, where the
+    reference leaves the choice to ``topk``.  Per step only token / parent / alpha records are kept; the sequences
+    that are returned are read off the parent chain here.  1 <= beam_size <= 8 <= vocab_size; fp32 only."""
+    from scnattn import _lib
+    k = beam_size
+    if not 1 <= k <= _lib.MAX_BEAM:
+        raise ValueError("sample_batch: beam_size must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, k))
+    V = len(word_map)
+    if V < k:
+        raise ValueError("sample_batch: vocab_size %d is smaller than beam_size %d" % (V, k))
+    _lib.require_cuda(encoder_out, tag_out)
+    N, hh, ww, E = encoder_out.shape
+    P = hh * ww
+    enc = encoder_out.reshape(N, P, E)
+    D = decoder.decoder_dim
+    if use_tags:
+        from models.decoders.attention_scn import _collect_weights
+        weights, Fd, S = _collect_weights(decoder), decoder.factored_dim, decoder.semantic_dim
+    else:       # PureAttention: the LSTM cell through its SCN view, one constant "tag" (pure_attention.py)
+        weights, Fd, S = decoder._scn_view_of_lstm(), D, 1
+        tag_out = torch.ones(N, 1, device=enc.device)
+    dims = (N, P, E, decoder.attention_dim if use_attention else 0, D, Fd, decoder.embed_dim, S, V, SF.BEAM_MAX_STEPS,
+            SF.BEAM_MAX_STEPS, int(use_attention))
+    start, end = word_map[start_token], word_map[end_token]
+    res, steps = SF.beam_search_run(dims, k, weights, enc, tag_out, start, end)
+    token, parent = res["token"].tolist(), res["parent"].tolist()
+    alpha = res["alpha"]
+    ones = torch.ones(1, hh, ww)
+
+    def chain(n, t, slot):
+        """sequence (and alpha rows) of the beam that sits in `slot` of image n after step t (0-based; -1: <start>)"""
+        words, rows = [], []
+        while t >= 0:
+            r = n * k + slot
+            words.append(token[t][r])
+            slot = parent[t][r]
+            rows.append((t, n * k + slot))
+            t -= 1
+        words.append(start)
+        return words[::-1], rows[::-1]
+
+    def alphas_of(rows):
+        if not use_attention:
+            return None
+        maps = [ones] + [alpha[t, r].view(1, hh, ww) for t, r in rows]
+        return torch.cat(maps).tolist()
+
+    out = []
+    for n in range(N):
+        done = []       # (sequence, alpha rows, score) in completion order
+        for ci in range(int(res["ncomp"][n])):
+            r = n * k + ci
+            t, src = int(res["comp_step"][r]), int(res["comp_parent"][r])
+            words, rows = chain(n, t - 1, src)
+            done.append((words + [end], rows + [(t, n * k + src)], float(res["comp_score"][r])))
+        if done:
+            i = int(res["best_idx"][n])
+        else:           # nothing reached <end> within the step limit: the best open beam (rank order: slot 0)
+            for s in range(int(res["nsrc"][n])):
+                words, rows = chain(n, steps - 1, s)
+                done.append((words, rows, float(res["scores"][n * k + s])))
+            scores = [x[2] for x in done]
+            i = scores.index(max(scores))
+        seq, rows, _ = done[i]
+        one = (seq, alphas_of(rows)) if use_attention else seq
+        out.append((one, [(s, sc) for s, _, sc in done]) if return_all else one)
+    return out

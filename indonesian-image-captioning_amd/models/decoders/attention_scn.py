@@ -83,6 +83,12 @@ class AttentionSCN(nn.Module):
     def sample(self, beam_size, word_map, encoder_out, tag_out):
         return _common.beam_search(self, beam_size, word_map, encoder_out, tag_out, use_attention=True, use_tags=True)
 
+    def sample_batch(self, beam_size, word_map, encoder_out, tag_out):
+        """``sample`` for a batch: encoder_out (N, h, w, E), tag_out (N, S) -> list of N (seq, alphas), the whole search
+        on the device (_common.beam_search_batched)."""
+        return _common.beam_search_batched(self, beam_size, word_map, encoder_out, tag_out, use_attention=True,
+                                           use_tags=True)
+
 
 _KEY_OF_FIELD = {
     "attention_encoder_att_weight": "attention.encoder_att.weight",

@@ -114,3 +114,9 @@ class PureAttention(nn.Module):
 
     def sample(self, beam_size, word_map, encoder_out):
         return _common.beam_search(self, beam_size, word_map, encoder_out, None, use_attention=True, use_tags=False)
+
+    def sample_batch(self, beam_size, word_map, encoder_out):
+        """``sample`` for a batch: encoder_out (N, h, w, E) -> list of N (seq, alphas); the LSTM cell runs through its
+        SCN view with the single constant tag, the whole search on the device (_common.beam_search_batched)."""
+        return _common.beam_search_batched(self, beam_size, word_map, encoder_out, None, use_attention=True,
+                                           use_tags=False)

@@ -63,3 +63,9 @@ class PureSCN(nn.Module):
 
     def sample(self, beam_size, word_map, encoder_out, tag_out):
         return _common.beam_search(self, beam_size, word_map, encoder_out, tag_out, use_attention=False, use_tags=True)
+
+    def sample_batch(self, beam_size, word_map, encoder_out, tag_out):
+        """``sample`` for a batch: encoder_out (N, h, w, E), tag_out (N, S) -> list of N sequences, the whole search on
+        the device (_common.beam_search_batched)."""
+        return _common.beam_search_batched(self, beam_size, word_map, encoder_out, tag_out, use_attention=False,
+                                           use_tags=True)

@@ -69,6 +69,15 @@ _SIGS = {
                          C.POINTER(Params), vp, vp, C.POINTER(Pool)], i32),
     "scnattn_seq_bwd_streams": ([vp, vp, C.POINTER(Dims), C.POINTER(Params), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                  C.POINTER(Params), vp, vp, C.POINTER(Pool)], i32),
+    "scnattn_beam_workspace": ([C.POINTER(Dims), i32, i32, C.POINTER(sz)], i32),
+    "scnattn_beam_layout": ([C.POINTER(Dims), i32, i32, C.POINTER(i64)], i32),
+    "scnattn_beam_init": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(Params), vp, vp, i32, vp], i32),
+    "scnattn_beam_steps": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(Params), vp, i32, i32, i32, vp], i32),
+    "scnattn_beam_attn_scores": ([vp, i32, i32, i32, i32, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp], i32),
+    "scnattn_beam_attn_context": ([vp, i32, i32, i32, i32, vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp], i32),
+    "scnattn_beam_row_topk": ([vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, i32], i32),
+    "scnattn_beam_merge": ([vp, i32, i32, i32, i32, i32, vp, vp, C.POINTER(vp)], i32),
+    "scnattn_beam_advance": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
     "scnattn_sgemm": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64], i32),
     "scnattn_sgemm_ws": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64,
                           vp, i64], i32),
@@ -143,6 +152,9 @@ _SIGS = {
     "scnattn_dp_comm_destroy": ([vp], i32),
     "scnattn_clamp_adam": ([vp, i64, vp, vp, vp, vp, f64, f64, f64, f64, i32, f64, f64], i32),
 }
+
+BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
+MAX_BEAM = 8
 
 EXPORTS = tuple(_SIGS) + ("scnattn_last_error",)
 

@@ -251,6 +251,70 @@ def decoder_sequence(dims, bt_host, enc, tags, caps, dl_dev, drop_mask, weights,
 
 
 # ----------------------------------------------------------------------------------------------
+# batched beam search (include/scnattn.h: scnattn_beam_*)
+# ----------------------------------------------------------------------------------------------
+BEAM_MAX_STEPS = 51       # the reference leaves its loop when `step > 50` holds after a step
+BEAM_CHUNK = 8            # steps enqueued between two looks at the open-image counter
+_BEAM_RESULTS = ("open_images", "nsrc", "kk", "ncomp", "best_idx", "best_score", "scores", "comp_score", "comp_step",
+                 "comp_parent", "token", "parent", "alpha")
+_BEAM_FLOAT = ("best_score", "scores", "comp_score", "alpha")
+
+
+def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token, max_steps=BEAM_MAX_STEPS,
+                    chunk=BEAM_CHUNK, guard=0):
+    """The whole search of N images on the device.  dims: 12-tuple in scnattn_dims order with B = N (T, L unused);
+    enc (N, P, E) as the caller has it (no copy per beam), tags (N, S) un-expanded; weights in PARAM_FIELDS order.
+    Returns (results, steps): host tensors by the names of scnattn_beam_layout -- token / parent (steps, N*K),
+    alpha (steps, N*K, P) or None -- and the number of steps that ran.  guard > 0 (tests): that many sentinel words
+    behind the workspace, returned as results["guard"] (host int32)."""
+    require_cuda(enc, tags, *weights)
+    if not 1 <= beam_size <= _lib.MAX_BEAM:
+        raise ValueError("beam_size must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, beam_size))
+    d = Dims(*dims)
+    if d.V < beam_size:
+        raise ValueError("vocab_size %d is smaller than beam_size %d" % (d.V, beam_size))
+    dev = enc.device
+    enc, tags = f32c(enc), f32c(tags)
+    weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
+    w = _params_struct(weights)
+    K, N = beam_size, d.B
+    nbytes = C.c_size_t()
+    call("scnattn_beam_workspace", C.byref(d), K, max_steps, C.byref(nbytes))
+    off = (C.c_long * _lib.BEAM_NOFF)()
+    call("scnattn_beam_layout", C.byref(d), K, max_steps, off)
+    nwords = nbytes.value // 4
+    ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_beam_init zero-fills what needs it
+    wsi = ws.view(torch.int32)
+    if guard:
+        wsi[nwords:].fill_(0x7FC5A5A5)
+    st = stream_of(enc)
+    call("scnattn_beam_init", st, C.byref(d), K, max_steps, C.byref(w), ptr(enc), ptr(tags), start_token, ptr(ws))
+    t = 0
+    while t < max_steps:
+        n = min(chunk, max_steps - t)
+        call("scnattn_beam_steps", st, C.byref(d), K, max_steps, C.byref(w), ptr(enc), end_token, t, n, ptr(ws))
+        t += n
+        if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
+            break
+    R = N * K
+    sizes = {"open_images": 1, "nsrc": N, "kk": N, "ncomp": N, "best_idx": N, "best_score": N, "scores": R,
+             "comp_score": R, "comp_step": R, "comp_parent": R, "token": t * R, "parent": t * R, "alpha": t * R * d.P}
+    out = {}
+    for i, name in enumerate(_BEAM_RESULTS):
+        if off[i] < 0:
+            out[name] = None
+            continue
+        src = ws if name in _BEAM_FLOAT else wsi
+        out[name] = src[off[i]:off[i] + sizes[name]].cpu()
+    out["token"], out["parent"] = out["token"].view(t, R), out["parent"].view(t, R)
+    if out["alpha"] is not None:
+        out["alpha"] = out["alpha"].view(t, R, d.P)
+    if guard:
+        out["guard"] = wsi[nwords:].cpu()
+    return out, t
+
+
+# ----------------------------------------------------------------------------------------------
 # stand-alone SCN cell (any batch size), split exactly where the reference splits it:
 #   scn_input      = SCNCell.forward's x side      (models/scn_cell.py:64-91)
 #   scn_recurrent  = SCNCell.recurrent_step        (models/scn_cell.py:112-154)

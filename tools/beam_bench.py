@@ -1,0 +1,100 @@
+"""Caption generation throughput: sample_batch() on a batch of images against sample() looped over the same images.
+
+    python tools/beam_bench.py [--images 32] [--beam 5] [--repeats 7] [--out profiles/NAME.txt]
+
+Both sides get the same random weights (one seed) at the train step's widths (P=196, E=2048, A=D=F=M=512, S=1000,
+V=10000), with the <end> bias raised so that searches end at mixed lengths.  Each side runs in a FRESH process
+(`--side batched|loop`, started from here): a warm-up pass over the whole batch, then `--repeats` timed passes, each
+bracketed by device events around the whole batch (the searches synchronise inside, so the events see host time too);
+the median is reported.  Prints one JSON line per side and one for the ratio.  Not part of bench.py."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, "indonesian-image-captioning_amd"), ROOT):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+
+def word_map(V):
+    wm = {"<pad>": 0, "<unk>": V - 3, "<start>": V - 2, "<end>": V - 1}
+    for i in range(1, V - 3):
+        wm["w%d" % i] = i
+    return wm
+
+
+def side(args):
+    import torch
+    from models.decoders.attention_scn import AttentionSCN
+    assert torch.cuda.is_available(), "beam_bench needs an MI355X: there is nothing to measure on a CPU"
+    dev = torch.device("cuda:0")
+    torch.manual_seed(args.seed)
+    V, E, S = args.vocab, 2048, 1000
+    m = AttentionSCN(512, 512, 512, 512, S, V, encoder_dim=E, dropout=0.0)
+    with torch.no_grad():
+        m.fc.weight.mul_(args.sharpen)              # random-init logits are nearly uniform: sharpen them ...
+        m.fc.bias[V - 1] += args.end_bias           # ... and raise <end> so that beams complete at different steps
+    m = m.to(dev).eval()
+    enc = torch.rand(args.images, 14, 14, E).to(dev)
+    tags = torch.rand(args.images, S).to(dev)
+    wm = word_map(V)
+
+    def run():
+        with torch.no_grad():
+            if args.side == "batched":
+                return [r[0] for r in m.sample_batch(args.beam, wm, enc, tags)]
+            return [m.sample(args.beam, wm, enc[i:i + 1], tags[i:i + 1])[0] for i in range(args.images)]
+
+    seqs = run()                                    # warm-up: code objects, allocator, workspaces
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(args.repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        run()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    med = statistics.median(ms)
+    lens = [len(s) for s in seqs]
+    print(json.dumps({"side": args.side, "images": args.images, "beam": args.beam, "median_ms": round(med, 3),
+                      "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "captions_per_s": round(args.images * 1e3 / med, 2),
+                      "steps_longest": max(lens) - 1, "lengths": sorted(lens), "digest": hash(tuple(map(tuple, seqs))) & 0xffffffff}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=32)
+    ap.add_argument("--beam", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--vocab", type=int, default=10000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--sharpen", type=float, default=10.0)
+    ap.add_argument("--end-bias", type=float, default=2.0)
+    ap.add_argument("--side", choices=["batched", "loop"])
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    if args.side:
+        side(args)
+        return
+    lines = []
+    for s in ("batched", "loop"):
+        cmd = [sys.executable, os.path.abspath(__file__), "--side", s] + [a for a in sys.argv[1:]]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, check=True, timeout=600)
+        lines.append(r.stdout.strip().splitlines()[-1])
+        print(lines[-1], flush=True)
+    a, b = (json.loads(x) for x in lines)
+    lines.append(json.dumps({"batched_over_loop": round(a["captions_per_s"] / b["captions_per_s"], 3),
+                             "same_captions": a["digest"] == b["digest"]}))
+    print(lines[-1])
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("tools/beam_bench.py %s\n" % " ".join(sys.argv[1:]) + "\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
