@@ -23,7 +23,8 @@
 extern "C" {
 #endif
 
-#define SCNATTN_VERSION 108 /* 0.1.8: + batched beam search (scnattn_beam_*; new symbols only, the version stays), + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
+#define SCNATTN_VERSION 108 /* 0.1.8: + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
+                               new symbols only, the version stays), + batched beam search (scnattn_beam_*; new symbols only, the version stays), + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
                                _conv3x3_fwd_bn_eval; new symbols only, the version stays), + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
                                epilogues inside the GEMM launch (options cgemm_combine, cgemm_combine_max), option dec_tail;
                                0.1.7: + halo-staged 3x3 weight gradient, strided 3x3 d input, the stem (scnattn_stem_*), BatchNorm
@@ -497,6 +498,27 @@ int scnattn_conv3x3_fwd16(void* stream, int N, int Hi, int Wi, int Cin, int Cout
                           void* y, const scnattn_conv_extra* ex, float* ws, long ws_floats);
 int scnattn_conv3x3_dgrad16(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const void* dy, const void* wt,
                             void* dx, const scnattn_conv_extra* ex, float* ws, long ws_floats);
+/* Forward convolutions of an EVAL-mode trunk on bf16 maps, the BatchNorm folded into the epilogue (csrc/cgemm16.hip, EPI 3):
+ * scnattn_conv1x1_fwd_bn_eval / scnattn_conv3x3_fwd_bn_eval above with x, w, y and res bf16 -- what a Bottleneck computes
+ * under torch.autocast("cuda", dtype=torch.bfloat16) after encoder.eval().
+ *     y [R][Cout] = bf16(act(fma(conv(x, w), scale, shift) (+ res))),  scale = gamma / sqrt(var + eps), shift = beta - mean * scale
+ * formed per output column from the four fp32 vectors (non-null, 16-byte aligned) at every call; accumulation and the epilogue
+ * are fp32, the result is rounded once (to nearest even).  w is [Cout][Cin] (1x1) or [Cout][3][3][Cin] (3x3); res (NULL:
+ * none) is a bf16 [R][Cout] map, 16-byte aligned, ldres % 8 == 0, ldres >= Cout, below 2 GB.  ex (may be NULL): geometry of
+ * the gathered 1x1 (stride, Hi / Wi / Ho / Wo), force_split, force_mi; pro = epi = 0.  1x1: Cin, Cout multiples of 8;
+ * 3x3: Cin a multiple of 32, Cout of 8, stride 1 or 2, odd maps allowed.  A split product (the policy of scnattn_cgemm16,
+ * or force_split) writes fp32 slabs to ws and a second launch sums them in slab order and applies the same epilogue.
+ * Every refusal returns -1 before anything is launched: y is untouched. */
+typedef struct scnattn_bn_eval16 {
+    const float* gamma; const float* beta; const float* mean; const float* var; float eps;
+    const void* res; long ldres;   /* bf16 residual, elements; NULL: none */
+    int relu;
+} scnattn_bn_eval16;
+int scnattn_conv1x1_fwd_bn_eval16(void* stream, int R, int Cin, int Cout, const void* x, const void* w, void* y,
+                                  const scnattn_bn_eval16* bn, const scnattn_conv_extra* ex, float* ws, long ws_floats);
+int scnattn_conv3x3_fwd_bn_eval16(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const void* x,
+                                  const void* w, void* y, const scnattn_bn_eval16* bn, const scnattn_conv_extra* ex,
+                                  float* ws, long ws_floats);
 int scnattn_wgrad16_3x3(void* stream, int N, int H, int W, int Cin, int Cout, const void* dy, const void* x, float* dw,
                         float* ws, long ws_floats, int k_slices);
 int scnattn_wgrad16_rows(void* stream, int R, int Cin, int Cout, const void* dy, const void* x, long src_rows, float* dw,

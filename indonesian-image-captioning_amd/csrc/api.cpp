@@ -366,6 +366,40 @@ int scnattn_conv3x3_fwd16(void* stream, int N, int Hi, int Wi, int Cin, int Cout
     return cgemm16(ST(stream), N * e.Ho * e.Wo, Cout, 9 * Cin, x, Cin, w, 9L * Cin, 0.f, y, Cout, 1, ws, ws ? ws_floats : 0, &e, 0);
 }
 
+// eval BatchNorm epilogue on bf16 maps (EPI 3 of csrc/cgemm16.hip): the rules of bn_eval_extra for ex; the vectors, the
+// residual and the widths are cgemm16's own checks, all before the GPU is touched
+static int bn_eval16_extra(const char* who, const scnattn_bn_eval16* bn, const scnattn_conv_extra* ex, ConvExtra* e) {
+    if (!bn) { set_error("%s: invalid argument: bn is NULL", who); return -1; }
+    if (ex && (ex->pro != 0 || ex->epi != 0)) { set_error("%s: invalid argument: ex carries geometry only (pro = epi = 0)", who); return -1; }
+    if (ex) {
+        e->stride = ex->stride < 1 ? 1 : ex->stride; e->Hi = ex->Hi; e->Wi = ex->Wi; e->Ho = ex->Ho; e->Wo = ex->Wo;
+        e->force_split = ex->force_split; e->force_mi = ex->force_mi;
+    }
+    e->epi = 3;
+    e->egamma = bn->gamma; e->ebeta = bn->beta; e->emean = bn->mean; e->evar = bn->var; e->eeps = bn->eps;
+    e->ez = (const float*)bn->res; e->ldz = bn->res ? bn->ldres : 0; e->erelu = bn->relu != 0;
+    return 0;
+}
+
+int scnattn_conv1x1_fwd_bn_eval16(void* stream, int R, int Cin, int Cout, const void* x, const void* w, void* y,
+                                  const scnattn_bn_eval16* bn, const scnattn_conv_extra* ex, float* ws, long ws_floats) {
+    ConvExtra e;
+    SCN_TRY(bn_eval16_extra("conv1x1_fwd_bn_eval16", bn, ex, &e));
+    SCN_ARG(R > 0 && Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0, "conv1x1_fwd_bn_eval16: R > 0, Cin and Cout positive multiples of 8");
+    return cgemm16(ST(stream), R, Cout, Cin, x, Cin, w, Cin, 0.f, y, Cout, 1, ws, ws ? ws_floats : 0, &e, 0);
+}
+
+int scnattn_conv3x3_fwd_bn_eval16(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const void* x,
+                                  const void* w, void* y, const scnattn_bn_eval16* bn, const scnattn_conv_extra* ex,
+                                  float* ws, long ws_floats) {
+    SCN_ARG(N > 0 && Hi > 0 && Wi > 0 && (stride == 1 || stride == 2), "conv3x3_fwd_bn_eval16: geometry");
+    ConvExtra e;
+    SCN_TRY(bn_eval16_extra("conv3x3_fwd_bn_eval16", bn, ex, &e));
+    SCN_ARG(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 8 == 0, "conv3x3_fwd_bn_eval16: Cin a positive multiple of 32, Cout of 8");
+    set_c3(e, 1, Cin, N, Hi, Wi, stride);
+    return cgemm16(ST(stream), N * e.Ho * e.Wo, Cout, 9 * Cin, x, Cin, w, 9L * Cin, 0.f, y, Cout, 1, ws, ws ? ws_floats : 0, &e, 0);
+}
+
 // wt: the TRANSPOSED bf16 weight copy [Cin][3][3][Cout] (scnattn_bf16_weights).  stride 1: a forward convolution of dy with
 // flipped taps; stride 2: four parity classes in one launch.
 int scnattn_conv3x3_dgrad16(void* stream, int N, int Hi, int Wi, int Cin, int Cout, int stride, const void* dy, const void* wt,

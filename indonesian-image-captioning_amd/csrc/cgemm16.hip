@@ -48,6 +48,7 @@ struct HArgs {
     int flip;                     // mode 1: weight tap = 8 - t (a stride-1 d input as a forward convolution of dY)
     float* stat_partial; const float* stat_shift; int ldp;
     const bf16_t* ez; long ldz; const float* emean; const float* einvstd; const float* egamma; const float* ebeta;   // EPI 2
+    const float* evar; float eeps; int erelu;     // EPI 3: running variance, eps, ReLU (ez / ldz: the optional bf16 residual)
 };
 
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {       // round to nearest even, NaN stays NaN (v_cvt_pk_bf16_f32)
@@ -60,6 +61,9 @@ __device__ __forceinline__ unsigned pack2(float lo, float hi) {       // round t
 // EPI 2 (bf16 output, un-split d-input products): g = dx * [relu mask of the consumer BatchNorm recomputed from its bf16
 // pre-activation z with the forward pass's own expression] stored, + column sums of g and g*xhat per 64-row block -- the
 // reduce pass of that BatchNorm's backward inside the product that feeds it (as EPI 2 of csrc/cgemm.hip).
+// EPI 3 (bf16 output, forward products): the eval-mode BatchNorm of the convolution's consumer, y = act(fma(acc, scale[n],
+// shift[n]) (+ res[m][n])) with scale / shift folded from the running statistics here (bn_eval_fold), rounded once -- EPI 3
+// of csrc/cgemm.hip on bf16 maps.  A split product runs EPI 0 and creduce16_kernel applies it.
 // GATHER: rows of A are gathered (strided 1x1 convolution).  OBF: C is bf16.  C3: 0 plain, 1 3x3 taps over K (forward, or a
 // stride-1 d input with `flip`), 4 stride-2 d input, one parity class per blockIdx.y.
 template <int MI, int EPI, bool GATHER, bool OBF, int C3>
@@ -284,7 +288,9 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
         const int rl = lane >> 3, c8 = (lane & 7) * 8, ncol = n0 + wn * 64 + c8;
         const bool use_c = g.beta != 0.f;
         [[maybe_unused]] float mu[8], is[8], ga[8], be[8], s1[8], s2[8];
-        [[maybe_unused]] const __amdgpu_buffer_rsrc_t zrs = make_rsrc(g.ez, EPI == 2 ? (unsigned)(((long)(g.M - 1) * g.ldz + g.N) * 2) : 0u);
+        [[maybe_unused]] float sc[8], sh[8];                      // EPI 3: folded scale / shift of this lane's eight columns
+        [[maybe_unused]] const bool use_r = EPI == 3 && g.ez != nullptr;
+        [[maybe_unused]] const __amdgpu_buffer_rsrc_t zrs = make_rsrc(g.ez, (EPI == 2 || use_r) ? (unsigned)(((long)(g.M - 1) * g.ldz + g.N) * 2) : 0u);
         if constexpr (EPI == 2) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
@@ -292,6 +298,19 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
                 mu[q] = ok ? g.emean[ncol + q] : 0.f; is[q] = ok ? g.einvstd[ncol + q] : 0.f;
                 ga[q] = ok ? g.egamma[ncol + q] : 0.f; be[q] = ok ? g.ebeta[ncol + q] : 0.f;
                 s1[q] = 0.f; s2[q] = 0.f;
+            }
+        }
+        if constexpr (EPI == 3) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) { sc[q] = 0.f; sh[q] = 0.f; }
+            if (ncol < g.N) {       // N % 8 == 0: all eight columns or none
+#pragma unroll
+                for (int v = 0; v < 2; ++v) {
+                    const f32x4 gv = *reinterpret_cast<const f32x4*>(g.egamma + ncol + 4 * v), bv = *reinterpret_cast<const f32x4*>(g.ebeta + ncol + 4 * v);
+                    const f32x4 mv = *reinterpret_cast<const f32x4*>(g.emean + ncol + 4 * v), vv = *reinterpret_cast<const f32x4*>(g.evar + ncol + 4 * v);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) bn_eval_fold(gv[q], bv[q], mv[q], vv[q], g.eeps, sc[4 * v + q], sh[4 * v + q]);
+                }
             }
         }
 #pragma unroll
@@ -310,6 +329,15 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
                 for (int it = 0; it < 4; ++it) {
                     const int m = mw0 + i * 32 + it * 8 + rl;
                     zv[it] = __builtin_amdgcn_raw_buffer_load_b128(zrs, (m < g.M && ncol < g.N) ? (unsigned)(((long)m * g.ldz + ncol) * 2) + opq : OOB_OFF, 0, 0);
+                }
+            }
+            if constexpr (EPI == 3) {       // residual rows: in flight while the product is dumped
+                if (use_r) {
+#pragma unroll
+                    for (int it = 0; it < 4; ++it) {
+                        const int m = mw0 + i * 32 + it * 8 + rl;
+                        zv[it] = __builtin_amdgcn_raw_buffer_load_b128(zrs, (m < g.M && ncol < g.N) ? (unsigned)(((long)m * g.ldz + ncol) * 2) + opq : OOB_OFF, 0, 0);
+                    }
                 }
             }
             dump_half(i);
@@ -339,6 +367,20 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
                         vv[q] = on ? bf16_to_f32(pack2(vv[q], 0.f) & 0xffffu) : 0.f;
                         s1[q] += vv[q];
                         s2[q] = fmaf(vv[q], xh, s2[q]);
+                    }
+                    v0 = f32x4{vv[0], vv[1], vv[2], vv[3]};
+                    v1 = f32x4{vv[4], vv[5], vv[6], vv[7]};
+                }
+                if constexpr (EPI == 3) {
+                    float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        float y = fmaf(vv[q], sc[q], sh[q]);
+                        if (use_r) {
+                            const unsigned w = zv[it][q >> 1];
+                            y += bf16_to_f32((q & 1) ? (w >> 16) : (w & 0xffffu));
+                        }
+                        vv[q] = g.erelu ? fmaxf(y, 0.f) : y;
                     }
                     v0 = f32x4{vv[0], vv[1], vv[2], vv[3]};
                     v1 = f32x4{vv[4], vv[5], vv[6], vv[7]};
@@ -414,7 +456,8 @@ __global__ __launch_bounds__(256, 3) void cgemm16_kernel(HArgs g) {
 
 // Sum split-K slabs [S][M][N] (fp32) in slab order -> C (bf16 or fp32, + beta * C); 4 columns per thread.  STATS: also the
 // column sums of (y - s), (y - s)^2 per 64-row block (the statistics epilogue of a split product), channel-major.
-template <bool OBF, bool STATS>
+// EVAL (bf16 C): the eval BatchNorm epilogue of a split product (EPI 3 above) on the summed slabs.
+template <bool OBF, bool STATS, bool EVAL = false>
 __global__ __launch_bounds__(256) void creduce16_kernel(HArgs g) {
     __shared__ float red[16][2][64 + 1];
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
@@ -425,6 +468,17 @@ __global__ __launch_bounds__(256) void creduce16_kernel(HArgs g) {
     if (c < g.N) {
         f32x4 sft = {0.f, 0.f, 0.f, 0.f};
         if (STATS && g.stat_shift) sft = *reinterpret_cast<const f32x4*>(g.stat_shift + c);
+        [[maybe_unused]] f32x4 esc = sft, esh = sft;
+        if constexpr (EVAL) {
+            const f32x4 gv = *reinterpret_cast<const f32x4*>(g.egamma + c), bv = *reinterpret_cast<const f32x4*>(g.ebeta + c);
+            const f32x4 mv = *reinterpret_cast<const f32x4*>(g.emean + c), vv = *reinterpret_cast<const f32x4*>(g.evar + c);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float sc, sh;
+                bn_eval_fold(gv[k], bv[k], mv[k], vv[k], g.eeps, sc, sh);
+                esc[k] = sc; esh[k] = sh;
+            }
+        }
         f32x4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -455,7 +509,17 @@ __global__ __launch_bounds__(256) void creduce16_kernel(HArgs g) {
                     s2[k] = fmaf(d, d, s2[k]);
                 }
             }
-            if (OBF) {
+            if constexpr (EVAL) {
+                f32x4 res = {0.f, 0.f, 0.f, 0.f};
+                if (g.ez) res = ld4(g.ez + (long)r * g.ldz + c);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float y = fmaf(v[u][k], esc[k], esh[k]);
+                    if (g.ez) y += res[k];
+                    v[u][k] = g.erelu ? fmaxf(y, 0.f) : y;
+                }
+                *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(g.C) + (long)r * g.ldc + c) = u32x2{pack2(v[u][0], v[u][1]), pack2(v[u][2], v[u][3])};
+            } else if (OBF) {
                 bf16_t* cp = reinterpret_cast<bf16_t*>(g.C) + (long)r * g.ldc + c;
                 if (g.beta != 0.f) {
                     const u32x2 o = *reinterpret_cast<const u32x2*>(cp);
@@ -481,6 +545,11 @@ template <int MI, int C3>
 void launch16(hipStream_t st, dim3 grid, const HArgs& g, int kepi, bool gather, bool obf) {
     dim3 block(256);
 #define SCN_L16(EPI_, G_, O_) hipLaunchKernelGGL((cgemm16_kernel<MI, EPI_, G_, O_, C3>), grid, block, 0, st, g)
+    if (kepi == 3) {        // eval BatchNorm epilogue: forward products, bf16 maps (host-checked)
+        if constexpr (C3 == 0) { if (gather) SCN_L16(3, true, true); else SCN_L16(3, false, true); }
+        if constexpr (C3 == 1) SCN_L16(3, false, true);
+        return;
+    }
     if constexpr (C3 == 0) {
         if (gather) { if (kepi) { if (obf) SCN_L16(1, true, true); else SCN_L16(1, true, false); } else { if (obf) SCN_L16(0, true, true); else SCN_L16(0, true, false); } }
         else if (kepi == 2) SCN_L16(2, false, true);
@@ -495,7 +564,7 @@ void launch16(hipStream_t st, dim3 grid, const HArgs& g, int kepi, bool gather, 
 }  // namespace
 
 // C[M][N] = A . B^T (+ beta*C).  A bf16 [M][K] (lda), B bf16 [N][K] (ldb); C bf16 (out_bf16) or fp32, leading dimension ldc
-// in ELEMENTS.  ex: epi 0 / 1 (statistics, channel-major partials), stride > 1 (row gather), c3 = 1 (3x3 taps over K;
+// in ELEMENTS.  ex: epi 0 / 1 (statistics, channel-major partials) / 3 (eval BatchNorm), stride > 1 (row gather), c3 = 1 (3x3 taps over K;
 // ex->force_mi == -1 ... no: `flip` is passed separately) or 4 (stride-2 d input).  ws: fp32 split-K slabs.
 int cgemm16(hipStream_t st, int M, int N, int K, const void* A, long lda, const void* B, long ldb, float beta, void* C, long ldc,
             int out_bf16, float* ws, long ws_floats, const ConvExtra* ex, int flip) {
@@ -505,7 +574,13 @@ int cgemm16(hipStream_t st, int M, int N, int K, const void* A, long lda, const 
     SCN_ARG(N % 8 == 0 && ldc % (out_bf16 ? 8 : 4) == 0, "cgemm16: N / ldc granularity");
     const int epi = ex ? ex->epi : 0, c3 = ex ? ex->c3 : 0;
     const bool gather = ex && ex->stride > 1 && c3 == 0;
-    SCN_ARG(epi == 0 || ((epi == 1 || epi == 2) && ex->stat_partial && beta == 0.f), "cgemm16: statistics / mask epilogue needs a plain product");
+    SCN_ARG(epi == 0 || epi == 3 || ((epi == 1 || epi == 2) && ex->stat_partial && beta == 0.f), "cgemm16: statistics / mask epilogue needs a plain product");
+    SCN_ARG(epi != 3 || (out_bf16 && beta == 0.f && (c3 == 0 || c3 == 1)), "cgemm16: eval BatchNorm epilogue needs a bf16 output, beta == 0 and a forward product");
+    SCN_ARG(epi != 3 || (ex->egamma && ex->ebeta && ex->emean && ex->evar && aligned16(ex->egamma) && aligned16(ex->ebeta) &&
+                         aligned16(ex->emean) && aligned16(ex->evar)),
+            "cgemm16: eval BatchNorm vectors must be non-null and 16-byte aligned");
+    SCN_ARG(epi != 3 || !ex->ez || (aligned16(ex->ez) && ex->ldz % 8 == 0 && ex->ldz >= N && ((long)(M - 1) * ex->ldz + N) * 2 < 0x7fffffffL),
+            "cgemm16: eval BatchNorm residual must be 16-byte aligned with ldres % 8 == 0 and ldres >= N, within the 2 GB descriptor range");
     SCN_ARG(epi != 2 || (out_bf16 && !gather && c3 != 4 && ex->ez && ex->emean && ex->einvstd && ex->egamma && ex->ebeta && ex->ldz % 8 == 0 &&
                          aligned16(ex->ez) && ((long)(M - 1) * ex->ldz + N) * 2 < 0x7fffffffL),
             "cgemm16: mask epilogue needs a bf16 output, an un-gathered product and the consumer BatchNorm's z / mean / invstd / gamma / beta");
@@ -548,6 +623,7 @@ int cgemm16(hipStream_t st, int M, int N, int K, const void* A, long lda, const 
         g.geo = conv_geom(*ex);
         g.stat_partial = ex->stat_partial; g.stat_shift = ex->stat_shift; g.ldp = cgemm_stat_ld(M);
         g.ez = (const bf16_t*)ex->ez; g.ldz = ex->ldz; g.emean = ex->emean; g.einvstd = ex->einvstd; g.egamma = ex->egamma; g.ebeta = ex->ebeta;
+        g.evar = ex->evar; g.eeps = ex->eeps; g.erelu = ex->erelu;
     }
     dim3 grid(mt * nt, c3 == 4 ? 4 : S);
     const int kepi = S > 1 ? 0 : epi;
@@ -558,7 +634,8 @@ int cgemm16(hipStream_t st, int M, int N, int K, const void* A, long lda, const 
     SCN_LAUNCH_CHECK();
     if (S > 1) {
         dim3 sgrid(cdiv(N, 64), cdiv(M, SROWS)), block(256);
-        if (epi == 1) { if (obf) hipLaunchKernelGGL((creduce16_kernel<true, true>), sgrid, block, 0, st, g); else hipLaunchKernelGGL((creduce16_kernel<false, true>), sgrid, block, 0, st, g); }
+        if (epi == 3)      hipLaunchKernelGGL((creduce16_kernel<true, false, true>), sgrid, block, 0, st, g);
+        else if (epi == 1) { if (obf) hipLaunchKernelGGL((creduce16_kernel<true, true>), sgrid, block, 0, st, g); else hipLaunchKernelGGL((creduce16_kernel<false, true>), sgrid, block, 0, st, g); }
         else          { if (obf) hipLaunchKernelGGL((creduce16_kernel<true, false>), sgrid, block, 0, st, g); else hipLaunchKernelGGL((creduce16_kernel<false, false>), sgrid, block, 0, st, g); }
         SCN_LAUNCH_CHECK();
     }

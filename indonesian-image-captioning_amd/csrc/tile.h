@@ -57,6 +57,11 @@ __device__ __forceinline__ float bn_xhat(float z, float mean, float invstd) { re
 __device__ __forceinline__ float bn_norm(float z, float mean, float invstd, float gamma, float beta) {
     return fmaf(bn_xhat(z, mean, invstd), gamma, beta);
 }
+// Eval mode (running statistics): the BatchNorm folded to y = fma(z, scale, shift), as EPI 3 of csrc/cgemm.hip forms it.
+__device__ __forceinline__ void bn_eval_fold(float gamma, float beta, float mean, float var, float eps, float& scale, float& shift) {
+    scale = gamma * (1.f / sqrtf(var + eps));
+    shift = beta - mean * scale;
+}
 // ReLU mask of a BatchNorm recomputed from its pre-activation z: the function the forward pass evaluated was
 // relu(bn_norm(z, ...)), or -- folded -- relu(fma(z, scale, shift)); (a, b) is that pair.  xhat is handed back for
 // the g * xhat sum.  Not folded, this IS bn_norm(z, mean, invstd, a, b) > 0: the same fma of the same bn_xhat; it selects

@@ -58,6 +58,10 @@ class BnEval(C.Structure):         # scnattn_bn_eval
                 ("res", C.c_void_p), ("ldres", C.c_long), ("relu", C.c_int)]
 
 
+class BnEval16(C.Structure):       # scnattn_bn_eval16: the same layout, res is a bf16 map
+    _fields_ = BnEval._fields_
+
+
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
@@ -102,6 +106,9 @@ _SIGS = {
     "scnattn_bf16_weights": ([vp, i32, vp, vp, i32], i32),
     "scnattn_cgemm16": ([vp, i32, i32, i32, vp, i64, vp, i64, f32, vp, i64, i32, vp, i64, C.POINTER(ConvExtra)], i32),
     "scnattn_conv3x3_fwd16": ([vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(ConvExtra), vp, i64], i32),
+    "scnattn_conv1x1_fwd_bn_eval16": ([vp, i32, i32, i32, vp, vp, vp, C.POINTER(BnEval16), C.POINTER(ConvExtra), vp, i64], i32),
+    "scnattn_conv3x3_fwd_bn_eval16": ([vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(BnEval16), C.POINTER(ConvExtra),
+                                       vp, i64], i32),
     "scnattn_conv3x3_dgrad16": ([vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(ConvExtra), vp, i64], i32),
     "scnattn_wgrad16_3x3": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, i32], i32),
     "scnattn_block16_sizes": ([vp, vp, vp, vp, vp, vp], i32),

@@ -1,8 +1,9 @@
-"""What the three hand-written Bottleneck paths share (scnattn/resnet.py `Bottleneck.forward` tries them in this order):
+"""What the four hand-written Bottleneck paths share (scnattn/resnet.py `Bottleneck.forward` tries them in this order):
 
     fp32 maps, training mode    scnattn/conv.py       train_reason / bottleneck
     fp32 maps, eval mode        scnattn/conv_eval.py  eval_reason / bottleneck_eval
     bf16 maps, training mode    scnattn/conv16.py     bf16_reason / bottleneck
+    bf16 maps, eval mode        scnattn/conv_eval16.py  eval16_reason / bottleneck_eval16
 
 Each `*_reason(mod, x)` returns None when its path applies, else a short reason: `reason` below, then its own terms.
 These run on the host before every block call (the bf16 step is host-bound), so they read submodules from `_modules`:

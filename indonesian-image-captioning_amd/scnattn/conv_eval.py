@@ -18,7 +18,7 @@ fused forward is one autograd node that saves only its input and, in backward, r
 unchanged module-path ops (`Bottleneck.module_forward`) and returns their gradients -- backward keeps today's kernels.
 
 `Bottleneck.forward` (scnattn/resnet.py) takes this path when `eval_reason` returns None; every other case (bf16
-autocast, widths that are not multiples of 16, CPU tensors, `conv.ENABLED = False`) keeps the module path."""
+autocast -- bf16 maps then take scnattn/conv_eval16.py --, widths that are not multiples of 16, CPU tensors, `conv.ENABLED = False`) keeps the module path."""
 import ctypes as C
 
 import torch

@@ -6,9 +6,9 @@ the module tree -- and therefore every state_dict key -- equals
 torchvision is not installed in this image (nor on the GPU box), and the reference's
 ``pretrained=True`` needs a download, so weights are random-init by torchvision's own recipe
 (kaiming-normal fan-out convs, BN gamma=1 beta=0) unless a state_dict is loaded.  On MI355X every
-Bottleneck runs on the hand-written kernels of one of the three paths of scnattn/block.py (fp32 training, fp32
-eval, bf16 training); what none of them covers (CPU tensors, fp32 under autocast, widths that are not multiples
-of 16) takes the module path: nn.Conv2d (MIOpen) + the fused BatchNorm kernels."""
+Bottleneck runs on the hand-written kernels of one of the four paths of scnattn/block.py (fp32 training, fp32
+eval, bf16 training, bf16 eval); what none of them covers (CPU tensors, fp32 under autocast, widths that are not
+multiples of 16, a bf16 eval block that needs a gradient) takes the module path: nn.Conv2d (MIOpen) + the fused BatchNorm kernels."""
 import os
 
 import torch
@@ -66,14 +66,17 @@ class Bottleneck(nn.Module):
 
     def forward(self, x):
         # the hand-written paths of scnattn/block.py in this order: fp32 training (scnattn/conv.py: one autograd node, the
-        # BatchNorm fused into the convolutions), fp32 eval (scnattn/conv_eval.py), bf16 training (scnattn/conv16.py)
-        from . import conv as _conv, conv_eval as _ce, conv16 as _c16
+        # BatchNorm fused into the convolutions), fp32 eval (scnattn/conv_eval.py), bf16 training (scnattn/conv16.py),
+        # bf16 eval (scnattn/conv_eval16.py)
+        from . import conv as _conv, conv_eval as _ce, conv16 as _c16, conv_eval16 as _ce16
         if _conv.usable(self, x):
             return _conv.bottleneck(self, x)
         if _ce.eval_reason(self, x) is None:
             return _ce.bottleneck_eval(self, x)
         if _c16.usable(self, x):
             return _c16.bottleneck(self, x)
+        if _ce16.eval16_reason(self, x) is None:
+            return _ce16.bottleneck_eval16(self, x)
         return self.module_forward(x)
 
     def module_forward(self, x):

@@ -5,6 +5,9 @@ after warm-up, timed with device events; B = 32 and B = 1 at 3 x 256 x 256, chan
 kernel launches of one Bottleneck forward on each path (torch.profiler device trace).
 
     python tools/eval_bench.py [--reps 5] [--iters 4]
+    python tools/eval_bench.py --bf16                # the same protocol under torch.autocast("cuda", dtype=torch.bfloat16):
+                                                     # fused bf16 eval (scnattn/conv_eval16.py), the bf16 module path
+                                                     # (conv.ENABLED = False under autocast) and the fused fp32 eval forward
     python tools/eval_bench.py --validate-batch      # one validate() batch (EncoderCaption + EncoderTagger +
                                                      # AttentionSCN, B = 32), for `rocprofv3 --kernel-trace --stats`"""
 import argparse
@@ -112,6 +115,65 @@ def bench(args):
                                                      ", ".join(n[:60] for n in names)), flush=True)
 
 
+def bench_bf16(args):
+    """Three paths, one process, alternating after warm-up, device events: fused bf16 eval, bf16 module path, fused fp32."""
+    print("eval_bench --bf16: EncoderCaption(...).eval() forward under no_grad, 3x256x256, images/s (median of %d rounds x %d "
+          "forwards; fused bf16, bf16 module path and fused fp32 alternating)" % (args.reps, args.iters), flush=True)
+    torch.manual_seed(0)
+    ac = lambda: torch.autocast("cuda", dtype=torch.bfloat16)      # noqa: E731
+
+    def path(kind, enc, x, **kw):
+        if kind == "fp32":
+            return enc(x, **kw)
+        with ac():
+            return run_path(kind == "bf16", lambda: enc(x, **kw))
+
+    kinds = ("bf16", "bf16-module", "fp32")
+    for cl in (True, False):
+        enc = EncoderCaption(channels_last=cl).to(dev).eval()
+        for B in (32, 1):
+            x = torch.randn(B, 3, 256, 256, device=dev)
+            t0 = time.time()
+            with torch.no_grad():
+                for kind in kinds:       # warm-up (the module path's first call pays MIOpen's solver selection)
+                    for _ in range(2):
+                        path(kind, enc, x)
+            torch.cuda.synchronize()
+            warm = time.time() - t0
+            ms = {k: [] for k in kinds}
+            with torch.no_grad():
+                for _ in range(args.reps):
+                    for kind in kinds:
+                        ms[kind].append(timed_ms(lambda: path(kind, enc, x), args.iters))
+                maps = {k: path(k, enc, x, pooled=False) for k in kinds}
+            d16 = ((maps["bf16"] - maps["fp32"]).norm() / maps["fp32"].norm()).item()
+            dm = ((maps["bf16-module"] - maps["fp32"]).norm() / maps["fp32"].norm()).item()
+            t = {k: statistics.median(v) for k, v in ms.items()}
+            print("channels_last=%-5s B=%-2d  fused bf16 %8.3f ms %8.1f img/s | bf16 module %8.3f ms %8.1f img/s | fused fp32 %8.3f ms "
+                  "%8.1f img/s | bf16 fused vs module %.2fx, vs fused fp32 %.2fx | trunk map rel-l2 vs fused fp32: fused bf16 %.1e, "
+                  "bf16 module %.1e | warm-up %.1f s" % (cl, B, t["bf16"], B * 1e3 / t["bf16"], t["bf16-module"], B * 1e3 / t["bf16-module"],
+                                                         t["fp32"], B * 1e3 / t["fp32"], t["bf16-module"] / t["bf16"], t["fp32"] / t["bf16"],
+                                                         d16, dm, warm), flush=True)
+        del enc
+        torch.cuda.empty_cache()
+    # launches of one Bottleneck forward on bf16 maps (layer3.1 and layer3.0 at B = 32, 256 x 256 input)
+    from scnattn import conv16 as C16
+    enc = EncoderCaption(channels_last=True).to(dev).eval()
+    C16.refresh_weights(enc.resnet)
+    for name, idx, cin, H in (("layer3.1", 1, 1024, 16), ("layer3.0", 0, 512, 32)):
+        block = enc.resnet[6][idx]
+        x = torch.randn(32, cin, H, H, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        with ac():
+            got = launches_per_block(block, x)
+        for fused in (True, False):
+            names = got[fused]
+            if names is None:
+                print("%s bf16 %s: launches n/a" % (name, "fused " if fused else "module"), flush=True)
+                continue
+            print("%s bf16 %s: %d kernel launches: %s" % (name, "fused " if fused else "module", len(names),
+                                                          ", ".join(n[:60] for n in names)), flush=True)
+
+
 def validate_batch():
     """One validate() batch through the real EncoderCaption + EncoderTagger (full ResNet-152 trunks, channels-last)
     and an AttentionSCN decoder at B = 32, 256 x 256: the eval path a training run takes once per epoch."""
@@ -144,8 +206,11 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--validate-batch", action="store_true")
+    ap.add_argument("--bf16", action="store_true")
     a = ap.parse_args()
     if a.validate_batch:
         validate_batch()
+    elif a.bf16:
+        bench_bf16(a)
     else:
         bench(a)
