@@ -14,14 +14,15 @@ the second term being the single round-to-nearest-even to bf16 of a value within
 roundoff 2^-8).  ReLU is 1-Lipschitz and commutes with the rounding, so the bound holds after the clamp and no element is
 excluded.
 
-The mirror follows csrc/cgemm16.hip `cgemm16()`: row tile mi (1 when the 128-row grid has < 256 tiles and M > 64;
-force_mi), S (policy: tiles < 192 and K >= 512 with a workspace -> ceil(512 / tiles), at most K / 256, 16 and what the
+The mirror is conv16_refs.mirror_cgemm16, the one mirror of csrc/cgemm16.hip `cgemm16()`, with epi = 3: row tile mi (1 when
+the 128-row grid has < 256 tiles and M > 64; force_mi), S (policy: tiles < 192 and K >= 512 with a workspace -> ceil(512 / tiles), at most K / 256, 16 and what the
 workspace holds; force_split), kper in whole 32s, and the epilogue: inside the product launch when S == 1 (EPI 3), else
 EPI 0 + the eval creduce16.  It names instances, it never computes a value."""
 from collections import namedtuple
 
 import torch
 
+import conv16_refs as C16
 import conv_refs as CR
 
 BF = torch.bfloat16
@@ -95,26 +96,10 @@ def mkn(c):
 def mirror(c, ws_floats=WS_FLOATS):
     """-> dict(mi, S, kper, inst = (MI, EPI, GATHER, C3) of the product launch, reduce = 'eval' | None, forced)"""
     M, N, K = mkn(c)
-    c3 = 1 if c.op == "f3" else 0
-    mi = 2
-    if CR.cdiv(M, 128) * CR.cdiv(N, 128) < 256 and M > 64:
-        mi = 1
-    if c.mi in (1, 2):
-        mi = c.mi
-    tiles = CR.cdiv(M, 64 * mi) * CR.cdiv(N, 128)
-    S = 1
-    if ws_floats and tiles < 192 and K >= 512:
-        S = min((512 + tiles - 1) // tiles, K // 256, 16)
-        while S > 1 and S * M * N > ws_floats:
-            S -= 1
-        S = max(S, 1)
-    if c.split > 0:
-        S = c.split
-        assert S == 1 or (S * M * N <= ws_floats and S <= 64), "forced split does not fit"
-    kper = CR.cdiv(CR.cdiv(K, S), 32) * 32
-    S = CR.cdiv(K, kper)
-    return dict(mi=mi, S=S, kper=kper, inst=(mi, 0 if S > 1 else 3, c.gather, c3), reduce="eval" if S > 1 else None,
-                forced=c.split > 0)
+    d = C16.mirror_cgemm16(M, N, K, c3=1 if c.op == "f3" else 0, epi=3, gather=c.gather, obf=True, force_mi=c.mi, force_split=c.split,
+                           ws_floats=ws_floats)
+    mi, kepi, gather, _, c3 = d["inst"]
+    return dict(mi=mi, S=d["S"], kper=d["kper"], inst=(mi, kepi, gather, c3), reduce=d["reduce"], forced=c.split > 0)
 
 
 # ==== inputs and the reference ===========================================================================================

@@ -1,5 +1,6 @@
-"""What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_gemm_kernels.py): guarded
-buffers, the C-ABI call, the per-element sum judge and the parity-report fixture.  How a case is judged: DESIGN.md 3.
+"""What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_gemm_kernels.py, and for the
+bf16 windows tests/test_gpu_eval16_kernels.py, tests/test_gpu_conv16_kernels.py): guarded buffers, the C-ABI call, the
+per-element sum judge and the parity-report fixture.  How a case is judged: DESIGN.md 3.
 A plain module (tests/ is on sys.path, like decoder_kernel_refs); a test module imports `_write_report` by name to get
 its own table in the run's parity report."""
 import ctypes as C
@@ -10,6 +11,8 @@ import torch
 U = 2.0 ** -24
 SENT = 0x7FC5A5A5          # a quiet-NaN bit pattern: a kernel that reads its own output margin poisons its result too
 NAN = float("nan")
+SENT16 = 0x7FC5            # the same for bf16 windows (GBuf16)
+BF = torch.bfloat16
 
 
 # ---- report -------------------------------------------------------------------------------------------------------------
@@ -80,6 +83,38 @@ class GBuf:
         assert bad.numel() == 0, "%s: %d guard words overwritten (first at window offset %d)" % (
             what, bad.numel(), int(guard.nonzero().reshape(-1)[bad[0]]) - self.base)
         return host[self.pos]
+
+
+class GBuf16:
+    """A [rows][cols] bf16 window with leading dimension `ld` inside a flat allocation, 64 elements in front and behind.
+    Inputs: NaN everywhere outside the window (and in [cols, ld)).  Outputs (vals None, or out=True with the old values of
+    an accumulated-into window): the sentinel everywhere else."""
+
+    def __init__(self, dev, rows, cols, ld=None, vals=None, out=False):
+        ld = ld or cols
+        self.base, self.rows, self.cols, self.ld = 64, rows, cols, ld
+        total = 64 + (rows - 1) * ld + cols + 64
+        if vals is None or out:
+            host = torch.full((total,), SENT16, dtype=torch.int16).view(BF).clone()
+        else:
+            host = torch.full((total,), float("nan"), dtype=BF)
+        self.pos = (self.base + torch.arange(rows).unsqueeze(1) * ld + torch.arange(cols)).reshape(-1)
+        if vals is not None:
+            host[self.pos] = vals.reshape(-1)
+        self.flat = host.to(dev)
+        assert self.flat.data_ptr() % 64 == 0
+        self.ptr = self.flat.data_ptr() + 2 * self.base
+
+    def read(self, what):
+        host = self.flat.cpu()
+        guard = torch.ones(host.numel(), dtype=torch.bool)
+        guard[self.pos] = False
+        bad = (host.view(torch.int16)[guard] != SENT16).nonzero().reshape(-1)
+        assert bad.numel() == 0, "%s: %d guard elements overwritten" % (what, bad.numel())
+        return host[self.pos].view(self.rows, self.cols)
+
+    def untouched(self):
+        return bool((self.flat.view(torch.int16) == SENT16).all())
 
 
 def _call(name, dev, *args):

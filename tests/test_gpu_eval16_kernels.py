@@ -16,11 +16,11 @@ import pytest
 import torch
 
 import eval16_refs as E
+from kernel_harness import GBuf16, SENT16  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
-SENT16 = 0x7FC5         # a quiet-NaN bf16 pattern
 _WORST = {}             # instance name -> [worst err/bound, cases]
 
 
@@ -52,37 +52,6 @@ def _write_report():
     _report(["%-74s %-9s %s" % ("instance", "err/bound", "cases")] + ["%-74s %-9.3f %d" % (k, r, n) for k, (r, n) in sorted(_WORST.items())],
             "bf16 eval BatchNorm epilogue vs fp64: worst |got - ref| / bound per instance, bound = b + 2^-8 (|pre| + b), "
             "b = (n+16) 2^-24 mag")
-
-
-class GBuf16:
-    """A [rows][cols] bf16 window with leading dimension `ld` inside a flat allocation, 64 elements in front and behind.
-    Inputs: NaN everywhere outside the window (and in [cols, ld)).  Outputs (vals None): the sentinel everywhere."""
-
-    def __init__(self, dev, rows, cols, ld=None, vals=None):
-        ld = ld or cols
-        self.base, self.rows, self.cols, self.ld = 64, rows, cols, ld
-        total = 64 + (rows - 1) * ld + cols + 64
-        if vals is None:
-            host = torch.full((total,), SENT16, dtype=torch.int16).view(BF).clone()
-        else:
-            host = torch.full((total,), float("nan"), dtype=BF)
-        self.pos = (self.base + torch.arange(rows).unsqueeze(1) * ld + torch.arange(cols)).reshape(-1)
-        if vals is not None:
-            host[self.pos] = vals.reshape(-1)
-        self.flat = host.to(dev)
-        assert self.flat.data_ptr() % 64 == 0
-        self.ptr = self.flat.data_ptr() + 2 * self.base
-
-    def read(self, what):
-        host = self.flat.cpu()
-        guard = torch.ones(host.numel(), dtype=torch.bool)
-        guard[self.pos] = False
-        bad = (host.view(torch.int16)[guard] != SENT16).nonzero().reshape(-1)
-        assert bad.numel() == 0, "%s: %d guard elements overwritten" % (what, bad.numel())
-        return host[self.pos].view(self.rows, self.cols)
-
-    def untouched(self):
-        return bool((self.flat.view(torch.int16) == SENT16).all())
 
 
 def _inst_name(c, d):
