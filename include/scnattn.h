@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define SCNATTN_VERSION 108 /* 0.1.8: + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
+#define SCNATTN_VERSION 108 /* 0.1.8: + the tagger head (scnattn_tag_pool_fwd/_bwd, scnattn_bce_fwd/_bwd; new symbols only, the version stays), + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
                                new symbols only, the version stays), + batched beam search (scnattn_beam_*; new symbols only, the version stays), + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
                                _conv3x3_fwd_bn_eval; new symbols only, the version stays), + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
                                epilogues inside the GEMM launch (options cgemm_combine, cgemm_combine_max), option dec_tail;
@@ -301,6 +301,30 @@ int scnattn_caption_loss_fwd(void* stream, int B, int T, int V, int P, const flo
 int scnattn_caption_loss_bwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
                              long ldt, const int32_t* decode_lengths, long n_tokens, const float* row_lse,
                              const float* sm1, float alpha_c, const float* grad_loss, float* dscores, float* dalphas);
+/* The head of the tagger step (models/encoders/tagger.py, trains/tagger.py:161-176) around its Linear layer.
+ * The trunk map is addressed as x[b, q, c], q over the HW pixels, by ELEMENT strides sb / sp / sc; it holds fp32, or bf16
+ * when bf16 != 0.  The channel-contiguous case (sc = 1, C and the other strides multiples of 16 bytes, aligned base) runs
+ * on 16-byte accesses, anything else on the scalar form.
+ *   tag_pool_fwd  pooled[b][c] (ldo) = (sum_q x[b,q,c]) / HW * ks[b][c] (ldk); ks = pre-scaled dropout keep mask or NULL
+ *                 bf16 = 2: a bf16 map whose mean is rounded to bf16 (nearest even) before the mask, as
+ *                 nn.AdaptiveAvgPool2d returns it for a bf16 map (the module path under bf16 autocast); pooled stays fp32
+ *   tag_pool_bwd  dx[b,q,c] = dpooled[b][c] (ldd) * ks[b][c] / HW for every q, in the map's dtype (bf16: one round to
+ *                 nearest even)
+ *   bce_fwd       probs = 1 / (1 + expf(-z)); out[0] = mean over B*S of -(t * max(logf(p), -100) + (1 - t) *
+ *                 max(log1pf(-p), -100)) (nn.BCELoss on nn.Sigmoid, evaluated at the rounded p, clamped before the
+ *                 multiplication); out[1] = count of (p >= 0.5) == (t >= 0.5) (binary_accuracy's numerator, exact as a
+ *                 float: B*S <= 2^24).  targets fp32 in [0, 1]; rows: workspace of 2*B floats (row sums, row counts).
+ *   bce_bwd       dz = grad_loss[0] / (B*S) * (p - t) * p(1-p) / max(p(1-p), 1e-12) from the stored probs (grad_loss is
+ *                 the DEVICE scalar d/d loss); exactly 0 where p saturated to 0 or 1.
+ * Fixed summation order (bit-reproducible).  Every refusal returns -1 before anything is launched. */
+int scnattn_tag_pool_fwd(void* stream, int B, int HW, int C, const void* x, int bf16, long sb, long sp, long sc,
+                         const float* ks, long ldk, float* pooled, long ldo);
+int scnattn_tag_pool_bwd(void* stream, int B, int HW, int C, const float* dpooled, long ldd, const float* ks, long ldk,
+                         void* dx, int bf16, long sb, long sp, long sc);
+int scnattn_bce_fwd(void* stream, int B, int S, const float* z, long ldz, const float* targets, long ldt, float* probs,
+                    long ldp, float* rows, float* out);
+int scnattn_bce_bwd(void* stream, int B, int S, const float* probs, long ldp, const float* targets, long ldt,
+                    const float* grad_loss, float* dz, long lddz);
 /* Input assembly: replaces the per-sample host arithmetic of datasets/caption.py:51-53
  * (`torch.FloatTensor(imgs[i // cpi] / 255.)` + torchvision Normalize, trains/attention_scn.py:121-126).
  * src: n_src uint8 images [n_src][C][HW] in HBM (a staged batch or the whole dataset); idx: n_out int64

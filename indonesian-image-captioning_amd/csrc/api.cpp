@@ -572,6 +572,26 @@ int scnattn_caption_loss_bwd(void* stream, int B, int T, int V, int P, const flo
                             row_lse, sm1, alpha_c, grad_loss, dscores, dalphas);
 }
 
+int scnattn_tag_pool_fwd(void* stream, int B, int HW, int C, const void* x, int bf16, long sb, long sp, long sc,
+                         const float* ks, long ldk, float* pooled, long ldo) {
+    return tag_pool_fwd(ST(stream), B, HW, C, x, bf16, sb, sp, sc, ks, ldk, pooled, ldo);
+}
+
+int scnattn_tag_pool_bwd(void* stream, int B, int HW, int C, const float* dpooled, long ldd, const float* ks, long ldk,
+                         void* dx, int bf16, long sb, long sp, long sc) {
+    return tag_pool_bwd(ST(stream), B, HW, C, dpooled, ldd, ks, ldk, dx, bf16, sb, sp, sc);
+}
+
+int scnattn_bce_fwd(void* stream, int B, int S, const float* z, long ldz, const float* targets, long ldt, float* probs,
+                    long ldp, float* rows, float* out) {
+    return bce_fwd(ST(stream), B, S, z, ldz, targets, ldt, probs, ldp, rows, out);
+}
+
+int scnattn_bce_bwd(void* stream, int B, int S, const float* probs, long ldp, const float* targets, long ldt,
+                    const float* grad_loss, float* dz, long lddz) {
+    return bce_bwd(ST(stream), B, S, probs, ldp, targets, ldt, grad_loss, dz, lddz);
+}
+
 int scnattn_u8_gather_normalize(void* stream, const uint8_t* src, long n_src, const int64_t* idx, long n_out, int C,
                                 long HW, const float* lut, void* dst, int dst_bf16, int channels_last) {
     return u8_gather_normalize(ST(stream), src, n_src, (const long long*)idx, n_out, C, HW, lut, dst, dst_bf16,

@@ -51,12 +51,6 @@ struct HArgs {
     const float* evar; float eeps; int erelu;     // EPI 3: running variance, eps, ReLU (ez / ldz: the optional bf16 residual)
 };
 
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {       // round to nearest even, NaN stays NaN (v_cvt_pk_bf16_f32)
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 p = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned, p);
-}
-
 // MI: 32-row MFMA tiles per wave along m (block tile 64*MI x 128, waves 2 x 2).  EPI 1: + column statistics.
 // EPI 2 (bf16 output, un-split d-input products): g = dx * [relu mask of the consumer BatchNorm recomputed from its bf16
 // pre-activation z with the forward pass's own expression] stored, + column sums of g and g*xhat per 64-row block -- the

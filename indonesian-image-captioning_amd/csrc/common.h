@@ -74,6 +74,12 @@ __device__ __forceinline__ f32x4 ld4(const bf16_t* p) {     // 4 consecutive ele
 }
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return bf16_to_f32(*p); }
+// two fp32 -> two bf16 in one word (lo in the low half)
+__device__ __forceinline__ unsigned pack2(float lo, float hi) {       // round to nearest even, NaN stays NaN (v_cvt_pk_bf16_f32)
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 p = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(unsigned, p);
+}
 
 // Sum `nslab` partial slabs (split-K outputs of skinny_gemm) at element `idx`, fixed order.
 // All loads are issued before the first add (a run-time-bounded loop would serialise one memory

@@ -202,6 +202,17 @@ int caption_loss_fwd(hipStream_t st, int B, int T, int V, int P, const float* sc
 int caption_loss_bwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
                      const int* dl, long n_tokens, const float* row_lse, const float* sm1, float alpha_c,
                      const float* gout, float* dscores, float* dalphas);
+// taghead.hip: the tagger's head around its Linear layer.  The map is x[b, q, c] (q over HW pixels) by element strides,
+// fp32 or bf16; pooled = sum_q x / HW * ks (ks: pre-scaled dropout keep mask [B][ldk], may be null); bce_*: sigmoid +
+// BCELoss (mean) + binary accuracy of the reference, rows: workspace [2][B], out: {loss, agreement count}
+int tag_pool_fwd(hipStream_t st, int B, int HW, int C, const void* x, int bf16, long sb, long sp, long sc, const float* ks,
+                 long ldk, float* out, long ldo);
+int tag_pool_bwd(hipStream_t st, int B, int HW, int C, const float* dpooled, long ldd, const float* ks, long ldk, void* dx,
+                 int bf16, long sb, long sp, long sc);
+int bce_fwd(hipStream_t st, int B, int S, const float* z, long ldz, const float* t, long ldt, float* probs, long ldp,
+            float* rows, float* out);
+int bce_bwd(hipStream_t st, int B, int S, const float* probs, long ldp, const float* t, long ldt, const float* g, float* dz,
+            long lddz);
 // data.hip: uint8 image rows (gathered by index) -> normalised fp32/bf16 batch, NCHW or channels-last
 int u8_gather_normalize(hipStream_t st, const uint8_t* src, long n_src, const long long* idx, long n_out, int C,
                         long HW, const float* lut, void* dst, int dst_bf16, int channels_last);

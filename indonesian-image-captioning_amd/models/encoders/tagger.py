@@ -42,6 +42,36 @@ class EncoderTagger(nn.Module):
         out = SF.linear(out, self.linear.weight, self.linear.bias)
         return self.sigmoid(out)
 
+    def tag_loss(self, images, targets):
+        """One call for the train step and validation of trains/tagger.py:161-163,176: (probs, loss, agree) with
+        probs = forward(images), loss = nn.BCELoss()(probs, targets) and agree = binary_accuracy's count of
+        (probs >= 0.5) == (targets >= 0.5), the last two as 0-d device tensors.  The trunk is the one `forward` runs; pool,
+        dropout mask, sigmoid, loss and count run on csrc/taghead.hip (scnattn.functional.tag_head_loss)."""
+        SF.require_cuda(images, targets)
+        if self.channels_last and not stem_usable(self.resnet, images):
+            images = images.contiguous(memory_format=torch.channels_last)
+        if self.training:
+            flat = getattr(self, "_bn_counters", None)
+            if flat is None or flat.device != images.device:
+                self._bn_counters = flat = manage_bn_counters(self.resnet)
+            if flat is not None:
+                flat.add_(1)
+        # the trunk's parameters, listed once per trunk object: walking ~500 modules costs 0.3 ms of host time per step
+        cached = self.__dict__.get("_trunk_info")
+        if cached is None or cached[0] is not self.resnet:
+            pooled = isinstance(list(self.resnet.children())[-1], nn.AdaptiveAvgPool2d)     # the fused head pools the map itself
+            cached = self.__dict__["_trunk_info"] = (self.resnet, pooled, tuple(self.resnet.parameters()))
+        _, pooled, params = cached
+        # a frozen trunk keeps nothing for a backward pass that never comes
+        trains = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        with torch.set_grad_enabled(trains):
+            x4 = run_trunk(self.resnet, images, drop_last=1 if pooled else 0)
+        ks = None
+        if self.training:       # the module's own draw, pre-scaled by 1 / (1 - p); honours a replaced dropout module
+            ks = self.dropout(torch.ones(x4.shape[0], x4.shape[1], device=x4.device))
+        # a bf16 map (bf16 autocast): forward()'s pool hands its mean on in bf16; the step trains the function forward() evaluates
+        return SF.tag_head_loss(x4, ks, self.linear.weight, self.linear.bias, targets, pooled_bf16=x4.dtype == torch.bfloat16)
+
     def fine_tune(self, fine_tune=True):
         for p in self.resnet.parameters():
             p.requires_grad = False

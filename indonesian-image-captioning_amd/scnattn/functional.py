@@ -7,6 +7,7 @@ wrapper covers, by reference file:
   scn_cell         -> models/scn_cell.py:52-154
   attention        -> models/attention.py:26-44
   pool_permute     -> models/encoders/caption.py:41-43
+  tag_head_loss    -> models/encoders/tagger.py:24-31 + trains/tagger.py:161-163,176 (BCELoss, binary_accuracy)
 """
 import ctypes as C
 import os
@@ -562,6 +563,90 @@ class _PoolPermute(torch.autograd.Function):
 
 def pool_permute(x, out_size):
     return _PoolPermute.apply(x, out_size)
+
+
+# ----------------------------------------------------------------------------------------------
+# tagger head: global average pool (+ dropout mask) -> Linear -> Sigmoid -> BCELoss + binary accuracy  (csrc/taghead.hip)
+# ----------------------------------------------------------------------------------------------
+def _pixel_strides(x4):
+    """(sb, sp, sc) of a (B, C, H, W) map read as x[b, q, c], q = h * W + w; None when the pixels have no common stride."""
+    _, _, H, Wd = x4.shape
+    sb, sc, sh, sw = x4.stride()
+    if H == 1:
+        return sb, sw, sc
+    if Wd == 1 or sh == Wd * sw:
+        return sb, (sh if Wd == 1 else sw), sc
+    return None
+
+
+class _TagHeadLoss(torch.autograd.Function):
+    """probs = sigmoid(linear(mean_pixels(x4) * ks)), loss = BCELoss()(probs, targets), agree = #((probs >= .5) == (targets >= .5)).
+    The two reductions and the element-wise chain are the kernels of csrc/taghead.hip, the three products stay on the GEMM."""
+
+    @staticmethod
+    def forward(ctx, x4, ks, W, b, targets, pooled_bf16=False):
+        require_cuda(x4, ks, W, b, targets)
+        if x4.dtype not in (torch.float32, torch.bfloat16):
+            x4 = x4.float()
+        if _pixel_strides(x4) is None:
+            x4 = x4.contiguous(memory_format=torch.channels_last)
+        Bn, Cn, H, Wd = x4.shape
+        S = W.shape[0]
+        bf16 = 1 if x4.dtype == torch.bfloat16 else 0
+        ks, targets = f32c(ks), f32c(targets)
+        W = f32c(W.detach())
+        b = None if b is None else f32c(b.detach())
+        dev, st = x4.device, stream_of(x4)
+        f32 = dict(device=dev, dtype=torch.float32)
+        xd = torch.empty((Bn, Cn), **f32)
+        sb, sp, sc = _pixel_strides(x4)
+        call("scnattn_tag_pool_fwd", st, Bn, H * Wd, Cn, ptr(x4), 2 if (bf16 and pooled_bf16) else bf16, sb, sp, sc, ptr(ks), Cn,
+             ptr(xd), Cn)
+        z = gemm(xd, W, tb=True, bias=b)
+        probs = torch.empty((Bn, S), **f32)
+        rows = torch.empty(2 * Bn, **f32)
+        out = torch.empty(2, **f32)
+        call("scnattn_bce_fwd", st, Bn, S, ptr(z), S, ptr(targets), S, ptr(probs), S, ptr(rows), ptr(out))
+        ctx.save_for_backward(xd, ks, W, probs, targets)
+        ctx.map = (x4.dtype, H, Wd)
+        ctx.has_bias = b is not None
+        loss, agree = out[0], out[1]
+        ctx.mark_non_differentiable(probs, agree)
+        ctx.set_materialize_grads(False)      # no zero-filled (B, S) gradient for probs
+        return probs, loss, agree
+
+    @staticmethod
+    def backward(ctx, _dprobs, dloss, _dagree):
+        if dloss is None:
+            return None, None, None, None, None, None
+        xd, ks, W, probs, targets = ctx.saved_tensors
+        dtype, H, Wd = ctx.map
+        Bn, Cn = xd.shape
+        S = W.shape[0]
+        need = ctx.needs_input_grad          # (x4, ks, W, b, targets)
+        st = stream_of(xd)
+        dz = torch.empty((Bn, S), device=xd.device, dtype=torch.float32)
+        call("scnattn_bce_bwd", st, Bn, S, ptr(probs), S, ptr(targets), S, ptr(f32c(dloss).reshape(1)), ptr(dz), S)
+        dW = gemm(dz, xd, ta=True) if need[2] else None
+        db = colsum(dz) if (ctx.has_bias and need[3]) else None
+        dx = None
+        if need[0]:
+            dxd = gemm(dz, W)
+            # channels-last in the map's dtype: what the last Bottleneck's backward reads in place (scnattn/conv.py, conv16.py)
+            dx = torch.empty((Bn, Cn, H, Wd), device=xd.device, dtype=dtype, memory_format=torch.channels_last)
+            sb, sp, sc = _pixel_strides(dx)
+            call("scnattn_tag_pool_bwd", st, Bn, H * Wd, Cn, ptr(dxd), Cn, ptr(ks), Cn, ptr(dx),
+                 1 if dtype == torch.bfloat16 else 0, sb, sp, sc)
+        return dx, None, dW, db, None, None
+
+
+def tag_head_loss(x4, ks, W, b, targets, pooled_bf16=False):
+    """The tagger's head and loss on the (B, C, H, W) trunk map `x4` (fp32 or bf16, any strides): returns (probs (B, S),
+    loss, agree), loss and agree 0-d device tensors.  `ks`: pre-scaled dropout keep mask (B, C) or None.  Gradients flow
+    from `loss` to x4 (its own dtype, channels-last), W and b; probs and agree carry none.  `pooled_bf16` (bf16 maps only): round
+    the pooled mean to bf16 as nn.AdaptiveAvgPool2d does on a bf16 map, i.e. compute what EncoderTagger.forward computes under
+    bf16 autocast; off, the mean keeps its fp32 accumulation."""
+    return _TagHeadLoss.apply(x4, ks, W, b, targets, pooled_bf16)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -83,17 +83,24 @@ def stem(trunk, x, bf16=False):
     return out.view(N, Hp, Wp, 64).permute(0, 3, 1, 2)
 
 
-def run_trunk(trunk, x):
+def run_trunk(trunk, x, drop_last=0):
     """`trunk(x)` with the four stem children on the fused kernels when they qualify.  Under bf16 autocast the blocks'
-    bf16 weight copies (scnattn/conv16.py) are refreshed first: when the stem qualifies, or the trunk already has copies."""
+    bf16 weight copies (scnattn/conv16.py) are refreshed first: when the stem qualifies, or the trunk already has copies.
+    `drop_last`: trailing children left out (the tagger's global average pool, which its fused head does itself)."""
     fused = usable(trunk, x)
     bf16 = torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16
     if bf16 and (fused or getattr(trunk, "_scn_w16", None) is not None):
         from . import conv16 as _c16
         _c16.refresh_weights(trunk)
+    children = list(trunk.children())
+    children = children[:len(children) - drop_last]
     if fused:
         y = stem(trunk, x, bf16)
-        for child in list(trunk.children())[4:]:
+        for child in children[4:]:
             y = child(y)
         return y
-    return trunk(x)
+    if not drop_last:
+        return trunk(x)
+    for child in children:
+        x = child(x)
+    return x

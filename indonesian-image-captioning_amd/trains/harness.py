@@ -6,7 +6,10 @@ One call of ``TrainStep.step()`` =
     encoder fwd -> decoder fwd -> CrossEntropy over packed tokens + alpha_c * doubly-stochastic term
     -> zero_grad -> backward (+ bucketed RCCL all-reduce when world > 1) -> clamp +-5 -> Adam.
 Data loading and the ``.item()`` metric syncs of the reference are outside the step.
-Tags are a synthetic input (the tagger encoder is a "next" row of SURVEY.md 8f)."""
+Tags are a synthetic input (the tagger encoder is a "next" row of SURVEY.md 8f).
+
+``TaggerTrainStep`` / ``validate_tagger`` are the fourth mode, trains/tagger.py:132-250: EncoderTagger under nn.BCELoss,
+the same clamp and Adam, binary accuracy as the metric."""
 import os
 
 import torch
@@ -262,3 +265,73 @@ def validate(batches, encoder, encoder_tagger, decoder, criterion, word_map, alp
             hypotheses.extend(p[:decode_lengths[j]] for j, p in enumerate(preds))
     assert len(references) == len(hypotheses)
     return corpus_bleu(references, hypotheses), losses.avg, top5accs.avg
+
+
+TAGGER_DEFAULTS = dict(semantic_size=1000, dropout=0.15, batch_size=32, encoder_lr=1e-4, grad_clip=5.0, image_size=256)
+
+
+class TaggerTrainStep:
+    """The body of the reference's tagger loop (trains/tagger.py:153-173) with its constants (:24-46) as defaults.
+
+    One call of ``step(imgs, tags)`` =
+        trunk fwd -> pool, dropout mask, Linear, Sigmoid, BCELoss and agreement count (EncoderTagger.tag_loss)
+        -> zero_grad -> backward (+ bucketed all-reduce when world > 1) -> clamp +-5 -> Adam
+    and returns (loss, agree) on the device: `loss.item()` and `agree / tags.numel() * 100` (binary_accuracy) are the
+    caller's syncs, as in TrainStep.  `encoder`: an EncoderTagger to train instead of a fresh one (a checkpoint's)."""
+
+    def __init__(self, fine_tune_encoder=False, device="cuda", seed=1234, encoder_dtype="f32", bucket_mb=32,
+                 force_reduce=False, encoder=None, **overrides):
+        unknown = set(overrides) - set(TAGGER_DEFAULTS)
+        if unknown:
+            raise TypeError("TaggerTrainStep: unknown setting(s) %s" % ", ".join(sorted(unknown)))
+        self.cfg = dict(TAGGER_DEFAULTS)
+        self.cfg.update(overrides)
+        self.device = torch.device(device)
+        self.encoder_bf16 = encoder_dtype == "bf16"       # the trunk under bf16 autocast; head, loss and master weights fp32
+        self.fine_tune_encoder = fine_tune_encoder
+        torch.manual_seed(seed)  # same seed on every rank => identical initial weights
+        if encoder is None:
+            encoder = EncoderTagger(semantic_size=self.cfg["semantic_size"], dropout=self.cfg["dropout"], channels_last=True)
+        self.encoder = encoder.to(self.device)
+        self.encoder.fine_tune(fine_tune_encoder)
+        self.optimizer = FusedClampAdam(filter(lambda p: p.requires_grad, self.encoder.parameters()),
+                                        lr=self.cfg["encoder_lr"], grad_clip=self.cfg["grad_clip"])
+        self.reducers = [GradReducer(self.optimizer.flat, max(bucket_mb << 20, 4096))]
+        broadcast_parameters(self.optimizer.flat)
+        if force_reduce:          # diagnostics: exercise hooks + collectives with a single rank
+            for r in self.reducers:
+                r.enabled = True
+        self.encoder.train()
+        self.probs = None         # the last step's tag probabilities (what the reference calls `scores`)
+
+    def step(self, imgs, tags):
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.encoder_bf16):
+            self.probs, loss, agree = self.encoder.tag_loss(imgs, tags)
+        self.optimizer.zero_grad()
+        for r in self.reducers:
+            r.reset()
+        loss.backward()
+        if self.fine_tune_encoder:
+            from scnattn import conv as _conv
+            _conv.join_side_streams()       # the trunk's weight gradients on the side stream belong to its backward pass
+        scale = 1.0
+        for r in self.reducers:
+            scale = r.finish()
+        self.optimizer.step(scale)
+        return loss, agree
+
+
+def validate_tagger(batches, encoder, losses=None):
+    """The reference's tagger validate() (trains/tagger.py:195-250): eval mode, no_grad, one unweighted `update(val)` per
+    batch for loss and accuracy (= agree / (B * S) * 100, binary_accuracy); returns the accuracy meter.  `batches` yields
+    (imgs, tags) on the device; `losses`: an AverageMeter that receives the per-batch losses."""
+    from utils.metric import AverageMeter
+    encoder.eval()
+    losses = AverageMeter() if losses is None else losses
+    accs = AverageMeter()
+    with torch.no_grad():
+        for imgs, tags in batches:
+            _, loss, agree = encoder.tag_loss(imgs, tags)
+            losses.update(loss.item())
+            accs.update(agree.item() / tags.numel() * 100.0)
+    return accs
