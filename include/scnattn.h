@@ -473,7 +473,8 @@ int scnattn_stem_bn_relu_maxpool(void* stream, int N, int Hz, int Wz, int C, con
  *                          partial holds {sum(z - s), sum((z - s)^2)}, s = shift[c] (NULL: 0).  `shift` must be the vector the
  *                          producer's epilogue used and must NOT alias run_mean (this kernel updates it while other
  *                          workgroups still read shift): callers pass the previous step's batch mean;
- *   scnattn_bn_bwd_reduce  g = dy * [y > 0] (relu != 0) or dy -> gout (may be NULL); partial = {sum g, sum g*xhat};
+ *   scnattn_bn_bwd_reduce  relu != 0: g = dy * [y > 0] -> gout (may be NULL); relu == 0: g is dy itself, nothing is written
+ *                          and gout must be NULL (refused otherwise); partial = {sum g, sum g*xhat};
  *                          *nchunk_out = chunk count (ldp = that rounded up to 4 <= ldp_cap);
  *   scnattn_bn_bwd_dx_fin  dz = gamma*invstd*(g - dbeta/R - xhat*dgamma/R) from an already masked g, dbeta = sum g and
  *                          dgamma = sum g*xhat summed from the partials inside (and written out as the parameter gradients). */

@@ -667,10 +667,12 @@ int bn_finalize_t(hipStream_t st, long R, int C, const float* partial, int ldp, 
 }
 
 // g = dy * [y > 0] (relu with the forward output y) or dy; sums of g and g*xhat as channel-major partials [2][C][ldp];
-// g is written to gout (it is the residual branch's gradient).  Returns the chunk count through nchunk_out.
+// with relu, g is written to gout when given (it is the residual branch's gradient); without relu g is dy itself and gout
+// must be NULL.  Returns the chunk count through nchunk_out.
 int bn_bwd_reduce_t(hipStream_t st, int R, int C, const void* dy, const void* y, const void* z, int bf16, const float* mean,
                     const float* invstd, int relu, float* partial, int ldp_cap, void* gout, int* nchunk_out) {
     SCN_ARG(R > 0 && C > 0 && C % 4 == 0 && dy && z && mean && invstd && partial && (!relu || y), "bn_bwd_reduce_t: bad argument");
+    SCN_ARG(relu || !gout, "bn_bwd_reduce_t: without relu g is dy itself, gout must be NULL");
     int rpc;
     const int nchunk = pick_chunks(R, C, &rpc);
     const int ldp = (nchunk + 3) & ~3;

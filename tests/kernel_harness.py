@@ -1,5 +1,6 @@
-"""What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_gemm_kernels.py, and for the
-bf16 windows tests/test_gpu_eval16_kernels.py, tests/test_gpu_conv16_kernels.py): guarded buffers, the C-ABI call, the
+"""What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_gemm_kernels.py,
+tests/test_gpu_bn_kernels.py, tests/test_gpu_stem_kernels.py, and for the bf16 windows tests/test_gpu_eval16_kernels.py,
+tests/test_gpu_conv16_kernels.py): guarded buffers, the C-ABI call, the
 per-element sum judge and the parity-report fixture.  How a case is judged: DESIGN.md 3.
 A plain module (tests/ is on sys.path, like decoder_kernel_refs); a test module imports `_write_report` by name to get
 its own table in the run's parity report."""
@@ -26,7 +27,8 @@ def _note(kernel, name, ratio, kind, yard=0.0):
 
 @pytest.fixture(scope="module", autouse=True)
 def _write_report(request):
-    """Module-scoped: a test module imports it by name; its REPORT_TITLE heads the table (the decode-step title otherwise)."""
+    """Module-scoped: a test module imports it by name; its REPORT_TITLE heads the table (the decode-step title otherwise).
+    A `kind` that starts with "=" is the bound's own description and is printed as it stands."""
     _STATS.clear()
     yield
     if not _STATS:
@@ -36,7 +38,8 @@ def _write_report(request):
     fmt = "%%-%ds %%-10s %%-9s %%-6s %%s" % w
     lines = [fmt % ("kernel", "result", "err/bound", "cases", "bound")]
     for (kern, name), (ratio, kind, yard, n) in sorted(_STATS.items()):
-        how = "(n+8)*2^-24*sum|terms|" if kind == "sum" else "(n+16)*2^-24*(sum|terms|*|scale|+|mean*scale|+|beta|+|res|)" \
+        how = kind[1:] if kind.startswith("=") else "(n+8)*2^-24*sum|terms|" if kind == "sum" else \
+            "(n+16)*2^-24*(sum|terms|*|scale|+|mean*scale|+|beta|+|res|)" \
             if kind == "eval" else "min(4 x CPU-fp32 worst element error [worst seen %.3e], %s x row max)" % (yard, kind)
         lines.append(fmt.replace("%-9s %-6s", "%-9.3f %-6d") % (kern, name, ratio, n, how))
     _report(lines, getattr(request.module, "REPORT_TITLE",
