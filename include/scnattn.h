@@ -23,10 +23,12 @@
 extern "C" {
 #endif
 
-#define SCNATTN_VERSION 108 /* 0.1.8: + the tagger head (scnattn_tag_pool_fwd/_bwd, scnattn_bce_fwd/_bwd; new symbols only, the version stays), + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
+#define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
+                               kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
+                               0.1.8: + the tagger head (scnattn_tag_pool_fwd/_bwd, scnattn_bce_fwd/_bwd; new symbols only, the version stays), + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
                                new symbols only, the version stays), + batched beam search (scnattn_beam_*; new symbols only, the version stays), + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
                                _conv3x3_fwd_bn_eval; new symbols only, the version stays), + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
-                               epilogues inside the GEMM launch (options cgemm_combine, cgemm_combine_max), option dec_tail;
+                               epilogues inside the GEMM launch (options cgemm_combine, cgemm_combine_max);
                                0.1.7: + halo-staged 3x3 weight gradient, strided 3x3 d input, the stem (scnattn_stem_*), BatchNorm
                                finalize on load; - whole-block drivers, scnattn_stream_*, the experiment options of rounds 1-2 */
 
@@ -44,10 +46,11 @@ const char* scnattn_last_error(void);
  *     "cgemm_kmin" (smallest K per slab, 128), "gemm_target" / "gemm_gate" / "gemm_kmin" / "gemm_kmin_small" (the same for
  *     sgemm), "cgemm_combine" (1, default: a split product's epilogue is run inside the launch by the workgroup that arrives
  *     last at each tile -- write-through slabs, arrival counters per stream, bit-identical to the reduce launch; 2: plain
- *     slab stores + an agent release; 0: always the reduce launch), "cgemm_combine_max" (deepest split combined in-launch, 8),
- *     "dec_tail" (0, default; 1: the decode step's element-wise cell kernels run inside the skinny launches that feed
- *     them -- bit-identical, measured slower: DESIGN.md 6c).  The experiment switches of rounds 1-2 (fuse_attn, chains, attn_handoff, cgemm_stagger, cgemm_w41, cgemm_vec,
- *     bn_gfirst, skinny_tail) were removed together with the code paths they selected; DESIGN.md keeps their numbers.
+ *     slab stores + an agent release; 0: always the reduce launch), "cgemm_combine_max" (deepest split combined in-launch, 8).
+ *     The experiment switches of rounds 1-2 (fuse_attn, chains, attn_handoff, cgemm_stagger, cgemm_w41, cgemm_vec,
+ *     bn_gfirst, skinny_tail) and "dec_tail" (the decode step's element-wise cell kernels inside the skinny launches that
+ *     feed them: bit-identical, measured slower) were removed together with the code paths they selected; DESIGN.md keeps
+ *     their numbers.
  * Returns -1 for an unknown name or an out-of-range value. */
 int scnattn_set_option(const char* name, int value);
 /* Sums since the last call: out6 = {forward loop ms, forward steps, backward loop ms, backward steps,
@@ -148,17 +151,6 @@ int scnattn_seq_bwd(void* stream, const scnattn_dims* d, const scnattn_params* w
                     const float* drop_mask, const float* saved, float* scratch, const float* dpreds,
                     const float* dalphas, const scnattn_params* g, float* denc, float* dtags,
                     const scnattn_pool* pool);
-/* The same with the weight gradients on a second stream.  Nothing needs d loss / d weight before the optimizer step,
- * while denc heads the encoder's whole backward pass (trains/attention_scn.py:238-240 runs them as one autograd
- * sweep): `wgrad_stream` carries d fc.weight beside the reverse recurrence and the post-loop weight-gradient GEMMs
- * beside whatever the caller enqueues next on `stream`.  Event-ordered inside; on return `stream` holds denc / dtags
- * and does NOT wait for `wgrad_stream`: the caller joins it before reading `g`, and keeps saved / scratch / dpreds /
- * enc / tags alive until then.  wgrad_stream == NULL or == stream: identical to scnattn_seq_bwd. */
-int scnattn_seq_bwd_streams(void* stream, void* wgrad_stream, const scnattn_dims* d, const scnattn_params* w,
-                            const float* enc, const float* tags, const int64_t* caps, const int32_t* dl_dev,
-                            const int32_t* bt_host, const float* drop_mask, const float* saved, float* scratch,
-                            const float* dpreds, const float* dalphas, const scnattn_params* g, float* denc,
-                            float* dtags, const scnattn_pool* pool);
 
 /* ---- batched beam search: the reference's sample() (models/decoders/attention_scn.py:160-296, pure_scn.py:142-249,
  * pure_attention.py:153-281), which eval_caption.py:96-131 calls once per image, for N images at once ---------------------

@@ -23,14 +23,14 @@ extern int g_ksplit_scale;
 extern int g_profile;
 extern int g_attn_depth;
 extern int g_dec_bf16;
-extern int g_gemm_target, g_gemm_kmin, g_gemm_kmin_small, g_gemm_gate, g_use_cgemm, g_cgemm_target, g_cgemm_kmin, g_cgemm_mi, g_cgemm_combine, g_cgemm_combine_max, g_dec_tail;
+extern int g_gemm_target, g_gemm_kmin, g_gemm_kmin_small, g_gemm_gate, g_use_cgemm, g_cgemm_target, g_cgemm_kmin, g_cgemm_mi, g_cgemm_combine, g_cgemm_combine_max;
 int profile_collect(double* out);
 int seq_workspace(const scnattn_dims* d, const scnattn_pool* pool, size_t* saved_bytes, size_t* scratch_bytes);
 int seq_fwd(hipStream_t st, const scnattn_dims* d, const scnattn_params* w, const float* enc, const float* tags,
             const int64_t* caps, const int32_t* dl_dev, const int32_t* bt, const float* drop_mask, float* saved,
             float* scratch, float* preds, float* alphas, const scnattn_pool* pool);
-int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* d, const scnattn_params* w, const float* enc,
-            const float* tags, const int64_t* caps, const int32_t* dl_dev, const int32_t* bt, const float* drop_mask,
+int seq_bwd(hipStream_t st, const scnattn_dims* d, const scnattn_params* w, const float* enc, const float* tags,
+            const int64_t* caps, const int32_t* dl_dev, const int32_t* bt, const float* drop_mask,
             const float* saved, float* scratch, const float* dpreds, const float* dalphas, const scnattn_params* g,
             float* denc, float* dtags, const scnattn_pool* pool);
 int beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes);
@@ -61,7 +61,6 @@ int scnattn_set_option(const char* name, int value) {
         {"decoder_bf16", &g_dec_bf16, 0, 2},   {"profile", &g_profile, 0, 2},
         {"ksplit", &g_ksplit_scale, 0, SCN_MAX_KSPLIT}, {"attn_depth", &g_attn_depth, 0, 1},
         {"use_cgemm", &g_use_cgemm, 0, 1},     {"cgemm_mi", &g_cgemm_mi, 0, 2},
-        {"dec_tail", &g_dec_tail, 0, 1},
         {"cgemm_combine", &g_cgemm_combine, 0, 2}, {"cgemm_combine_max", &g_cgemm_combine_max, 1, 128},
         {"cgemm_target", &g_cgemm_target, 1, 1 << 20}, {"cgemm_kmin", &g_cgemm_kmin, 16, 1 << 20},
         {"gemm_target", &g_gemm_target, 1, 1 << 20},   {"gemm_gate", &g_gemm_gate, 1, 1 << 20},
@@ -142,17 +141,8 @@ int scnattn_seq_bwd(void* stream, const scnattn_dims* d, const scnattn_params* w
                     const float* drop_mask, const float* saved, float* scratch, const float* dpreds,
                     const float* dalphas, const scnattn_params* g, float* denc, float* dtags,
                     const scnattn_pool* pool) {
-    return seq_bwd(ST(stream), nullptr, d, w, enc, tags, caps, dl_dev, bt_host, drop_mask, saved, scratch, dpreds,
-                   dalphas, g, denc, dtags, pool);
-}
-
-int scnattn_seq_bwd_streams(void* stream, void* wgrad_stream, const scnattn_dims* d, const scnattn_params* w,
-                            const float* enc, const float* tags, const int64_t* caps, const int32_t* dl_dev,
-                            const int32_t* bt_host, const float* drop_mask, const float* saved, float* scratch,
-                            const float* dpreds, const float* dalphas, const scnattn_params* g, float* denc,
-                            float* dtags, const scnattn_pool* pool) {
-    return seq_bwd(ST(stream), ST(wgrad_stream), d, w, enc, tags, caps, dl_dev, bt_host, drop_mask, saved, scratch,
-                   dpreds, dalphas, g, denc, dtags, pool);
+    return seq_bwd(ST(stream), d, w, enc, tags, caps, dl_dev, bt_host, drop_mask, saved, scratch, dpreds, dalphas, g,
+                   denc, dtags, pool);
 }
 
 int scnattn_sgemm(void* stream, int transA, int transB, int M, int N, int K, float alpha, const float* A,

@@ -88,7 +88,7 @@ struct FwdScratch {
 struct BwdScratch {
     float *WDb, *WaTz, *WcatT, *dHd_bm, *dhfc_tm, *dr_all, *dpx_all, *dcat_all, *dawe_all, *de_all, *dalpha, *dc,
         *dqx_acc, *dqh_acc, *sDb, *sZ, *sH, *datt1, *dwpart, *dwtmp, *demb_tm, *dmean, *dh0, *mx_all, *gws, *present,
-        *dalphaq, *dy, *gws2, *WDbh, *WaTzh, *WcatTh;
+        *dalphaq, *dy, *WDbh, *WaTzh, *WcatTh;
 };
 
 // Q > 0: pooled path (encoder_out given as its un-pooled source map x [B][Q][E])
@@ -169,7 +169,6 @@ size_t carve_bwd(const scnattn_dims& d, int Q, float* base, BwdScratch& s) {
     s.gws = c.take(GEMM_WS_FLOATS);
     s.dalphaq = (d.has_att && Q > 0) ? c.take(sz(B, Q)) : nullptr;
     s.dy = (d.has_att && Q > 0) ? c.take(sz(B, Q, A)) : nullptr;
-    s.gws2 = c.take(GEMM_WS_FLOATS);      // split-K partials of the weight-gradient stream
     s.WDbh = c.take((sz(4, D, 2 * F) + 1) / 2);
     s.WaTzh = d.has_att ? c.take((sz(F4, E) + 1) / 2) : nullptr;
     s.WcatTh = c.take((sz(NC, D) + 1) / 2);
@@ -313,7 +312,6 @@ int seq_fwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, con
         SCN_TRY(skinny_gemm(st, rows, NA, D, 1, h, D, 0, WcatA, NA, 0, f.slabA, NA, 0, (long)B * NA, ksA, bfm));
         const Slabs ph{f.slabA + colph, ksA, (long)B * NA, NA};
         Slabs pz{nullptr, 0, 0, 0};
-        bool mixed = false;
         if (d.has_att) {
             const Slabs att2{f.slabA, ksA, (long)B * NA, NA}, gpre{f.slabA + A, ksA, (long)B * NA, NA};
             float* alpha_out = alphas + (long)t * P;
@@ -329,25 +327,19 @@ int seq_fwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, con
                                      s.alpha_tm + rowT * P, s.awe_all + rowT * E, s.gate_all + rowT * E, s.z_all + rowT * E,
                                      bf));
             prof_end(st, evc, 2, 1);
-            // z . Wa[M:], and -- inside the same launch, by the workgroup that arrives last at each 32-column unit --
-            // the SCN mix that consumes it (scn_cell.py:73-86); stand-alone kernel when the launch cannot take it
+            // z . Wa[M:], consumed by the SCN mix (scn_cell.py:73-86)
             const int ksC = pick(rows, F4, E, 1);
-            SkinnyTail mix{2, rows, 0, F4, {ex, s.qx, s.qh, nullptr}, {pa, phs, f.xcat, nullptr}, 0, ph};
             SCN_TRY(skinny_gemm(st, rows, F4, E, 1, s.z_all + rowT * E, E, 0, WaM, F4, 0, f.slabC, F4, 0, (long)B * F4, ksC,
-                                bfm, &mix, &mixed));
+                                bfm));
             pz = Slabs{f.slabC, ksC, (long)B * F4, F4};
         }
-        if (!mixed) SCN_TRY(scn_mix_fwd(st, rows, F4, pz, ex, ph, s.qx, s.qh, pa, phs, f.xcat));
-        // [mx | mh] . [Wc; Hc] for the four gates, and the LSTM update of the units each 32-column tile feeds
+        SCN_TRY(scn_mix_fwd(st, rows, F4, pz, ex, ph, s.qx, s.qh, pa, phs, f.xcat));
+        // [mx | mh] . [Wc; Hc] for the four gates, then the LSTM update
         const int ksD = pick(rows, D, 2 * F, 4);
-        SkinnyTail cell{1, rows, 0, D, {w->decode_step_bias_ih, w->decode_step_bias_hh, c, nullptr},
-                        {gates, c_new, h_new, tanhc}, 0, Slabs{nullptr, 0, 0, 0}};
-        bool celled = false;
         SCN_TRY(skinny_gemm(st, rows, D, 2 * F, 4, f.xcat, 8 * F, 2 * F, WD, D, (long)2 * F * D, f.slabD, D, BD, 4 * BD, ksD,
-                            bfm, &cell, &celled));
-        if (!celled)
-            SCN_TRY(lstm_fwd(st, rows, D, Slabs{f.slabD, ksD, 4 * BD, D}, BD, w->decode_step_bias_ih,
-                             w->decode_step_bias_hh, c, gates, c_new, h_new, tanhc));
+                            bfm));
+        SCN_TRY(lstm_fwd(st, rows, D, Slabs{f.slabD, ksD, 4 * BD, D}, BD, w->decode_step_bias_ih, w->decode_step_bias_hh, c,
+                         gates, c_new, h_new, tanhc));
     }
     prof_end(st, ev0, 0, T);
 
@@ -358,13 +350,8 @@ int seq_fwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, con
     return 0;
 }
 
-// `wst`: optional second stream for the weight gradients.  Nothing downstream of this call needs d loss / d weight
-// before the optimizer step, while d encoder_out heads the whole encoder backward pass: with `wst` the fc weight
-// gradient runs beside the (latency-bound) reverse recurrence and the post-loop weight-gradient GEMMs beside whatever
-// the caller enqueues next on `st`.  Ordering is by events: `wst` waits for what it reads, `st` never waits for `wst`
-// -- the CALLER joins `wst` before it reads `g`.  NULL (or == st): everything in order on `st`.
-int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnattn_params* w, const float* enc,
-            const float* tags, const int64_t* caps, const int32_t* dl_dev, const int32_t* bt, const float* drop_mask,
+int seq_bwd(hipStream_t st, const scnattn_dims* dp, const scnattn_params* w, const float* enc, const float* tags,
+            const int64_t* caps, const int32_t* dl_dev, const int32_t* bt, const float* drop_mask,
             const float* saved, float* scratch, const float* dpreds, const float* dalphas, const scnattn_params* g,
             float* denc, float* dtags, const scnattn_pool* pool) {
     SCN_TRY(check_dims(dp));
@@ -388,27 +375,12 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     const int bfm = sm.bfm;
     const int R = Q > 0 ? Q : P;                // pixels per image of the map `enc` holds
     const float* dproj = Q > 0 ? k.dy : k.datt1;    // d (enc . We^T) on those pixels: d y (pooled) or d att1
-    const bool two = wst && wst != st;
-    hipStream_t ws = two ? wst : st;            // stream of the weight gradients
-    const GemmWs wgws = two ? GemmWs{k.gws2, GEMM_WS_FLOATS} : gws;    // ... and its split-K workspace
-    // ws_after_main(): everything enqueued on `st` so far happens-before what is enqueued on `ws` next
-    auto ws_after_main = [&]() -> int {
-        if (!two) return 0;
-        hipEvent_t e = nullptr;
-        SCN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        hipError_t r = hipEventRecord(e, st);
-        if (r == hipSuccess) r = hipStreamWaitEvent(ws, e, 0);
-        (void)hipEventDestroy(e);               // released once the wait has been satisfied
-        SCN_HIP(r);
-        return 0;
-    };
 
     // ---- fc / dropout ----------------------------------------------------------------------------
-    SCN_TRY(ws_after_main());
     if (g->fc_weight)
-        SCN_TRY(gemm(ws, true, false, V, D, B * T, dpreds, V, s.Hd_bm, D, 0.f, g->fc_weight, D, wgws));
+        SCN_TRY(gemm(st, true, false, V, D, B * T, dpreds, V, s.Hd_bm, D, 0.f, g->fc_weight, D, gws));
     if (g->fc_bias)  // only rows that were decoded carry the bias
-        SCN_TRY(colsum_masked(ws, B * T, V, dpreds, V, s.rowmask, g->fc_bias, 0.f));
+        SCN_TRY(colsum_masked(st, B * T, V, dpreds, V, s.rowmask, g->fc_bias, 0.f));
     SCN_TRY(gemm(st, false, false, B * T, D, V, dpreds, V, w->fc_weight, D, 0.f, k.dHd_bm, D, gws));
     SCN_TRY(hidden_from_bm(st, B, T, D, dl_dev, k.dHd_bm, drop_mask, k.dhfc_tm));
 
@@ -439,7 +411,6 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
     // ---- reverse recurrence ----------------------------------------------------------------------
     hipEvent_t ev0 = prof_begin(st);
     int ksH = 0;
-    bool lstm_done = false;
     for (int t = T - 1; t >= 0; --t) {
         const int rows = bt[t];                                    // check_bt: 1 <= rows <= B, non-increasing in t
         const int rows_next = (t + 1 < T) ? bt[t + 1] : 0;
@@ -448,33 +419,21 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
         float* dcat = k.dcat_all + rowT * NC;
         float* dpx = k.dpx_all + rowT * F4;
         const float *pa = s.pa_all + rowT * F4, *phs = s.ph_all + rowT * F4;
-        // the LSTM backward of this step ran inside the previous iteration's last product (below) unless that launch
-        // could not take it, or this is the first iteration
-        if (!lstm_done)
-            SCN_TRY(lstm_bwd(st, rows, rows_next, D, k.dhfc_tm + rowT * D,
-                             rows_next > 0 ? Slabs{k.sH, ksH, BD, D} : Slabs{nullptr, 0, 0, 0}, k.dc,
-                             s.gates_all + rowT * 4 * D, s.Cs + rowT * D, s.tanhc_all + rowT * D, dr));
-        lstm_done = false;
+        // d h of step t+1 (the previous iteration's last product) is this step's dh_next
+        SCN_TRY(lstm_bwd(st, rows, rows_next, D, k.dhfc_tm + rowT * D,
+                         rows_next > 0 ? Slabs{k.sH, ksH, BD, D} : Slabs{nullptr, 0, 0, 0}, k.dc,
+                         s.gates_all + rowT * 4 * D, s.Cs + rowT * D, s.tanhc_all + rowT * D, dr));
         const int ksDb = pick(rows, 2 * F, D, 4);
-        SkinnyTail mixb{3, rows, 0, F4, {s.qx, s.qh, pa, phs}, {dpx, dcat, k.dqx_acc, k.dqh_acc}, NC,
-                        Slabs{nullptr, 0, 0, 0}};
-        bool mixed = false;
         SCN_TRY(skinny_gemm(st, rows, 2 * F, D, 4, dr, 4 * D, D, WDb, 2 * F, (long)D * 2 * F, k.sDb, 2 * F, (long)B * 2 * F,
-                            (long)4 * B * 2 * F, ksDb, bfm, &mixb, &mixed));
-        if (!mixed)
-            SCN_TRY(scn_mix_bwd(st, rows, F4, Slabs{k.sDb, ksDb, (long)4 * B * 2 * F, 2 * F}, (long)B * 2 * F, s.qx, s.qh,
-                                pa, phs, dpx, dcat, NC, k.dqx_acc, k.dqh_acc));
+                            (long)4 * B * 2 * F, ksDb, bfm));
+        SCN_TRY(scn_mix_bwd(st, rows, F4, Slabs{k.sDb, ksDb, (long)4 * B * 2 * F, 2 * F}, (long)B * 2 * F, s.qx, s.qh, pa,
+                            phs, dpx, dcat, NC, k.dqx_acc, k.dqh_acc));
         if (d.has_att) {
             const int ksZ = pick(rows, E, F4, 1);
             float* dawe = k.dawe_all + rowT * E;
             const float *awe = s.awe_all + rowT * E, *gate = s.gate_all + rowT * E;
-            SkinnyTail gateb{4, rows, 0, E, {awe, gate, nullptr, nullptr}, {dawe, dcat + F4, nullptr, nullptr}, NC,
-                             Slabs{nullptr, 0, 0, 0}};
-            bool gated = false;
-            SCN_TRY(skinny_gemm(st, rows, E, F4, 1, dpx, F4, 0, WaTz, E, 0, k.sZ, E, 0, (long)B * E, ksZ, bfm, &gateb,
-                                &gated));
-            if (!gated)
-                SCN_TRY(gate_bwd(st, rows, E, Slabs{k.sZ, ksZ, (long)B * E, E}, awe, gate, dawe, dcat + F4, NC));
+            SCN_TRY(skinny_gemm(st, rows, E, F4, 1, dpx, F4, 0, WaTz, E, 0, k.sZ, E, 0, (long)B * E, ksZ, bfm));
+            SCN_TRY(gate_bwd(st, rows, E, Slabs{k.sZ, ksZ, (long)B * E, E}, awe, gate, dawe, dcat + F4, NC));
             const float* din = dalphas ? dalphas + (long)t * P : nullptr;
             if (Q > 0) {
                 // Q dot products per image against x, folded onto the P pooled pixels inside softmax_bwd
@@ -489,104 +448,60 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
             }
         }
         ksH = pick(rows, D, NC, 1);
-        // d cat . Wcat^T = this step's d h, and with it -- same launch -- the LSTM backward of step t-1, whose only
-        // missing input it is (scn_cell.py:134-152 transposed)
-        SkinnyTail cellb{5, t > 0 ? bt[t - 1] : 0, rows, D,
-                         {t > 0 ? k.dhfc_tm + (rowT - B) * D : nullptr, t > 0 ? s.gates_all + (rowT - B) * 4 * D : nullptr,
-                          t > 0 ? s.Cs + (rowT - B) * D : nullptr, t > 0 ? s.tanhc_all + (rowT - B) * D : nullptr},
-                         {k.dc, t > 0 ? k.dr_all + (rowT - B) * 4 * D : nullptr, nullptr, nullptr}, 0,
-                         Slabs{nullptr, 0, 0, 0}};
-        SCN_TRY(skinny_gemm(st, rows, D, NC, 1, dcat, NC, 0, WcatT, D, 0, k.sH, D, 0, BD, ksH, bfm, t > 0 ? &cellb : nullptr,
-                            &lstm_done));
+        // d cat . Wcat^T = this step's d h, the missing input of the LSTM backward of step t-1 (scn_cell.py:134-152
+        // transposed)
+        SCN_TRY(skinny_gemm(st, rows, D, NC, 1, dcat, NC, 0, WcatT, D, 0, k.sH, D, 0, BD, ksH, bfm));
     }
     // d loss / d h0 (d/d c0 is k.dc): the last product ran at t = 0, where every row decodes
     SCN_TRY(reduce_slabs(st, B, D, Slabs{k.sH, ksH, BD, D}, k.dh0));
     prof_end(st, ev0, 1, T);
 
-    // ---- after the loop: two strands ------------------------------------------------------------------
-    // (1) weight gradients, one GEMM per weight over the stacked (t,b) rows: stream `ws`, off the critical path;
-    // (2) d tags, d att1 -> d encoder_out: stream `st`, heads the encoder's backward pass.
-    // The events are recorded where the inputs of (1) come into being; with two streams its launches are enqueued
-    // LAST, so that the host reaches strand (2) first.
-    hipEvent_t ev_loop = nullptr, ev_att = nullptr;
-    auto mark = [&](hipEvent_t* e) -> int {
-        if (!two) return 0;
-        SCN_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        SCN_HIP(hipEventRecord(*e, st));
-        return 0;
-    };
-    auto ws_wait = [&](hipEvent_t* e) -> int {
-        if (!two || !*e) return 0;
-        const hipError_t r = hipStreamWaitEvent(ws, *e, 0);
-        (void)hipEventDestroy(*e);
-        *e = nullptr;
-        SCN_HIP(r);
-        return 0;
-    };
-    auto wgrad_loop = [&]() -> int {      // everything whose operands the reverse recurrence produced
-        SCN_TRY(ws_wait(&ev_loop));
-        if (g->decode_step_weight_ia) {
-            SCN_TRY(gemm(ws, true, false, M, F4, TB, s.emb_tm, M, k.dpx_all, F4, 0.f, g->decode_step_weight_ia, F4,
-                         wgws));
-            if (d.has_att)
-                SCN_TRY(gemm(ws, true, false, E, F4, TB, s.z_all, E, k.dpx_all, F4, 0.f,
-                             g->decode_step_weight_ia + (long)M * F4, F4, wgws));
-        }
-        if (g->embedding_weight) {
-            SCN_TRY(gemm(ws, false, true, TB, M, F4, k.dpx_all, F4, w->decode_step_weight_ia, F4, 0.f, k.demb_tm, M,
-                         wgws));
-            SCN_TRY(scatter_add_rows_tm(ws, B, T, d.L, M, (const long long*)caps, dl_dev, k.demb_tm, V,
-                                        g->embedding_weight, reinterpret_cast<int*>(k.present)));
-        }
-        if (g->decode_step_weight_ic) {
-            SCN_TRY(mul_bcast(ws, T, B, F4, s.pa_all, s.qx, k.mx_all));
-            SCN_TRY(sgemm_ws(ws, true, false, D, F, TB, 1.f, k.dr_all, 4 * D, k.mx_all, F4, 0.f, g->decode_step_weight_ic, F4,
-                             nullptr, nullptr, 4, D, F, F, wgws.p, wgws.floats));
-        }
-        if (g->decode_step_weight_hc) {
-            SCN_TRY(mul_bcast(ws, T, B, F4, s.ph_all, s.qh, k.mx_all));
-            SCN_TRY(sgemm_ws(ws, true, false, D, F, TB, 1.f, k.dr_all, 4 * D, k.mx_all, F4, 0.f, g->decode_step_weight_hc, F4,
-                             nullptr, nullptr, 4, D, F, F, wgws.p, wgws.floats));
-        }
-        if (g->decode_step_weight_ha)
-            SCN_TRY(gemm(ws, true, false, D, F4, TB, s.Hs, D, k.dcat_all, NC, 0.f, g->decode_step_weight_ha, F4, wgws));
-        if (g->decode_step_weight_ib)
-            SCN_TRY(gemm(ws, true, false, d.S, F4, B, tags, d.S, k.dqx_acc, F4, 0.f, g->decode_step_weight_ib, F4,
-                         wgws));
-        if (g->decode_step_weight_hb)
-            SCN_TRY(gemm(ws, true, false, d.S, F4, B, tags, d.S, k.dqh_acc, F4, 0.f, g->decode_step_weight_hb, F4,
-                         wgws));
-        if (g->decode_step_bias_ih) SCN_TRY(colsum(ws, TB, 4 * D, k.dr_all, 4 * D, g->decode_step_bias_ih, 0.f));
-        if (g->decode_step_bias_hh) SCN_TRY(colsum(ws, TB, 4 * D, k.dr_all, 4 * D, g->decode_step_bias_hh, 0.f));
-        if (d.has_att) {
-            if (g->f_beta_weight)
-                SCN_TRY(gemm(ws, true, false, E, D, TB, k.dcat_all + F4, NC, s.Hs, D, 0.f, g->f_beta_weight, D, wgws));
-            if (g->f_beta_bias) SCN_TRY(colsum(ws, TB, E, k.dcat_all + F4, NC, g->f_beta_bias, 0.f));
-            if (g->attention_decoder_att_weight)
-                SCN_TRY(gemm(ws, true, false, A, D, TB, k.dcat_all + F4 + E, NC, s.Hs, D, 0.f,
-                             g->attention_decoder_att_weight, D, wgws));
-            if (g->attention_decoder_att_bias)
-                SCN_TRY(colsum(ws, TB, A, k.dcat_all + F4 + E, NC, g->attention_decoder_att_bias, 0.f));
-        }
-        if (g->init_h_weight)
-            SCN_TRY(gemm(ws, true, false, D, E, B, k.dh0, D, s.mean_enc, E, 0.f, g->init_h_weight, E, wgws));
-        if (g->init_h_bias) SCN_TRY(colsum(ws, B, D, k.dh0, D, g->init_h_bias, 0.f));
-        if (g->init_c_weight)
-            SCN_TRY(gemm(ws, true, false, D, E, B, k.dc, D, s.mean_enc, E, 0.f, g->init_c_weight, E, wgws));
-        if (g->init_c_bias) SCN_TRY(colsum(ws, B, D, k.dc, D, g->init_c_bias, 0.f));
-        return 0;
-    };
-    auto wgrad_att = [&]() -> int {       // d encoder_att: needs d att1 (/ d y)
-        SCN_TRY(ws_wait(&ev_att));
-        if (!d.has_att) return 0;
-        if (g->attention_encoder_att_weight)
-            SCN_TRY(gemm(ws, true, false, A, E, B * R, dproj, A, enc, E, 0.f, g->attention_encoder_att_weight, E, wgws));
-        if (g->attention_encoder_att_bias)
-            SCN_TRY(colsum(ws, B * P, A, k.datt1, A, g->attention_encoder_att_bias, 0.f));
-        return 0;
-    };
-    SCN_TRY(mark(&ev_loop));
-    if (!two) SCN_TRY(wgrad_loop());
+    // ---- after the loop: weight gradients, one GEMM per weight over the stacked (t,b) rows ----------------
+    if (g->decode_step_weight_ia) {
+        SCN_TRY(gemm(st, true, false, M, F4, TB, s.emb_tm, M, k.dpx_all, F4, 0.f, g->decode_step_weight_ia, F4, gws));
+        if (d.has_att)
+            SCN_TRY(gemm(st, true, false, E, F4, TB, s.z_all, E, k.dpx_all, F4, 0.f,
+                         g->decode_step_weight_ia + (long)M * F4, F4, gws));
+    }
+    if (g->embedding_weight) {
+        SCN_TRY(gemm(st, false, true, TB, M, F4, k.dpx_all, F4, w->decode_step_weight_ia, F4, 0.f, k.demb_tm, M, gws));
+        SCN_TRY(scatter_add_rows_tm(st, B, T, d.L, M, (const long long*)caps, dl_dev, k.demb_tm, V,
+                                    g->embedding_weight, reinterpret_cast<int*>(k.present)));
+    }
+    if (g->decode_step_weight_ic) {
+        SCN_TRY(mul_bcast(st, T, B, F4, s.pa_all, s.qx, k.mx_all));
+        SCN_TRY(sgemm_ws(st, true, false, D, F, TB, 1.f, k.dr_all, 4 * D, k.mx_all, F4, 0.f, g->decode_step_weight_ic, F4,
+                         nullptr, nullptr, 4, D, F, F, gws.p, gws.floats));
+    }
+    if (g->decode_step_weight_hc) {
+        SCN_TRY(mul_bcast(st, T, B, F4, s.ph_all, s.qh, k.mx_all));
+        SCN_TRY(sgemm_ws(st, true, false, D, F, TB, 1.f, k.dr_all, 4 * D, k.mx_all, F4, 0.f, g->decode_step_weight_hc, F4,
+                         nullptr, nullptr, 4, D, F, F, gws.p, gws.floats));
+    }
+    if (g->decode_step_weight_ha)
+        SCN_TRY(gemm(st, true, false, D, F4, TB, s.Hs, D, k.dcat_all, NC, 0.f, g->decode_step_weight_ha, F4, gws));
+    if (g->decode_step_weight_ib)
+        SCN_TRY(gemm(st, true, false, d.S, F4, B, tags, d.S, k.dqx_acc, F4, 0.f, g->decode_step_weight_ib, F4, gws));
+    if (g->decode_step_weight_hb)
+        SCN_TRY(gemm(st, true, false, d.S, F4, B, tags, d.S, k.dqh_acc, F4, 0.f, g->decode_step_weight_hb, F4, gws));
+    if (g->decode_step_bias_ih) SCN_TRY(colsum(st, TB, 4 * D, k.dr_all, 4 * D, g->decode_step_bias_ih, 0.f));
+    if (g->decode_step_bias_hh) SCN_TRY(colsum(st, TB, 4 * D, k.dr_all, 4 * D, g->decode_step_bias_hh, 0.f));
+    if (d.has_att) {
+        if (g->f_beta_weight)
+            SCN_TRY(gemm(st, true, false, E, D, TB, k.dcat_all + F4, NC, s.Hs, D, 0.f, g->f_beta_weight, D, gws));
+        if (g->f_beta_bias) SCN_TRY(colsum(st, TB, E, k.dcat_all + F4, NC, g->f_beta_bias, 0.f));
+        if (g->attention_decoder_att_weight)
+            SCN_TRY(gemm(st, true, false, A, D, TB, k.dcat_all + F4 + E, NC, s.Hs, D, 0.f,
+                         g->attention_decoder_att_weight, D, gws));
+        if (g->attention_decoder_att_bias)
+            SCN_TRY(colsum(st, TB, A, k.dcat_all + F4 + E, NC, g->attention_decoder_att_bias, 0.f));
+    }
+    if (g->init_h_weight)
+        SCN_TRY(gemm(st, true, false, D, E, B, k.dh0, D, s.mean_enc, E, 0.f, g->init_h_weight, E, gws));
+    if (g->init_h_bias) SCN_TRY(colsum(st, B, D, k.dh0, D, g->init_h_bias, 0.f));
+    if (g->init_c_weight)
+        SCN_TRY(gemm(st, true, false, D, E, B, k.dc, D, s.mean_enc, E, 0.f, g->init_c_weight, E, gws));
+    if (g->init_c_bias) SCN_TRY(colsum(st, B, D, k.dc, D, g->init_c_bias, 0.f));
     if (dtags) {
         SCN_TRY(gemm(st, false, true, B, d.S, F4, k.dqx_acc, F4, w->decode_step_weight_ib, F4, 0.f, dtags, d.S, gws));
         SCN_TRY(gemm(st, false, true, B, d.S, F4, k.dqh_acc, F4, w->decode_step_weight_hb, F4, 1.f, dtags, d.S, gws));
@@ -601,9 +516,12 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
         if (g->attention_full_att_bias) SCN_TRY(copy2d(st, 1, 1, k.dwtmp + A, 1, g->attention_full_att_bias, 1));
         if (Q > 0 && (g->attention_encoder_att_weight || denc))
             SCN_TRY(pool_transpose(st, B, P, A, pd, k.datt1, k.dy));      // d y = pool^T (d att1): [B*Q][A]
+        // d encoder_att: needs d att1 (/ d y)
+        if (g->attention_encoder_att_weight)
+            SCN_TRY(gemm(st, true, false, A, E, B * R, dproj, A, enc, E, 0.f, g->attention_encoder_att_weight, E, gws));
+        if (g->attention_encoder_att_bias)
+            SCN_TRY(colsum(st, B * P, A, k.datt1, A, g->attention_encoder_att_bias, 0.f));
     }
-    SCN_TRY(mark(&ev_att));
-    if (!two) SCN_TRY(wgrad_att());
 
     // ---- d loss / d encoder_out (only when the encoder is fine-tuned) -------------------------------
     if (denc) {
@@ -621,10 +539,6 @@ int seq_bwd(hipStream_t st, hipStream_t wst, const scnattn_dims* dp, const scnat
         SCN_TRY(gemm(st, false, false, B, E, D, k.dc, D, w->init_c_weight, E, 1.f, k.dmean, E, gws));
         if (Q > 0) SCN_TRY(add_bcast_rows_w(st, B, Q, E, pd.col_w, k.dmean, denc));
         else SCN_TRY(add_bcast_rows(st, B, P, E, k.dmean, 1.f / (float)P, denc));
-    }
-    if (two) {
-        SCN_TRY(wgrad_loop());
-        SCN_TRY(wgrad_att());
     }
     return 0;
 }

@@ -71,8 +71,6 @@ _SIGS = {
                          C.POINTER(Pool)], i32),
     "scnattn_seq_bwd": ([vp, C.POINTER(Dims), C.POINTER(Params), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                          C.POINTER(Params), vp, vp, C.POINTER(Pool)], i32),
-    "scnattn_seq_bwd_streams": ([vp, vp, C.POINTER(Dims), C.POINTER(Params), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                 C.POINTER(Params), vp, vp, C.POINTER(Pool)], i32),
     "scnattn_beam_workspace": ([C.POINTER(Dims), i32, i32, C.POINTER(sz)], i32),
     "scnattn_beam_layout": ([C.POINTER(Dims), i32, i32, C.POINTER(i64)], i32),
     "scnattn_beam_init": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(Params), vp, vp, i32, vp], i32),
@@ -188,7 +186,7 @@ def lib():
                 fn.restype = res
             h.scnattn_last_error.argtypes = []
             h.scnattn_last_error.restype = C.c_char_p
-            # A/B runs without touching code: SCNATTN_OPTIONS="cgemm_combine=0,dec_tail=1" (scnattn_set_option names)
+            # A/B runs without touching code: SCNATTN_OPTIONS="cgemm_combine=0,cgemm_mi=2" (scnattn_set_option names)
             for item in filter(None, os.environ.get("SCNATTN_OPTIONS", "").split(",")):
                 name, _, val = item.partition("=")
                 if h.scnattn_set_option(name.strip().encode(), int(val)) != 0:

@@ -20,7 +20,7 @@ d weight -- runs on the hand-written kernels of csrc/cgemm.hip / csrc/conv3.hip,
             conv2 dgrad: nine flipped taps over K (stride 1) / four parity classes of d-input pixels (stride 2)
             bn1 backward (two passes) ; conv1 wgrad ; conv1 dgrad ACCUMULATING into d identity (beta = 1)
 The strided 1x1 downsample convolution gathers its input rows inside the kernel.  No library (MIOpen / rocBLAS) kernel
-runs in a block; `SCNATTN_CONV3=miopen` swaps conv2 back to MIOpen for A/B measurements only.
+runs in a block.
 
 `Bottleneck.forward` (scnattn/resnet.py) calls `bottleneck()` when `train_reason` returns None; scnattn/block.py holds
 what this path shares with the eval block (scnattn/conv_eval.py) and the bf16 one (scnattn/conv16.py)."""
@@ -35,10 +35,10 @@ from ._lib import ConvExtra
 
 ENABLED = True          # class-wide switch: tests / A-B runs compare against the unfused path
 SIDE_WGRAD = True       # weight gradients on a second HIP stream (see _Side)
-CONV3 = os.environ.get("SCNATTN_CONV3", "hip")     # conv2 (3x3): "hip" = the hand-written kernels (the product path);
-                        # "miopen" = MIOpen for all three directions (A/B measurements; tools/, tests that ask for it)
-if CONV3 not in ("hip", "miopen"):
-    raise RuntimeError("SCNATTN_CONV3 must be 'hip' or 'miopen' (the per-shape stopwatch of round 2 is gone)")
+CONV3 = "hip"           # conv2 (3x3) runs on the hand-written kernels; bench.py's JSON line prints this
+if os.environ.get("SCNATTN_CONV3", "hip") != "hip":
+    raise RuntimeError("SCNATTN_CONV3=%s: the MIOpen A/B branch of conv2 is gone (as is round 2's per-shape stopwatch); "
+                       "unset the variable or set it to 'hip'" % os.environ["SCNATTN_CONV3"])
 W3_SLICES = int(os.environ.get("SCNATTN_W3_SLICES", "0"))   # tuning: K slices of the halo-staged 3x3 weight gradient (0: policy)
 
 _bufs = {}
@@ -196,7 +196,7 @@ def _as2d(t4):
 
 
 def _as4d(t2, n, h, w):
-    """[N*H*W, C] -> the (N, C, H, W) channels-last view MIOpen takes (no copy)."""
+    """[N*H*W, C] -> its (N, C, H, W) channels-last view (no copy)."""
     return t2.view(n, h, w, t2.shape[1]).permute(0, 3, 1, 2)
 
 
@@ -313,23 +313,11 @@ class _BottleneckFn(torch.autograd.Function):
         a1, st1 = _apply_fin(h, st, Rin, p, z1, None, part, bn1, sh1, g1, b1, True)
         # conv2 (3x3, strided for layerN.0): the implicit-GEMM mode of the same kernel with the bn2 statistics epilogue
         sh2 = _shift(bn2)
-        if CONV3 == "hip":
-            z2 = torch.empty((Rout, p), device=dev, dtype=torch.float32)
-            ex3 = ConvExtra(epi=1, stat_partial=part.data_ptr(), stat_shift=sh2.data_ptr())
-            _chk(h.scnattn_conv3x3_fwd(st, N, Hi, Wi, p, p, s, a1.data_ptr(), w2.data_ptr(), z2.data_ptr(), C.byref(ex3),
-                                       ws.data_ptr(), ws.numel()), "scnattn_conv3x3_fwd")
-            st2, ss2 = _finalize(h, st, Rout, p, part, bn2, sh2, g2, b2, True)
-        else:       # A/B only: MIOpen + a statistics pass over z2
-            z4 = torch.ops.aten.convolution(_as4d(a1, N, Hi, Wi), w2, None, [s, s], [1, 1], [1, 1], False, [0, 0], 1)
-            if not z4.is_contiguous(memory_format=torch.channels_last):
-                z4 = z4.contiguous(memory_format=torch.channels_last)
-            z2 = _as2d(z4)
-            st2 = torch.empty((2, p), device=dev, dtype=torch.float32)
-            ss2 = torch.empty((p, 2), device=dev, dtype=torch.float32)
-            _chk(h.scnattn_bn_stats_fold(st, Rout, p, z2.data_ptr(), bn2.eps, bn2.momentum, bnpart.data_ptr(),
-                                         st2[0].data_ptr(), st2[1].data_ptr(), bn2.running_mean.data_ptr(),
-                                         bn2.running_var.data_ptr(), g2.data_ptr(), b2.data_ptr(), ss2.data_ptr()),
-                 "scnattn_bn_stats_fold")
+        z2 = torch.empty((Rout, p), device=dev, dtype=torch.float32)
+        ex3 = ConvExtra(epi=1, stat_partial=part.data_ptr(), stat_shift=sh2.data_ptr())
+        _chk(h.scnattn_conv3x3_fwd(st, N, Hi, Wi, p, p, s, a1.data_ptr(), w2.data_ptr(), z2.data_ptr(), C.byref(ex3),
+                                   ws.data_ptr(), ws.numel()), "scnattn_conv3x3_fwd")
+        st2, ss2 = _finalize(h, st, Rout, p, part, bn2, sh2, g2, b2, True)
         # conv3 with the bn2+relu prologue (+ bn3 statistics into `part`)
         sh3 = _shift(bn3)
         ex = ConvExtra(pro=1, epi=1, pro_ss=ss2.data_ptr(), stat_partial=part.data_ptr(), stat_shift=sh3.data_ptr())
@@ -399,36 +387,21 @@ class _BottleneckFn(torch.autograd.Function):
         # ---- conv2: weight gradient (side stream) and d input; bn1's mask / reduction rides on the d input ---------------
         dw2 = None
         dz1 = torch.empty((Rin, p), **f32)         # first d a1 (masked), then (in place) dz1
-        if CONV3 == "hip":
-            if need[5]:
-                dw2 = _grad_out(w2)
-                sw, wsw = (side.fork(main, dz2, a1, dw2), side.ws) if side else (st, ws)
-                _chk(h.scnattn_conv3x3_wgrad(sw, N, Hi, Wi, p, p, s, dz2.data_ptr(), a1.data_ptr(), dw2.data_ptr(),
-                                             wsw.data_ptr(), wsw.numel(), W3_SLICES), "scnattn_conv3x3_wgrad")
-            if s == 1:      # mask = [fma((z1-mean)*invstd, gamma, beta) > 0]: the expression bn1's apply evaluated
-                ex = ConvExtra(epi=2, stat_partial=part.data_ptr(), ez=z1.data_ptr(), emean=st1[0].data_ptr(),
-                               einvstd=st1[1].data_ptr(), egamma=g1.data_ptr(), ebeta=b1.data_ptr(), ldz=p)
-                _chk(h.scnattn_conv3x3_dgrad(st, N, Hi, Wi, p, p, dz2.data_ptr(), w2.data_ptr(), dz1.data_ptr(), C.byref(ex),
-                                             ws.data_ptr(), ws.numel()), "scnattn_conv3x3_dgrad")
-                dgb1 = _bwd_dx_fin(h, st, Rin, p, dz1, z1, st1, g1, part, ld_in, nc_in, dz1)
-            else:
-                da1 = torch.empty((Rin, p), **f32)
-                _chk(h.scnattn_conv3x3_dgrad_strided(st, N, Hi, Wi, p, p, s, dz2.data_ptr(), w2.data_ptr(), da1.data_ptr(),
-                                                     ws.data_ptr(), ws.numel()), "scnattn_conv3x3_dgrad_strided")
-        else:       # A/B only: MIOpen
-            dz2_4, a1_4 = _as4d(dz2, N, Ho, Wo), _as4d(a1, N, Hi, Wi)
-            if need[5]:
-                if side:
-                    side.fork(main, dz2, a1)
-                with torch.cuda.stream(side.stream if side else main):
-                    dw2 = torch.ops.aten.convolution_backward(dz2_4, a1_4, w2, None, [s, s], [1, 1], [1, 1], False, [0, 0], 1,
-                                                              [False, True, False])[1]
-            da1_4 = torch.ops.aten.convolution_backward(dz2_4, a1_4, w2, None, [s, s], [1, 1], [1, 1], False, [0, 0], 1,
-                                                        [True, False, False])[0]
-            if not da1_4.is_contiguous(memory_format=torch.channels_last):
-                da1_4 = da1_4.contiguous(memory_format=torch.channels_last)
-            da1 = _as2d(da1_4)
-        if not (CONV3 == "hip" and s == 1):     # the mask comes from a1 itself: a1 = relu(bn1(z1)) > 0
+        if need[5]:
+            dw2 = _grad_out(w2)
+            sw, wsw = (side.fork(main, dz2, a1, dw2), side.ws) if side else (st, ws)
+            _chk(h.scnattn_conv3x3_wgrad(sw, N, Hi, Wi, p, p, s, dz2.data_ptr(), a1.data_ptr(), dw2.data_ptr(),
+                                         wsw.data_ptr(), wsw.numel(), W3_SLICES), "scnattn_conv3x3_wgrad")
+        if s == 1:      # mask = [fma((z1-mean)*invstd, gamma, beta) > 0]: the expression bn1's apply evaluated
+            ex = ConvExtra(epi=2, stat_partial=part.data_ptr(), ez=z1.data_ptr(), emean=st1[0].data_ptr(),
+                           einvstd=st1[1].data_ptr(), egamma=g1.data_ptr(), ebeta=b1.data_ptr(), ldz=p)
+            _chk(h.scnattn_conv3x3_dgrad(st, N, Hi, Wi, p, p, dz2.data_ptr(), w2.data_ptr(), dz1.data_ptr(), C.byref(ex),
+                                         ws.data_ptr(), ws.numel()), "scnattn_conv3x3_dgrad")
+            dgb1 = _bwd_dx_fin(h, st, Rin, p, dz1, z1, st1, g1, part, ld_in, nc_in, dz1)
+        else:           # s != 1: the mask comes from a1 itself, a1 = relu(bn1(z1)) > 0
+            da1 = torch.empty((Rin, p), **f32)
+            _chk(h.scnattn_conv3x3_dgrad_strided(st, N, Hi, Wi, p, p, s, dz2.data_ptr(), w2.data_ptr(), da1.data_ptr(),
+                                                 ws.data_ptr(), ws.numel()), "scnattn_conv3x3_dgrad_strided")
             g1m, nch = _bwd_reduce(h, st, Rin, p, da1, a1, z1, st1, True, bnpart, True)
             dgb1 = _bwd_dx_fin(h, st, Rin, p, g1m, z1, st1, g1, bnpart, (nch + 3) & ~3, nch, dz1)
             del g1m, da1
@@ -487,7 +460,7 @@ def train_reason(mod, x):
         return r
     g = B.geometry(mod, x)
     # the 3x3 kernels: 32-channel blocks (stride 1), 128-channel column tiles and even maps (stride 2)
-    if CONV3 == "hip" and (g.p % 32 if g.s == 1 else g.p % 128 or g.Hi % 2 or g.Wi % 2):
+    if g.p % 32 if g.s == 1 else g.p % 128 or g.Hi % 2 or g.Wi % 2:
         return "conv2's width / map parity is not one the 3x3 kernels address"
     if not mod.conv2.weight.is_contiguous(memory_format=torch.channels_last):
         return "conv2's weight is not channels-last"

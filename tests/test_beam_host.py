@@ -80,4 +80,4 @@ def test_header_declares_every_new_export():
     for name in NEW:
         assert name in declared and name in L.EXPORTS and hasattr(h, name), name
     assert int(re.search(r"#define SCNATTN_BEAM_NOFF (\d+)", header).group(1)) == L.BEAM_NOFF
-    assert h.scnattn_version() == 108
+    assert h.scnattn_version() == 109
