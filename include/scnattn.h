@@ -25,6 +25,7 @@ extern "C" {
 
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
+                               + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
                                0.1.8: + the tagger head (scnattn_tag_pool_fwd/_bwd, scnattn_bce_fwd/_bwd; new symbols only, the version stays), + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
                                new symbols only, the version stays), + batched beam search (scnattn_beam_*; new symbols only, the version stays), + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
                                _conv3x3_fwd_bn_eval; new symbols only, the version stays), + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
@@ -293,6 +294,23 @@ int scnattn_caption_loss_fwd(void* stream, int B, int T, int V, int P, const flo
 int scnattn_caption_loss_bwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
                              long ldt, const int32_t* decode_lengths, long n_tokens, const float* row_lse,
                              const float* sm1, float alpha_c, const float* grad_loss, float* dscores, float* dalphas);
+/* scnattn_caption_loss_fwd with the caption loops' metrics counted in the same pass over the scores (the top-5 accuracy of
+ * trains/attention_scn.py:255-257 / :338-339 and the arg-max hypotheses of :366-372); new symbol only, the version stays.
+ * Elements of a row are ordered by (value descending, index ascending), the beam search's tie rule.  For a decoded row
+ * r = b*T + t (t < decode_lengths[b]) with target tg:
+ *   row_rank[r]       = #{v : x[v] > x[tg]} + #{v < tg : x[v] == x[tg]}: the target's position in that order, so the target
+ *                       is among the top k exactly when row_rank[r] < k; INT32_MAX for a target outside [0,V) (never a hit;
+ *                       the loss is NaN as above);
+ *   preds[b*ldp + t]  = the index of the first element in that order: the arg-max, the lowest index among equal maxima.
+ * A row that was not decoded gets row_rank = -1 and preds = 0, and its scores are not read.  hits[0] = #{0 <= row_rank < k},
+ * hits[1] = #{row_rank == 0}: exact counts, so top-k accuracy in percent is hits[0] * (100 / n_tokens).  k > V is legal
+ * (every decoded row with a valid target is a hit).  row_rank [B*T] is a workspace like row_lse; row_lse, row_loss and loss
+ * hold the same bits as after scnattn_caption_loss_fwd, so scnattn_caption_loss_bwd runs on them unchanged.  k < 1,
+ * ldp < T or a null output returns -1 before anything is launched.  With NaN scores the metrics are unspecified. */
+int scnattn_caption_loss_metrics_fwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
+                                     long ldt, const int32_t* decode_lengths, long n_tokens, const float* alphas,
+                                     float alpha_c, float* row_lse, float* row_loss, float* sm1, float* reg_part,
+                                     float* loss, int k, int32_t* row_rank, int32_t* preds, long ldp, int32_t* hits);
 /* The head of the tagger step (models/encoders/tagger.py, trains/tagger.py:161-176) around its Linear layer.
  * The trunk map is addressed as x[b, q, c], q over the HW pixels, by ELEMENT strides sb / sp / sc; it holds fp32, or bf16
  * when bf16 != 0.  The channel-contiguous case (sc = 1, C and the other strides multiples of 16 bytes, aligned base) runs

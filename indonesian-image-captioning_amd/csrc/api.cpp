@@ -555,6 +555,15 @@ int scnattn_caption_loss_fwd(void* stream, int B, int T, int V, int P, const flo
                             alphas, alpha_c, row_lse, row_loss, sm1, reg_part, loss);
 }
 
+int scnattn_caption_loss_metrics_fwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
+                                     long ldt, const int32_t* decode_lengths, long n_tokens, const float* alphas,
+                                     float alpha_c, float* row_lse, float* row_loss, float* sm1, float* reg_part,
+                                     float* loss, int k, int32_t* row_rank, int32_t* preds, long ldp, int32_t* hits) {
+    return caption_loss_metrics_fwd(ST(stream), B, T, V, P, scores, (const long long*)targets, ldt, decode_lengths,
+                                    n_tokens, alphas, alpha_c, row_lse, row_loss, sm1, reg_part, loss, k, row_rank, preds,
+                                    ldp, hits);
+}
+
 int scnattn_caption_loss_bwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
                              long ldt, const int32_t* decode_lengths, long n_tokens, const float* row_lse,
                              const float* sm1, float alpha_c, const float* grad_loss, float* dscores, float* dalphas) {

@@ -179,6 +179,11 @@ int add_bcast_rows(hipStream_t st, int B, int P, int E, const float* v, float sc
 int caption_loss_fwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
                      const int* dl, long n_tokens, const float* alphas, float alpha_c, float* row_lse, float* row_loss,
                      float* sm1, float* reg_part, float* loss);
+// the same launches with the metrics in the row pass: the target's rank per row, the arg-max token, top-k / top-1 counts
+int caption_loss_metrics_fwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets,
+                             long ldt, const int* dl, long n_tokens, const float* alphas, float alpha_c, float* row_lse,
+                             float* row_loss, float* sm1, float* reg_part, float* loss, int k, int* row_rank, int* preds,
+                             long ldp, int* hits);
 int caption_loss_bwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
                      const int* dl, long n_tokens, const float* row_lse, const float* sm1, float alpha_c,
                      const float* gout, float* dscores, float* dalphas);

@@ -69,11 +69,17 @@ class TrainStep:
     def __init__(self, kind="attention_scn", fine_tune_encoder=True, device="cuda", seed=1234, encoder=True,
                  bucket_mb=32, graph_encoder=False, tagger=False, force_reduce=False, encoder_dtype="f32",
                  decoder_dtype="f32", tagger_overlap=True,
-                 fused_loss=True, pooled_attention=True, **overrides):
+                 fused_loss=True, pooled_attention=True, metrics=False, **overrides):
         self.cfg = dict(DEFAULTS)
         self.cfg.update(overrides)
         self.kind = kind
         self.fused_loss = fused_loss
+        # metrics=True: the loss pass also counts the step's top-5 / top-1 hits (trains/attention_scn.py:255-257) and leaves
+        # them in `last_metrics` on the device; the loss, its gradient and the update keep their bits.  topk_percent() syncs.
+        if metrics and not fused_loss:
+            raise ValueError("TrainStep: metrics=True rides in the fused loss pass (fused_loss=True)")
+        self.metrics = metrics
+        self.last_metrics = None     # (loss.detach(), hits int32 (2,) = [top-5 hits, top-1 hits], n_tokens)
         self.pooled_attention = pooled_attention   # attention on the trunk's 8x8 map instead of its 14x14 pooling
         # "bf16": the ResNet trunk runs under bf16 autocast (MIOpen bf16 MFMA convolutions, bf16 feature maps
         # through the fused BatchNorm kernels, fp32 master weights/statistics); the decoder stays fp32.
@@ -138,6 +144,10 @@ class TrainStep:
     def loss_fn(self, scores, caps_sorted, decode_lengths, alphas, dl_dev=None):
         """trains/attention_scn.py:222-236.  On the GPU: one fused forward/backward pair on the unpacked
         scores (csrc/loss.hip); `fused_loss=False` keeps the reference's op sequence (tests compare the two)."""
+        if self.metrics:
+            loss, hits, _ = SF.caption_loss_metrics(scores, caps_sorted, decode_lengths, alphas, self.cfg["alpha_c"], dl_dev, k=5)
+            self.last_metrics = (loss.detach(), hits, sum(decode_lengths))
+            return loss
         if self.fused_loss and scores.is_cuda:
             return SF.caption_loss(scores, caps_sorted, decode_lengths, alphas, self.cfg["alpha_c"], dl_dev)
         targets = caps_sorted[:, 1:]
@@ -232,12 +242,27 @@ class TrainStep:
             self.encoder_optimizer.step(scale)
         return loss
 
+    def topk_percent(self):
+        """The last step's top-5 accuracy in percent (metrics=True), the reference's `accuracy(scores, targets, 5)`;
+        the one place that waits for the device."""
+        if self.last_metrics is None:
+            raise RuntimeError("TrainStep.topk_percent: no step has run with metrics=True")
+        return topk_percent(self.last_metrics[1], self.last_metrics[2])
 
-def validate(batches, encoder, encoder_tagger, decoder, criterion, word_map, alpha_c=1.0):
+
+def topk_percent(hits, n_tokens):
+    """utils/metric.py::accuracy from the hit count of SF.caption_loss_metrics: `correct_total.item() * (100.0 / batch_size)`"""
+    return float(int(hits[0])) * (100.0 / n_tokens)
+
+
+def validate(batches, encoder, encoder_tagger, decoder, criterion, word_map, alpha_c=1.0, fused=False):
     """The reference's validate() (trains/attention_scn.py:274-385): eval-mode forward under no_grad,
     loss / top-5 accuracy bookkeeping, references and arg-max hypotheses, corpus BLEU-4.
     `batches` yields (imgs, caps, caplens, allcaps) already on the device; `encoder_tagger` may be a
-    callable returning tags or None when the batch tuple carries tags in place of images for it."""
+    callable returning tags or None when the batch tuple carries tags in place of images for it.
+    `fused=True`: loss, top-5 and hypotheses from one pass over the scores (_validate_fused), any of the three decoders."""
+    if fused:
+        return _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c)
     from utils.metric import AverageMeter, accuracy, corpus_bleu
     decoder.eval()
     encoder.eval()
@@ -263,6 +288,56 @@ def validate(batches, encoder, encoder_tagger, decoder, criterion, word_map, alp
                 references.append([[w for w in c if w not in skip] for c in allcaps[j].tolist()])
             preds = torch.max(scores_copy, dim=2)[1].tolist()
             hypotheses.extend(p[:decode_lengths[j]] for j, p in enumerate(preds))
+    assert len(references) == len(hypotheses)
+    return corpus_bleu(references, hypotheses), losses.avg, top5accs.avg
+
+
+def _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c):
+    """validate() on SF.caption_loss_metrics: per batch the decoder's forward and one loss pass that also yields the top-5
+    hit count and the arg-max tokens; no clone, no packed copies, no topk, no synchronisation of its own.  What a batch
+    leaves stays on the device -- loss bits, hits and preds in one int32 vector, allcaps[sort_ind] -- and comes down in two
+    copies after the last batch; the AverageMeter arithmetic is then replayed in the reference's order, so the averages are
+    formed as the eager path forms them.  The decoder's kind decides its call, as in TrainStep.step()."""
+    from utils.metric import AverageMeter, corpus_bleu
+    decoder.eval()
+    encoder.eval()
+    if hasattr(encoder_tagger, "eval"):
+        encoder_tagger.eval()
+    skip = {word_map['<start>'], word_map['<pad>']}
+    words, caps_dev, shapes = [], [], []
+    with torch.no_grad():
+        for imgs, caps, caplens, allcaps in batches:
+            encoder_out = encoder(imgs)
+            alphas = None
+            if isinstance(decoder, PureAttention):
+                scores, caps_sorted, decode_lengths, alphas, sort_ind = decoder(encoder_out, caps, caplens)
+            elif isinstance(decoder, PureSCN):
+                scores, caps_sorted, decode_lengths, sort_ind = decoder(encoder_out, encoder_tagger(imgs), caps, caplens)
+            else:
+                scores, caps_sorted, decode_lengths, alphas, sort_ind = decoder(encoder_out, encoder_tagger(imgs), caps, caplens)
+            dl_dev = (caplens.reshape(-1)[sort_ind] - 1).to(torch.int32)
+            loss, hits, preds = SF.caption_loss_metrics(scores, caps_sorted, decode_lengths, alphas, alpha_c, dl_dev, k=5)
+            words.append(torch.cat([loss.reshape(1).view(torch.int32), hits, preds.reshape(-1)]))
+            allcaps = allcaps[sort_ind]
+            caps_dev.append(allcaps.reshape(-1))
+            shapes.append((tuple(preds.shape), tuple(allcaps.shape), list(decode_lengths)))
+    losses, top5accs = AverageMeter(), AverageMeter()
+    references, hypotheses = [], []
+    if shapes:
+        words, caps_host = torch.cat(words).cpu(), torch.cat(caps_dev).cpu()
+    w = c = 0
+    for (B, T), cshape, decode_lengths in shapes:
+        n = sum(decode_lengths)
+        losses.update(words[w:w + 1].view(torch.float32).item(), n)
+        top5accs.update(topk_percent(words[w + 1:w + 3], n), n)
+        preds = words[w + 3:w + 3 + B * T].view(B, T).tolist()
+        w += 3 + B * T
+        ncap = cshape[0] * cshape[1] * cshape[2]
+        allcaps = caps_host[c:c + ncap].view(cshape)
+        c += ncap
+        for j in range(cshape[0]):
+            references.append([[x for x in cap if x not in skip] for cap in allcaps[j].tolist()])
+        hypotheses.extend(p[:decode_lengths[j]] for j, p in enumerate(preds))
     assert len(references) == len(hypotheses)
     return corpus_bleu(references, hypotheses), losses.avg, top5accs.avg
 
