@@ -345,6 +345,37 @@ int scnattn_bce_bwd(void* stream, int B, int S, const float* probs, long ldp, co
  * A row index outside [0, n_src) yields a NaN image instead of a fault. */
 int scnattn_u8_gather_normalize(void* stream, const uint8_t* src, long n_src, const int64_t* idx, long n_out, int C,
                                 long HW, const float* lut, void* dst, int dst_bf16, int channels_last);
+/* Image resize of the inference path: replaces the host-side `scipy.misc.imresize(img, (OH, OW))` of inference.py:33-38
+ * and utils/dataset.py:368-373, i.e. `PIL.Image.resize((OW, OH), BILINEAR)` on the uint8 image, the grey -> three planes
+ * replication before it and the `transpose(2, 0, 1)` after it -- bit for bit: Pillow's 8-bit resize is integer
+ * arithmetic (per pass clip8((2^21 + sum coeff * byte) >> 22), horizontal pass first, its result a uint8 before the
+ * vertical pass reads it) on coefficient tables the host computes in double (scnattn.data.resize_taps).
+ *   src      packed device buffer of src_bytes bytes holding N decoded images, each H x W x C interleaved uint8
+ *   desc     one descriptor per image; desc_host is validated here, before the launch, desc_dev is the same array in
+ *            device memory and is what the kernel reads (a device copy that disagrees skips the image, it never reads
+ *            out of range)
+ *   taps     device int32 buffer of taps_len words holding the axis tables.  A table of (in, out), in != out, is
+ *            xmin[out], n[out], coeff[out][ksize] with ksize = 2 * ceil(max(in / out, 1)) + 1, in all
+ *            scnattn_resize_table_ints(in, out) words; output i is clip8((2^21 + sum_{k < n[i]} coeff[i][k] *
+ *            in[xmin[i] + k]) >> 22).  An axis with in == out has no pass and no table (tab_* is ignored).
+ *   dst      dst_kind 0: uint8 [N][3][OH][OW] (channels_last must be 0);  1 / 2: fp32 / bf16 lut[c][byte], lut as for
+ *            scnattn_u8_gather_normalize with C = 3, [N][3][OH][OW] or, channels_last, [N][OH][OW][3] -- the tensor
+ *            scnattn_u8_gather_normalize writes from the uint8 rows.  A C == 1 image fills all three planes.
+ * One launch for the whole batch.  1 <= H, W, OH, OW <= SCNATTN_RESIZE_MAX_DIM, N <= 65535.  Every refusal (C not 1 or
+ * 3, a size out of range, a null pointer, an image or table that runs past its buffer) returns -1 with a message
+ * before anything is launched.  scnattn_resize_table_ints returns -1 for a size out of range. */
+#define SCNATTN_RESIZE_MAX_DIM 16384
+typedef struct scnattn_image_desc {
+    int64_t offset;      /* byte offset of the image in src */
+    int32_t H, W, C;
+    int32_t tab_h;       /* word offset in taps of the (W, OW) table */
+    int32_t tab_v;       /* word offset in taps of the (H, OH) table */
+    int32_t reserved;
+} scnattn_image_desc;
+long scnattn_resize_table_ints(int in_size, int out_size);
+int scnattn_u8_resize_bilinear(void* stream, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
+                               const scnattn_image_desc* desc_dev, int N, const int32_t* taps, long taps_len, int OH,
+                               int OW, const float* lut, void* dst, int dst_kind, int channels_last);
 /* Fused BatchNorm2d (+ residual) (+ ReLU) on channels-last maps viewed as [R = N*H*W, C] (C % 4 == 0):
  * the `bn -> relu` / `bn -> (+identity) -> relu` groups of torchvision's Bottleneck behind
  * models/encoders/caption.py:17-22.  `partial` needs scnattn_bn_workspace_floats(C) floats.

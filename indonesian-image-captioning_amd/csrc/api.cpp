@@ -597,6 +597,19 @@ int scnattn_u8_gather_normalize(void* stream, const uint8_t* src, long n_src, co
                                channels_last);
 }
 
+int scnattn_u8_resize_bilinear(void* stream, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
+                               const scnattn_image_desc* desc_dev, int N, const int32_t* taps, long taps_len, int OH,
+                               int OW, const float* lut, void* dst, int dst_kind, int channels_last) {
+    return u8_resize_bilinear(ST(stream), src, src_bytes, desc_host, desc_dev, N, taps, taps_len, OH, OW, lut, dst,
+                              dst_kind, channels_last);
+}
+
+long scnattn_resize_table_ints(int in_size, int out_size) {
+    const long n = resize_table_ints(in_size, out_size);
+    if (n < 0) set_error("scnattn_resize_table_ints: size outside 1..SCNATTN_RESIZE_MAX_DIM");
+    return n;
+}
+
 int scnattn_bn_workspace_floats(int C) { return bn_max_chunks() * 2 * C; }
 
 int scnattn_bn_stats(void* stream, int R, int C, const void* x, int bf16, float eps, float momentum, float* partial,

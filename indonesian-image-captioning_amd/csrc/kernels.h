@@ -201,6 +201,11 @@ int bce_bwd(hipStream_t st, int B, int S, const float* probs, long ldp, const fl
 // data.hip: uint8 image rows (gathered by index) -> normalised fp32/bf16 batch, NCHW or channels-last
 int u8_gather_normalize(hipStream_t st, const uint8_t* src, long n_src, const long long* idx, long n_out, int C,
                         long HW, const float* lut, void* dst, int dst_bf16, int channels_last);
+// resize.hip: a packed batch of decoded uint8 images -> Pillow's bilinear resize, as uint8 rows or normalised
+int u8_resize_bilinear(hipStream_t st, const uint8_t* src, long src_bytes, const struct scnattn_image_desc* desc_host,
+                       const struct scnattn_image_desc* desc_dev, int N, const int* taps, long taps_len, int OH, int OW,
+                       const float* lut, void* dst, int dst_kind, int channels_last);
+long resize_table_ints(int in, int out);
 int pool_permute_fwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* x,
                      long sxb, long sxc, long sxh, long sxw, float* y);
 int pool_permute_bwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* dy,

@@ -62,6 +62,11 @@ class BnEval16(C.Structure):       # scnattn_bn_eval16: the same layout, res is 
     _fields_ = BnEval._fields_
 
 
+class ImageDesc(C.Structure):      # scnattn_image_desc
+    _fields_ = [("offset", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("tab_h", C.c_int32),
+                ("tab_v", C.c_int32), ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
@@ -150,6 +155,8 @@ _SIGS = {
     "scnattn_bce_fwd": ([vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp], i32),
     "scnattn_bce_bwd": ([vp, i32, i32, vp, i64, vp, i64, vp, vp, i64], i32),
     "scnattn_u8_gather_normalize": ([vp, vp, i64, vp, i64, i32, i64, vp, vp, i32, i32], i32),
+    "scnattn_resize_table_ints": ([i32, i32], i64),
+    "scnattn_u8_resize_bilinear": ([vp, vp, i64, vp, vp, i32, vp, i64, i32, i32, vp, vp, i32, i32], i32),
     "scnattn_bn_workspace_floats": ([i32], i32),
     "scnattn_bn_stats": ([vp, i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp], i32),
     "scnattn_bn_apply": ([vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp], i32),
@@ -166,6 +173,7 @@ _SIGS = {
 
 BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
 MAX_BEAM = 8
+RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM
 
 EXPORTS = tuple(_SIGS) + ("scnattn_last_error",)
 

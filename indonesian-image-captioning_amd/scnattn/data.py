@@ -19,6 +19,7 @@ MI355X-first shape of the same thing:
 The arithmetic is bit-identical to the reference's (table lookup of its own per-value results,
 `normalize_lut`).  There is no CPU fallback: batches are produced on the GPU.
 """
+import functools
 import json
 import os
 import queue
@@ -28,7 +29,7 @@ import numpy as np
 import torch
 
 from . import h5lite
-from ._lib import call, ptr, require_cuda, stream_of
+from ._lib import RESIZE_MAX_DIM, ImageDesc, call, ptr, require_cuda, stream_of
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)      # trains/attention_scn.py:121-122
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -80,6 +81,151 @@ def gather_normalize(src, idx, lut, n_out=None, dtype=torch.float32, channels_la
     call("scnattn_u8_gather_normalize", stream_of(src), ptr(src), N, ptr(idx), n_out, Cn, H * W, ptr(lut), ptr(out),
          int(dtype == torch.bfloat16), int(bool(channels_last)))
     return out
+
+
+# ---- raw images -> the rows above: `scipy.misc.imresize(img, size)` of inference.py:33-38 and utils/dataset.py:368-373 ----
+@functools.lru_cache(maxsize=1024)
+def resize_taps(in_size, out_size):
+    """Pillow's bilinear coefficient table of one axis (`precompute_coeffs` + `normalize_coeffs_8bpc`), the same
+    float64 operations in the same order, in numpy so that no compiler contracts a multiply-add:
+    `(xmin int32[out], n int32[out], coeff int32[out, ksize])`; output i of the 8-bit pass is
+    clip8((2^21 + sum_{k < n[i]} coeff[i, k] * in[xmin[i] + k]) >> 22).  Cached per (in, out); the arrays are read-only.
+    An axis with in == out has no pass in Pillow -- `pack_images` leaves it out, it does not apply this table."""
+    in_size, out_size = int(in_size), int(out_size)
+    if not (1 <= in_size <= RESIZE_MAX_DIM and 1 <= out_size <= RESIZE_MAX_DIM):
+        raise ValueError("resize_taps: sizes must be in [1, %d] (got %d -> %d)" % (RESIZE_MAX_DIM, in_size, out_size))
+    scale = np.float64(in_size) / np.float64(out_size)
+    filterscale = max(scale, np.float64(1.0))
+    support = np.float64(1.0) * filterscale                 # the bilinear filter's support is 1
+    ksize = int(np.ceil(support)) * 2 + 1
+    ss = np.float64(1.0) / filterscale
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size)
+    n = xmax - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    a = np.abs(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
+    w = np.where((a < 1.0) & (x < n[:, None]), 1.0 - a, 0.0)
+    ww = np.cumsum(w, axis=1)[:, -1:]                       # Pillow adds the weights one by one, left to right
+    w = np.divide(w, ww, out=w.copy(), where=ww != 0.0)
+    coeff = np.trunc(0.5 + w * np.float64(1 << 22)).astype(np.int32)
+    out = (xmin.astype(np.int32), n.astype(np.int32), coeff)
+    for arr in out:
+        arr.setflags(write=False)
+    return out
+
+
+class PackedImages:
+    """A batch of decoded images in ONE pinned byte buffer -- descriptors, then the tap tables, then the pixels -- so
+    that the batch is one host-to-device copy.  `desc` (ctypes array of `ImageDesc`) and `taps` (int32) are views of it."""
+
+    def __init__(self, buffer, n, size, desc_bytes, taps_len, src_off):
+        self.buffer, self.n, self.size = buffer, n, size
+        self.taps_off, self.taps_len, self.src_off = desc_bytes, taps_len, src_off
+        self.src_bytes = buffer.numel() - src_off
+        raw = buffer.numpy()
+        self.desc = (ImageDesc * n).from_buffer(raw[:desc_bytes])
+        self.taps = raw[desc_bytes:desc_bytes + 4 * taps_len].view(np.int32)
+
+
+def pack_images(images, size=(256, 256)):
+    """images: numpy uint8 arrays, each H x W x 3 or H x W (grey), as a decoder hands them over; size: (OH, OW).
+    Returns the `PackedImages` `resize_u8` / `resize_normalize` upload: per image a descriptor (byte offset, H, W, C,
+    the offsets of its two axis tables), one table per distinct (in, out) pair of the batch (none for an axis that
+    keeps its size), and the pixels, each image 16-byte aligned."""
+    OH, OW = int(size[0]), int(size[1])
+    if not (1 <= OH <= RESIZE_MAX_DIM and 1 <= OW <= RESIZE_MAX_DIM):
+        raise ValueError("pack_images: target size must be in [1, %d]" % RESIZE_MAX_DIM)
+    images = list(images)
+    if not images:
+        raise ValueError("pack_images: no images")
+    tables, tab_off, taps_len = [], {}, 0
+    metas, nbytes = [], 0
+    for k, im in enumerate(images):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8:
+            raise ValueError("pack_images: image %d is not a numpy uint8 array" % k)
+        if im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] != 3):
+            raise ValueError("pack_images: image %d has shape %r; H x W or H x W x 3 is required" % (k, im.shape))
+        H, W = im.shape[:2]
+        if not (1 <= H <= RESIZE_MAX_DIM and 1 <= W <= RESIZE_MAX_DIM):
+            raise ValueError("pack_images: image %d has shape %r; sides must be in [1, %d]" % (k, im.shape, RESIZE_MAX_DIM))
+        offs = []
+        for pair in ((W, OW), (H, OH)):
+            if pair[0] != pair[1] and pair not in tab_off:
+                xmin, n, coeff = resize_taps(*pair)
+                tab_off[pair] = taps_len
+                tables += [xmin, n, coeff.ravel()]
+                taps_len += xmin.size + n.size + coeff.size
+            offs.append(tab_off.get(pair, -1))
+        metas.append((nbytes, H, W, 1 if im.ndim == 2 else im.shape[2], offs[0], offs[1]))
+        nbytes += -(-im.size // 16) * 16
+    desc_bytes = len(images) * 32
+    src_off = -(-(desc_bytes + 4 * taps_len) // 16) * 16
+    buffer = torch.empty(src_off + nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    packed = PackedImages(buffer, len(images), (OH, OW), desc_bytes, taps_len, src_off)
+    if tables:
+        np.concatenate(tables, out=packed.taps)
+    pixels = buffer.numpy()[src_off:]
+    for k, (im, m) in enumerate(zip(images, metas)):
+        packed.desc[k] = ImageDesc(*m, 0)
+        pixels[m[0]:m[0] + im.size] = im.reshape(-1)
+    return packed
+
+
+def upload_images(packed, device):
+    """The packed batch on the device: descriptors, tables and pixels in one (asynchronous) copy."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("scnattn: images are resized on an MI355X device (got %s); there is no CPU fallback" % device)
+    return packed.buffer.to(device, non_blocking=True)
+
+
+def resize_uploaded(packed, dev_buffer, lut=None, dtype=torch.float32, channels_last=False):
+    """One launch of `scnattn_u8_resize_bilinear` on `upload_images(packed, device)`: the uint8 rows (lut None) or the
+    normalised batch."""
+    require_cuda(dev_buffer, lut)
+    if dev_buffer.dtype != torch.uint8 or dev_buffer.numel() != packed.buffer.numel() or not dev_buffer.is_contiguous():
+        raise RuntimeError("resize_uploaded: dev_buffer is not the upload of this batch")
+    OH, OW = packed.size
+    if lut is None:
+        out = torch.empty((packed.n, 3, OH, OW), device=dev_buffer.device, dtype=torch.uint8)
+        kind = 0
+    else:
+        if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
+            raise RuntimeError("resize_normalize: lut must be float32 [3, 256]")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError("resize_normalize: dtype must be float32 or bfloat16")
+        out = torch.empty((packed.n, 3, OH, OW), device=dev_buffer.device, dtype=dtype,
+                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+        kind = 1 if dtype == torch.float32 else 2
+    base = dev_buffer.data_ptr()
+    call("scnattn_u8_resize_bilinear", stream_of(out), base + packed.src_off, packed.src_bytes, packed.desc, base,
+         packed.n, base + packed.taps_off, packed.taps_len, OH, OW, ptr(lut), ptr(out), kind,
+         int(bool(channels_last) and kind != 0))
+    return out
+
+
+def _resize(images, size, device, lut, dtype, channels_last):
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("scnattn: images are resized on an MI355X device (got %s); there is no CPU fallback" % device)
+    packed = images if isinstance(images, PackedImages) else pack_images(images, size)
+    return resize_uploaded(packed, upload_images(packed, device), lut, dtype, channels_last)
+
+
+def resize_u8(images, size=(256, 256), device="cuda"):
+    """`imresize(img, size).transpose(2, 0, 1)` of every image (a grey one replicated to three planes first), on the
+    device, byte for byte what Pillow gives: uint8 [N, 3, OH, OW] -- the rows utils/dataset.py:373-379 stores and
+    `gather_normalize` reads.  images: a list for `pack_images`, or its result.  One copy, one launch."""
+    return _resize(images, size, device, None, None, False)
+
+
+def resize_normalize(images, lut, size=(256, 256), dtype=torch.float32, channels_last=False):
+    """The batch the encoders consume, straight from decoded images: equals
+    `gather_normalize(resize_u8(images, size), None, lut, dtype=dtype, channels_last=channels_last)` bit for bit
+    without the uint8 rows ever being written.  lut: float32 [3, 256] on the device (`normalize_lut`)."""
+    if lut is None:
+        raise RuntimeError("resize_normalize: lut is required (normalize_lut / identity_lut)")
+    return _resize(images, size, lut.device, lut, dtype, channels_last)
 
 
 class CaptionFiles:

@@ -1,0 +1,92 @@
+"""Images in, captions out: the batched body of the reference's inference.py:81-160.
+
+Reference, per image: `read_image` (imresize to 256 x 256, transpose, / 255., Normalize), `encoder_tagger(image)`,
+`encoder_caption(image)`, `decoder.sample(beam_size, word_map, encoder_out[, tags])`, then the words through the
+reversed word map.  Here a batch of decoded images goes through one resize-and-normalise launch
+(`data.resize_normalize`), the eval-mode trunks and the batched beam search (`decoder.sample_batch`), all on the device.
+The modules are taken as given: no checkpoint loading, no file decoding, no CLI, no attention overlay.
+"""
+import numpy as np
+import torch
+
+from . import data
+from ._lib import require_cuda
+
+_SPECIAL = ("<start>", "<end>", "<pad>")        # utils/token.py; dropped from the sentence (inference.py:156-157)
+
+
+class Captioner:
+    """`captioner(images, tag_count=0)` -> one record per image:
+        tokens  the best sequence, `<start>` included, as `sample` returns it
+        words   the sequence without <start>, <end>, <pad>, through the reversed word map
+        alphas  the attention maps of the sequence for the two attention decoders, else None
+        tags    with tag_count > 0 and a tagger: (indices, values) of the largest tag scores in the order
+                `np.argsort(tags)[-tag_count:]` gives (inference.py:139-140), else None
+    encoder / tagger: modules mapping the normalised batch [N, 3, OH, OW] to (N, h, w, E) / (N, S); `size` is their
+    input size (default: the module's `input_size` attribute, else 256 x 256).  The batch is produced in the layout and
+    type a `DeviceBatchLoader` hands the same encoder: channels-last when the encoder asks for it, fp32 values
+    (`image_dtype`; the fused stem reads fp32 images in both modes).  `dtype` bf16 runs the trunks under bf16 autocast, as
+    `TrainStep` runs them; the decoder stays fp32."""
+
+    def __init__(self, encoder, decoder, word_map, tagger=None, beam_size=5, dtype=torch.float32,
+                 mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD, size=None, image_dtype=torch.float32):
+        from models.decoders.pure_attention import PureAttention
+        from models.decoders.pure_scn import PureSCN
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("Captioner: dtype must be float32 or bfloat16")
+        self.needs_tags = not isinstance(decoder, PureAttention)          # inference.py:73-74 (scn_based_model)
+        self.has_alphas = not isinstance(decoder, PureSCN)                # att_based_model
+        if self.needs_tags and tagger is None:
+            raise ValueError("Captioner: a %s decoder needs a tagger" % type(decoder).__name__)
+        for tok in _SPECIAL:
+            if tok not in word_map:
+                raise ValueError("Captioner: word_map lacks %r" % tok)
+        self.encoder, self.decoder, self.tagger = encoder, decoder, tagger
+        self.word_map, self.beam_size, self.dtype, self.image_dtype = word_map, int(beam_size), dtype, image_dtype
+        self.rev_word_map = {v: k for k, v in word_map.items()}
+        self.skip = {word_map[tok] for tok in _SPECIAL}
+        if size is None:
+            size = getattr(encoder, "input_size", (256, 256))
+        self.size = (int(size[0]), int(size[1]))
+        self.channels_last = bool(getattr(encoder, "channels_last", False))
+        p = next(decoder.parameters())
+        require_cuda(p)
+        self.device = p.device
+        lut = data.identity_lut(3) if mean is None else data.normalize_lut(mean, std)
+        self.lut = torch.from_numpy(lut).to(self.device)
+
+    def images_to_batch(self, images):
+        return data.resize_normalize(images, self.lut, size=self.size, dtype=self.image_dtype,
+                                     channels_last=self.channels_last)
+
+    @torch.no_grad()
+    def __call__(self, images, tag_count=0):
+        for m in (self.encoder, self.decoder, self.tagger):
+            if m is not None and any(c.training for c in m.modules()):      # eval() itself walks and writes every module
+                m.eval()
+        with torch.cuda.device(self.device):
+            batch = self.images_to_batch(images)
+            tags = None
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.dtype == torch.bfloat16):
+                encoder_out = self.encoder(batch)
+                if self.tagger is not None and (self.needs_tags or tag_count > 0):
+                    tags = self.tagger(batch)
+            encoder_out = encoder_out.float()
+            if tags is not None:
+                tags = tags.float()
+            if self.needs_tags:
+                results = self.decoder.sample_batch(self.beam_size, self.word_map, encoder_out, tags)
+            else:
+                results = self.decoder.sample_batch(self.beam_size, self.word_map, encoder_out)
+        tags_host = tags.cpu().numpy() if tags is not None and tag_count > 0 else None
+        records = []
+        for i, res in enumerate(results):
+            seq, alphas = res if self.has_alphas else (res, None)
+            rec = {"tokens": seq, "words": [self.rev_word_map[w] for w in seq if w not in self.skip], "alphas": alphas,
+                   "tags": None}
+            if tags_host is not None:
+                t = np.asarray(tags_host[i].flatten().tolist())            # inference.py:139
+                idx = np.argsort(t)[-tag_count:]
+                rec["tags"] = (idx, t[idx])
+            records.append(rec)
+        return records
