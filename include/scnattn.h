@@ -376,6 +376,55 @@ long scnattn_resize_table_ints(int in_size, int out_size);
 int scnattn_u8_resize_bilinear(void* stream, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
                                const scnattn_image_desc* desc_dev, int N, const int32_t* taps, long taps_len, int OH,
                                int OW, const float* lut, void* dst, int dst_kind, int channels_last);
+/* The same resize on tables of any filter (new symbols only, the version stays): scnattn.data.resize_taps(in, out,
+ * filter="lanczos") is Pillow's `lanczos_filter` (support 3, negative weights), and the launch then gives
+ * `PIL.Image.resize((OW, OH), LANCZOS)` byte for byte -- what utils/vizualize.py:26 shows under the attention maps.
+ * Pillow's 8-bit arithmetic is the same for every filter; only the tables differ.  Source, descriptors, lut and dst are
+ * as for scnattn_u8_resize_bilinear (which keeps its own table layout and ignores `reserved`, as this one does).
+ *   taps     A table of (in, out), in != out, is  ksize, xmin[out], n[out], coeff[out][ksize]  -- 1 + out * (2 + ksize)
+ *            words, tab_h / tab_v point at the header word ksize.  The row length is CARRIED, never re-derived from
+ *            (in, out): Pillow computes it as (int)ceil(support * max(in / out, 1)) * 2 + 1 in double, which an integer
+ *            formula need not reproduce for support 3.
+ *   taps_host  the host copy of taps_dev (taps_len words each).  Checked before the launch, every row of every table
+ *            the batch uses: 1 <= ksize <= 6 * SCNATTN_RESIZE_MAX_DIM + 1, 1 <= n <= ksize, xmin >= 0, xmin + n <= in,
+ *            every |coeff| < 2^23 and sum |coeff| * 255 + 2^21 < 2^31 -- so the kernel's 24-bit multiplies and 32-bit
+ *            sums are a checked precondition, not a property of one filter.  Any failure returns -1 with a message.
+ * The kernel reads taps_dev only; a device copy that disagrees with the host copy skips the image or clamps the row, it
+ * never reads out of range. */
+int scnattn_u8_resize_taps(void* stream, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
+                           const scnattn_image_desc* desc_dev, int N, const int32_t* taps_host, const int32_t* taps_dev,
+                           long taps_len, int OH, int OW, const float* lut, void* dst, int dst_kind, int channels_last);
+/* Attention overlays (new symbols only, the version stays): the per-word pictures of utils/vizualize.py:38-48.  Each
+ * h x w attention map is blown up and smoothed -- `skimage.transform.pyramid_expand(alpha, upscale, sigma)`, DEFINED here
+ * as scipy.ndimage.zoom(order=1, mode='mirror', grid_mode=True) followed by gaussian_filter(sigma, mode='reflect',
+ * truncate=4.0); both are linear and separable, so S = Mv . a . Mh^T with the operators Mv [OH][h] and Mh [OW][w] the
+ * caller builds in fp64 and uploads as fp32 (scnattn.viz.expand_operator; entries >= 0, rows sum to 1) -- and laid over
+ * a photograph with a linear grey ramp.  fp32, fixed order, one fused multiply-add per term:
+ *     U[i][X] = sum_j a[i][j] * Mh[X][j]  (j ascending),    S[Y][X] = sum_i Mv[Y][i] * U[i][X]  (i ascending);
+ * a map whose entries are all equal is returned as that value (the exact result, the rows summing to 1).
+ *   scnattn_attn_strips(OH)  strips of output rows a map is cut into; `partial` holds n_maps * strips * 2 floats
+ *            (per strip min and max of S); -1 for OH out of range.
+ *   scnattn_attn_expand   alphas [n_maps][h][w] -> S [n_maps][OH][OW] (may be NULL), lohi [n_maps][2] = {min, max} of S
+ *            (may be NULL; exact, independent of order) and `partial`, which scnattn_attn_overlay reads.
+ *   scnattn_attn_overlay  out [n_maps][OH][OW][3] uint8 from the same alphas / operators and the `partial` of
+ *            scnattn_attn_expand.  S NULL: the maps are recomputed with the same code, bit for bit; S given: the maps
+ *            scnattn_attn_expand stored are read back (the same bytes out, 4 * OH * OW bytes of memory per map more).  With {lo, hi} of map
+ *            m, norm = hi > lo ? clamp((S - lo) / (hi - lo), 0, 1) : 0 and p = img[img_index[m]][c][Y][X],
+ *                v = (1 - beta[m]) * p + (beta[m] * 255) * norm,   out = (uint8) clamp((int)(v + 0.5f), 0, 255),
+ *            every operation a separately rounded fp32 one.  img: uint8 [n_img][3][OH][OW], the rows of the resize above;
+ *            beta [n_maps] floats on the device; beta = 0 gives the photograph exactly.  img_index is validated on the
+ *            host copy before the launch, the kernel reads the device copy and clamps it.
+ * 1 <= h, w <= SCNATTN_OVERLAY_MAX_MAP, 1 <= OH, OW <= SCNATTN_OVERLAY_MAX_OUT, n_maps <= 65535, and the LDS a
+ * workgroup needs, 4 * (h * w + 16 * h + OW * w) + 48 * OW bytes (each term rounded up to 16), at most 65280.  Every
+ * refusal (a size out of range, a null pointer, an img_index out of range) returns -1 before anything is launched. */
+#define SCNATTN_OVERLAY_MAX_MAP 32
+#define SCNATTN_OVERLAY_MAX_OUT 1024
+int scnattn_attn_strips(int OH);
+int scnattn_attn_expand(void* stream, const float* alphas, int n_maps, int h, int w, const float* Mv, const float* Mh,
+                        int OH, int OW, float* S, float* lohi, float* partial);
+int scnattn_attn_overlay(void* stream, const float* alphas, int n_maps, int h, int w, const float* Mv, const float* Mh,
+                         int OH, int OW, const float* S, const float* partial, const uint8_t* img, int n_img,
+                         const int32_t* img_index_host, const int32_t* img_index_dev, const float* beta, uint8_t* out);
 /* Fused BatchNorm2d (+ residual) (+ ReLU) on channels-last maps viewed as [R = N*H*W, C] (C % 4 == 0):
  * the `bn -> relu` / `bn -> (+identity) -> relu` groups of torchvision's Bottleneck behind
  * models/encoders/caption.py:17-22.  `partial` needs scnattn_bn_workspace_floats(C) floats.

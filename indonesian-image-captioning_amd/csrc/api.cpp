@@ -604,6 +604,31 @@ int scnattn_u8_resize_bilinear(void* stream, const uint8_t* src, long src_bytes,
                               dst_kind, channels_last);
 }
 
+int scnattn_u8_resize_taps(void* stream, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
+                           const scnattn_image_desc* desc_dev, int N, const int32_t* taps_host, const int32_t* taps_dev,
+                           long taps_len, int OH, int OW, const float* lut, void* dst, int dst_kind, int channels_last) {
+    return u8_resize_taps(ST(stream), src, src_bytes, desc_host, desc_dev, N, taps_host, taps_dev, taps_len, OH, OW, lut,
+                          dst, dst_kind, channels_last);
+}
+
+int scnattn_attn_strips(int OH) {
+    const int n = attn_strips(OH);
+    if (n < 0) set_error("scnattn_attn_strips: OH outside 1..SCNATTN_OVERLAY_MAX_OUT");
+    return n;
+}
+
+int scnattn_attn_expand(void* stream, const float* alphas, int n_maps, int h, int w, const float* Mv, const float* Mh,
+                        int OH, int OW, float* S, float* lohi, float* partial) {
+    return attn_expand(ST(stream), alphas, n_maps, h, w, Mv, Mh, OH, OW, S, lohi, partial);
+}
+
+int scnattn_attn_overlay(void* stream, const float* alphas, int n_maps, int h, int w, const float* Mv, const float* Mh,
+                         int OH, int OW, const float* S, const float* partial, const uint8_t* img, int n_img,
+                         const int32_t* img_index_host, const int32_t* img_index_dev, const float* beta, uint8_t* out) {
+    return attn_overlay(ST(stream), alphas, n_maps, h, w, Mv, Mh, OH, OW, S, partial, img, n_img, img_index_host,
+                        img_index_dev, beta, out);
+}
+
 long scnattn_resize_table_ints(int in_size, int out_size) {
     const long n = resize_table_ints(in_size, out_size);
     if (n < 0) set_error("scnattn_resize_table_ints: size outside 1..SCNATTN_RESIZE_MAX_DIM");

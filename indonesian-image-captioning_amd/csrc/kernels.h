@@ -206,6 +206,18 @@ int u8_resize_bilinear(hipStream_t st, const uint8_t* src, long src_bytes, const
                        const struct scnattn_image_desc* desc_dev, int N, const int* taps, long taps_len, int OH, int OW,
                        const float* lut, void* dst, int dst_kind, int channels_last);
 long resize_table_ints(int in, int out);
+// the same kernel on tables that carry their row length in a header word (any filter; Pillow's LANCZOS), every row of
+// the host copy of the tables checked before the launch
+int u8_resize_taps(hipStream_t st, const uint8_t* src, long src_bytes, const struct scnattn_image_desc* desc_host,
+                   const struct scnattn_image_desc* desc_dev, int N, const int* taps_host, const int* taps_dev,
+                   long taps_len, int OH, int OW, const float* lut, void* dst, int dst_kind, int channels_last);
+// overlay.hip: attention maps -> separable up-sampling + Gaussian (one operator per axis) -> min/max, blend over photographs
+int attn_expand(hipStream_t st, const float* alphas, int n_maps, int h, int w, const float* Mv, const float* Mh, int OH,
+                int OW, float* S, float* lohi, float* partial);
+int attn_overlay(hipStream_t st, const float* alphas, int n_maps, int h, int w, const float* Mv, const float* Mh, int OH,
+                 int OW, const float* S, const float* partial, const uint8_t* img, int n_img, const int* idx_host,
+                 const int* idx_dev, const float* beta, uint8_t* out);
+int attn_strips(int OH);
 int pool_permute_fwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* x,
                      long sxb, long sxc, long sxh, long sxw, float* y);
 int pool_permute_bwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* dy,

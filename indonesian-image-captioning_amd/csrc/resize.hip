@@ -18,7 +18,14 @@
 // interleaved source row.  Nothing is sized by the scale factor, so a 251-tap row and a 4000-row source run the same
 // code.  The finished 8 x 64 x 3 bytes go through LDS once, so that the stores are the 16-value vector stores of
 // data.hip whatever the output layout.
+//
+// Two table layouts share the kernel.  The bilinear entry point derives a table's row length from (in, out); the
+// tap-table entry point (any filter of scnattn.data.resize_taps, Pillow's LANCZOS among them: support 3, negative
+// weights) reads it from a header word in front of each table, and its host side checks every row of the host copy of
+// the tables -- bounds, 24-bit weights, 32-bit sums -- before the launch, so the arithmetic below rests on a checked
+// precondition instead of on one filter's shape.
 #include <type_traits>
+#include <vector>
 #include "../../include/scnattn.h"
 #include "common.h"
 #include "kernels.h"
@@ -44,13 +51,16 @@ __host__ __device__ inline long axis_table_ints(int in, int out) {
 __device__ __forceinline__ int clip8(int v) { return min(max(v >> 22, 0), 255); }
 
 constexpr int ONE = 1 << 22;     // the weight 1.0
-constexpr int KREG = 7;          // horizontal tables of up to 7 taps (a shrink by up to 3) live in registers
+constexpr int KREG = 7;          // horizontal tables of up to 7 taps (a bilinear shrink by up to 3, a Lanczos up-scale)
+                                 // live in registers
+constexpr int KSIZE_MAX = 2 * 3 * SCNATTN_RESIZE_MAX_DIM + 1;      // header-word tables: support <= 3
 constexpr int WR = 32;           // input rows per chunk of the vertical weight table in LDS
 
 // The walk over the input rows [r0, r1) of one chunk by one thread: per row the horizontal pass of its (column,
 // channel), rounded to a byte, then weight x byte into the RT accumulators.  wt[r - r0][j] is the weight of input row r
 // in output row j of the tile, 0 outside that row's bounds: one broadcast LDS read per row and no branch.  Weights are
-// at most 2^22 and bytes at most 255, so the products are 24-bit multiplies (full rate, where a 32-bit one is not).
+// below 2^23 in magnitude (bilinear: at most 2^22; header-word tables: checked on the host) and bytes at most 255, so
+// the products are signed 24-bit multiplies (full rate, where a 32-bit one is not).
 // The image is a buffer of exactly its bytes: a 32-bit lane offset per tap plus a scalar row offset, range-checked by
 // the hardware on top of the clamps of the caller.
 // KH > 0: at most KH horizontal taps, weights and byte offsets in registers, the KH loads of a row independent of each
@@ -122,7 +132,9 @@ template <> struct Out<__bf16> {
 
 // T: uint8_t (planar rows, no table), float or __bf16 (through lut[3][256]); nhwc: channels-last memory.
 // `fast`: OW % 16 == 0 and dst 16-byte aligned, so every 16-value group of a row is one aligned vector store.
-template <typename T>
+// HDR: every table is led by a header word holding its row length (scnattn_u8_resize_taps); otherwise the row length
+// is the bilinear filter's (scnattn_u8_resize_bilinear).
+template <typename T, bool HDR>
 __global__ __launch_bounds__(NT) void u8_resize_kernel(const uint8_t* __restrict__ src, long src_bytes,
                                                         const scnattn_image_desc* __restrict__ desc,
                                                         const int* __restrict__ taps, long taps_len, int OH, int OW,
@@ -139,9 +151,16 @@ __global__ __launch_bounds__(NT) void u8_resize_kernel(const uint8_t* __restrict
         d.offset < 0 || d.offset + (long)H * W * C > src_bytes)
         return;
     const bool hpass = W != OW, vpass = H != OH;
-    const int ksh = axis_ksize(W, OW), ksv = axis_ksize(H, OH);
-    if ((hpass && (d.tab_h < 0 || d.tab_h + axis_table_ints(W, OW) > taps_len)) ||
-        (vpass && (d.tab_v < 0 || d.tab_v + axis_table_ints(H, OH) > taps_len)))
+    int ksh = axis_ksize(W, OW), ksv = axis_ksize(H, OH);
+    long tab_h = d.tab_h, tab_v = d.tab_v;
+    if (HDR) {
+        if ((hpass && (tab_h < 0 || tab_h >= taps_len)) || (vpass && (tab_v < 0 || tab_v >= taps_len))) return;
+        ksh = hpass ? taps[tab_h++] : 1;
+        ksv = vpass ? taps[tab_v++] : 1;
+        if (ksh < 1 || ksv < 1 || ksh > KSIZE_MAX || ksv > KSIZE_MAX) return;
+    }
+    if ((hpass && (tab_h < 0 || tab_h + (long)OW * (2 + ksh) > taps_len)) ||
+        (vpass && (tab_v < 0 || tab_v + (long)OH * (2 + ksv) > taps_len)))
         return;
     if (!std::is_same<T, uint8_t>::value) {
         for (int i = t; i < 768; i += NT) tab[i] = lut[i];
@@ -159,7 +178,7 @@ __global__ __launch_bounds__(NT) void u8_resize_kernel(const uint8_t* __restrict
     int xmin = (live && !hpass) ? x : 0, xn = 1;
     const int* kh = nullptr;
     if (hpass && live) {
-        const int* th = taps + d.tab_h;
+        const int* th = taps + tab_h;
         xmin = min(max(th[x], 0), W - 1);
         xn = min(min(max(th[OW + x], 0), ksh), W - xmin);
         kh = th + 2 * OW + (long)x * ksh;
@@ -167,7 +186,7 @@ __global__ __launch_bounds__(NT) void u8_resize_kernel(const uint8_t* __restrict
     const int one_tap = (live && !hpass) ? ONE : 0;
     // the input rows the tile needs (uniform): output row y0 + j takes rows [ymin, ymin + yn) of its table, clamped to
     // the image; without a vertical pass it is row y0 + j itself
-    const int* tv = vpass ? taps + d.tab_v : nullptr;
+    const int* tv = vpass ? taps + tab_v : nullptr;
     int rlo = H, rhi = 0;
 #pragma unroll
     for (int j = 0; j < RT; ++j) {
@@ -193,7 +212,7 @@ __global__ __launch_bounds__(NT) void u8_resize_kernel(const uint8_t* __restrict
             if (vpass) {
                 const int ymin = min(max(tv[y], 0), H - 1);
                 const int yn = min(min(max(tv[OH + y], 0), ksv), H - ymin);
-                if (r >= ymin && r < ymin + yn) w = tv[2 * OH + y * ksv + (r - ymin)];
+                if (r >= ymin && r < ymin + yn) w = tv[2 * OH + (long)y * ksv + (r - ymin)];
             } else if (r == y) {
                 w = ONE;
             }
@@ -256,43 +275,113 @@ long resize_table_ints(int in, int out) {
     return axis_table_ints(in, out);
 }
 
-int u8_resize_bilinear(hipStream_t st, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
-                       const scnattn_image_desc* desc_dev, int N, const int* taps, long taps_len, int OH, int OW,
-                       const float* lut, void* dst, int dst_kind, int channels_last) {
-    SCN_ARG(N >= 0 && N <= 65535, "u8_resize_bilinear: the batch must hold 0..65535 images");
-    SCN_ARG(OH >= 1 && OW >= 1 && OH <= SCNATTN_RESIZE_MAX_DIM && OW <= SCNATTN_RESIZE_MAX_DIM,
-            "u8_resize_bilinear: target size outside 1..SCNATTN_RESIZE_MAX_DIM");
-    SCN_ARG(dst_kind >= 0 && dst_kind <= 2, "u8_resize_bilinear: dst_kind must be 0 (uint8), 1 (fp32) or 2 (bf16)");
-    SCN_ARG(dst_kind != 0 || !channels_last, "u8_resize_bilinear: the uint8 rows are planar");
+namespace {
+
+#define RS_ARG(cond, msg)                                                                            \
+    do {                                                                                             \
+        if (!(cond)) {                                                                               \
+            scn::set_error("%s:%d: invalid argument: %s: %s", __FILE__, __LINE__, name, msg);        \
+            return -1;                                                                               \
+        }                                                                                            \
+    } while (0)
+
+// One table of the header-word layout, on the host copy: header, extent, then every row's bounds and magnitudes.
+int check_table(const char* name, const int* taps, long taps_len, long off, int in, int out, bool vertical) {
+    const char* past = vertical ? "a vertical tap table runs past the tap buffer"
+                                : "a horizontal tap table runs past the tap buffer";
+    RS_ARG(off >= 0 && off < taps_len, past);
+    const long ks = taps[off];
+    RS_ARG(ks >= 1 && ks <= KSIZE_MAX, "a table's row length (its header word) is outside 1..6 * SCNATTN_RESIZE_MAX_DIM + 1");
+    RS_ARG((long)out * (2 + ks) <= taps_len - off - 1, past);
+    const int *xmin = taps + off + 1, *n = xmin + out, *coeff = n + out;
+    for (int i = 0; i < out; ++i) {
+        RS_ARG(n[i] >= 1 && n[i] <= ks, "a table row's tap count n is outside 1..ksize");
+        RS_ARG(xmin[i] >= 0 && (long)xmin[i] + n[i] <= in, "a table row's taps leave the source axis");
+        long sum = 0;
+        for (int k = 0; k < n[i]; ++k) {
+            const long c = coeff[i * ks + k], a = c < 0 ? -c : c;
+            RS_ARG(a < (1L << 23), "a coefficient does not fit the 24-bit multiply (|coeff| >= 2^23)");
+            sum += a;
+        }
+        RS_ARG(sum * 255 + (1L << 21) < (1L << 31), "a row's sum of |coeff| * 255 + 2^21 does not fit 32 bits");
+    }
+    return 0;
+}
+
+// hdr false: the bilinear layout (row length derived from (in, out), tables range-checked only, taps_host unused); hdr
+// true: the header-word layout, every distinct table of the batch checked row by row on the host copy taps_host.
+int resize_launch(const char* name, hipStream_t st, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
+                  const scnattn_image_desc* desc_dev, int N, bool hdr, const int* taps_host, const int* taps, long taps_len,
+                  int OH, int OW, const float* lut, void* dst, int dst_kind, int channels_last) {
+    RS_ARG(N >= 0 && N <= 65535, "the batch must hold 0..65535 images");
+    RS_ARG(OH >= 1 && OW >= 1 && OH <= SCNATTN_RESIZE_MAX_DIM && OW <= SCNATTN_RESIZE_MAX_DIM,
+           "target size outside 1..SCNATTN_RESIZE_MAX_DIM");
+    RS_ARG(dst_kind >= 0 && dst_kind <= 2, "dst_kind must be 0 (uint8), 1 (fp32) or 2 (bf16)");
+    RS_ARG(dst_kind != 0 || !channels_last, "the uint8 rows are planar");
     if (N == 0) return 0;
-    SCN_ARG(src && desc_host && desc_dev && dst && (lut || dst_kind == 0), "u8_resize_bilinear: null pointer");
-    SCN_ARG(src_bytes > 0 && taps_len >= 0 && taps_len < (1L << 31) && (taps || taps_len == 0),
-            "u8_resize_bilinear: bad buffer length");
+    RS_ARG(src && desc_host && desc_dev && dst && (lut || dst_kind == 0), "null pointer");
+    RS_ARG(src_bytes > 0 && taps_len >= 0 && taps_len < (1L << 31) && (taps || taps_len == 0) &&
+               (!hdr || taps_host || taps_len == 0),
+           "bad buffer length");
+    struct Seen { long off; int in, out; };
+    std::vector<Seen> seen;      // header-word tables already checked
     for (int i = 0; i < N; ++i) {
         const scnattn_image_desc& d = desc_host[i];
-        SCN_ARG(d.C == 1 || d.C == 3, "u8_resize_bilinear: an image must have 1 or 3 channels");
-        SCN_ARG(d.H >= 1 && d.W >= 1 && d.H <= SCNATTN_RESIZE_MAX_DIM && d.W <= SCNATTN_RESIZE_MAX_DIM,
-                "u8_resize_bilinear: image size outside 1..SCNATTN_RESIZE_MAX_DIM");
-        SCN_ARG(d.offset >= 0 && d.offset <= src_bytes && (long)d.H * d.W * d.C <= src_bytes - d.offset,
-                "u8_resize_bilinear: an image runs past the packed buffer");
-        SCN_ARG(d.W == OW || (d.tab_h >= 0 && d.tab_h + axis_table_ints(d.W, OW) <= taps_len),
-                "u8_resize_bilinear: a horizontal tap table runs past the tap buffer");
-        SCN_ARG(d.H == OH || (d.tab_v >= 0 && d.tab_v + axis_table_ints(d.H, OH) <= taps_len),
-                "u8_resize_bilinear: a vertical tap table runs past the tap buffer");
+        RS_ARG(d.C == 1 || d.C == 3, "an image must have 1 or 3 channels");
+        RS_ARG(d.H >= 1 && d.W >= 1 && d.H <= SCNATTN_RESIZE_MAX_DIM && d.W <= SCNATTN_RESIZE_MAX_DIM,
+               "image size outside 1..SCNATTN_RESIZE_MAX_DIM");
+        RS_ARG(d.offset >= 0 && d.offset <= src_bytes && (long)d.H * d.W * d.C <= src_bytes - d.offset,
+               "an image runs past the packed buffer");
+        if (!hdr) {
+            RS_ARG(d.W == OW || (d.tab_h >= 0 && d.tab_h + axis_table_ints(d.W, OW) <= taps_len),
+                   "a horizontal tap table runs past the tap buffer");
+            RS_ARG(d.H == OH || (d.tab_v >= 0 && d.tab_v + axis_table_ints(d.H, OH) <= taps_len),
+                   "a vertical tap table runs past the tap buffer");
+            continue;
+        }
+        for (int v = 0; v < 2; ++v) {
+            const int in = v ? d.H : d.W, out = v ? OH : OW;
+            const long off = v ? d.tab_v : d.tab_h;
+            if (in == out) continue;
+            bool done = false;
+            for (const Seen& q : seen) done = done || (q.off == off && q.in == in && q.out == out);
+            if (done) continue;
+            SCN_TRY(check_table(name, taps_host, taps_len, off, in, out, v != 0));
+            seen.push_back({off, in, out});
+        }
     }
     const int fast = OW % 16 == 0 && aligned16(dst);
     const dim3 grid(cdiv(OW, CT), cdiv(OH, RT), N);
-    if (dst_kind == 0)
-        hipLaunchKernelGGL((u8_resize_kernel<uint8_t>), grid, dim3(NT), 0, st, src, src_bytes, desc_dev, taps, taps_len,
-                           OH, OW, lut, (uint8_t*)dst, 0, fast);
-    else if (dst_kind == 1)
-        hipLaunchKernelGGL((u8_resize_kernel<float>), grid, dim3(NT), 0, st, src, src_bytes, desc_dev, taps, taps_len, OH,
-                           OW, lut, (float*)dst, channels_last, fast);
-    else
-        hipLaunchKernelGGL((u8_resize_kernel<__bf16>), grid, dim3(NT), 0, st, src, src_bytes, desc_dev, taps, taps_len,
-                           OH, OW, lut, (__bf16*)dst, channels_last, fast);
+#define RS_LAUNCH(T, HDR, cl)                                                                                            \
+    hipLaunchKernelGGL((u8_resize_kernel<T, HDR>), grid, dim3(NT), 0, st, src, src_bytes, desc_dev, taps, taps_len, OH, OW, \
+                       lut, (T*)dst, cl, fast)
+    if (dst_kind == 0) {
+        if (hdr) RS_LAUNCH(uint8_t, true, 0); else RS_LAUNCH(uint8_t, false, 0);
+    } else if (dst_kind == 1) {
+        if (hdr) RS_LAUNCH(float, true, channels_last); else RS_LAUNCH(float, false, channels_last);
+    } else {
+        if (hdr) RS_LAUNCH(__bf16, true, channels_last); else RS_LAUNCH(__bf16, false, channels_last);
+    }
+#undef RS_LAUNCH
     SCN_LAUNCH_CHECK();
     return 0;
+}
+#undef RS_ARG
+
+}  // namespace
+
+int u8_resize_bilinear(hipStream_t st, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
+                       const scnattn_image_desc* desc_dev, int N, const int* taps, long taps_len, int OH, int OW,
+                       const float* lut, void* dst, int dst_kind, int channels_last) {
+    return resize_launch("u8_resize_bilinear", st, src, src_bytes, desc_host, desc_dev, N, false, nullptr, taps, taps_len,
+                         OH, OW, lut, dst, dst_kind, channels_last);
+}
+
+int u8_resize_taps(hipStream_t st, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
+                   const scnattn_image_desc* desc_dev, int N, const int* taps_host, const int* taps_dev, long taps_len,
+                   int OH, int OW, const float* lut, void* dst, int dst_kind, int channels_last) {
+    return resize_launch("u8_resize_taps", st, src, src_bytes, desc_host, desc_dev, N, true, taps_host, taps_dev, taps_len,
+                         OH, OW, lut, dst, dst_kind, channels_last);
 }
 
 }  // namespace scn

@@ -157,6 +157,10 @@ _SIGS = {
     "scnattn_u8_gather_normalize": ([vp, vp, i64, vp, i64, i32, i64, vp, vp, i32, i32], i32),
     "scnattn_resize_table_ints": ([i32, i32], i64),
     "scnattn_u8_resize_bilinear": ([vp, vp, i64, vp, vp, i32, vp, i64, i32, i32, vp, vp, i32, i32], i32),
+    "scnattn_u8_resize_taps": ([vp, vp, i64, vp, vp, i32, vp, vp, i64, i32, i32, vp, vp, i32, i32], i32),
+    "scnattn_attn_strips": ([i32], i32),
+    "scnattn_attn_expand": ([vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp], i32),
+    "scnattn_attn_overlay": ([vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp], i32),
     "scnattn_bn_workspace_floats": ([i32], i32),
     "scnattn_bn_stats": ([vp, i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp], i32),
     "scnattn_bn_apply": ([vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp], i32),
@@ -174,6 +178,7 @@ _SIGS = {
 BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
 MAX_BEAM = 8
 RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM
+OVERLAY_MAX_MAP, OVERLAY_MAX_OUT = 32, 1024      # SCNATTN_OVERLAY_MAX_MAP, SCNATTN_OVERLAY_MAX_OUT
 
 EXPORTS = tuple(_SIGS) + ("scnattn_last_error",)
 

@@ -21,6 +21,7 @@ The arithmetic is bit-identical to the reference's (table lookup of its own per-
 """
 import functools
 import json
+import math
 import os
 import queue
 import threading
@@ -84,19 +85,37 @@ def gather_normalize(src, idx, lut, n_out=None, dtype=torch.float32, channels_la
 
 
 # ---- raw images -> the rows above: `scipy.misc.imresize(img, size)` of inference.py:33-38 and utils/dataset.py:368-373 ----
-@functools.lru_cache(maxsize=1024)
-def resize_taps(in_size, out_size):
-    """Pillow's bilinear coefficient table of one axis (`precompute_coeffs` + `normalize_coeffs_8bpc`), the same
-    float64 operations in the same order, in numpy so that no compiler contracts a multiply-add:
+FILTERS = ("bilinear", "lanczos")
+_libm_sin = np.frompyfunc(math.sin, 1, 1)      # Pillow calls libm's sin; numpy's own may differ in the last bit
+
+
+def _sinc(x):                                   # Pillow's sinc_filter: 1 at 0, else sin(x * pi) / (x * pi)
+    xp = x * np.float64(math.pi)
+    s = _libm_sin(xp).astype(np.float64)
+    return np.divide(s, xp, out=np.ones_like(xp), where=x != 0.0)
+
+
+def resize_taps(in_size, out_size, filter="bilinear"):
+    """Pillow's coefficient table of one axis (`precompute_coeffs` + `normalize_coeffs_8bpc`), the same float64
+    operations in the same order, in numpy so that no compiler contracts a multiply-add:
     `(xmin int32[out], n int32[out], coeff int32[out, ksize])`; output i of the 8-bit pass is
-    clip8((2^21 + sum_{k < n[i]} coeff[i, k] * in[xmin[i] + k]) >> 22).  Cached per (in, out); the arrays are read-only.
-    An axis with in == out has no pass in Pillow -- `pack_images` leaves it out, it does not apply this table."""
-    in_size, out_size = int(in_size), int(out_size)
+    clip8((2^21 + sum_{k < n[i]} coeff[i, k] * in[xmin[i] + k]) >> 22).  filter: "bilinear" (`bilinear_filter`, support
+    1, ksize = 2 * ceil(max(in / out, 1)) + 1) or "lanczos" (`lanczos_filter`, support 3, negative weights, ksize =
+    2 * ceil(3 * max(in / out, 1)) + 1 evaluated in double as Pillow does).  Cached per (in, out, filter); the arrays
+    are read-only.  An axis with in == out has no pass in Pillow -- `pack_images` leaves it out, it does not apply this
+    table."""
+    return _resize_taps(int(in_size), int(out_size), filter)
+
+
+@functools.lru_cache(maxsize=1024)
+def _resize_taps(in_size, out_size, filter):
+    if filter not in FILTERS:
+        raise ValueError("resize_taps: filter must be one of %r (got %r)" % (FILTERS, filter))
     if not (1 <= in_size <= RESIZE_MAX_DIM and 1 <= out_size <= RESIZE_MAX_DIM):
         raise ValueError("resize_taps: sizes must be in [1, %d] (got %d -> %d)" % (RESIZE_MAX_DIM, in_size, out_size))
     scale = np.float64(in_size) / np.float64(out_size)
     filterscale = max(scale, np.float64(1.0))
-    support = np.float64(1.0) * filterscale                 # the bilinear filter's support is 1
+    support = np.float64(1.0 if filter == "bilinear" else 3.0) * filterscale
     ksize = int(np.ceil(support)) * 2 + 1
     ss = np.float64(1.0) / filterscale
     center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
@@ -104,11 +123,16 @@ def resize_taps(in_size, out_size):
     xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size)
     n = xmax - xmin
     x = np.arange(ksize, dtype=np.int64)[None, :]
-    a = np.abs(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss)
-    w = np.where((a < 1.0) & (x < n[:, None]), 1.0 - a, 0.0)
+    a = ((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss
+    if filter == "bilinear":
+        a = np.abs(a)
+        w = np.where((a < 1.0) & (x < n[:, None]), 1.0 - a, 0.0)
+    else:
+        w = np.where((a >= -3.0) & (a < 3.0) & (x < n[:, None]), _sinc(a) * _sinc(a / np.float64(3.0)), 0.0)
     ww = np.cumsum(w, axis=1)[:, -1:]                       # Pillow adds the weights one by one, left to right
     w = np.divide(w, ww, out=w.copy(), where=ww != 0.0)
-    coeff = np.trunc(0.5 + w * np.float64(1 << 22)).astype(np.int32)
+    w = w * np.float64(1 << 22)
+    coeff = np.trunc(np.where(w < 0, -0.5, 0.5) + w).astype(np.int32)      # a negative weight rounds with -0.5
     out = (xmin.astype(np.int32), n.astype(np.int32), coeff)
     for arr in out:
         arr.setflags(write=False)
@@ -119,8 +143,8 @@ class PackedImages:
     """A batch of decoded images in ONE pinned byte buffer -- descriptors, then the tap tables, then the pixels -- so
     that the batch is one host-to-device copy.  `desc` (ctypes array of `ImageDesc`) and `taps` (int32) are views of it."""
 
-    def __init__(self, buffer, n, size, desc_bytes, taps_len, src_off):
-        self.buffer, self.n, self.size = buffer, n, size
+    def __init__(self, buffer, n, size, desc_bytes, taps_len, src_off, filter="bilinear"):
+        self.buffer, self.n, self.size, self.filter = buffer, n, size, filter
         self.taps_off, self.taps_len, self.src_off = desc_bytes, taps_len, src_off
         self.src_bytes = buffer.numel() - src_off
         raw = buffer.numpy()
@@ -128,12 +152,16 @@ class PackedImages:
         self.taps = raw[desc_bytes:desc_bytes + 4 * taps_len].view(np.int32)
 
 
-def pack_images(images, size=(256, 256)):
+def pack_images(images, size=(256, 256), filter="bilinear"):
     """images: numpy uint8 arrays, each H x W x 3 or H x W (grey), as a decoder hands them over; size: (OH, OW).
     Returns the `PackedImages` `resize_u8` / `resize_normalize` upload: per image a descriptor (byte offset, H, W, C,
     the offsets of its two axis tables), one table per distinct (in, out) pair of the batch (none for an axis that
-    keeps its size), and the pixels, each image 16-byte aligned."""
+    keeps its size), and the pixels, each image 16-byte aligned.  filter "bilinear": the tables of
+    `scnattn_u8_resize_bilinear`; any other filter of `resize_taps`: those of `scnattn_u8_resize_taps`, each led by a
+    header word holding its row length ksize."""
     OH, OW = int(size[0]), int(size[1])
+    if filter not in FILTERS:
+        raise ValueError("pack_images: filter must be one of %r (got %r)" % (FILTERS, filter))
     if not (1 <= OH <= RESIZE_MAX_DIM and 1 <= OW <= RESIZE_MAX_DIM):
         raise ValueError("pack_images: target size must be in [1, %d]" % RESIZE_MAX_DIM)
     images = list(images)
@@ -152,8 +180,11 @@ def pack_images(images, size=(256, 256)):
         offs = []
         for pair in ((W, OW), (H, OH)):
             if pair[0] != pair[1] and pair not in tab_off:
-                xmin, n, coeff = resize_taps(*pair)
+                xmin, n, coeff = resize_taps(*pair, filter=filter)
                 tab_off[pair] = taps_len
+                if filter != "bilinear":
+                    tables.append(np.asarray([coeff.shape[1]], np.int32))
+                    taps_len += 1
                 tables += [xmin, n, coeff.ravel()]
                 taps_len += xmin.size + n.size + coeff.size
             offs.append(tab_off.get(pair, -1))
@@ -162,7 +193,7 @@ def pack_images(images, size=(256, 256)):
     desc_bytes = len(images) * 32
     src_off = -(-(desc_bytes + 4 * taps_len) // 16) * 16
     buffer = torch.empty(src_off + nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-    packed = PackedImages(buffer, len(images), (OH, OW), desc_bytes, taps_len, src_off)
+    packed = PackedImages(buffer, len(images), (OH, OW), desc_bytes, taps_len, src_off, filter)
     if tables:
         np.concatenate(tables, out=packed.taps)
     pixels = buffer.numpy()[src_off:]
@@ -181,8 +212,8 @@ def upload_images(packed, device):
 
 
 def resize_uploaded(packed, dev_buffer, lut=None, dtype=torch.float32, channels_last=False):
-    """One launch of `scnattn_u8_resize_bilinear` on `upload_images(packed, device)`: the uint8 rows (lut None) or the
-    normalised batch."""
+    """One launch of `scnattn_u8_resize_bilinear` (`scnattn_u8_resize_taps` for a batch packed with another filter)
+    on `upload_images(packed, device)`: the uint8 rows (lut None) or the normalised batch."""
     require_cuda(dev_buffer, lut)
     if dev_buffer.dtype != torch.uint8 or dev_buffer.numel() != packed.buffer.numel() or not dev_buffer.is_contiguous():
         raise RuntimeError("resize_uploaded: dev_buffer is not the upload of this batch")
@@ -199,33 +230,39 @@ def resize_uploaded(packed, dev_buffer, lut=None, dtype=torch.float32, channels_
                           memory_format=torch.channels_last if channels_last else torch.contiguous_format)
         kind = 1 if dtype == torch.float32 else 2
     base = dev_buffer.data_ptr()
-    call("scnattn_u8_resize_bilinear", stream_of(out), base + packed.src_off, packed.src_bytes, packed.desc, base,
-         packed.n, base + packed.taps_off, packed.taps_len, OH, OW, ptr(lut), ptr(out), kind,
-         int(bool(channels_last) and kind != 0))
+    if packed.filter == "bilinear":
+        call("scnattn_u8_resize_bilinear", stream_of(out), base + packed.src_off, packed.src_bytes, packed.desc, base,
+             packed.n, base + packed.taps_off, packed.taps_len, OH, OW, ptr(lut), ptr(out), kind,
+             int(bool(channels_last) and kind != 0))
+    else:       # the tables carry their row length; the entry point checks the host copy of them before the launch
+        call("scnattn_u8_resize_taps", stream_of(out), base + packed.src_off, packed.src_bytes, packed.desc, base,
+             packed.n, packed.taps.ctypes.data, base + packed.taps_off, packed.taps_len, OH, OW, ptr(lut), ptr(out), kind,
+             int(bool(channels_last) and kind != 0))
     return out
 
 
-def _resize(images, size, device, lut, dtype, channels_last):
+def _resize(images, size, device, lut, dtype, channels_last, filter):
     if torch.device(device).type != "cuda":
         raise RuntimeError("scnattn: images are resized on an MI355X device (got %s); there is no CPU fallback" % device)
-    packed = images if isinstance(images, PackedImages) else pack_images(images, size)
+    packed = images if isinstance(images, PackedImages) else pack_images(images, size, filter)
     return resize_uploaded(packed, upload_images(packed, device), lut, dtype, channels_last)
 
 
-def resize_u8(images, size=(256, 256), device="cuda"):
+def resize_u8(images, size=(256, 256), device="cuda", filter="bilinear"):
     """`imresize(img, size).transpose(2, 0, 1)` of every image (a grey one replicated to three planes first), on the
     device, byte for byte what Pillow gives: uint8 [N, 3, OH, OW] -- the rows utils/dataset.py:373-379 stores and
-    `gather_normalize` reads.  images: a list for `pack_images`, or its result.  One copy, one launch."""
-    return _resize(images, size, device, None, None, False)
+    `gather_normalize` reads.  images: a list for `pack_images`, or its result (which carries its own filter).
+    filter "lanczos": `Image.resize(..., LANCZOS)`, what utils/vizualize.py:22 shows.  One copy, one launch."""
+    return _resize(images, size, device, None, None, False, filter)
 
 
-def resize_normalize(images, lut, size=(256, 256), dtype=torch.float32, channels_last=False):
+def resize_normalize(images, lut, size=(256, 256), dtype=torch.float32, channels_last=False, filter="bilinear"):
     """The batch the encoders consume, straight from decoded images: equals
     `gather_normalize(resize_u8(images, size), None, lut, dtype=dtype, channels_last=channels_last)` bit for bit
     without the uint8 rows ever being written.  lut: float32 [3, 256] on the device (`normalize_lut`)."""
     if lut is None:
         raise RuntimeError("resize_normalize: lut is required (normalize_lut / identity_lut)")
-    return _resize(images, size, lut.device, lut, dtype, channels_last)
+    return _resize(images, size, lut.device, lut, dtype, channels_last, filter)
 
 
 class CaptionFiles:

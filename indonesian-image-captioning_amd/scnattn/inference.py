@@ -4,24 +4,29 @@ Reference, per image: `read_image` (imresize to 256 x 256, transpose, / 255., No
 `encoder_caption(image)`, `decoder.sample(beam_size, word_map, encoder_out[, tags])`, then the words through the
 reversed word map.  Here a batch of decoded images goes through one resize-and-normalise launch
 (`data.resize_normalize`), the eval-mode trunks and the batched beam search (`decoder.sample_batch`), all on the device.
-The modules are taken as given: no checkpoint loading, no file decoding, no CLI, no attention overlay.
+With `overlays=True` the records also carry the pictures of `visualize_att` (utils/vizualize.py): per word the
+photograph under that word's smoothed attention map, made on the device by `scnattn.viz`.
+The modules are taken as given: no checkpoint loading, no file decoding, no CLI, no matplotlib figure.
 """
 import numpy as np
 import torch
 
-from . import data
+from . import data, viz
 from ._lib import require_cuda
 
 _SPECIAL = ("<start>", "<end>", "<pad>")        # utils/token.py; dropped from the sentence (inference.py:156-157)
 
 
 class Captioner:
-    """`captioner(images, tag_count=0)` -> one record per image:
+    """`captioner(images, tag_count=0, overlays=False)` -> one record per image:
         tokens  the best sequence, `<start>` included, as `sample` returns it
         words   the sequence without <start>, <end>, <pad>, through the reversed word map
         alphas  the attention maps of the sequence for the two attention decoders, else None
         tags    with tag_count > 0 and a tagger: (indices, values) of the largest tag scores in the order
                 `np.argsort(tags)[-tag_count:]` gives (inference.py:139-140), else None
+        overlays  only with overlays=True: uint8 device tensor [len(alphas), 336, 336, 3], per word the photograph
+                (Pillow LANCZOS to `overlay_size`) under the word's attention map, expanded by overlay_size / map size and
+                smoothed with `overlay_sigma` (`viz.attention_overlays`); None for a decoder without attention
     encoder / tagger: modules mapping the normalised batch [N, 3, OH, OW] to (N, h, w, E) / (N, S); `size` is their
     input size (default: the module's `input_size` attribute, else 256 x 256).  The batch is produced in the layout and
     type a `DeviceBatchLoader` hands the same encoder: channels-last when the encoder asks for it, fp32 values
@@ -29,7 +34,8 @@ class Captioner:
     `TrainStep` runs them; the decoder stays fp32."""
 
     def __init__(self, encoder, decoder, word_map, tagger=None, beam_size=5, dtype=torch.float32,
-                 mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD, size=None, image_dtype=torch.float32):
+                 mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD, size=None, image_dtype=torch.float32,
+                 overlay_size=(336, 336), overlay_sigma=8, overlay_weight=0.8):
         from models.decoders.pure_attention import PureAttention
         from models.decoders.pure_scn import PureSCN
         if dtype not in (torch.float32, torch.bfloat16):
@@ -49,6 +55,8 @@ class Captioner:
             size = getattr(encoder, "input_size", (256, 256))
         self.size = (int(size[0]), int(size[1]))
         self.channels_last = bool(getattr(encoder, "channels_last", False))
+        self.overlay_size = (int(overlay_size[0]), int(overlay_size[1]))       # utils/vizualize.py:26, 40-48
+        self.overlay_sigma, self.overlay_weight = overlay_sigma, overlay_weight
         p = next(decoder.parameters())
         require_cuda(p)
         self.device = p.device
@@ -60,7 +68,7 @@ class Captioner:
                                      channels_last=self.channels_last)
 
     @torch.no_grad()
-    def __call__(self, images, tag_count=0):
+    def __call__(self, images, tag_count=0, overlays=False):
         for m in (self.encoder, self.decoder, self.tagger):
             if m is not None and any(c.training for c in m.modules()):      # eval() itself walks and writes every module
                 m.eval()
@@ -89,4 +97,17 @@ class Captioner:
                 idx = np.argsort(t)[-tag_count:]
                 rec["tags"] = (idx, t[idx])
             records.append(rec)
+        if overlays:
+            pictures = [None] * len(records)
+            if self.has_alphas:
+                hh, ww = np.asarray(records[0]["alphas"]).shape[1:]
+                if self.overlay_size[0] % hh or self.overlay_size[0] * ww != self.overlay_size[1] * hh:
+                    raise ValueError("Captioner: overlay_size %r is not a multiple of the %d x %d attention maps"
+                                     % (self.overlay_size, hh, ww))
+                with torch.cuda.device(self.device):
+                    pictures = viz.attention_overlays(images, [r["alphas"] for r in records], size=self.overlay_size,
+                                                      upscale=self.overlay_size[0] // hh, sigma=self.overlay_sigma,
+                                                      weight=self.overlay_weight, device=self.device)
+            for rec, pic in zip(records, pictures):
+                rec["overlays"] = pic
         return records
