@@ -275,6 +275,30 @@ int scnattn_gate_bwd(void* stream, int rows, int E, const float* dz, int nslab, 
 int scnattn_transpose2d(void* stream, int R, int C, const float* in, long ldi, float* out, long ldo);
 int scnattn_colsum(void* stream, int R, int N, const float* X, long ld, float* out, float beta);
 int scnattn_mul_bcast(void* stream, int T, int B, int N, const float* x, const float* q, float* out);
+/* The sequence glue of scnattn_seq_fwd / scnattn_seq_bwd, each launcher alone.  Every entry returns -1 for a null operand or a
+ * bad shape before anything is launched, and 0 without a launch for an empty problem.
+ * gather:  out_tm[t][b][:] = table[caps[b][t]][:] (caps [B][L] int64, T <= L; a token outside [0, V) reads row 0 or V-1);
+ * scatter: dtable[v][:] += sum over the cells (b, t < decode_lengths[b]) with caps[b][t] == v of demb_tm[t][b][:], in a fixed
+ *          order; a token outside [0, V) is skipped; present [V] ints is a workspace (1 where the token occurs). */
+int scnattn_gather_rows_tm(void* stream, int B, int T, int L, int M, const int64_t* caps, const float* table, int V,
+                           float* out_tm);
+int scnattn_scatter_add_rows_tm(void* stream, int B, int T, int L, int M, const int64_t* caps, const int32_t* decode_lengths,
+                                const float* demb_tm, int V, float* dtable, int32_t* present);
+/* out_bm[b][t][:] = t < decode_lengths[b] ? hs_tm[t][b][:] * mask_bm[b][t][:] : 0 (mask_bm may be NULL: no mask);
+ * rowmask[b*T+t] = t < decode_lengths[b] (may be NULL).  hidden_from_bm is the same the other way round. */
+int scnattn_hidden_to_bm(void* stream, int B, int T, int D, const int32_t* decode_lengths, const float* hs_tm,
+                         const float* mask_bm, float* out_bm, float* rowmask);
+int scnattn_hidden_from_bm(void* stream, int B, int T, int D, const int32_t* decode_lengths, const float* dbm,
+                           const float* mask_bm, float* out_tm);
+/* out[n] = beta*out[n] + sum over the rows with rowmask[r] != 0 of X[r][n]; a masked-out row is not summed whatever it holds,
+ * and beta == 0 does not read out */
+int scnattn_colsum_masked(void* stream, int R, int N, const float* X, long ld, const float* rowmask, float* out, float beta);
+/* out[r][c] (dense [rows][N]) = sum over 1..16 slabs of slabs[s*slab_stride + r*slab_ld + c], in slab order */
+int scnattn_reduce_slabs(void* stream, int rows, int N, const float* slabs, int nslab, long slab_stride, long slab_ld,
+                         float* out);
+int scnattn_copy2d(void* stream, int R, int C, const float* in, long ldi, float* out, long ldo);
+/* x[b][p][e] += scale * v[b][e] (x dense [B][P][E], v dense [B][E]) */
+int scnattn_add_bcast_rows(void* stream, int B, int P, int E, const float* v, float scale, float* x);
 /* models/encoders/caption.py:41-43: AdaptiveAvgPool2d((Ho,Wo)) + permute(0,2,3,1); x given by strides */
 int scnattn_pool_permute_fwd(void* stream, int B, int C, int Hin, int Win, int Ho, int Wo, const float* x,
                              long sxb, long sxc, long sxh, long sxw, float* y);
@@ -287,7 +311,8 @@ int scnattn_pool_permute_bwd(void* stream, int B, int C, int Hin, int Win, int H
  * n_tokens = sum_b min(decode_lengths[b], T) (the row count of pack_padded_sequence(...).data).
  * Workspaces (kept for the backward): row_lse, row_loss [B*T], sm1 [B*P], reg_part [B]; loss [1].
  * bwd: grad_loss is the DEVICE scalar d/d loss; dscores [B,T,V] is written everywhere (0 for rows that were
- * not decoded), dalphas [B,T,P] likewise.  A target outside [0,V) makes the loss NaN instead of faulting. */
+ * not decoded), dalphas [B,T,P] likewise.  A target outside [0,V) (compared in 64 bits) makes the loss NaN instead of
+ * faulting; its row of dscores is the softmax term without a one-hot. */
 int scnattn_caption_loss_fwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
                              long ldt, const int32_t* decode_lengths, long n_tokens, const float* alphas, float alpha_c,
                              float* row_lse, float* row_loss, float* sm1, float* reg_part, float* loss);
@@ -698,7 +723,8 @@ int scnattn_dp_comm_world(const scnattn_dp_comm* comm);
 int scnattn_dp_comm_destroy(scnattn_dp_comm* comm);
 
 /* utils/optimizer.py:1-11 (element-wise clamp) fused with torch.optim.Adam's update
- * (trains/attention_scn.py:244-252); g is first scaled by gscale (1/world for data parallel). */
+ * (trains/attention_scn.py:244-252); g is first scaled by gscale (1/world for data parallel).  The clamp keeps a NaN
+ * gradient, as grad.clamp_ does: that element's m, v and p become NaN (a diverged step shows, it does not train on). */
 int scnattn_clamp_adam(void* stream, long n, float* p, const float* g, float* m, float* v, double lr,
                        double beta1, double beta2, double eps, int step, double clip, double gscale);
 

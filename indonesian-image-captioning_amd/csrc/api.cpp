@@ -538,6 +538,62 @@ int scnattn_mul_bcast(void* stream, int T, int B, int N, const float* x, const f
     return mul_bcast(ST(stream), T, B, N, x, q, out);
 }
 
+// The sequence glue of scnattn_seq_fwd / scnattn_seq_bwd, each launcher alone (csrc/misc.hip).  The launchers return 0 for an
+// empty problem before they look at anything else; these entries refuse null operands and bad shapes first, so that a
+// caller's mistake is an error whatever the sizes.
+int scnattn_gather_rows_tm(void* stream, int B, int T, int L, int M, const int64_t* caps, const float* table, int V,
+                           float* out_tm) {
+    SCN_ARG(B >= 0 && T >= 0 && M >= 0 && V > 0 && T <= L, "gather_rows_tm: bad shape");
+    SCN_ARG(caps && table && out_tm, "gather_rows_tm: null operand");
+    return gather_rows_tm(ST(stream), B, T, L, M, (const long long*)caps, table, V, out_tm);
+}
+
+int scnattn_scatter_add_rows_tm(void* stream, int B, int T, int L, int M, const int64_t* caps, const int32_t* decode_lengths,
+                                const float* demb_tm, int V, float* dtable, int32_t* present) {
+    SCN_ARG(B >= 0 && T >= 0 && M >= 0 && V > 0 && T <= L, "scatter_add_rows_tm: bad shape");
+    SCN_ARG(caps && decode_lengths && demb_tm && dtable && present, "scatter_add_rows_tm: null operand");
+    return scatter_add_rows_tm(ST(stream), B, T, L, M, (const long long*)caps, decode_lengths, demb_tm, V, dtable, present);
+}
+
+int scnattn_hidden_to_bm(void* stream, int B, int T, int D, const int32_t* decode_lengths, const float* hs_tm,
+                         const float* mask_bm, float* out_bm, float* rowmask) {
+    SCN_ARG(B >= 0 && T >= 0 && D >= 0, "hidden_to_bm: bad shape");
+    SCN_ARG(decode_lengths && hs_tm && out_bm, "hidden_to_bm: null operand");
+    return hidden_to_bm(ST(stream), B, T, D, decode_lengths, hs_tm, mask_bm, out_bm, rowmask);
+}
+
+int scnattn_hidden_from_bm(void* stream, int B, int T, int D, const int32_t* decode_lengths, const float* dbm,
+                           const float* mask_bm, float* out_tm) {
+    SCN_ARG(B >= 0 && T >= 0 && D >= 0, "hidden_from_bm: bad shape");
+    SCN_ARG(decode_lengths && dbm && out_tm, "hidden_from_bm: null operand");
+    return hidden_from_bm(ST(stream), B, T, D, decode_lengths, dbm, mask_bm, out_tm);
+}
+
+int scnattn_colsum_masked(void* stream, int R, int N, const float* X, long ld, const float* rowmask, float* out, float beta) {
+    SCN_ARG(R >= 0 && N >= 0 && ld >= N, "colsum_masked: bad shape");
+    SCN_ARG(X && rowmask && out, "colsum_masked: null operand");
+    return colsum_masked(ST(stream), R, N, X, ld, rowmask, out, beta);
+}
+
+int scnattn_reduce_slabs(void* stream, int rows, int N, const float* slabs, int nslab, long slab_stride, long slab_ld,
+                         float* out) {
+    SCN_ARG(rows >= 0 && N >= 0 && nslab >= 1 && nslab <= 16 && slab_ld >= N, "reduce_slabs: bad shape (1 to 16 slabs)");
+    SCN_ARG(slabs && out, "reduce_slabs: null operand");
+    return reduce_slabs(ST(stream), rows, N, Slabs{slabs, nslab, slab_stride, slab_ld}, out);
+}
+
+int scnattn_copy2d(void* stream, int R, int C, const float* in, long ldi, float* out, long ldo) {
+    SCN_ARG(R >= 0 && C >= 0 && ldi >= C && ldo >= C, "copy2d: bad shape");
+    SCN_ARG(in && out, "copy2d: null operand");
+    return copy2d(ST(stream), R, C, in, ldi, out, ldo);
+}
+
+int scnattn_add_bcast_rows(void* stream, int B, int P, int E, const float* v, float scale, float* x) {
+    SCN_ARG(B >= 0 && P > 0 && E > 0, "add_bcast_rows: bad shape");
+    SCN_ARG(v && x, "add_bcast_rows: null operand");
+    return add_bcast_rows(ST(stream), B, P, E, v, scale, x);
+}
+
 int scnattn_pool_permute_fwd(void* stream, int B, int C, int Hin, int Win, int Ho, int Wo, const float* x,
                              long sxb, long sxc, long sxh, long sxw, float* y) {
     return pool_permute_fwd(ST(stream), B, C, Hin, Win, Ho, Wo, x, sxb, sxc, sxh, sxw, y);

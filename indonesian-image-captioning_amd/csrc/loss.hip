@@ -139,7 +139,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(int T, int V, const float* 
     const float* x = scores + (long)r * V;
     const float lse = on ? row_lse[r] : 0.f;
     const float g = on ? gout[0] * inv_n : 0.f;
-    const int tg = on ? (int)targets[(long)b * ldt + t] : -1;
+    const long long tl = on ? targets[(long)b * ldt + t] : -1;
+    const int tg = (tl >= 0 && tl < V) ? (int)tl : -1;      // compared in 64 bits: 2^32 + 3 is a bad label, not label 3
     if (VEC) {
         for (int v = threadIdx.x * 4; v < V; v += 1024) {
             f32x4 o = {0.f, 0.f, 0.f, 0.f};

@@ -247,7 +247,9 @@ __global__ __launch_bounds__(256) void clamp_adam_kernel(long n, float* __restri
                                                          float clip, float gscale) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         float gi = g[i] * gscale;
-        if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
+        // comparisons, not fminf / fmaxf: their maxNum semantics turn a NaN gradient into -clip and the step goes on
+        // training; torch's clamp_ keeps the NaN and Adam then makes the parameter NaN -- diverge as loudly
+        if (clip > 0.f) gi = gi < -clip ? -clip : (gi > clip ? clip : gi);
         const float mi = b1 * m[i] + (1.f - b1) * gi;
         const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
         m[i] = mi;

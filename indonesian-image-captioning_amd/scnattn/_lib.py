@@ -144,6 +144,14 @@ _SIGS = {
     "scnattn_transpose2d": ([vp, i32, i32, vp, i64, vp, i64], i32),
     "scnattn_colsum": ([vp, i32, i32, vp, i64, vp, f32], i32),
     "scnattn_mul_bcast": ([vp, i32, i32, i32, vp, vp, vp], i32),
+    "scnattn_gather_rows_tm": ([vp, i32, i32, i32, i32, vp, vp, i32, vp], i32),
+    "scnattn_scatter_add_rows_tm": ([vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp], i32),
+    "scnattn_hidden_to_bm": ([vp, i32, i32, i32, vp, vp, vp, vp, vp], i32),
+    "scnattn_hidden_from_bm": ([vp, i32, i32, i32, vp, vp, vp, vp], i32),
+    "scnattn_colsum_masked": ([vp, i32, i32, vp, i64, vp, vp, f32], i32),
+    "scnattn_reduce_slabs": ([vp, i32, i32, vp, i32, i64, i64, vp], i32),
+    "scnattn_copy2d": ([vp, i32, i32, vp, i64, vp, i64], i32),
+    "scnattn_add_bcast_rows": ([vp, i32, i32, i32, vp, f32, vp], i32),
     "scnattn_pool_permute_fwd": ([vp, i32, i32, i32, i32, i32, i32, vp, i64, i64, i64, i64, vp], i32),
     "scnattn_pool_permute_bwd": ([vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, i64, i64, i64], i32),
     "scnattn_caption_loss_fwd": ([vp, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp, f32, vp, vp, vp, vp, vp], i32),

@@ -120,6 +120,28 @@ class GBuf16:
         return bool((self.flat.view(torch.int16) == SENT16).all())
 
 
+SENTI = 0x5A5AA5A5         # the sentinel of integer windows (GBufI): no token, length or flag a test uses
+
+
+class GBufI:
+    """A dense window of `n` int32 (or int64: wide=True) elements, 16 in front and behind, the sentinel everywhere (an
+    integer has no NaN) except where `vals` are given; read() proves the margins intact."""
+
+    def __init__(self, dev, n, vals=None, wide=False):
+        self.n, self.dtype = int(n), torch.int64 if wide else torch.int32
+        host = torch.full((self.n + 32,), SENTI, dtype=self.dtype)
+        if vals is not None:
+            host[16:16 + self.n] = vals.reshape(-1).to(self.dtype)
+        self.flat = host.to(dev)
+        self.ptr = C.c_void_p(self.flat.data_ptr() + (8 if wide else 4) * 16)
+
+    def read(self, what):
+        host = self.flat.cpu()
+        assert bool((host[:16] == SENTI).all()) and bool((host[16 + self.n:] == SENTI).all()), \
+            "%s: guard words overwritten" % what
+        return host[16:16 + self.n]
+
+
 def _call(name, dev, *args):
     from scnattn._lib import call
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
