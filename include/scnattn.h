@@ -255,6 +255,47 @@ int scnattn_attn_datt1_post_blocks(int B, int P);
 int scnattn_attn_datt1_post(void* stream, int B, int P, int A, int T, const int32_t* dl, const float* att1,
                             const float* att2_all, const float* de_all, const float* w, float* datt1,
                             float* dwpart);
+/* The same five with the streamed operand (att1 / enc) stored as bf16 (raw 16-bit elements, dimensions in elements), widened
+ * to fp32 in registers: what the sequence drivers launch under option "decoder_bf16".  Everything else stays fp32. */
+int scnattn_attn_scores_bf16(void* stream, int rows, int P, int A, const void* att1_bf16, const float* att2, int nslab,
+                             long slab_stride, long att2_ld, const float* dec_bias, const float* w, const float* b0,
+                             float* e, float* att2_out);
+int scnattn_attn_context_bf16(void* stream, int rows, int P, int E, const void* enc_bf16, const float* e,
+                              const float* gpre, int nslab, long slab_stride, long gpre_ld, const float* gate_bias,
+                              float* alpha_out, long alpha_ld, float* alpha_save, float* awe, float* gate, float* z);
+int scnattn_attn_dalpha_bf16(void* stream, int rows, int P, int E, const void* enc_bf16, const float* dawe,
+                             const float* dalpha_in, long dalpha_in_ld, float* dalpha);
+int scnattn_attn_softmax_bwd_bf16(void* stream, int rows, int P, int A, const void* att1_bf16, const float* att2,
+                                  const float* w, const float* alpha, const float* dalpha, float* de, float* datt2,
+                                  long datt2_ld);
+int scnattn_attn_datt1_post_bf16(void* stream, int B, int P, int A, int T, const int32_t* dl, const void* att1_bf16,
+                                 const float* att2_all, const float* de_all, const float* w, float* datt1,
+                                 float* dwpart);
+/* The kernels of the pooled path (scnattn_pool above), one launch each.  Every entry that takes a descriptor returns -1 for
+ * Q <= 0, qtap_max outside 1..64 or a null table before anything is launched.  bf16 != 0: x / att1 holds bf16 elements.
+ *   _attn_context_pooled      x [rows][Q][E]; alpha = softmax(e) over the P pooled pixels (alpha_out / alpha_save),
+ *                             alphaq[q] = sum_k qtap_w[q][k] * alpha[qtap_idx[q][k]] (alphaq_save [rows][Q], may be NULL),
+ *                             awe = sum_q alphaq[q] * x[q]; gate / z as scnattn_attn_context.  Any E (no multiple of 4 needed).
+ *   _attn_softmax_bwd_pooled  dalpha[p] = dalpha_in[p] (may be NULL; row stride dalpha_in_ld) +
+ *                             sum_k tap_w[p][k] * dalphaq[tap_idx[p][k]], dalphaq [rows][Q], Q <= 1024; then as
+ *                             scnattn_attn_softmax_bwd
+ *   _weighted_rows            out[b][:] = sum_q wts[q] * x[b][q][:]   (x [rows][Q][E], wts [Q])
+ *   _pool_expand              out[b][p][:] = sum_k tap_w[p][k] * y[b][tap_idx[p][k]][:] + bias[:]   (y [B][Q][A], bias may be NULL)
+ *   _pool_transpose           out[b][q][:] = sum over the live taps k of qtap_w[q][k] * in[b][qtap_idx[q][k]][:]   (in [B][P][A])
+ *   _add_bcast_rows_w         out[b][q][:] += wts[q] * v[b][:]        (out [B][Q][E], v [B][E])
+ * The last three need a width that is a multiple of 4 and 16-byte aligned operands, and return -1 otherwise. */
+int scnattn_attn_context_pooled(void* stream, int rows, int P, int E, const void* x, int bf16, const scnattn_pool* pool,
+                                const float* e, const float* gpre, int nslab, long slab_stride, long gpre_ld,
+                                const float* gate_bias, float* alpha_out, long alpha_ld, float* alpha_save,
+                                float* alphaq_save, float* awe, float* gate, float* z);
+int scnattn_attn_softmax_bwd_pooled(void* stream, int rows, int P, int A, const void* att1, int bf16, const float* att2,
+                                    const float* w, const float* alpha, const scnattn_pool* pool, const float* dalphaq,
+                                    const float* dalpha_in, long dalpha_in_ld, float* de, float* datt2, long datt2_ld);
+int scnattn_weighted_rows(void* stream, int rows, int Q, int E, const float* x, const float* wts, float* out);
+int scnattn_pool_expand(void* stream, int B, int P, int A, const scnattn_pool* pool, const float* y, const float* bias,
+                        float* out);
+int scnattn_pool_transpose(void* stream, int B, int P, int A, const scnattn_pool* pool, const float* in, float* out);
+int scnattn_add_bcast_rows_w(void* stream, int B, int Q, int E, const float* wts, const float* v, float* out);
 /* models/scn_cell.py:73-91 / 134-144 element-wise parts */
 int scnattn_scn_mix_fwd(void* stream, int rows, int F4, const float* pz, int pz_nslab, long pz_stride, long pz_ld,
                         const float* ex, const float* ph, int ph_nslab, long ph_stride, long ph_ld,

@@ -40,6 +40,15 @@ int beam_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const
 int beam_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                int end_token, int t0, int n_steps, float* ws);
 
+int pool_desc(const scnattn_pool* p, PoolDesc& out) {
+    out = PoolDesc{0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    SCN_ARG(p, "scnattn_pool: null descriptor");
+    SCN_ARG(p->Q > 0 && p->qtap_max > 0 && p->qtap_max <= 64, "scnattn_pool: bad Q / qtap_max");
+    SCN_ARG(p->tap_idx && p->tap_w && p->qtap_idx && p->qtap_w && p->col_w, "scnattn_pool: null table");
+    out = PoolDesc{p->Q, p->qtap_max, p->tap_idx, p->tap_w, p->qtap_idx, p->qtap_w, p->col_w};
+    return 0;
+}
+
 }  // namespace scn
 
 using namespace scn;
@@ -491,6 +500,79 @@ int scnattn_attn_datt1_post(void* stream, int B, int P, int A, int T, const int3
                             const float* att2_all, const float* de_all, const float* w, float* datt1,
                             float* dwpart) {
     return attn_datt1_post(ST(stream), B, P, A, T, dl, att1, att2_all, de_all, w, datt1, dwpart, nullptr);
+}
+
+// The instances the sequence drivers launch and the entries above do not reach: the streamed operand as raw bf16, and the
+// pooled forms.  Thin wrappers like the ones above; a scnattn_pool goes through the same check the drivers make.
+int scnattn_attn_scores_bf16(void* stream, int rows, int P, int A, const void* att1_bf16, const float* att2, int nslab,
+                             long slab_stride, long att2_ld, const float* dec_bias, const float* w, const float* b0,
+                             float* e, float* att2_out) {
+    return attn_scores(ST(stream), rows, P, A, att1_bf16, Slabs{att2, nslab, slab_stride, att2_ld}, dec_bias, w, b0, e,
+                       att2_out, true);
+}
+
+int scnattn_attn_context_bf16(void* stream, int rows, int P, int E, const void* enc_bf16, const float* e,
+                              const float* gpre, int nslab, long slab_stride, long gpre_ld, const float* gate_bias,
+                              float* alpha_out, long alpha_ld, float* alpha_save, float* awe, float* gate, float* z) {
+    return attn_context(ST(stream), rows, P, E, enc_bf16, e, Slabs{gpre, nslab, slab_stride, gpre_ld}, gate_bias,
+                        alpha_out, alpha_ld, alpha_save, awe, gate, z, true);
+}
+
+int scnattn_attn_dalpha_bf16(void* stream, int rows, int P, int E, const void* enc_bf16, const float* dawe,
+                             const float* dalpha_in, long dalpha_in_ld, float* dalpha) {
+    return attn_dalpha(ST(stream), rows, P, E, enc_bf16, dawe, dalpha_in, dalpha_in_ld, dalpha, true);
+}
+
+int scnattn_attn_softmax_bwd_bf16(void* stream, int rows, int P, int A, const void* att1_bf16, const float* att2,
+                                  const float* w, const float* alpha, const float* dalpha, float* de, float* datt2,
+                                  long datt2_ld) {
+    return attn_softmax_bwd(ST(stream), rows, P, A, att1_bf16, att2, w, alpha, dalpha, de, datt2, datt2_ld, true);
+}
+
+int scnattn_attn_datt1_post_bf16(void* stream, int B, int P, int A, int T, const int32_t* dl, const void* att1_bf16,
+                                 const float* att2_all, const float* de_all, const float* w, float* datt1,
+                                 float* dwpart) {
+    return attn_datt1_post(ST(stream), B, P, A, T, dl, att1_bf16, att2_all, de_all, w, datt1, dwpart, nullptr, true);
+}
+
+int scnattn_attn_context_pooled(void* stream, int rows, int P, int E, const void* x, int bf16, const scnattn_pool* pool,
+                                const float* e, const float* gpre, int nslab, long slab_stride, long gpre_ld,
+                                const float* gate_bias, float* alpha_out, long alpha_ld, float* alpha_save,
+                                float* alphaq_save, float* awe, float* gate, float* z) {
+    PoolDesc pd;
+    SCN_TRY(pool_desc(pool, pd));
+    return attn_context_pooled(ST(stream), rows, P, E, x, pd, e, Slabs{gpre, nslab, slab_stride, gpre_ld}, gate_bias,
+                               alpha_out, alpha_ld, alpha_save, alphaq_save, awe, gate, z, bf16 != 0);
+}
+
+int scnattn_attn_softmax_bwd_pooled(void* stream, int rows, int P, int A, const void* att1, int bf16, const float* att2,
+                                    const float* w, const float* alpha, const scnattn_pool* pool, const float* dalphaq,
+                                    const float* dalpha_in, long dalpha_in_ld, float* de, float* datt2, long datt2_ld) {
+    PoolDesc pd;
+    SCN_TRY(pool_desc(pool, pd));
+    return attn_softmax_bwd_pooled(ST(stream), rows, P, A, att1, att2, w, alpha, pd, dalphaq, dalpha_in, dalpha_in_ld, de,
+                                   datt2, datt2_ld, bf16 != 0);
+}
+
+int scnattn_weighted_rows(void* stream, int rows, int Q, int E, const float* x, const float* wts, float* out) {
+    return weighted_rows(ST(stream), rows, Q, E, x, wts, out);
+}
+
+int scnattn_pool_expand(void* stream, int B, int P, int A, const scnattn_pool* pool, const float* y, const float* bias,
+                        float* out) {
+    PoolDesc pd;
+    SCN_TRY(pool_desc(pool, pd));
+    return pool_expand(ST(stream), B, P, A, pd, y, bias, out);
+}
+
+int scnattn_pool_transpose(void* stream, int B, int P, int A, const scnattn_pool* pool, const float* in, float* out) {
+    PoolDesc pd;
+    SCN_TRY(pool_desc(pool, pd));
+    return pool_transpose(ST(stream), B, P, A, pd, in, out);
+}
+
+int scnattn_add_bcast_rows_w(void* stream, int B, int Q, int E, const float* wts, const float* v, float* out) {
+    return add_bcast_rows_w(ST(stream), B, Q, E, wts, v, out);
 }
 
 int scnattn_scn_mix_fwd(void* stream, int rows, int F4, const float* pz, int pz_nslab, long pz_stride, long pz_ld,

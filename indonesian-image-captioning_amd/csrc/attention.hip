@@ -790,8 +790,8 @@ __global__ __launch_bounds__(256) void add_bcast_rows_w_kernel(long n4, int Q, i
 }  // namespace
 
 int pool_expand(hipStream_t st, int B, int P, int A, const PoolDesc& pool, const float* y, const float* bias, float* out) {
-    SCN_ARG(B > 0 && P > 0 && A > 0 && A % 4 == 0 && y && out && pool.tap_idx && pool.tap_w && aligned16(y) && aligned16(out),
-            "pool_expand: bad argument (A must be a multiple of 4)");
+    SCN_ARG(B > 0 && P > 0 && A > 0 && A % 4 == 0 && y && out && pool.tap_idx && pool.tap_w && aligned16(y) && aligned16(out) &&
+                aligned16(bias), "pool_expand: bad argument (A must be a multiple of 4)");
     const long n4 = (long)B * P * (A / 4);
     hipLaunchKernelGGL(pool_expand_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, st, n4, P, pool.Q, A / 4, pool.tap_idx,
                        pool.tap_w, y, bias, out);

@@ -6,6 +6,8 @@
 
 #define SCN_MAX_KSPLIT 16
 
+struct scnattn_pool;      // include/scnattn.h
+
 namespace scn {
 
 // ---- sgemm.hip -------------------------------------------------------------------------------
@@ -80,7 +82,6 @@ int attn_context(hipStream_t st, int rows, int P, int E, const void* enc, const 
                  const float* bbeta, float* alpha_out, long alpha_ld, float* alpha_save, float* awe,
                  float* gate, float* z, bool bf = false);
 int mean_pixels(hipStream_t st, int rows, int P, int E, const float* enc, float* out);
-// dalpha[b,p] = enc[b,p,:] . dawe[b,:] + dalpha_in[b,p]
 // Pooled path (include/scnattn.h, scnattn_pool): encoder_out = fixed linear pooling of x [B][Q][E]
 struct PoolDesc {
     int Q, qtap_max;
@@ -90,6 +91,9 @@ struct PoolDesc {
     const float* qtap_w;    // [Q][qtap_max]
     const float* col_w;     // [Q]: column sums of the pooling matrix / P (pixel mean of the pooled map)
 };
+// What every taker of a scnattn_pool checks before it reads one (api.cpp): Q > 0, 0 < qtap_max <= 64, no null table.
+// The sequence drivers add what only they need (Q <= P, A % 4, E % 4: csrc/sequence.cpp check_pool).
+int pool_desc(const ::scnattn_pool* p, PoolDesc& out);
 int attn_context_pooled(hipStream_t st, int rows, int P, int E, const void* x, const PoolDesc& pool, const float* e,
                         Slabs gpre, const float* bbeta, float* alpha_out, long alpha_ld, float* alpha_save,
                         float* alphaq_save, float* awe, float* gate, float* z, bool bf = false);
@@ -100,6 +104,7 @@ int attn_softmax_bwd_pooled(hipStream_t st, int rows, int P, int A, const void* 
 int pool_expand(hipStream_t st, int B, int P, int A, const PoolDesc& pool, const float* y, const float* bias, float* out);
 int pool_transpose(hipStream_t st, int B, int P, int A, const PoolDesc& pool, const float* in, float* out);
 int add_bcast_rows_w(hipStream_t st, int B, int Q, int E, const float* wts, const float* v, float* out);
+// dalpha[b,p] = enc[b,p,:] . dawe[b,:] + dalpha_in[b,p]
 int attn_dalpha(hipStream_t st, int rows, int P, int E, const void* enc, const float* dawe,
                 const float* dalpha_in, long dalpha_in_ld, float* dalpha, bool bf = false);
 // de = alpha*(dalpha - sum(alpha*dalpha));  datt2[b,a] = w[a] * sum_p de[b,p]*[att1+att2 > 0]

@@ -198,11 +198,12 @@ int check_pool(const scnattn_dims* d, const scnattn_pool* p, PoolDesc& out) {
     out = PoolDesc{0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!p) return 0;
     // (without attention only the initial state reads encoder_out: its pixel mean becomes a weighted mean of x)
-    SCN_ARG(p->Q > 0 && p->Q <= d->P && p->qtap_max > 0 && p->qtap_max <= 64, "scnattn_pool: bad Q / qtap_max");
-    SCN_ARG(p->tap_idx && p->tap_w && p->qtap_idx && p->qtap_w && p->col_w, "scnattn_pool: null table");
+    PoolDesc pd;
+    SCN_TRY(pool_desc(p, pd));
+    SCN_ARG(p->Q <= d->P, "scnattn_pool: bad Q / qtap_max");
     SCN_ARG((!d->has_att || d->A % 4 == 0) && d->E % 4 == 0,
             "scnattn_pool: attention_dim and encoder_dim must be multiples of 4");
-    out = PoolDesc{p->Q, p->qtap_max, p->tap_idx, p->tap_w, p->qtap_idx, p->qtap_w, p->col_w};
+    out = pd;
     return 0;
 }
 

@@ -136,6 +136,19 @@ _SIGS = {
     "scnattn_attn_softmax_bwd": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64], i32),
     "scnattn_attn_datt1_post_blocks": ([i32, i32], i32),
     "scnattn_attn_datt1_post": ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp], i32),
+    "scnattn_attn_scores_bf16": ([vp, i32, i32, i32, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp], i32),
+    "scnattn_attn_context_bf16": ([vp, i32, i32, i32, vp, vp, vp, i32, i64, i64, vp, vp, i64, vp, vp, vp, vp], i32),
+    "scnattn_attn_dalpha_bf16": ([vp, i32, i32, i32, vp, vp, vp, i64, vp], i32),
+    "scnattn_attn_softmax_bwd_bf16": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64], i32),
+    "scnattn_attn_datt1_post_bf16": ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp], i32),
+    "scnattn_attn_context_pooled": ([vp, i32, i32, i32, vp, i32, C.POINTER(Pool), vp, vp, i32, i64, i64, vp, vp, i64, vp, vp,
+                                     vp, vp, vp], i32),
+    "scnattn_attn_softmax_bwd_pooled": ([vp, i32, i32, i32, vp, i32, vp, vp, vp, C.POINTER(Pool), vp, vp, i64, vp, vp,
+                                         i64], i32),
+    "scnattn_weighted_rows": ([vp, i32, i32, i32, vp, vp, vp], i32),
+    "scnattn_pool_expand": ([vp, i32, i32, i32, C.POINTER(Pool), vp, vp, vp], i32),
+    "scnattn_pool_transpose": ([vp, i32, i32, i32, C.POINTER(Pool), vp, vp], i32),
+    "scnattn_add_bcast_rows_w": ([vp, i32, i32, i32, vp, vp, vp], i32),
     "scnattn_scn_mix_fwd": ([vp, i32, i32, vp, i32, i64, i64, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp], i32),
     "scnattn_lstm_fwd": ([vp, i32, i32, vp, i32, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp], i32),
     "scnattn_lstm_bwd": ([vp, i32, i32, i32, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp], i32),

@@ -8,7 +8,8 @@ tensors it is "the same formula evaluated by torch on the CPU in fp32" that the 
 against.  For every result `x` that is a sum the dict also carries `x_abs`, the sum of the absolute values of the same
 terms (what the forward error bound of a summation is relative to), and `x_n`, the number of terms / roundings.
 
-tests/test_decoder_kernel_refs.py pins these against oracle/scnattn_ref.py (itself pinned by the golden vectors).
+tests/test_decoder_kernel_refs.py pins these against oracle/scnattn_ref.py (itself pinned by the golden vectors), and the
+references of the pooled path (scnattn_pool; tests/test_gpu_attn_variant_kernels.py) against the dense ones and autograd.
 """
 import torch
 
@@ -71,20 +72,91 @@ def attn_dalpha(enc, dawe, dalpha_in=None):
     return {"dalpha": d, "dalpha_abs": d_abs, "dalpha_n": enc.shape[-1] + 1}
 
 
-def attn_softmax_bwd(att1, att2, w, alpha, dalpha):
+def attn_softmax_bwd(att1, att2, w, alpha, dalpha, dalpha_abs=None, dalpha_n=0):
     """de = alpha * (dalpha - sum_p alpha*dalpha)   (softmax backward)
-    datt2[b,a] = w[a] * sum_p de[b,p] * [att1[b,p,a] + att2[b,a] > 0]   (through full_att and the ReLU)"""
+    datt2[b,a] = w[a] * sum_p de[b,p] * [att1[b,p,a] + att2[b,a] > 0]   (through full_att and the ReLU)
+    dalpha_abs / dalpha_n: when dalpha is itself a sum the kernel forms (the pooled form below), the sum of its |terms| and
+    the roundings it costs; they are carried into de and datt2."""
     P = alpha.shape[1]
+    if dalpha_abs is None:
+        dalpha_abs = dalpha.abs()
     dot = (alpha * dalpha).sum(1, keepdim=True)
-    dot_abs = (alpha * dalpha).abs().sum(1, keepdim=True)
+    dot_abs = (alpha.abs() * dalpha_abs).sum(1, keepdim=True)
     de = alpha * (dalpha - dot)
-    de_abs = alpha.abs() * (dalpha.abs() + dot_abs)          # |terms| of de written out as one sum of P + 1 products
+    de_abs = alpha.abs() * (dalpha_abs + dot_abs)            # |terms| of de written out as one sum of P + 1 products
     pre = att1 + att2.unsqueeze(1)
     mask = (pre > 0).to(att1.dtype)
     datt2 = w * (mask * de.unsqueeze(2)).sum(1)
     datt2_abs = w.abs() * (mask * de_abs.unsqueeze(2)).sum(1)
-    return {"de": de, "de_abs": de_abs, "de_n": P + 2, "datt2": datt2, "datt2_abs": datt2_abs, "datt2_n": 2 * P + 3,
-            "pre": pre}
+    return {"de": de, "de_abs": de_abs, "de_n": P + 2 + dalpha_n, "datt2": datt2, "datt2_abs": datt2_abs,
+            "datt2_n": 2 * P + 3 + dalpha_n, "pre": pre}
+
+
+# ---- the pooled path: encoder_out = M x, M = the fixed pooling matrix a scnattn_pool encodes (include/scnattn.h) ----
+# `pool` is anything with the tables of scnattn.functional.PoolTaps: tap_idx / tap_w [P,4] (row p of M; unused taps weight 0),
+# qtap_idx / qtap_w [Q,qmax] (column q of M; unused taps index -1).
+def _qtaps(pool, like):
+    idx = pool.qtap_idx.long().cpu()
+    live = idx >= 0
+    return idx.clamp_min(0), pool.qtap_w.cpu().to(like.dtype) * live.to(like.dtype), live
+
+
+def attn_context_pooled(x, pool, e, gpre_slabs=None, gate_bias=None):
+    """x [rows,Q,E]; e [rows,P].  alpha = softmax(e) over P; alphaq[q] = sum_k qtap_w[q][k] * alpha[qtap_idx[q][k]];
+    awe = sum_q alphaq[q] * x[q]; gate / z as attn_context."""
+    alpha = softmax_rows(e)
+    idx, qw, _ = _qtaps(pool, x)
+    alphaq = (alpha[:, idx] * qw).sum(-1)
+    awe = (x * alphaq.unsqueeze(2)).sum(1)
+    out = {"alpha": alpha, "alphaq": alphaq, "awe": awe, "gate": None, "z": awe}
+    if gpre_slabs is not None:
+        gp = gpre_slabs.sum(0)
+        if gate_bias is not None:
+            gp = gp + gate_bias
+        out["gate"] = torch.sigmoid(gp)
+        out["z"] = out["gate"] * awe
+    return out
+
+
+def attn_softmax_bwd_pooled(att1, att2, w, alpha, pool, dalphaq, dalpha_in=None):
+    """dalpha[p] = dalpha_in[p] + sum_k tap_w[p][k] * dalphaq[tap_idx[p][k]] (dalphaq [rows,Q]), then attn_softmax_bwd: the
+    |terms| of that gather go into de_abs / datt2_abs, and its 4 products + the sum with dalpha_in are 5 more roundings."""
+    t = dalphaq[:, pool.tap_idx.long().cpu()] * pool.tap_w.cpu().to(dalphaq.dtype)          # [rows,P,4]
+    d, d_abs = t.sum(-1), t.abs().sum(-1)
+    if dalpha_in is not None:
+        d, d_abs = d + dalpha_in, d_abs + dalpha_in.abs()
+    out = attn_softmax_bwd(att1, att2, w, alpha, d, d_abs, 5)
+    out["dalpha"] = d
+    return out
+
+
+def pool_expand(y, pool, bias=None):
+    """y [B,Q,A] -> out[b,p,:] = sum_k tap_w[p][k] * y[b,tap_idx[p][k],:] + bias   (M y + bias)"""
+    t = y[:, pool.tap_idx.long().cpu()] * pool.tap_w.cpu().to(y.dtype).unsqueeze(-1)        # [B,P,4,A]
+    o, o_abs, n = t.sum(2), t.abs().sum(2), 4
+    if bias is not None:
+        o, o_abs, n = o + bias, o_abs + bias.abs(), n + 1
+    return {"out": o, "out_abs": o_abs, "out_n": n}
+
+
+def pool_transpose(g, pool):
+    """g [B,P,A] -> out[b,q,:] = sum over the live taps of qtap_w[q][k] * g[b,qtap_idx[q][k],:]   (M^T g).
+    out_n is per source pixel: [Q,1], its live taps."""
+    idx, qw, live = _qtaps(pool, g)
+    t = g[:, idx] * qw.unsqueeze(-1)                                                        # [B,Q,qmax,A]
+    return {"out": t.sum(2), "out_abs": t.abs().sum(2), "out_n": live.sum(1, keepdim=True)}
+
+
+def add_bcast_rows_w(out0, wts, v):
+    """out[b,q,:] = out0[b,q,:] + wts[q] * v[b,:]"""
+    t = wts.view(1, -1, 1) * v.unsqueeze(1)
+    return {"out": out0 + t, "out_abs": out0.abs() + t.abs(), "out_n": 2}
+
+
+def weighted_rows(x, wts):
+    """out[b,:] = sum_q wts[q] * x[b,q,:]"""
+    t = x * wts.view(1, -1, 1)
+    return {"out": t.sum(1), "out_abs": t.abs().sum(1), "out_n": x.shape[1]}
 
 
 def attn_datt1_post(dl, att1, att2_all, de_all, w):

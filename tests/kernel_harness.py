@@ -1,4 +1,5 @@
-"""What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_gemm_kernels.py,
+"""What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_attn_variant_kernels.py,
+tests/test_gpu_gemm_kernels.py,
 tests/test_gpu_bn_kernels.py, tests/test_gpu_stem_kernels.py, and for the bf16 windows tests/test_gpu_eval16_kernels.py,
 tests/test_gpu_conv16_kernels.py): guarded buffers, the C-ABI call, the
 per-element sum judge and the parity-report fixture.  How a case is judged: DESIGN.md 3.
@@ -91,12 +92,13 @@ class GBuf:
 class GBuf16:
     """A [rows][cols] bf16 window with leading dimension `ld` inside a flat allocation, 64 elements in front and behind.
     Inputs: NaN everywhere outside the window (and in [cols, ld)).  Outputs (vals None, or out=True with the old values of
-    an accumulated-into window): the sentinel everywhere else."""
+    an accumulated-into window): the sentinel everywhere else.  mis offsets the base by that many elements (1: not 4-byte
+    aligned, 2: 4-byte but not 8-byte aligned)."""
 
-    def __init__(self, dev, rows, cols, ld=None, vals=None, out=False):
+    def __init__(self, dev, rows, cols, ld=None, vals=None, out=False, mis=0):
         ld = ld or cols
-        self.base, self.rows, self.cols, self.ld = 64, rows, cols, ld
-        total = 64 + (rows - 1) * ld + cols + 64
+        self.base, self.rows, self.cols, self.ld = 64 + mis, rows, cols, ld
+        total = self.base + (rows - 1) * ld + cols + 64
         if vals is None or out:
             host = torch.full((total,), SENT16, dtype=torch.int16).view(BF).clone()
         else:

@@ -738,9 +738,10 @@ def test_decoder_bf16_option_at_odd_sizes_runs_fp32(dev, mode):
 
 @pytest.mark.parametrize("hin,mis", [(8, 0), (10, 0), (8, 1), (10, 1)])
 def test_pooled_driver_instances_vs_oracle(dev, hin, mis, monkeypatch):
-    """The instances without a public entry -- attn_context_kernel<.., POOLED = true> (CU = 8 for the 8x8 map, Q = 64;
-    CU = 13 for a 10x10 map, Q = 100), attn_softmax_bwd with taps, weighted_rows (MODE 2), pool_expand / pool_transpose /
-    add_bcast_rows_w -- through the pooled sequence driver, against the fp64 oracle fed with AdaptiveAvgPool2d(14)(x).
+    """The pooled instances -- attn_context_kernel<.., POOLED = true> (CU = 8 for the 8x8 map, Q = 64; CU = 13 for a
+    10x10 map, Q = 100), attn_softmax_bwd with taps, weighted_rows (MODE 2), pool_expand / pool_transpose /
+    add_bcast_rows_w -- chained by the pooled sequence driver, against the fp64 oracle fed with AdaptiveAvgPool2d(14)(x).
+    (Each of them alone, per element, through its own entry: tests/test_gpu_attn_variant_kernels.py.)
     mis = 1: the driver is handed the un-pooled map one float off 16-byte alignment (the module layer always passes a
     fresh, aligned tensor, so the map is re-homed on the way in): the scalar forms of the same instances."""
     import torch.nn.functional as F
