@@ -491,6 +491,54 @@ int scnattn_attn_expand(void* stream, const float* alphas, int n_maps, int h, in
 int scnattn_attn_overlay(void* stream, const float* alphas, int n_maps, int h, int w, const float* Mv, const float* Mh,
                          int OH, int OW, const float* S, const float* partial, const uint8_t* img, int n_img,
                          const int32_t* img_index_host, const int32_t* img_index_dev, const float* beta, uint8_t* out);
+/* ---- caption text metrics over token ids (csrc/textmetrics.hip): what eval_caption.py:135-165 gets from NLGEval after the
+ * beam search -- Bleu_1..4, ROUGE_L, CIDEr -- and the counting half of corpus BLEU in validate() ----------------------------
+ * Inputs, all int32 on the device: hyp [N][Lh] with hyp_len [N]; ref [N][R][Lr] with ref_len [N][R], a NEGATIVE length marks
+ * an absent reference slot.  skip_hyp / skip_ref are HOST arrays of 0..4 token ids; the kernel drops those ids from the
+ * sequence (order kept) before anything else, and every length below is the length AFTER that.  Lengths read from memory are
+ * clamped to [0, padded width], so a wrong length never indexes out of bounds.  1 <= Lh, Lr <= SCNATTN_TEXT_MAX_LEN,
+ * 1 <= R <= SCNATTN_TEXT_MAX_REFS, N >= 0.  Token values are compared (and, for CIDEr-D, packed), never used as indices.
+ *   scnattn_text_ngram_stats   stats int32 [N][10], exact:
+ *        [n-1], n = 1..4   clipped matches: sum over the DISTINCT n-grams g of the hypothesis of
+ *                          min(count of g in hyp, max over the present refs of count of g in that ref);
+ *        [4 + n-1]         guesses max(0, len_hyp - n + 1);   [8] len_hyp;
+ *        [9]               the present reference length closest to len_hyp, the shorter one on a tie; 0 when no slot is present.
+ *   scnattn_text_lcs           lcs int32 [N][R]: length of the longest common subsequence of hyp and each ref (0 for an absent
+ *        slot); score fp64 [N]: with P = max_r lcs/len_hyp, Rc = max_r lcs/len_ref (terms with a zero length left out) and
+ *        beta = 1.2, (1 + beta^2) P Rc / (Rc + beta^2 P), and 0 when P or Rc is 0 (pycocoevalcap's Rouge).  mean (may be
+ *        NULL): one fp64, the mean of score[0..N) summed in a fixed order (0 for N = 0).
+ *   scnattn_text_ref_keys      keys int64 [N][R][Lr] for ONE order n in 1..4: at [i][r][j] the n-gram starting at position j of
+ *        reference r of image i, its tokens t_0..t_{n-1} packed as sum t_k << 16k -- exact, no hashing -- or the sentinel -1
+ *        where no n-gram starts there, the slot is absent, or the same n-gram stands earlier in image i's references: every
+ *        image emits each of its n-grams once, so sorting the keys and counting runs gives the document frequencies.
+ *        Tokens must lie in 0..SCNATTN_TEXT_CIDER_MAX_TOKEN (65534), which keeps 0xffff out of every field and the sentinel
+ *        apart from every real key; a token outside sets *flag (int32 on the device, cleared by the call) to 1.
+ *   scnattn_text_cider         score fp64 [N], CIDEr-D with n = 1..4, sigma = 6, x10 (pycocoevalcap's Cider).  The table: per
+ *        order n the unique keys ascending AS SIGNED int64 with their df, the four orders one after the other in table_keys /
+ *        table_df (device), order n at [table_off[n-1], table_off[n]) (table_off: HOST, 5 entries, [0] = 0).  Per order, the
+ *        weight of a distinct n-gram g of a sentence is tf(g) * (log n_images - log max(1, df(g))); with h, r the weight
+ *        vectors of the hypothesis and one reference, val_n = sum_g min(h_g, r_g) r_g, divided by |h| |r| when that is non-zero,
+ *        times exp(-(len_hyp - len_ref)^2 / (2 sigma^2)); score = 10 * (sum_n (sum_refs val_n) / 4) / (present refs), 0 when
+ *        none is present.  All of it in fp64, sums in a fixed order.  n_images = 1 gives exactly 0.  flag as above; mean as
+ *        for scnattn_text_lcs.
+ * Every refusal (a null pointer, N < 0, R or a padded width out of range, more than four skip ids, n outside 1..4, a table
+ * that is not ascending) returns -1 before anything touches the GPU. */
+#define SCNATTN_TEXT_MAX_LEN 128
+#define SCNATTN_TEXT_MAX_REFS 32
+#define SCNATTN_TEXT_CIDER_MAX_TOKEN 65534
+int scnattn_text_max_len(void);
+int scnattn_text_ngram_stats(void* stream, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref,
+                             int Lr, const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref,
+                             int n_skip_ref, int32_t* stats);
+int scnattn_text_lcs(void* stream, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref, int Lr,
+                     const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref, int n_skip_ref,
+                     int32_t* lcs, double* score, double* mean);
+int scnattn_text_ref_keys(void* stream, int n, int N, int R, const int32_t* ref, int Lr, const int32_t* ref_len,
+                          const int32_t* skip_ref, int n_skip_ref, int64_t* keys, int32_t* flag);
+int scnattn_text_cider(void* stream, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref,
+                       int Lr, const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref,
+                       int n_skip_ref, const int64_t* table_keys, const int32_t* table_df, const long* table_off, long n_images,
+                       double* score, double* mean, int32_t* flag);
 /* Fused BatchNorm2d (+ residual) (+ ReLU) on channels-last maps viewed as [R = N*H*W, C] (C % 4 == 0):
  * the `bn -> relu` / `bn -> (+identity) -> relu` groups of torchvision's Bottleneck behind
  * models/encoders/caption.py:17-22.  `partial` needs scnattn_bn_workspace_floats(C) floats.

@@ -767,6 +767,35 @@ int scnattn_attn_overlay(void* stream, const float* alphas, int n_maps, int h, i
                         img_index_dev, beta, out);
 }
 
+int scnattn_text_max_len(void) { return text_max_len(); }
+
+int scnattn_text_ngram_stats(void* stream, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref,
+                             int Lr, const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref,
+                             int n_skip_ref, int32_t* stats) {
+    return text_ngram_stats(ST(stream), N, R, hyp, Lh, hyp_len, ref, Lr, ref_len, skip_hyp, n_skip_hyp, skip_ref, n_skip_ref,
+                            stats);
+}
+
+int scnattn_text_lcs(void* stream, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref, int Lr,
+                     const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref, int n_skip_ref,
+                     int32_t* lcs, double* score, double* mean) {
+    return text_lcs(ST(stream), N, R, hyp, Lh, hyp_len, ref, Lr, ref_len, skip_hyp, n_skip_hyp, skip_ref, n_skip_ref, lcs,
+                    score, mean);
+}
+
+int scnattn_text_ref_keys(void* stream, int n, int N, int R, const int32_t* ref, int Lr, const int32_t* ref_len,
+                          const int32_t* skip_ref, int n_skip_ref, int64_t* keys, int32_t* flag) {
+    return text_ref_keys(ST(stream), n, N, R, ref, Lr, ref_len, skip_ref, n_skip_ref, keys, flag);
+}
+
+int scnattn_text_cider(void* stream, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref,
+                       int Lr, const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref,
+                       int n_skip_ref, const int64_t* table_keys, const int32_t* table_df, const long* table_off, long n_images,
+                       double* score, double* mean, int32_t* flag) {
+    return text_cider(ST(stream), N, R, hyp, Lh, hyp_len, ref, Lr, ref_len, skip_hyp, n_skip_hyp, skip_ref, n_skip_ref,
+                      table_keys, table_df, table_off, n_images, score, mean, flag);
+}
+
 long scnattn_resize_table_ints(int in_size, int out_size) {
     const long n = resize_table_ints(in_size, out_size);
     if (n < 0) set_error("scnattn_resize_table_ints: size outside 1..SCNATTN_RESIZE_MAX_DIM");

@@ -223,6 +223,20 @@ int attn_overlay(hipStream_t st, const float* alphas, int n_maps, int h, int w, 
                  int OW, const float* S, const float* partial, const uint8_t* img, int n_img, const int* idx_host,
                  const int* idx_dev, const float* beta, uint8_t* out);
 int attn_strips(int OH);
+// textmetrics.hip: caption text metrics over token ids (n-gram statistics, LCS / ROUGE-L, CIDEr-D); layouts in include/scnattn.h
+int text_max_len();
+int text_ngram_stats(hipStream_t st, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref,
+                     int Lr, const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref,
+                     int n_skip_ref, int32_t* stats);
+int text_lcs(hipStream_t st, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref, int Lr,
+             const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref, int n_skip_ref,
+             int32_t* lcs, double* score, double* mean);
+int text_ref_keys(hipStream_t st, int n, int N, int R, const int32_t* ref, int Lr, const int32_t* ref_len,
+                  const int32_t* skip_ref, int n_skip_ref, int64_t* keys, int32_t* flag);
+int text_cider(hipStream_t st, int N, int R, const int32_t* hyp, int Lh, const int32_t* hyp_len, const int32_t* ref, int Lr,
+               const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref, int n_skip_ref,
+               const int64_t* table_keys, const int32_t* table_df, const long* table_off, long n_images, double* score,
+               double* mean, int32_t* flag);
 int pool_permute_fwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* x,
                      long sxb, long sxc, long sxh, long sxw, float* y);
 int pool_permute_bwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* dy,

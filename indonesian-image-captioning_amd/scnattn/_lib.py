@@ -182,6 +182,11 @@ _SIGS = {
     "scnattn_attn_strips": ([i32], i32),
     "scnattn_attn_expand": ([vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp], i32),
     "scnattn_attn_overlay": ([vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp], i32),
+    "scnattn_text_max_len": ([], i32),
+    "scnattn_text_ngram_stats": ([vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp], i32),
+    "scnattn_text_lcs": ([vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp], i32),
+    "scnattn_text_ref_keys": ([vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp], i32),
+    "scnattn_text_cider": ([vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp], i32),
     "scnattn_bn_workspace_floats": ([i32], i32),
     "scnattn_bn_stats": ([vp, i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp], i32),
     "scnattn_bn_apply": ([vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp], i32),
@@ -200,6 +205,7 @@ BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
 MAX_BEAM = 8
 RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM
 OVERLAY_MAX_MAP, OVERLAY_MAX_OUT = 32, 1024      # SCNATTN_OVERLAY_MAX_MAP, SCNATTN_OVERLAY_MAX_OUT
+TEXT_MAX_LEN, TEXT_MAX_REFS, TEXT_CIDER_MAX_TOKEN = 128, 32, 65534      # SCNATTN_TEXT_MAX_LEN, _MAX_REFS, _CIDER_MAX_TOKEN
 
 EXPORTS = tuple(_SIGS) + ("scnattn_last_error",)
 

@@ -255,14 +255,18 @@ def topk_percent(hits, n_tokens):
     return float(int(hits[0])) * (100.0 / n_tokens)
 
 
-def validate(batches, encoder, encoder_tagger, decoder, criterion, word_map, alpha_c=1.0, fused=False):
+def validate(batches, encoder, encoder_tagger, decoder, criterion, word_map, alpha_c=1.0, fused=False, device_bleu=False):
     """The reference's validate() (trains/attention_scn.py:274-385): eval-mode forward under no_grad,
     loss / top-5 accuracy bookkeeping, references and arg-max hypotheses, corpus BLEU-4.
     `batches` yields (imgs, caps, caplens, allcaps) already on the device; `encoder_tagger` may be a
     callable returning tags or None when the batch tuple carries tags in place of images for it.
-    `fused=True`: loss, top-5 and hypotheses from one pass over the scores (_validate_fused), any of the three decoders."""
+    `fused=True`: loss, top-5 and hypotheses from one pass over the scores (_validate_fused), any of the three decoders;
+    with `device_bleu=True` as well, BLEU's n-gram counting runs on the device too and only ten integers per pass come down
+    for it (the same BLEU-4, bit for bit)."""
+    if device_bleu and not fused:
+        raise ValueError("validate: device_bleu=True needs fused=True")
     if fused:
-        return _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c)
+        return _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c, device_bleu)
     from utils.metric import AverageMeter, accuracy, corpus_bleu
     decoder.eval()
     encoder.eval()
@@ -292,19 +296,25 @@ def validate(batches, encoder, encoder_tagger, decoder, criterion, word_map, alp
     return corpus_bleu(references, hypotheses), losses.avg, top5accs.avg
 
 
-def _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c):
+def _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c, device_bleu=False):
     """validate() on SF.caption_loss_metrics: per batch the decoder's forward and one loss pass that also yields the top-5
     hit count and the arg-max tokens; no clone, no packed copies, no topk, no synchronisation of its own.  What a batch
     leaves stays on the device -- loss bits, hits and preds in one int32 vector, allcaps[sort_ind] -- and comes down in two
     copies after the last batch; the AverageMeter arithmetic is then replayed in the reference's order, so the averages are
-    formed as the eager path forms them.  The decoder's kind decides its call, as in TrainStep.step()."""
-    from utils.metric import AverageMeter, corpus_bleu
+    formed as the eager path forms them.  The decoder's kind decides its call, as in TrainStep.step().
+    device_bleu=True: preds and allcaps[sort_ind] are not downloaded at all.  Per batch scnattn.textmetrics.ngram_stats counts
+    the clipped matches on them (hypothesis length = decode_lengths, references without <start>/<pad>), the ten corpus
+    integers of utils.metric.bleu_from_totals accumulate on the device, and the one download holds them, the loss bits and the
+    hit counts; corpus_bleu ends in that same bleu_from_totals on the same integers."""
+    from utils.metric import AverageMeter, bleu_from_totals, corpus_bleu
+    from scnattn import textmetrics as TM
     decoder.eval()
     encoder.eval()
     if hasattr(encoder_tagger, "eval"):
         encoder_tagger.eval()
     skip = {word_map['<start>'], word_map['<pad>']}
     words, caps_dev, shapes = [], [], []
+    totals = None
     with torch.no_grad():
         for imgs, caps, caplens, allcaps in batches:
             encoder_out = encoder(imgs)
@@ -317,11 +327,31 @@ def _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c
                 scores, caps_sorted, decode_lengths, alphas, sort_ind = decoder(encoder_out, encoder_tagger(imgs), caps, caplens)
             dl_dev = (caplens.reshape(-1)[sort_ind] - 1).to(torch.int32)
             loss, hits, preds = SF.caption_loss_metrics(scores, caps_sorted, decode_lengths, alphas, alpha_c, dl_dev, k=5)
-            words.append(torch.cat([loss.reshape(1).view(torch.int32), hits, preds.reshape(-1)]))
             allcaps = allcaps[sort_ind]
+            if device_bleu:
+                refs = allcaps.to(torch.int32).contiguous()
+                ref_len = torch.full(refs.shape[:2], refs.shape[2], dtype=torch.int32, device=refs.device)
+                stats = TM.ngram_stats(preds.contiguous(), dl_dev.contiguous(), refs, ref_len, (), sorted(skip))
+                batch_totals = TM.nltk_totals(stats)
+                totals = batch_totals if totals is None else totals + batch_totals
+                words.append(torch.cat([loss.reshape(1).view(torch.int32), hits]))
+                shapes.append(list(decode_lengths))
+                continue
+            words.append(torch.cat([loss.reshape(1).view(torch.int32), hits, preds.reshape(-1)]))
             caps_dev.append(allcaps.reshape(-1))
             shapes.append((tuple(preds.shape), tuple(allcaps.shape), list(decode_lengths)))
     losses, top5accs = AverageMeter(), AverageMeter()
+    if device_bleu:
+        if not shapes:
+            return corpus_bleu([], []), losses.avg, top5accs.avg
+        # ten int64 as twenty int32 words behind the per-batch (loss bits, hits, hits1): one copy
+        words = torch.cat(words + [totals.view(torch.int32)]).cpu()
+        for i, decode_lengths in enumerate(shapes):
+            n = sum(decode_lengths)
+            losses.update(words[3 * i:3 * i + 1].view(torch.float32).item(), n)
+            top5accs.update(topk_percent(words[3 * i + 1:3 * i + 3], n), n)
+        tot = words[3 * len(shapes):].clone().view(torch.int64).tolist()
+        return bleu_from_totals(tot[0:4], tot[4:8], tot[8], tot[9]), losses.avg, top5accs.avg
     references, hypotheses = [], []
     if shapes:
         words, caps_host = torch.cat(words).cpu(), torch.cat(caps_dev).cpu()
@@ -340,6 +370,44 @@ def _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c
         hypotheses.extend(p[:decode_lengths[j]] for j, p in enumerate(preds))
     assert len(references) == len(hypotheses)
     return corpus_bleu(references, hypotheses), losses.avg, top5accs.avg
+
+
+def evaluate_captions(batches, encoder, encoder_tagger, decoder, word_map, beam_size=5):
+    """The reference's eval_caption.py:95-165, batched: per batch (imgs, allcaps) on the device both trunks in eval mode, the
+    batched beam search (sample_batch), then BLEU-1..4, ROUGE-L and CIDEr-D of the whole split from ONE
+    scnattn.textmetrics.CaptionScorer.score with <start>, <end> and <pad> dropped on both sides inside the kernels -- what the
+    reference strips in Python before it hands words to NLGEval.  The references never leave the device; each batch uploads
+    its hypotheses once.  Returns the scorer's dict (NLGEval's key names, plus 'bleu4_nltk'; no METEOR); writing the JSON files
+    of the reference is the caller's business."""
+    import torch.nn.functional as F
+    from scnattn import textmetrics as TM
+    decoder.eval()
+    encoder.eval()
+    if hasattr(encoder_tagger, "eval"):
+        encoder_tagger.eval()
+    special = sorted({word_map['<start>'], word_map['<end>'], word_map['<pad>']})
+    hyps, hyp_lens, refs, ref_lens = [], [], [], []
+    with torch.no_grad():
+        for imgs, allcaps in batches:
+            encoder_out = encoder(imgs)
+            if isinstance(decoder, PureAttention):
+                results = decoder.sample_batch(beam_size, word_map, encoder_out)
+            else:
+                results = decoder.sample_batch(beam_size, word_map, encoder_out, encoder_tagger(imgs))
+            seqs = [r[0] if isinstance(r, tuple) else r for r in results]
+            tok, n = TM.pack_captions(seqs, allcaps.device)
+            hyps.append(tok)
+            hyp_lens.append(n)
+            ref, n = TM.pack_references(allcaps, allcaps.device)
+            refs.append(ref)
+            ref_lens.append(n)
+    if not hyps:
+        raise ValueError("evaluate_captions: no batches")
+    Lh, Lr = max(t.shape[1] for t in hyps), max(t.shape[2] for t in refs)
+    hyp = torch.cat([F.pad(t, (0, Lh - t.shape[1])) for t in hyps])
+    ref = torch.cat([F.pad(t, (0, Lr - t.shape[2])) for t in refs])
+    scorer = TM.CaptionScorer((ref, torch.cat(ref_lens)), skip_ref=special, device=ref.device)
+    return scorer.score((hyp, torch.cat(hyp_lens)), skip_hyp=special)
 
 
 TAGGER_DEFAULTS = dict(semantic_size=1000, dropout=0.15, batch_size=32, encoder_lr=1e-4, grad_clip=5.0, image_size=256)

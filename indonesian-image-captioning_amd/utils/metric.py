@@ -59,14 +59,23 @@ def corpus_bleu(list_of_references, hypotheses, weights=(0.25, 0.25, 0.25, 0.25)
             p_den[n] += max(1, sum(counts.values()))
         hyp_len += len(hyp)
         ref_len += min((len(r) for r in refs), key=lambda rl: (abs(rl - len(hyp)), rl))
-    if p_num[1] == 0:
+    return bleu_from_totals([p_num[n] for n in range(1, len(weights) + 1)], [p_den[n] for n in range(1, len(weights) + 1)],
+                            hyp_len, ref_len, weights)
+
+
+def bleu_from_totals(p_num, p_den, hyp_len, ref_len, weights=(0.25, 0.25, 0.25, 0.25)):
+    """The tail of ``corpus_bleu``: the score from the corpus totals.  p_num[n-1] / p_den[n-1] are the clipped matches and
+    the denominators of order n summed over the corpus (each hypothesis contributing max(1, its n-gram count), as NLTK's
+    ``modified_precision`` does), hyp_len / ref_len the summed hypothesis and closest-reference lengths.  Plain ints in,
+    so the host loop above and the device counts of scnattn.textmetrics give the same bits."""
+    if p_num[0] == 0:
         return 0.0
     if hyp_len == 0:
         return 0.0
     bp = 1.0 if hyp_len > ref_len else math.exp(1 - ref_len / hyp_len)
     s = 0.0
     for n, w in enumerate(weights, start=1):
-        p = Fraction(p_num[n], p_den[n])
+        p = Fraction(p_num[n - 1], p_den[n - 1])
         if p == 0:   # NLTK (no smoothing) multiplies by a tiny epsilon-free 0 -> score 0 with a warning
             return 0.0
         s += w * math.log(p)
