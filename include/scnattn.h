@@ -788,6 +788,49 @@ int scnattn_bn_stats_fold(void* stream, int R, int C, const void* x, float eps, 
                           float* mean, float* invstd, float* run_mean, float* run_var, const float* gamma,
                           const float* beta, float* ss_out);
 
+/* ---- launch plans: what a dense product would launch, asked of the code that launches it ----------------------------------
+ * Each of the seven host launchers behind the dense-product entry points (cgemm, cgemm16, sgemm_ws, skinny_gemm,
+ * conv3x3_wgrad_halo, wgrad16_3x3, wgrad16_rows) checks its arguments, computes a plan -- a pure function of shapes, layout
+ * and alignment facts, the scnattn_conv_extra selectors, the workspace size and the options -- and launches from that plan
+ * alone.  scnattn_plan_next(out) arms the calling thread: the next call on it that reaches one of those launchers
+ * (scnattn_sgemm(_ws), _cgemm, _cgemm16, _conv1x1_*, _conv3x3_*, the four _bn_eval(16) forms, _wgrad16_*, _skinny_gemm*) runs
+ * its checks and its plan, fills *out, launches nothing, calls no HIP API, disarms and returns 0.  A refusal returns its
+ * usual error and message, an empty problem 0; both disarm with out->family == 0.  scnattn_plan_next(NULL) disarms; a second
+ * arming replaces the first.  scnattn_block16_* makes many launches per call and cannot be planned: it disarms and runs.
+ * Fields a family does not use are 0. */
+enum { SCNATTN_PLAN_NONE = 0, SCNATTN_PLAN_CGEMM, SCNATTN_PLAN_SGEMM, SCNATTN_PLAN_SKINNY, SCNATTN_PLAN_CGEMM16,
+       SCNATTN_PLAN_CONV3_WGRAD, SCNATTN_PLAN_WGRAD16_W9, SCNATTN_PLAN_WGRAD16_W1 };
+/* the launch that follows the product, if any */
+enum { SCNATTN_SECOND_NONE = 0,
+       SCNATTN_SECOND_CREDUCE,          /* creduce<vec>: sum of the slabs + the plain epilogue */
+       SCNATTN_SECOND_CSTATS1,          /* cstats<1>: slab sum + column statistics */
+       SCNATTN_SECOND_CSTATS2_SLABS,    /* cstats<2>: slab sum + mask epilogue */
+       SCNATTN_SECOND_CSTATS2_C,        /* cstats<2> on the un-split product read back from C */
+       SCNATTN_SECOND_CREDUCE16,        /* creduce16<out_bf16, second_mode>: 0 plain, 1 statistics, 2 eval BatchNorm */
+       SCNATTN_SECOND_CGEMM_REDUCE,     /* creduce<1> over the slabs of a wave-split weight gradient */
+       SCNATTN_SECOND_SPLITK_REDUCE };  /* sgemm's splitk_reduce */
+typedef struct scnattn_launch_plan {
+    int family;                 /* SCNATTN_PLAN_* */
+    int mi;                     /* cgemm / cgemm16: row tile (1: 64 rows, 2: 128 rows, 4: 128 x 64) */
+    int tA, tB;                 /* cgemm / sgemm: operand layouts as launched */
+    int pro, epi;               /* prologue / epilogue of the product KERNEL (a split product's epilogue may move to `second`) */
+    int gather, c3;             /* row gather of a strided 1x1 convolution; 3x3 mode */
+    int vec;                    /* cgemm: 16-byte C stores; sgemm: 16-byte operand loads; skinny: XVEC */
+    int out_bf16;               /* cgemm16 */
+    int wbf;                    /* skinny: 0 fp32 weights, 1 bf16 weights, 2 bf16 matrix instruction */
+    int nb, chunks, empty;      /* skinny: 8-k blocks per wave and chunk (NB), chunks per wave, empty K-slices */
+    int kslice;                 /* skinny: k per slice */
+    int seg;                    /* wave-split weight gradients: pixels per line (SEG of conv3_wgrad) */
+    int Q, ntiles;              /* wave-split weight gradients: lines, output blocks */
+    int S, kper;                /* K-slices and their length */
+    int mt, nt;                 /* cgemm / cgemm16: tile grid */
+    long tiles;                 /* output tiles (x batch) */
+    int grid_x, grid_y, grid_z;
+    int in_launch;              /* cgemm: the split product is finished inside the launch (arrival counters) */
+    int second, second_mode;    /* SCNATTN_SECOND_* */
+} scnattn_launch_plan;
+int scnattn_plan_next(scnattn_launch_plan* out);
+
 /* ---- data-parallel gradient exchange (the reference has no distributed code) ---------------------
  * One process per GPU.  RCCL SUM all-reduce of gradient buckets on a library-owned communication stream, ordered
  * against the caller's compute stream by HIP events, so a bucket's reduction overlaps the rest of the backward pass:

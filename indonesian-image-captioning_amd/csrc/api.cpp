@@ -19,6 +19,8 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
+thread_local LaunchPlan* t_plan_out = nullptr;
+
 extern int g_ksplit_scale;
 extern int g_profile;
 extern int g_attn_depth;
@@ -58,6 +60,7 @@ extern "C" {
 
 int scnattn_version(void) { return SCNATTN_VERSION; }
 const char* scnattn_last_error(void) { return last_error(); }
+int scnattn_plan_next(scnattn_launch_plan* out) { t_plan_out = out; return 0; }
 
 // Process-wide knobs.  Two kinds only (the experiment switches of rounds 1-2 -- fuse_attn, chains,
 // attn_handoff, cgemm_stagger, cgemm_w41, cgemm_vec, bn_gfirst, skinny_tail -- are gone with the code paths they selected):

@@ -84,6 +84,7 @@ int scnattn_block16_sizes(const scnattn_block16* b, long* save_elems, long* out_
 }
 
 int scnattn_block16_fwd(void* st, const scnattn_block16* b) {
+    scn::t_plan_out = nullptr;  // many launches per call: not plannable (include/scnattn.h, scnattn_plan_next)
     Carve c;
     SCN_TRY(carve(b, c));
     SCN_ARG(b->x && b->save && b->stats && b->ws && b->part && b->bnpart, "block16_fwd: null buffer");
@@ -125,6 +126,7 @@ int scnattn_block16_fwd(void* st, const scnattn_block16* b) {
 }
 
 int scnattn_block16_bwd(void* st, const scnattn_block16* b, void** dx_out, void** dxd_out) {
+    scn::t_plan_out = nullptr;  // many launches per call: not plannable (include/scnattn.h, scnattn_plan_next)
     Carve c;
     SCN_TRY(carve(b, c));
     SCN_ARG(b->x && b->save && b->stats && b->ws && b->bnpart && b->dout && b->tmp && b->dgb, "block16_bwd: null buffer");

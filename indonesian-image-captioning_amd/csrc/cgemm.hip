@@ -1071,51 +1071,150 @@ bool cgemm_supported(bool tA, bool tB, int M, int N, int K, const float* A, long
 namespace {
 
 template <int MI, bool AMC, bool BMC, int PRO, bool G>
-void launch_ev(hipStream_t st, dim3 grid, const CArgs& g, int kepi, bool vec) {
+void launch_ev(hipStream_t st, dim3 grid, const CArgs& g, const LaunchPlan& p) {
     dim3 block(256);
-    if (kepi == 2) {       // mask epilogue: the d-input products only (host-checked)
+    if (p.epi == 2) {       // mask epilogue: the d-input products only (plan-checked)
         if constexpr (!AMC && BMC && PRO == 0 && !G) hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 2, false, true>), grid, block, 0, st, g);
-    } else if (kepi == 3) {   // eval BatchNorm epilogue: forward products without a prologue only (host-checked)
+    } else if (p.epi == 3) {   // eval BatchNorm epilogue: forward products without a prologue only (plan-checked)
         if constexpr (!AMC && !BMC && PRO == 0) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 3, G, true>), grid, block, 0, st, g);
-    } else if (kepi == 1) hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 1, G, true>), grid, block, 0, st, g);
-    else if (vec)  hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 0, G, true>), grid, block, 0, st, g);
-    else           hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 0, G, false>), grid, block, 0, st, g);
+    } else if (p.epi == 1) hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 1, G, true>), grid, block, 0, st, g);
+    else if (p.vec) hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 0, G, true>), grid, block, 0, st, g);
+    else            hipLaunchKernelGGL((cgemm_kernel<MI, AMC, BMC, PRO, 0, G, false>), grid, block, 0, st, g);
 }
 
 template <int MI>
-int launch_conv3(hipStream_t st, dim3 grid, const CArgs& g, int c3, int kepi) {
+void launch_conv3(hipStream_t st, dim3 grid, const CArgs& g, const LaunchPlan& p) {
     dim3 block(256);
-    if (c3 == 1) {
-        if (kepi == 1) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 1, false, true, 1>), grid, block, 0, st, g);
-        else if (kepi == 3) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 3, false, true, 1>), grid, block, 0, st, g);
-        else           hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 0, false, true, 1>), grid, block, 0, st, g);
-    } else if (c3 == 2) {
-        if (kepi == 2) hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 2, false, true, 2>), grid, block, 0, st, g);
-        else           hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 0, false, true, 2>), grid, block, 0, st, g);
-    } else if (c3 == 4) {
+    if (p.c3 == 1) {
+        if (p.epi == 1) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 1, false, true, 1>), grid, block, 0, st, g);
+        else if (p.epi == 3) hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 3, false, true, 1>), grid, block, 0, st, g);
+        else            hipLaunchKernelGGL((cgemm_kernel<MI, false, false, 0, 0, false, true, 1>), grid, block, 0, st, g);
+    } else if (p.c3 == 2) {
+        if (p.epi == 2) hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 2, false, true, 2>), grid, block, 0, st, g);
+        else            hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 0, false, true, 2>), grid, block, 0, st, g);
+    } else if (p.c3 == 4) {
         hipLaunchKernelGGL((cgemm_kernel<MI, false, true, 0, 0, false, true, 4>), grid, block, 0, st, g);
     } else {
         hipLaunchKernelGGL((cgemm_kernel<MI, true, true, 0, 0, false, true, 3>), grid, block, 0, st, g);
     }
-    return 0;
 }
 
 template <int MI>
-int launch_layout(hipStream_t st, dim3 grid, const CArgs& g, bool tA, bool tB, int pro, int kepi, bool gather, bool vec) {
-    if (!tA && tB) {            // forward of a 1x1 convolution, nn.Linear: both k-contiguous
-        if (gather) { if (pro == 1) launch_ev<MI, false, false, 1, true>(st, grid, g, kepi, vec); else launch_ev<MI, false, false, 0, true>(st, grid, g, kepi, vec); }
-        else        { if (pro == 1) launch_ev<MI, false, false, 1, false>(st, grid, g, kepi, vec); else launch_ev<MI, false, false, 0, false>(st, grid, g, kepi, vec); }
-    } else if (!tA && !tB) {    // dgrad: A k-contiguous, B [K][N]
-        SCN_ARG(!gather && pro == 0, "cgemm: NN product takes no gather / prologue");
-        launch_ev<MI, false, true, 0, false>(st, grid, g, kepi, vec);
-    } else if (tA && !tB) {     // wgrad: A [K][M], B [K][N]
-        SCN_ARG(kepi == 0, "cgemm: TN product takes no statistics epilogue");
-        if (gather) { if (pro == 2) launch_ev<MI, true, true, 2, true>(st, grid, g, 0, vec); else launch_ev<MI, true, true, 0, true>(st, grid, g, 0, vec); }
-        else        { if (pro == 2) launch_ev<MI, true, true, 2, false>(st, grid, g, 0, vec); else launch_ev<MI, true, true, 0, false>(st, grid, g, 0, vec); }
+void launch_layout(hipStream_t st, dim3 grid, const CArgs& g, const LaunchPlan& p) {
+    if (!p.tA && p.tB) {            // forward of a 1x1 convolution, nn.Linear: both k-contiguous
+        if (p.gather) { if (p.pro == 1) launch_ev<MI, false, false, 1, true>(st, grid, g, p); else launch_ev<MI, false, false, 0, true>(st, grid, g, p); }
+        else          { if (p.pro == 1) launch_ev<MI, false, false, 1, false>(st, grid, g, p); else launch_ev<MI, false, false, 0, false>(st, grid, g, p); }
+    } else if (!p.tA && !p.tB) {    // dgrad: A k-contiguous, B [K][N]
+        launch_ev<MI, false, true, 0, false>(st, grid, g, p);
+    } else if (p.tA && !p.tB) {     // wgrad: A [K][M], B [K][N]
+        if (p.gather) { if (p.pro == 2) launch_ev<MI, true, true, 2, true>(st, grid, g, p); else launch_ev<MI, true, true, 0, true>(st, grid, g, p); }
+        else          { if (p.pro == 2) launch_ev<MI, true, true, 2, false>(st, grid, g, p); else launch_ev<MI, true, true, 0, false>(st, grid, g, p); }
     } else {
-        SCN_ARG(!gather && pro == 0 && kepi == 0, "cgemm: TT product is plain");
-        launch_ev<MI, true, false, 0, false>(st, grid, g, 0, vec);
+        launch_ev<MI, true, false, 0, false>(st, grid, g, p);
     }
+}
+
+// What cgemm_plan needs beyond the shapes: the selectors of a ConvExtra and the facts about pointers it decides on.
+struct CgemmFacts {
+    int pro, epi, c3;
+    bool gather, vec;         // strided 1x1 row gather; C takes 16-byte row stores
+    int force_mi, force_split;
+    bool ws;                  // a workspace was passed
+    long ws_floats;
+};
+
+// The dispatch policy of cgemm(), all of it: row tile, split-K depth and slice length, in-launch combine or second launch,
+// the template instance.  A pure function of its arguments and the option globals.  counters_ok: the stream's arrival
+// counters can be had (cgemm() plans with true and asks for them only when the plan wants them).
+int cgemm_plan(LaunchPlan& p, bool tA, bool tB, int M, int N, int K, int batch, const CgemmFacts& f, bool counters_ok) {
+    const int c3 = f.c3, epi = f.epi;
+    // row tile: 64 rows when the 128-row grid alone cannot give every CU a workgroup but the 64-row grid can come closer
+    int mi = 2;
+    if ((long)cdiv(M, 128) * cdiv(N, TN) * batch < 256 && M > 64 && c3 != 1 && c3 != 2 && c3 != 4) mi = 1;
+    // stride-2 d input: the four classes carry 1 / 2 / 2 / 4 taps, so the grid is uneven by construction; 64-row tiles
+    // (twice the workgroups, all resident at once) let the dispatcher even it out when the 128-row grid is small
+    if (c3 == 4 && (long)cdiv(M, 128) * cdiv(N, TN) * 4 < 768) mi = 1;
+    if (N <= 64 && M >= 128 && c3 != 3) mi = 4;     // 128 x 64 tiles, waves 4 x 1 (layer1's 64-channel maps)
+    if (g_cgemm_mi == 1 || g_cgemm_mi == 2) mi = g_cgemm_mi;
+    if (f.force_mi > 0) mi = f.force_mi;
+    SCN_ARG(mi == 1 || mi == 2 || (mi == 4 && c3 != 3), "cgemm: bad tile selector");
+    const int nt = cdiv(N, mi == 4 ? 64 : TN);
+    const int tmrows = mi == 4 ? 128 : 64 * mi, mt = cdiv(M, tmrows);
+    const long tiles = (long)mt * nt * batch;
+    int S = 1;
+    if (f.ws && tiles < 224 && K >= 2 * g_cgemm_kmin) {
+        // 3x3 weight gradient: its gathered operand makes the k-loop latency-bound, a third resident workgroup per CU
+        // pays (measured 115-120 us at ~768 workgroups against 127-142 at ~512; the 1x1 weight gradients are best at 512).
+        // Very deep non-transposed products (the decoder's d hidden = d preds . fc.weight, K = vocabulary): ~1100
+        // workgroups (1632 x 512 x 10000: 208 -> 158 us, tools/cgemm_bench.py gemmsweep).
+        long target = g_cgemm_target;
+        if (g_cgemm_target == 512) {
+            if (c3 == 3) target = 768;
+            else if (!tA && K >= 4096 && !c3) target = 1100;
+        }
+        S = (int)((target + tiles - 1) / tiles);
+        const int smax = K / g_cgemm_kmin;
+        if (S > smax) S = smax;
+        if (S > CG_MAX_SPLIT) S = CG_MAX_SPLIT;
+        while (S > 1 && (long)S * batch * M * N > f.ws_floats) --S;
+        if (S < 1) S = 1;
+    }
+    // A grid of one to three residency rounds (224 .. 767 tiles of a deep product) ends in a long tail: the last round
+    // runs with most CUs idle.  Splitting K to ~1200 workgroups evens it out (10000 x 512 x 1632: 208 -> 154 us,
+    // 6272 x 512 x 2048: 143 -> 128 us).  K >= 1536 keeps the trunk's forward / d-input convolutions on their measured
+    // setting (layer3's 8192 x 256 x 1024 loses 3-5 us to such a split: its statistics epilogue moves into the reduce pass).
+    if (f.ws && !c3 && S == 1 && tiles >= 224 && tiles < 768 && K >= 1536 && g_cgemm_target == 512) {
+        S = (int)((1200 + tiles / 2) / tiles);
+        const int smax = K / (2 * g_cgemm_kmin);
+        if (S > smax) S = smax;
+        while (S > 1 && (long)S * batch * M * N > f.ws_floats) --S;
+        if (S < 1) S = 1;
+    }
+    if (c3 == 4) S = 1;       // the four parity classes ride on grid.y; their K (1, 2, 2, 4 taps) is never split
+    if ((c3 == 1 || c3 == 2) && f.ws) {   // deep K (9 taps): 128-row tiles, up to 4 K-slices to reach ~512 workgroups (measured)
+        S = (int)(512 / (tiles > 0 ? tiles : 1));
+        if (S > 4) S = 4;
+        if (S < 1) S = 1;
+        while (S > 1 && (long)S * M * N > f.ws_floats) --S;
+    }
+    if (f.force_split > 0 && c3 != 4) {
+        S = f.force_split;
+        SCN_ARG(S == 1 || (f.ws && (long)S * batch * M * N <= f.ws_floats && S <= CG_MAX_SPLIT), "cgemm: forced split does not fit");
+    }
+    // The in-launch combine needs: the option, 16-byte stores, a counter per tile, a slab stack within 2 GiB, the counters.
+    const bool comb_ok = g_cgemm_combine && f.vec && tiles <= CNT_N && counters_ok;
+    // EPI 3 has no second-launch form (creduce applies the plain epilogue only): a split product takes the in-launch
+    // combine, so S is clamped to what the last arriver sums alone (g_cgemm_combine_max) and drops to 1 when the combine
+    // is not available (option off, no counters -- e.g. inside a stream capture -- or a slab stack beyond 2 GiB).
+    if (epi == 3 && S > 1) {
+        if (S > g_cgemm_combine_max) S = g_cgemm_combine_max;
+        if (!(comb_ok && S > 1 && (long)S * M * N * 4 < 0x7fffffffL)) S = 1;
+    }
+    int kper = cdiv(K, S);
+    kper = (kper + TK - 1) / TK * TK;
+    S = cdiv(K, kper);
+    // The epilogue runs inside the launch: from the accumulators of an un-split product, or -- split product -- by the
+    // workgroup that arrives last at its tile (arrival counters of this stream).  Second launch (creduce / cstats) only
+    // for what the in-launch forms do not cover: scalar stores, very deep splits, a mask epilogue on another layout.
+    const bool epi_in = epi != 2 || (!tA && !tB && f.pro == 0 && !f.gather && c3 == 0) || c3 == 2;
+    const bool in_launch = S > 1 && comb_ok && S <= g_cgemm_combine_max && epi_in && (epi == 0 || !tA) &&
+                           (long)S * M * N * 4 < 0x7fffffffL;
+    SCN_ARG(epi != 3 || S == 1 || in_launch, "cgemm: eval BatchNorm epilogue of a split product needs the in-launch combine");
+    const int kepi = (S > 1 && !in_launch) ? 0 : (epi_in ? epi : 0);
+    // the instances that exist
+    if (c3) SCN_ARG(f.vec, "cgemm: 3x3 mode needs 16-byte row stores");
+    else if (!tA && !tB) SCN_ARG(!f.gather && f.pro == 0, "cgemm: NN product takes no gather / prologue");
+    else if (tA && !tB) SCN_ARG(kepi == 0, "cgemm: TN product takes no statistics epilogue");
+    else if (tA && tB) SCN_ARG(!f.gather && f.pro == 0 && kepi == 0, "cgemm: TT product is plain");
+    p = LaunchPlan{};
+    p.family = SCNATTN_PLAN_CGEMM;
+    p.mi = mi; p.tA = tA; p.tB = tB; p.pro = f.pro; p.epi = kepi; p.gather = f.gather; p.c3 = c3; p.vec = f.vec;
+    p.S = S; p.kper = kper; p.mt = mt; p.nt = nt; p.tiles = tiles;
+    p.grid_x = mt * nt; p.grid_y = c3 == 4 ? 4 : batch * S; p.grid_z = 1;
+    p.in_launch = in_launch;
+    if ((S > 1 && !in_launch) || (epi == 2 && !epi_in))
+        p.second = epi == 0 ? SCNATTN_SECOND_CREDUCE : epi == 1 ? SCNATTN_SECOND_CSTATS1
+                   : S == 1 ? SCNATTN_SECOND_CSTATS2_C : SCNATTN_SECOND_CSTATS2_SLABS;
     return 0;
 }
 
@@ -1126,6 +1225,7 @@ int launch_layout(hipStream_t st, dim3 grid, const CArgs& g, bool tA, bool tB, i
 int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, const float* A, long lda, const float* B,
           long ldb, float beta, float* C, long ldc, const float* bias, const float* rowmask, int batch, long sA, long sB,
           long sC, float* ws, long ws_floats, const ConvExtra* ex) {
+    const PlanQuery query;
     if (M <= 0 || N <= 0 || batch <= 0) return 0;
     SCN_ARG(A && B && C, "cgemm: null operand");
     SCN_ARG(cgemm_supported(tA, tB, M, N, K, A, lda, B, ldb, sA, sB), "cgemm: operand alignment / size not supported");
@@ -1159,73 +1259,19 @@ int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, co
     const bool vec = N % 4 == 0 && ldc % 4 == 0 && sC % 4 == 0 && aligned16(C) &&
                      ((long)(M - 1) * ldc + N) * 4 < 0x7fffffffL && (long)M * N * 4 < 0x7fffffffL;
     SCN_ARG(epi == 0 || vec, "cgemm: the statistics epilogues need N % 4 == 0, ldc % 4 == 0 and a 16-byte aligned C");
-    // row tile: 64 rows when the 128-row grid alone cannot give every CU a workgroup but the 64-row grid can come closer
-    int mi = 2;
-    if ((long)cdiv(M, 128) * cdiv(N, TN) * batch < 256 && M > 64 && c3 != 1 && c3 != 2 && c3 != 4) mi = 1;
-    // stride-2 d input: the four classes carry 1 / 2 / 2 / 4 taps, so the grid is uneven by construction; 64-row tiles
-    // (twice the workgroups, all resident at once) let the dispatcher even it out when the 128-row grid is small
-    if (c3 == 4 && (long)cdiv(M, 128) * cdiv(N, TN) * 4 < 768) mi = 1;
-    if (N <= 64 && M >= 128 && c3 != 3) mi = 4;     // 128 x 64 tiles, waves 4 x 1 (layer1's 64-channel maps)
-    if (g_cgemm_mi == 1 || g_cgemm_mi == 2) mi = g_cgemm_mi;
-    if (ex && ex->force_mi > 0) mi = ex->force_mi;
-    SCN_ARG(mi == 1 || mi == 2 || (mi == 4 && c3 != 3), "cgemm: bad tile selector");
-    const int nt = cdiv(N, mi == 4 ? 64 : TN);
-    const int tmrows = mi == 4 ? 128 : 64 * mi, mt = cdiv(M, tmrows);
-    const long tiles = (long)mt * nt * batch;
-    int S = 1;
-    if (ws && tiles < 224 && K >= 2 * g_cgemm_kmin) {
-        // 3x3 weight gradient: its gathered operand makes the k-loop latency-bound, a third resident workgroup per CU
-        // pays (measured 115-120 us at ~768 workgroups against 127-142 at ~512; the 1x1 weight gradients are best at 512).
-        // Very deep non-transposed products (the decoder's d hidden = d preds . fc.weight, K = vocabulary): ~1100
-        // workgroups (1632 x 512 x 10000: 208 -> 158 us, tools/cgemm_bench.py gemmsweep).
-        long target = g_cgemm_target;
-        if (g_cgemm_target == 512) {
-            if (c3 == 3) target = 768;
-            else if (!tA && K >= 4096 && !c3) target = 1100;
-        }
-        S = (int)((target + tiles - 1) / tiles);
-        const int smax = K / g_cgemm_kmin;
-        if (S > smax) S = smax;
-        if (S > CG_MAX_SPLIT) S = CG_MAX_SPLIT;
-        while (S > 1 && (long)S * batch * M * N > ws_floats) --S;
-        if (S < 1) S = 1;
-    }
-    // A grid of one to three residency rounds (224 .. 767 tiles of a deep product) ends in a long tail: the last round
-    // runs with most CUs idle.  Splitting K to ~1200 workgroups evens it out (10000 x 512 x 1632: 208 -> 154 us,
-    // 6272 x 512 x 2048: 143 -> 128 us).  K >= 1536 keeps the trunk's forward / d-input convolutions on their measured
-    // setting (layer3's 8192 x 256 x 1024 loses 3-5 us to such a split: its statistics epilogue moves into the reduce pass).
-    if (ws && !c3 && S == 1 && tiles >= 224 && tiles < 768 && K >= 1536 && g_cgemm_target == 512) {
-        S = (int)((1200 + tiles / 2) / tiles);
-        const int smax = K / (2 * g_cgemm_kmin);
-        if (S > smax) S = smax;
-        while (S > 1 && (long)S * batch * M * N > ws_floats) --S;
-        if (S < 1) S = 1;
-    }
-    if (c3 == 4) S = 1;       // the four parity classes ride on grid.y; their K (1, 2, 2, 4 taps) is never split
-    if ((c3 == 1 || c3 == 2) && ws) {   // deep K (9 taps): 128-row tiles, up to 4 K-slices to reach ~512 workgroups (measured)
-        S = (int)(512 / (tiles > 0 ? tiles : 1));
-        if (S > 4) S = 4;
-        if (S < 1) S = 1;
-        while (S > 1 && (long)S * M * N > ws_floats) --S;
-    }
-    if (ex && ex->force_split > 0 && c3 != 4) {
-        S = ex->force_split;
-        SCN_ARG(S == 1 || (ws && (long)S * batch * M * N <= ws_floats && S <= CG_MAX_SPLIT), "cgemm: forced split does not fit");
-    }
-    // EPI 3 has no second-launch form (creduce applies the plain epilogue only): a split product takes the in-launch
-    // combine, so S is clamped to what the last arriver sums alone (g_cgemm_combine_max) and drops to 1 when the combine
-    // is not available (option off, no counters -- e.g. inside a stream capture -- or a slab stack beyond 2 GiB).
-    if (epi == 3 && S > 1) {
-        if (S > g_cgemm_combine_max) S = g_cgemm_combine_max;
-        if (!(g_cgemm_combine && S > 1 && vec && tiles <= CNT_N && (long)S * M * N * 4 < 0x7fffffffL && stream_counters(st))) S = 1;
-    }
-    int kper = cdiv(K, S);
-    kper = (kper + TK - 1) / TK * TK;
-    S = cdiv(K, kper);
+
+    const CgemmFacts f{pro, epi, c3, gather, vec, ex ? ex->force_mi : 0, ex ? ex->force_split : 0, ws != nullptr, ws_floats};
+    LaunchPlan p;
+    SCN_TRY(cgemm_plan(p, tA, tB, M, N, K, batch, f, true));
+    if (query.answer(p)) return 0;
+    int* cnt = nullptr;
+    if (p.in_launch && !(cnt = stream_counters(st)))      // inside a capture, or the allocation failed: plan without them
+        SCN_TRY(cgemm_plan(p, tA, tB, M, N, K, batch, f, false));
+
     CArgs g{};
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.rowmask = rowmask;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.sA = sA; g.sB = sB; g.sC = sC;
-    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.S = S; g.kper = kper; g.ws = ws; g.mt = mt; g.nt = nt;
+    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.S = p.S; g.kper = p.kper; g.ws = ws; g.mt = p.mt; g.nt = p.nt;
     if (ex) {
         g.geo = conv_geom(*ex);
         g.pro_ss = ex->pro_ss;
@@ -1233,36 +1279,25 @@ int cgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, co
         g.ez = ex->ez; g.emean = ex->emean; g.einvstd = ex->einvstd; g.egamma = ex->egamma; g.ebeta = ex->ebeta; g.ldz = ex->ldz;
         g.evar = ex->evar; g.eeps = ex->eeps; g.erelu = ex->erelu;
     }
-    dim3 grid(mt * nt, c3 == 4 ? 4 : batch * S), block(256);
-    // The epilogue runs inside the launch: from the accumulators of an un-split product, or -- split product -- by the
-    // workgroup that arrives last at its tile (arrival counters of this stream).  Second launch (creduce / cstats) only
-    // for what the in-launch forms do not cover: scalar stores, very deep splits, a mask epilogue on another layout.
-    const bool epi_in = epi != 2 || (!tA && !tB && pro == 0 && !gather && c3 == 0) || c3 == 2;
-    int* cnt = nullptr;
-    if (S > 1 && g_cgemm_combine && S <= g_cgemm_combine_max && vec && epi_in && (epi == 0 || !tA) && tiles <= CNT_N &&
-        (long)S * M * N * 4 < 0x7fffffffL)
-        cnt = stream_counters(st);
     g.cnt = cnt; g.comb = g_cgemm_combine;
-    SCN_ARG(epi != 3 || S == 1 || cnt, "cgemm: eval BatchNorm epilogue of a split product needs the in-launch combine");
-    const int kepi = (S > 1 && !cnt) ? 0 : (epi_in ? epi : 0);
-    if (c3) {
-        SCN_ARG(vec, "cgemm: 3x3 mode needs 16-byte row stores");
-        if (mi == 4) SCN_TRY(launch_conv3<4>(st, grid, g, c3, kepi));
-        else if (mi == 2) SCN_TRY(launch_conv3<2>(st, grid, g, c3, kepi));
-        else SCN_TRY(launch_conv3<1>(st, grid, g, c3, kepi));
-    } else if (mi == 4) SCN_TRY(launch_layout<4>(st, grid, g, tA, tB, pro, kepi, gather, vec));
-    else if (mi == 2) SCN_TRY(launch_layout<2>(st, grid, g, tA, tB, pro, kepi, gather, vec));
-    else SCN_TRY(launch_layout<1>(st, grid, g, tA, tB, pro, kepi, gather, vec));
+    const dim3 grid(p.grid_x, p.grid_y), block(256);
+    if (p.c3) {
+        if (p.mi == 4) launch_conv3<4>(st, grid, g, p);
+        else if (p.mi == 2) launch_conv3<2>(st, grid, g, p);
+        else launch_conv3<1>(st, grid, g, p);
+    } else if (p.mi == 4) launch_layout<4>(st, grid, g, p);
+    else if (p.mi == 2) launch_layout<2>(st, grid, g, p);
+    else launch_layout<1>(st, grid, g, p);
     SCN_LAUNCH_CHECK();
-    if ((S > 1 && !cnt) || (epi == 2 && !epi_in)) {
-        if (epi == 0) {
-            if (vec) hipLaunchKernelGGL(creduce_kernel<true>, dim3(cdiv((long)M * N / 4, 256), batch), block, 0, st, g);
-            else     hipLaunchKernelGGL(creduce_kernel<false>, dim3(cdiv((long)M * N, 256), batch), block, 0, st, g);
+    if (p.second) {
+        if (p.second == SCNATTN_SECOND_CREDUCE) {
+            if (p.vec) hipLaunchKernelGGL(creduce_kernel<true>, dim3(cdiv((long)M * N / 4, 256), batch), block, 0, st, g);
+            else       hipLaunchKernelGGL(creduce_kernel<false>, dim3(cdiv((long)M * N, 256), batch), block, 0, st, g);
         } else {
-            if (S == 1) g.S = 0;      // un-split mask pass: read the product back from C
+            if (p.second == SCNATTN_SECOND_CSTATS2_C) g.S = 0;      // un-split mask pass: read the product back from C
             dim3 sgrid(cdiv(N, 64), cdiv(M, SROWS));
-            if (epi == 1) hipLaunchKernelGGL(cstats_kernel<1>, sgrid, block, 0, st, g);
-            else          hipLaunchKernelGGL(cstats_kernel<2>, sgrid, block, 0, st, g);
+            if (p.second == SCNATTN_SECOND_CSTATS1) hipLaunchKernelGGL(cstats_kernel<1>, sgrid, block, 0, st, g);
+            else                                    hipLaunchKernelGGL(cstats_kernel<2>, sgrid, block, 0, st, g);
         }
         SCN_LAUNCH_CHECK();
     }

@@ -536,8 +536,10 @@ __global__ __launch_bounds__(256) void creduce16_kernel(HArgs g) {
 }
 
 template <int MI, int C3>
-void launch16(hipStream_t st, dim3 grid, const HArgs& g, int kepi, bool gather, bool obf) {
+void launch16(hipStream_t st, dim3 grid, const HArgs& g, const LaunchPlan& p) {
     dim3 block(256);
+    const int kepi = p.epi;
+    const bool gather = p.gather, obf = p.out_bf16;
 #define SCN_L16(EPI_, G_, O_) hipLaunchKernelGGL((cgemm16_kernel<MI, EPI_, G_, O_, C3>), grid, block, 0, st, g)
     if (kepi == 3) {        // eval BatchNorm epilogue: forward products, bf16 maps (host-checked)
         if constexpr (C3 == 0) { if (gather) SCN_L16(3, true, true); else SCN_L16(3, false, true); }
@@ -555,13 +557,55 @@ void launch16(hipStream_t st, dim3 grid, const HArgs& g, int kepi, bool gather, 
 #undef SCN_L16
 }
 
+// The dispatch policy of cgemm16(): row tile, split-K depth and slice length, the epilogue in the product's launch or in the
+// reduce launch, the template instance.  A pure function of its arguments.
+int cgemm16_plan(LaunchPlan& p, int M, int N, int K, int epi, int c3, bool gather, bool out_bf16, int force_mi, int force_split,
+                 bool ws, long ws_floats) {
+    int mi = 2;
+    if ((long)cdiv(M, 128) * cdiv(N, TN) * (c3 == 4 ? 4 : 1) < 256 && M > 64) mi = 1;
+    if (force_mi == 1 || force_mi == 2) mi = force_mi;
+    const int nt = cdiv(N, TN), mt = cdiv(M, 64 * mi);
+    const long tiles = (long)mt * nt;
+    int S = 1;
+    if (c3 != 4 && ws && tiles < 192 && K >= 512) {      // few tiles, deep K: split to ~512 workgroups, >= 256 k per slab
+        S = (int)((512 + tiles - 1) / tiles);
+        if (S > K / 256) S = K / 256;
+        if (S > 16) S = 16;
+        while (S > 1 && (long)S * M * N > ws_floats) --S;
+        if (S < 1) S = 1;
+    }
+    if (epi == 2) S = 1;        // the mask epilogue lives in the product's own launch: un-split (only layer4's shapes would split)
+    if (force_split > 0 && c3 != 4 && epi != 2) {
+        S = force_split;
+        SCN_ARG(S == 1 || (ws && (long)S * M * N <= ws_floats && S <= 64), "cgemm16: forced split does not fit");
+    }
+    int kper = cdiv(K, S);
+    kper = (kper + TKE - 1) / TKE * TKE;
+    S = cdiv(K, kper);
+    p = LaunchPlan{};
+    p.family = SCNATTN_PLAN_CGEMM16;
+    p.mi = mi; p.tB = 1; p.c3 = c3; p.S = S; p.kper = kper; p.mt = mt; p.nt = nt; p.tiles = tiles;
+    // a split product's epilogue is the reduce launch's; the 3x3 modes always write bf16 maps, mode 4 is plain
+    p.epi = (S > 1 || c3 == 4) ? 0 : epi;
+    p.gather = c3 ? 0 : gather;
+    p.out_bf16 = c3 ? 1 : out_bf16;
+    p.grid_x = mt * nt; p.grid_y = c3 == 4 ? 4 : S; p.grid_z = 1;
+    if (S > 1) {
+        p.second = SCNATTN_SECOND_CREDUCE16;
+        p.second_mode = epi == 3 ? 2 : epi == 1 ? 1 : 0;
+    }
+    return 0;
+}
+
 }  // namespace
 
 // C[M][N] = A . B^T (+ beta*C).  A bf16 [M][K] (lda), B bf16 [N][K] (ldb); C bf16 (out_bf16) or fp32, leading dimension ldc
-// in ELEMENTS.  ex: epi 0 / 1 (statistics, channel-major partials) / 3 (eval BatchNorm), stride > 1 (row gather), c3 = 1 (3x3 taps over K;
-// ex->force_mi == -1 ... no: `flip` is passed separately) or 4 (stride-2 d input).  ws: fp32 split-K slabs.
+// in ELEMENTS.  ex: epi 0 / 1 (statistics, channel-major partials) / 2 (mask) / 3 (eval BatchNorm), stride > 1 (row gather),
+// c3 = 1 (3x3 taps over K) or 4 (stride-2 d input).  flip != 0: a c3 = 1 product reads weight tap 8 - t at tap t --
+// the stride-1 d input as a forward convolution of dy with the transposed weight copy.  ws: fp32 split-K slabs.
 int cgemm16(hipStream_t st, int M, int N, int K, const void* A, long lda, const void* B, long ldb, float beta, void* C, long ldc,
             int out_bf16, float* ws, long ws_floats, const ConvExtra* ex, int flip) {
+    const PlanQuery query;
     if (M <= 0 || N <= 0) return 0;
     SCN_ARG(A && B && C && K >= 8, "cgemm16: null operand / K");
     SCN_ARG(aligned16(A) && aligned16(B) && aligned16(C) && lda % 8 == 0 && ldb % 8 == 0 && K % 8 == 0, "cgemm16: operands need 16-byte rows (multiples of 8 elements)");
@@ -589,47 +633,28 @@ int cgemm16(hipStream_t st, int M, int N, int K, const void* A, long lda, const 
     SCN_ARG(!gather || (ex->Hi > 0 && ex->Wi > 0 && ex->Ho > 0 && ex->Wo > 0), "cgemm16: gather geometry");
     const long out_rows = c3 == 4 ? 4L * M : M;
     SCN_ARG(((out_rows - 1) * ldc + N) * (out_bf16 ? 2 : 4) < 0x7fffffffL && (long)M * N * 4 < 0x7fffffffL, "cgemm16: C too large");
-    int mi = 2;
-    if ((long)cdiv(M, 128) * cdiv(N, TN) * (c3 == 4 ? 4 : 1) < 256 && M > 64) mi = 1;
-    if (ex && (ex->force_mi == 1 || ex->force_mi == 2)) mi = ex->force_mi;
-    const int nt = cdiv(N, TN), mt = cdiv(M, 64 * mi);
-    const long tiles = (long)mt * nt;
-    int S = 1;
-    if (c3 != 4 && ws && tiles < 192 && K >= 512) {      // few tiles, deep K: split to ~512 workgroups, >= 256 k per slab
-        S = (int)((512 + tiles - 1) / tiles);
-        if (S > K / 256) S = K / 256;
-        if (S > 16) S = 16;
-        while (S > 1 && (long)S * M * N > ws_floats) --S;
-        if (S < 1) S = 1;
-    }
-    if (epi == 2) S = 1;        // the mask epilogue lives in the product's own launch: un-split (only layer4's shapes would split)
-    if (ex && ex->force_split > 0 && c3 != 4 && epi != 2) {
-        S = ex->force_split;
-        SCN_ARG(S == 1 || (ws && (long)S * M * N <= ws_floats && S <= 64), "cgemm16: forced split does not fit");
-    }
-    int kper = cdiv(K, S);
-    kper = (kper + TKE - 1) / TKE * TKE;
-    S = cdiv(K, kper);
+    LaunchPlan p;
+    SCN_TRY(cgemm16_plan(p, M, N, K, epi, c3, gather, out_bf16 != 0, ex ? ex->force_mi : 0, ex ? ex->force_split : 0, ws != nullptr, ws_floats));
+    if (query.answer(p)) return 0;
     HArgs g{};
     g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.M = M; g.N = N; g.K = K; g.beta = beta; g.S = S; g.kper = kper; g.ws = ws; g.mt = mt; g.nt = nt; g.flip = flip;
+    g.M = M; g.N = N; g.K = K; g.beta = beta; g.S = p.S; g.kper = p.kper; g.ws = ws; g.mt = p.mt; g.nt = p.nt; g.flip = flip;
     if (ex) {
         g.geo = conv_geom(*ex);
         g.stat_partial = ex->stat_partial; g.stat_shift = ex->stat_shift; g.ldp = cgemm_stat_ld(M);
         g.ez = (const bf16_t*)ex->ez; g.ldz = ex->ldz; g.emean = ex->emean; g.einvstd = ex->einvstd; g.egamma = ex->egamma; g.ebeta = ex->ebeta;
         g.evar = ex->evar; g.eeps = ex->eeps; g.erelu = ex->erelu;
     }
-    dim3 grid(mt * nt, c3 == 4 ? 4 : S);
-    const int kepi = S > 1 ? 0 : epi;
-    const bool obf = out_bf16 != 0;
-    if (c3 == 1)      { if (mi == 2) launch16<2, 1>(st, grid, g, kepi, false, true); else launch16<1, 1>(st, grid, g, kepi, false, true); }
-    else if (c3 == 4) { if (mi == 2) launch16<2, 4>(st, grid, g, 0, false, true); else launch16<1, 4>(st, grid, g, 0, false, true); }
-    else              { if (mi == 2) launch16<2, 0>(st, grid, g, kepi, gather, obf); else launch16<1, 0>(st, grid, g, kepi, gather, obf); }
+    const dim3 grid(p.grid_x, p.grid_y);
+    if (p.c3 == 1)      { if (p.mi == 2) launch16<2, 1>(st, grid, g, p); else launch16<1, 1>(st, grid, g, p); }
+    else if (p.c3 == 4) { if (p.mi == 2) launch16<2, 4>(st, grid, g, p); else launch16<1, 4>(st, grid, g, p); }
+    else                { if (p.mi == 2) launch16<2, 0>(st, grid, g, p); else launch16<1, 0>(st, grid, g, p); }
     SCN_LAUNCH_CHECK();
-    if (S > 1) {
+    if (p.second) {
         dim3 sgrid(cdiv(N, 64), cdiv(M, SROWS)), block(256);
-        if (epi == 3)      hipLaunchKernelGGL((creduce16_kernel<true, false, true>), sgrid, block, 0, st, g);
-        else if (epi == 1) { if (obf) hipLaunchKernelGGL((creduce16_kernel<true, true>), sgrid, block, 0, st, g); else hipLaunchKernelGGL((creduce16_kernel<false, true>), sgrid, block, 0, st, g); }
+        const bool obf = p.out_bf16;
+        if (p.second_mode == 2)      hipLaunchKernelGGL((creduce16_kernel<true, false, true>), sgrid, block, 0, st, g);
+        else if (p.second_mode == 1) { if (obf) hipLaunchKernelGGL((creduce16_kernel<true, true>), sgrid, block, 0, st, g); else hipLaunchKernelGGL((creduce16_kernel<false, true>), sgrid, block, 0, st, g); }
         else          { if (obf) hipLaunchKernelGGL((creduce16_kernel<true, false>), sgrid, block, 0, st, g); else hipLaunchKernelGGL((creduce16_kernel<false, false>), sgrid, block, 0, st, g); }
         SCN_LAUNCH_CHECK();
     }

@@ -179,23 +179,24 @@ bool conv3x3_wgrad_halo_ok(int N, int H, int W, int C, int Co, const float* dy, 
 // force_split > 0 fixes the workgroup-level K split (tests / tuning).
 int conv3x3_wgrad_halo(hipStream_t st, int N, int H, int W, int C, int Co, const float* dy, const float* x, float* dw,
                        float* ws, long ws_floats, int force_split) {
+    const PlanQuery query;
     SCN_ARG(conv3x3_wgrad_halo_ok(N, H, W, C, Co, dy, x, dw), "conv3x3_wgrad_halo: shape / alignment not supported");
     const int seg = (W % 16 == 0) ? 16 : 8;
+    const int nseg = (W + seg - 1) / seg;       // widths that are no multiple of 8: the last strip is ragged (zero-filled)
+    const LaunchPlan p = wgrad_plan(SCNATTN_PLAN_CONV3_WGRAD, seg, N * nseg * H, (Co / 32) * (C / 32), g_w3_target,
+                                    (long)Co * 9 * C, ws != nullptr, ws_floats, force_split);
+    SCN_ARG(force_split <= 0 || p.S == force_split, "conv3x3_wgrad_halo: forced split does not fit the workspace / the map");
+    if (query.answer(p)) return 0;
     W3Args g{};
     g.dy = dy; g.x = x; g.N = N; g.H = H; g.W = W; g.C = C; g.Co = Co;
-    g.nseg = (W + seg - 1) / seg;       // widths that are no multiple of 8: the last strip is ragged (zero-filled)
-    g.Q = N * g.nseg * H;
-    g.tci = C / 32;
-    g.ntiles = (Co / 32) * g.tci;
-    const int S = wgrad_split(g.ntiles, g.Q, g_w3_target, (long)Co * 9 * C, ws, ws_floats, force_split);
-    SCN_ARG(force_split <= 0 || S == force_split, "conv3x3_wgrad_halo: forced split does not fit the workspace / the map");
-    g.S = S;
-    g.out = S > 1 ? ws : dw;
-    dim3 grid(g.ntiles * S), block(256);
-    if (seg == 16) hipLaunchKernelGGL(conv3_wgrad_kernel<16>, grid, block, 0, st, g);
-    else           hipLaunchKernelGGL(conv3_wgrad_kernel<8>, grid, block, 0, st, g);
+    g.nseg = nseg; g.Q = p.Q; g.tci = C / 32; g.ntiles = p.ntiles;
+    g.S = p.S;
+    g.out = p.S > 1 ? ws : dw;
+    dim3 grid(p.grid_x), block(256);
+    if (p.seg == 16) hipLaunchKernelGGL(conv3_wgrad_kernel<16>, grid, block, 0, st, g);
+    else             hipLaunchKernelGGL(conv3_wgrad_kernel<8>, grid, block, 0, st, g);
     SCN_LAUNCH_CHECK();
-    if (S > 1) SCN_TRY(cgemm_reduce(st, ws, S, Co, 9 * C, dw, 9L * C));
+    if (p.second) SCN_TRY(cgemm_reduce(st, ws, p.S, Co, 9 * C, dw, 9L * C));
     return 0;
 }
 

@@ -4,11 +4,24 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/scnattn.h"
+
 #define SCN_MAX_KSPLIT 16
 
-struct scnattn_pool;      // include/scnattn.h
-
 namespace scn {
+
+// ---- launch plans (include/scnattn.h, scnattn_plan_next) --------------------------------------------------------------
+// Every dense-product launcher below is  argument checks -> a pure plan function -> a launch that reads only the plan.
+typedef ::scnattn_launch_plan LaunchPlan;
+extern thread_local LaunchPlan* t_plan_out;     // armed by scnattn_plan_next, null otherwise
+// First statement of such a launcher: takes the armed request off the thread and clears *out (family 0), so no return path
+// -- empty problem, refusal, answer -- leaves the thread armed.  One thread-local read when nothing is armed.
+struct PlanQuery {
+    LaunchPlan* out;
+    PlanQuery() : out(t_plan_out) { if (out) { t_plan_out = nullptr; *out = LaunchPlan{}; } }
+    bool answer(const LaunchPlan& p) const { if (out) *out = p; return out != nullptr; }     // true: launch nothing
+    void hand_on() const { t_plan_out = out; }      // a launcher that forwards to another one (sgemm_ws -> cgemm)
+};
 
 // ---- sgemm.hip -------------------------------------------------------------------------------
 int sgemm(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, const float* A, long lda,

@@ -217,21 +217,10 @@ int g_gemm_kmin = 256;        // at least this much K per split ...
 int g_gemm_kmin_small = 128;  // ... or this much when the product has <= 16 tiles (32-row operands)
 int g_use_cgemm = 1;          // 16-byte-aligned products go to the LDS-DMA pipelined kernel of cgemm.hip
 
-int sgemm_ws(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, const float* A, long lda,
-             const float* B, long ldb, float beta, float* C, long ldc, const float* bias, const float* rowmask,
-             int batch, long sA, long sB, long sC, float* ws, long ws_floats) {
-    if (M <= 0 || N <= 0 || batch <= 0) return 0;
-    SCN_ARG(A && B && C, "sgemm: null operand");
-    SCN_ARG(K >= 1, "sgemm: K must be >= 1");
-    if (g_use_cgemm && cgemm_supported(tA, tB, M, N, K, A, lda, B, ldb, sA, sB))
-        return cgemm(st, tA, tB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, rowmask, batch, sA, sB, sC, ws,
-                     ws_floats, nullptr);
-    {
-        const long abytes = (tA ? ((long)(K - 1) * lda + M) : ((long)(M - 1) * lda + K)) * 4;
-        const long bbytes = (tB ? ((long)(N - 1) * ldb + K) : ((long)(K - 1) * ldb + N)) * 4;
-        SCN_ARG(abytes < 0x7fffffffL && bbytes < 0x7fffffffL, "sgemm: operand exceeds the 2 GiB buffer-descriptor range");
-    }
-    SCN_ARG(beta == 0.f || ((long)(M - 1) * ldc + N) * 4 < 0x7fffffffL, "sgemm: C too large for beta != 0");
+namespace {
+// The dispatch policy of sgemm_ws(): split-K depth and slice length, 16-byte or scalar operand loads, the reduce launch.
+// A pure function of its arguments and the option globals.
+LaunchPlan sgemm_plan(bool tA, bool tB, int M, int N, int K, int batch, bool vec, bool ws, long ws_floats) {
     // split-K when the tile grid alone cannot fill the chip and K is deep enough to amortise the reduce
     // (measured on the decoder's shapes: one 128x128 tile per CU leaves the MFMA pipe ~45 % idle, and a
     //  32-row product with 16 tiles ran 85 us un-split)
@@ -249,24 +238,53 @@ int sgemm_ws(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha,
     int kper = cdiv(K, S);
     kper = (kper + BK - 1) / BK * BK;
     S = cdiv(K, kper);
-    GemmArgs g{A, B, C, bias, rowmask, lda, ldb, ldc, sA, sB, sC, M, N, K, alpha, beta, S, kper, ws};
+    LaunchPlan p{};
+    p.family = SCNATTN_PLAN_SGEMM;
+    p.tA = tA; p.tB = tB; p.vec = vec; p.S = S; p.kper = kper; p.tiles = tiles;
+    p.grid_x = cdiv(N, BN); p.grid_y = cdiv(M, BM); p.grid_z = batch * S;
+    if (S > 1) p.second = SCNATTN_SECOND_SPLITK_REDUCE;
+    return p;
+}
+}  // namespace
+
+int sgemm_ws(hipStream_t st, bool tA, bool tB, int M, int N, int K, float alpha, const float* A, long lda,
+             const float* B, long ldb, float beta, float* C, long ldc, const float* bias, const float* rowmask,
+             int batch, long sA, long sB, long sC, float* ws, long ws_floats) {
+    const PlanQuery query;
+    if (M <= 0 || N <= 0 || batch <= 0) return 0;
+    SCN_ARG(A && B && C, "sgemm: null operand");
+    SCN_ARG(K >= 1, "sgemm: K must be >= 1");
+    if (g_use_cgemm && cgemm_supported(tA, tB, M, N, K, A, lda, B, ldb, sA, sB)) {
+        query.hand_on();
+        return cgemm(st, tA, tB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, rowmask, batch, sA, sB, sC, ws,
+                     ws_floats, nullptr);
+    }
+    {
+        const long abytes = (tA ? ((long)(K - 1) * lda + M) : ((long)(M - 1) * lda + K)) * 4;
+        const long bbytes = (tB ? ((long)(N - 1) * ldb + K) : ((long)(K - 1) * ldb + N)) * 4;
+        SCN_ARG(abytes < 0x7fffffffL && bbytes < 0x7fffffffL, "sgemm: operand exceeds the 2 GiB buffer-descriptor range");
+    }
+    SCN_ARG(beta == 0.f || ((long)(M - 1) * ldc + N) * 4 < 0x7fffffffL, "sgemm: C too large for beta != 0");
     // 16-byte loads need: aligned bases/strides and the contiguous extent a multiple of 4
     const int contigA = tA ? M : K, contigB = tB ? K : N;
     const bool vec = aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0) && (sA % 4 == 0) &&
                      (sB % 4 == 0) && (contigA % 4 == 0) && (contigB % 4 == 0);
-    dim3 grid(cdiv(N, BN), cdiv(M, BM), batch * S), block(256);
+    const LaunchPlan p = sgemm_plan(tA, tB, M, N, K, batch, vec, ws != nullptr, ws_floats);
+    if (query.answer(p)) return 0;
+    GemmArgs g{A, B, C, bias, rowmask, lda, ldb, ldc, sA, sB, sC, M, N, K, alpha, beta, p.S, p.kper, ws};
+    dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(256);
 #define SCN_GEMM_LAUNCH(TA_, TB_)                                                        \
     do {                                                                                 \
-        if (vec) hipLaunchKernelGGL((sgemm_kernel<TA_, TB_, true>), grid, block, 0, st, g);  \
-        else     hipLaunchKernelGGL((sgemm_kernel<TA_, TB_, false>), grid, block, 0, st, g); \
+        if (p.vec) hipLaunchKernelGGL((sgemm_kernel<TA_, TB_, true>), grid, block, 0, st, g);  \
+        else       hipLaunchKernelGGL((sgemm_kernel<TA_, TB_, false>), grid, block, 0, st, g); \
     } while (0)
-    if (!tA && !tB) SCN_GEMM_LAUNCH(false, false);
-    else if (!tA && tB) SCN_GEMM_LAUNCH(false, true);
-    else if (tA && !tB) SCN_GEMM_LAUNCH(true, false);
+    if (!p.tA && !p.tB) SCN_GEMM_LAUNCH(false, false);
+    else if (!p.tA && p.tB) SCN_GEMM_LAUNCH(false, true);
+    else if (p.tA && !p.tB) SCN_GEMM_LAUNCH(true, false);
     else SCN_GEMM_LAUNCH(true, true);
 #undef SCN_GEMM_LAUNCH
     SCN_LAUNCH_CHECK();
-    if (S > 1) {
+    if (p.second) {
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv((long)M * N, 256), batch), dim3(256), 0, st, g);
         SCN_LAUNCH_CHECK();
     }

@@ -197,40 +197,57 @@ int skinny_pick_ksplit(int rows, int N, int K, int groups) {
     return ks;
 }
 
+namespace {
+// The dispatch policy of skinny_gemm() for a given ksplit: k per wave and slice, NB, chunks, the grid.  A pure function.
+LaunchPlan skinny_plan(int rows, int N, int K, int groups, int ksplit, int wbf, bool xvec) {
+    int per = cdiv(cdiv(K, ksplit), 4);      // k per wave
+    per = (per + 7) & ~7;                    // whole 8-k blocks
+    if (wbf == 2) per = (per + 15) & ~15;    // bf16 matrix instruction: whole 16-k blocks
+    if (per > KW) per = (per + KW - 1) / KW * KW;   // several full chunks
+    LaunchPlan p{};
+    p.family = SCNATTN_PLAN_SKINNY;
+    p.nb = per > KW ? NBW : per / 8;
+    p.chunks = cdiv(per, KW);
+    p.kslice = 4 * per;
+    p.vec = xvec; p.wbf = wbf; p.S = ksplit; p.kper = p.kslice;
+    for (int s = 0; s < ksplit; ++s) p.empty += (long)s * p.kslice >= K;
+    p.grid_x = cdiv(N, 32) * groups; p.grid_y = ksplit; p.grid_z = cdiv(rows, 32);
+    p.tiles = (long)p.grid_x * p.grid_z;
+    return p;
+}
+}  // namespace
+
 int skinny_gemm(hipStream_t st, int rows, int N, int K, int groups, const float* X, long ldx, long xg,
                 const void* W, long ldw, long wg, float* Y, long ldy, long yg, long yslab, int ksplit, int wbf) {
+    const PlanQuery query;
     if (rows <= 0 || N <= 0 || groups <= 0) return 0;
     SCN_ARG(X && W && Y, "skinny_gemm: null operand");
     SCN_ARG(K >= 1, "skinny_gemm: K must be >= 1");
     SCN_ARG(ksplit >= 1 && ksplit <= SCN_MAX_KSPLIT, "skinny_gemm: ksplit out of range");
     SCN_ARG((long)K * ldw * (wbf ? 2 : 4) < 0x7fffffffL && (long)rows * ldx * 4 < 0x7fffffffL,
             "skinny_gemm: operand exceeds the 2 GiB buffer-descriptor range");
-    int per = cdiv(cdiv(K, ksplit), 4);      // k per wave
-    per = (per + 7) & ~7;                    // whole 8-k blocks
-    if (wbf == 2) per = (per + 15) & ~15;    // bf16 matrix instruction: whole 16-k blocks
-    if (per > KW) per = (per + KW - 1) / KW * KW;   // several full chunks
-    const int nb = per > KW ? NBW : per / 8;
-    const int kslice = 4 * per;
-    const int xvec = (aligned16(X) && ldx % 4 == 0 && xg % 4 == 0 && K % 4 == 0 && K >= 4) ? 1 : 0;
-    SkinnyArgs a{X, W, Y, ldx, xg, ldw, wg, ldy, yg, yslab, rows, N, K, kslice, groups, xvec};
-    dim3 grid(cdiv(N, 32) * groups, ksplit, cdiv(rows, 32)), block(256);
+    const bool xvec = aligned16(X) && ldx % 4 == 0 && xg % 4 == 0 && K % 4 == 0 && K >= 4;
+    const LaunchPlan p = skinny_plan(rows, N, K, groups, ksplit, wbf, xvec);
+    SCN_ARG(p.nb >= 1 && p.nb <= NBW, "skinny_gemm: internal blocking error");
+    if (query.answer(p)) return 0;
+    SkinnyArgs a{X, W, Y, ldx, xg, ldw, wg, ldy, yg, yslab, rows, N, K, p.kslice, groups, p.vec};
+    dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(256);
 #define SCN_SKINNY_CASE(NB_)                                                                     \
     case NB_:                                                                                     \
-        if (wbf == 2 && (NB_ % 2) == 0) {                                                         \
-            if (xvec) hipLaunchKernelGGL((skinny_kernel<(NB_ % 2 ? NB_ + 1 : NB_), true, true, true>), grid, block, 0, st, a);   \
-            else      hipLaunchKernelGGL((skinny_kernel<(NB_ % 2 ? NB_ + 1 : NB_), false, true, true>), grid, block, 0, st, a);  \
-        } else if (wbf) {                                                                         \
-            if (xvec) hipLaunchKernelGGL((skinny_kernel<NB_, true, true>), grid, block, 0, st, a);    \
-            else      hipLaunchKernelGGL((skinny_kernel<NB_, false, true>), grid, block, 0, st, a);   \
+        if (p.wbf == 2 && (NB_ % 2) == 0) {                                                       \
+            if (p.vec) hipLaunchKernelGGL((skinny_kernel<(NB_ % 2 ? NB_ + 1 : NB_), true, true, true>), grid, block, 0, st, a);   \
+            else       hipLaunchKernelGGL((skinny_kernel<(NB_ % 2 ? NB_ + 1 : NB_), false, true, true>), grid, block, 0, st, a);  \
+        } else if (p.wbf) {                                                                       \
+            if (p.vec) hipLaunchKernelGGL((skinny_kernel<NB_, true, true>), grid, block, 0, st, a);    \
+            else       hipLaunchKernelGGL((skinny_kernel<NB_, false, true>), grid, block, 0, st, a);   \
         } else {                                                                                  \
-            if (xvec) hipLaunchKernelGGL((skinny_kernel<NB_, true, false>), grid, block, 0, st, a);   \
-            else      hipLaunchKernelGGL((skinny_kernel<NB_, false, false>), grid, block, 0, st, a);  \
+            if (p.vec) hipLaunchKernelGGL((skinny_kernel<NB_, true, false>), grid, block, 0, st, a);   \
+            else       hipLaunchKernelGGL((skinny_kernel<NB_, false, false>), grid, block, 0, st, a);  \
         }                                                                                         \
         break;
-    switch (nb) {
+    switch (p.nb) {
         SCN_SKINNY_CASE(1) SCN_SKINNY_CASE(2) SCN_SKINNY_CASE(3) SCN_SKINNY_CASE(4)
         SCN_SKINNY_CASE(5) SCN_SKINNY_CASE(6) SCN_SKINNY_CASE(7) SCN_SKINNY_CASE(8)
-        default: SCN_ARG(false, "skinny_gemm: internal blocking error");
     }
 #undef SCN_SKINNY_CASE
     SCN_LAUNCH_CHECK();

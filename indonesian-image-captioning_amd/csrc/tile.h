@@ -102,13 +102,23 @@ __device__ __forceinline__ void slab_colsum_tail(const Args& g, float (&red)[16]
 // Workgroup-level K split of those kernels: aim for `target` workgroups over `ntiles` output blocks, at least 4 of the Q
 // lines per wave, and no more slabs (mn floats each) than the workspace holds.  force_split > 0 replaces the aim; the
 // caller checks that it survived the clamps.
-static inline int wgrad_split(int ntiles, int Q, int target, long mn, const float* ws, long ws_floats, int force_split) {
+static inline int wgrad_split(int ntiles, int Q, int target, long mn, bool ws, long ws_floats, int force_split) {
     int S = force_split > 0 ? force_split : (target + ntiles / 2) / ntiles;
     const int smax = Q / 16 > 0 ? Q / 16 : 1;
     if (S > smax) S = smax;
     if (S < 1) S = 1;
     while (S > 1 && (!ws || (long)S * mn > ws_floats)) --S;
     return S;
+}
+// Their launch plan: Q lines of `seg` pixels, ntiles output blocks, S slabs of mn floats summed by cgemm_reduce when S > 1.
+static inline LaunchPlan wgrad_plan(int family, int seg, int Q, int ntiles, int target, long mn, bool ws, long ws_floats,
+                                    int force_split) {
+    LaunchPlan p{};
+    p.family = family; p.seg = seg; p.Q = Q; p.ntiles = ntiles; p.tiles = ntiles;
+    p.S = wgrad_split(ntiles, Q, target, mn, ws, ws_floats, force_split);
+    p.grid_x = ntiles * p.S; p.grid_y = p.grid_z = 1;
+    if (p.S > 1) p.second = SCNATTN_SECOND_CGEMM_REDUCE;
+    return p;
 }
 
 }  // namespace scn

@@ -292,23 +292,24 @@ __global__ __launch_bounds__(256, 2) void wgrad16_w1_kernel(W16Args g) {
 // dW [Co][3][3][C] fp32 from bf16 maps dy [N*H*W][Co], x [N*H*W][C]: stride 1, padding 1.  ws: slabs (S * Co*9*C floats).
 int wgrad16_3x3(hipStream_t st, int N, int H, int W, int C, int Co, const void* dy, const void* x, float* dw, float* ws,
                 long ws_floats, int force_split) {
+    const PlanQuery query;
     SCN_ARG(N > 0 && H > 0 && W > 0 && C % 32 == 0 && Co % 32 == 0 && dy && x && dw && aligned16(dy) && aligned16(x) && aligned16(dw),
             "wgrad16_3x3: shape / alignment");
     SCN_ARG((long)N * H * W * (C > Co ? C : Co) * 2 < 0x7fffffffL, "wgrad16_3x3: map exceeds the descriptor range");
+    const int nseg = (W + 15) / 16;
+    const long mn = (long)Co * 9 * C;
+    const LaunchPlan p = wgrad_plan(SCNATTN_PLAN_WGRAD16_W9, 16, N * nseg * H, (Co / 32) * (C / 32), 512, mn, ws != nullptr,
+                                    ws_floats, force_split);
+    SCN_ARG(force_split <= 0 || p.S == force_split, "wgrad16_3x3: forced split does not fit");
+    if (query.answer(p)) return 0;
     W16Args g{};
     g.dy = (const bf16_t*)dy; g.x = (const bf16_t*)x; g.N = N; g.H = H; g.W = W; g.C = C; g.Co = Co;
-    g.nseg = (W + 15) / 16;
-    g.Q = N * g.nseg * H;
-    g.tci = C / 32;
-    g.ntiles = (Co / 32) * g.tci;
-    const long mn = (long)Co * 9 * C;
-    const int S = wgrad_split(g.ntiles, g.Q, 512, mn, ws, ws_floats, force_split);
-    SCN_ARG(force_split <= 0 || S == force_split, "wgrad16_3x3: forced split does not fit");
-    g.S = S; g.ldo = 9L * C; g.slab_ld = 9L * C; g.slab_stride = mn;
-    g.out = S > 1 ? ws : dw;
-    hipLaunchKernelGGL(wgrad16_w9_kernel, dim3(g.ntiles * S), dim3(256), 0, st, g);
+    g.nseg = nseg; g.Q = p.Q; g.tci = C / 32; g.ntiles = p.ntiles;
+    g.S = p.S; g.ldo = 9L * C; g.slab_ld = 9L * C; g.slab_stride = mn;
+    g.out = p.S > 1 ? ws : dw;
+    hipLaunchKernelGGL(wgrad16_w9_kernel, dim3(p.grid_x), dim3(256), 0, st, g);
     SCN_LAUNCH_CHECK();
-    if (S > 1) SCN_TRY(cgemm_reduce(st, ws, S, Co, 9 * C, dw, 9L * C));
+    if (p.second) SCN_TRY(cgemm_reduce(st, ws, p.S, Co, 9 * C, dw, 9L * C));
     return 0;
 }
 
@@ -316,24 +317,25 @@ int wgrad16_3x3(hipStream_t st, int N, int H, int W, int C, int Co, const void* 
 // gs > 0 the pixel (ho*gs + goh, wo*gs + gow) of a gHi x gWi map for r = (n, ho, wo) of a gHo x gWo grid (zeros outside).
 int wgrad16_rows(hipStream_t st, int R, int C, int Co, const void* dy, const void* x, long src_rows, float* dw, long ldo,
                  int gs, int gHi, int gWi, int gHo, int gWo, int goh, int gow, float* ws, long ws_floats, int force_split) {
+    const PlanQuery query;
     SCN_ARG(R > 0 && C % 64 == 0 && Co % 64 == 0 && dy && x && dw && aligned16(dy) && aligned16(x) && aligned16(dw) && ldo % 4 == 0 && src_rows > 0,
             "wgrad16_rows: shape / alignment (channel counts in multiples of 64)");
     SCN_ARG((long)R * Co * 2 < 0x7fffffffL && src_rows * C * 2 < 0x7fffffffL, "wgrad16_rows: map exceeds the descriptor range");
     SCN_ARG(gs == 0 || (gHi > 0 && gWi > 0 && gHo > 0 && gWo > 0 && R % (gHo * gWo) == 0), "wgrad16_rows: gather geometry");
+    const long mn = (long)Co * C;
+    const LaunchPlan p = wgrad_plan(SCNATTN_PLAN_WGRAD16_W1, 16, (R + 15) / 16, (Co / 64) * (C / 64), 512, mn, ws != nullptr,
+                                    ws_floats, force_split);
+    SCN_ARG(force_split <= 0 || p.S == force_split, "wgrad16_rows: forced split does not fit");
+    if (query.answer(p)) return 0;
     W16Args g{};
     g.dy = (const bf16_t*)dy; g.x = (const bf16_t*)x; g.C = C; g.Co = Co; g.R = R; g.src_rows = src_rows;
     g.gs = gs; g.gHi = gHi; g.gWi = gWi; g.gHo = gHo; g.gWo = gWo; g.goh = goh; g.gow = gow;
-    g.Q = (R + 15) / 16;
-    g.tci = C / 64;
-    g.ntiles = (Co / 64) * g.tci;
-    const long mn = (long)Co * C;
-    const int S = wgrad_split(g.ntiles, g.Q, 512, mn, ws, ws_floats, force_split);
-    SCN_ARG(force_split <= 0 || S == force_split, "wgrad16_rows: forced split does not fit");
-    g.S = S; g.ldo = ldo; g.slab_ld = C; g.slab_stride = mn;
-    g.out = S > 1 ? ws : dw;
-    hipLaunchKernelGGL(wgrad16_w1_kernel, dim3(g.ntiles * S), dim3(256), 0, st, g);
+    g.Q = p.Q; g.tci = C / 64; g.ntiles = p.ntiles;
+    g.S = p.S; g.ldo = ldo; g.slab_ld = C; g.slab_stride = mn;
+    g.out = p.S > 1 ? ws : dw;
+    hipLaunchKernelGGL(wgrad16_w1_kernel, dim3(p.grid_x), dim3(256), 0, st, g);
     SCN_LAUNCH_CHECK();
-    if (S > 1) SCN_TRY(cgemm_reduce(st, ws, S, Co, C, dw, ldo));
+    if (p.second) SCN_TRY(cgemm_reduce(st, ws, p.S, Co, C, dw, ldo));
     return 0;
 }
 

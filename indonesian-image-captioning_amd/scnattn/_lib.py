@@ -62,6 +62,19 @@ class BnEval16(C.Structure):       # scnattn_bn_eval16: the same layout, res is 
     _fields_ = BnEval._fields_
 
 
+class LaunchPlan(C.Structure):     # scnattn_launch_plan
+    _fields_ = [(n, C.c_int) for n in ("family", "mi", "tA", "tB", "pro", "epi", "gather", "c3", "vec", "out_bf16", "wbf",
+                                       "nb", "chunks", "empty", "kslice", "seg", "Q", "ntiles", "S", "kper", "mt", "nt")] + \
+               [("tiles", C.c_long)] + \
+               [(n, C.c_int) for n in ("grid_x", "grid_y", "grid_z", "in_launch", "second", "second_mode")]
+
+
+# SCNATTN_PLAN_* / SCNATTN_SECOND_*
+PLAN_NONE, PLAN_CGEMM, PLAN_SGEMM, PLAN_SKINNY, PLAN_CGEMM16, PLAN_CONV3_WGRAD, PLAN_WGRAD16_W9, PLAN_WGRAD16_W1 = range(8)
+(SECOND_NONE, SECOND_CREDUCE, SECOND_CSTATS1, SECOND_CSTATS2_SLABS, SECOND_CSTATS2_C, SECOND_CREDUCE16, SECOND_CGEMM_REDUCE,
+ SECOND_SPLITK_REDUCE) = range(8)
+
+
 class ImageDesc(C.Structure):      # scnattn_image_desc
     _fields_ = [("offset", C.c_int64), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("tab_h", C.c_int32),
                 ("tab_v", C.c_int32), ("reserved", C.c_int32)]
@@ -70,6 +83,7 @@ class ImageDesc(C.Structure):      # scnattn_image_desc
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
+    "scnattn_plan_next": ([C.POINTER(LaunchPlan)], i32),
     "scnattn_profile_collect": ([C.POINTER(C.c_double)], i32),
     "scnattn_seq_workspace": ([C.POINTER(Dims), C.POINTER(Pool), C.POINTER(sz), C.POINTER(sz)], i32),
     "scnattn_seq_fwd": ([vp, C.POINTER(Dims), C.POINTER(Params), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -245,6 +259,19 @@ def check(rc, what):
 
 def call(name, *args):
     check(getattr(lib(), name)(*args), name)
+
+
+def plan(name, *args):
+    """The launch plan of the call `name(*args)` (scnattn_plan_next): its argument checks and its dispatch policy run, nothing
+    is launched, no HIP API is called -- the pointers may be host memory.  A refusal raises as the call would; an empty
+    problem gives family == PLAN_NONE."""
+    h, out = lib(), LaunchPlan()
+    try:
+        h.scnattn_plan_next(C.byref(out))
+        check(getattr(h, name)(*args), name)
+    finally:
+        h.scnattn_plan_next(None)
+    return out
 
 
 def ptr(t):

@@ -1,8 +1,8 @@
-"""fp64 references, case table, inputs, judges and dispatch mirrors of the bf16 TRAINING convolution kernels:
+"""fp64 references, case table, inputs, judges and instance names of the bf16 TRAINING convolution kernels:
 csrc/cgemm16.hip (cgemm16_kernel EPI 0 / 1 / 2, creduce16_kernel; through scnattn_cgemm16, scnattn_conv3x3_fwd16 and
 scnattn_conv3x3_dgrad16), csrc/wgrad16.hip (scnattn_wgrad16_3x3 = w9, scnattn_wgrad16_rows = w1) and scnattn_bf16_weights.
-Shared by tests/test_conv16_refs.py (CPU) and tests/test_gpu_conv16_kernels.py; tests/eval16_refs.py (EPI 3) calls the
-mirror of `cgemm16()` kept here.
+Shared by tests/test_conv16_refs.py (CPU) and tests/test_gpu_conv16_kernels.py; tests/eval16_refs.py (EPI 3) reads plans
+through `names` too.
 
 References: the index-arithmetic products of tests/conv_refs.py (conv1x1_* / conv3_* on gather_rows / fwd_taps /
 dgrad_taps) on the bf16 operands widened exactly to fp64.  The operands are generated as bf16, so every product term is
@@ -43,10 +43,10 @@ MFMA_WIDEN is the one admissible widening, the derived factor for TRUNCATING add
 the matrix-instruction products alone.  It is 1 unless a measurement on the GPU shows an fp32-output instance above b; an
 error above 2 b is a kernel bug.  DESIGN.md 3 states which value holds and why.
 
-The mirrors name kernel instances, they never compute a value: mirror_cgemm16 follows `cgemm16()` (csrc/cgemm16.hip: row
-tile MI with the c3 == 4 factor of 4, S by policy / force_split, epi == 2 un-split, c3 == 4 never split, kper in whole 32s
-with S recomputed, the launched instance (MI, EPI, GATHER, OBF, C3) and the creduce16<OBF, STATS> that follows);
-wgrad_split follows csrc/tile.h with Q and ntiles as wgrad16_3x3 / wgrad16_rows form them."""
+`names` renders the launch plan of a case's own call (scnattn_plan_next; test_gpu_conv16_kernels.dispatch) as the kernel
+instances of the parity report: the launched cgemm16 instance (MI, EPI, GATHER, OBF, C3) and the creduce16<OBF, STATS>
+that follows, or the wave-split weight gradient with its Q, ntiles and S.  The policy itself is stated once, in
+cgemm16_plan (csrc/cgemm16.hip) and wgrad_split (csrc/tile.h)."""
 import zlib
 from collections import namedtuple
 
@@ -55,6 +55,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_refs as CR
+from scnattn import _lib as L
 
 BF = torch.bfloat16
 U = CR.U
@@ -67,59 +68,25 @@ SENT16 = 0x7FC5
 cdiv = CR.cdiv
 
 
-# ==== the mirrors ========================================================================================================
-def mirror_cgemm16(M, N, K, c3=0, epi=0, gather=False, obf=True, force_mi=0, force_split=0, ws_floats=WS_FLOATS):
-    """csrc/cgemm16.hip cgemm16() -> dict(mi, S, kper, tiles, inst = (MI, EPI, GATHER, OBF, C3) of the product launch,
-    reduce = (OBF, STATS) of the creduce16 that follows | 'eval' | None, forced).  ValueError where the host refuses."""
-    mi = 2
-    if cdiv(M, 128) * cdiv(N, 128) * (4 if c3 == 4 else 1) < 256 and M > 64:
-        mi = 1
-    if force_mi in (1, 2):
-        mi = force_mi
-    tiles = cdiv(M, 64 * mi) * cdiv(N, 128)
-    S = 1
-    if c3 != 4 and ws_floats and tiles < 192 and K >= 512:
-        S = min(cdiv(512, tiles), K // 256, 16)
-        while S > 1 and S * M * N > ws_floats:
-            S -= 1
-        S = max(S, 1)
-    if epi == 2:
-        S = 1
-    forced = False
-    if force_split > 0 and c3 != 4 and epi != 2:
-        S, forced = force_split, True
-        if not (S == 1 or (ws_floats and S * M * N <= ws_floats and S <= 64)):
-            raise ValueError("cgemm16: forced split does not fit")
-    kper = cdiv(cdiv(K, S), 32) * 32
-    S = cdiv(K, kper)
-    obf_k = True if c3 else bool(obf)
-    kepi = 0 if (S > 1 or c3 == 4) else epi
-    reduce = None
-    if S > 1:
-        reduce = "eval" if epi == 3 else (obf_k, epi == 1)
-    return dict(mi=mi, S=S, kper=kper, tiles=tiles, inst=(mi, kepi, bool(gather) and c3 == 0, obf_k, c3), reduce=reduce,
-                forced=forced)
-
-
-def wgrad_split(ntiles, Q, target, mn, ws_floats, force_split):
-    """csrc/tile.h wgrad_split"""
-    S = force_split if force_split > 0 else (target + ntiles // 2) // ntiles
-    S = max(1, min(S, max(Q // 16, 1)))
-    while S > 1 and (not ws_floats or S * mn > ws_floats):
-        S -= 1
-    return S
-
-
-def mirror_wgrad(c, ws_floats=WS_FLOATS):
-    """wgrad16_3x3 / wgrad16_rows -> dict(kernel, Q, ntiles, S); ValueError where a forced split does not survive the clamps"""
-    if c.op == "w9":
-        Q, ntiles, mn = c.N * cdiv(c.Wi, 16) * c.Hi, (c.Cout // 32) * (c.Cin // 32), c.Cout * 9 * c.Cin
-    else:
-        Q, ntiles, mn = cdiv(rows_out(c), 16), (c.Cout // 64) * (c.Cin // 64), c.Cout * c.Cin
-    S = wgrad_split(ntiles, Q, 512, mn, ws_floats, c.split)
-    if c.split > 0 and S != c.split:
-        raise ValueError("wgrad16: forced split does not fit")
-    return dict(kernel=c.op, Q=Q, ntiles=ntiles, S=S)
+# ==== instance names, rendered from the launch plan of the real call (scnattn_plan_next) ===============================
+def names(p):
+    """launch plan -> dict(names = the kernel instances in launch order, S, and per family: cgemm16 mi, kper, tiles, inst =
+    (MI, EPI, GATHER, OBF, C3) of the product launch, reduce = (OBF, STATS) of the creduce16 that follows | 'eval' | None;
+    wave-split weight gradients kernel = 'w9' | 'w1', Q, ntiles)"""
+    if p.family in (L.PLAN_WGRAD16_W9, L.PLAN_WGRAD16_W1):
+        kernel = "w9" if p.family == L.PLAN_WGRAD16_W9 else "w1"
+        assert (p.second == L.SECOND_CGEMM_REDUCE) == (p.S > 1)
+        return dict(kernel=kernel, Q=p.Q, ntiles=p.ntiles, S=p.S, names=["wgrad16_%s (S %s 1)" % (kernel, ">" if p.S > 1 else "=")])
+    assert p.family == L.PLAN_CGEMM16 and (p.second == L.SECOND_CREDUCE16) == (p.S > 1)
+    obf = bool(p.out_bf16)
+    d = dict(mi=p.mi, S=p.S, kper=p.kper, tiles=p.tiles, inst=(p.mi, p.epi, bool(p.gather), obf, p.c3), reduce=None,
+             names=["cgemm16<MI %d, EPI %d, %s, %s, C3 %d>" % (p.mi, p.epi, "gather" if p.gather else "plain",
+                                                               "bf16" if obf else "fp32", p.c3)])
+    if p.second:
+        d["reduce"] = "eval" if p.second_mode == 2 else (obf, p.second_mode == 1)
+        if p.second_mode != 2:
+            d["names"].append("creduce16<%s, %s>" % ("bf16" if obf else "fp32", "stats" if p.second_mode == 1 else "plain"))
+    return d
 
 
 # ==== cases ==============================================================================================================
@@ -169,21 +136,6 @@ def out_shape(c):
     if c.op in ("d1", "d3", "s3"):
         return rows_in(c), c.Cin
     return c.Cout, (9 if c.op == "w9" or "t" in c.var else 1) * c.Cin
-
-
-def mirror(c):
-    """-> dict(names = the kernel instances of the case in launch order, S, + the fields of the op's own mirror)"""
-    if c.op in ("w9", "w1"):
-        d = mirror_wgrad(c)
-        d["names"] = ["wgrad16_%s (S %s 1)" % (c.op, ">" if d["S"] > 1 else "=")]
-        return d
-    p = gemm_of(c)
-    d = mirror_cgemm16(p["M"], p["N"], p["K"], p["c3"], c.epi, p["gather"], c.obf, c.mi, c.split)
-    mi, kepi, gather, obf, c3 = d["inst"]
-    d["names"] = ["cgemm16<MI %d, EPI %d, %s, %s, C3 %d>" % (mi, kepi, "gather" if gather else "plain", "bf16" if obf else "fp32", c3)]
-    if d["reduce"]:
-        d["names"].append("creduce16<%s, %s>" % ("bf16" if d["reduce"][0] else "fp32", "stats" if d["reduce"][1] else "plain"))
-    return d
 
 
 # ---- the table: the smallest shapes at which a path can go wrong ----------------------------------------------------------
@@ -523,7 +475,8 @@ def applies(defect, c):
     if defect == "pad_row_stats":
         return c.epi == 1 and "s" in c.var and M % 64 != 0
     if defect == "slot_tm":
-        return c.epi in (1, 2) and M > 64 and mirror(c)["mi"] == 2 and mirror(c)["S"] == 1
+        from test_gpu_conv16_kernels import dispatch        # the row tile and the split the library plans for the case
+        return c.epi in (1, 2) and M > 64 and dispatch(c)["mi"] == 2 and dispatch(c)["S"] == 1
     if defect in ("mask_ge", "sums_unrounded"):
         return c.epi == 2 and c.Cin >= 8
     if defect == "mask_unfused":                # the residual is planted at a row past the first three

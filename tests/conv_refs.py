@@ -1,7 +1,7 @@
-"""fp64 references of the fp32 convolution forms of the trunk (include/scnattn.h:282-373: scnattn_cgemm with a
+"""fp64 references of the fp32 convolution forms of the trunk (include/scnattn.h: scnattn_cgemm with a
 scnattn_conv_extra, scnattn_conv1x1_fwd / _dgrad / _wgrad, scnattn_conv3x3_fwd / _dgrad / _dgrad_strided / _wgrad,
-the two _bn_eval forms), the case tables of tests/test_gpu_conv_kernels.py, their inputs, the judges, and a Python mirror
-of the host dispatch that says which kernel instance (and which second launch) a case reaches.
+the two _bn_eval forms), the case tables of tests/test_gpu_conv_kernels.py, their inputs, the judges, and `name`, which
+renders the launch plan of a case's own call (scnattn_plan_next) as the kernel instance and second launch it reaches.
 
 Written from the header comments.  Row gathers, the nine taps and the zero padding are plain index arithmetic here
 (gather_rows, fwd_taps, dgrad_taps): an index table [rows][9] of source rows, -1 where the tap falls outside the image.
@@ -9,10 +9,9 @@ Nothing comes from F.conv2d; tests/test_conv_refs.py compares the two.  Like tes
 the dtype of its operands and carries `out_abs` (sum of the magnitudes of the terms of each element) and `out_n` (their
 number: the K of the launch) for the bound (n + 8) * 2^-24 * sum|terms| of DESIGN.md 3.
 
-The mirror follows csrc/api.cpp:145-262 (which product an entry point is), csrc/cgemm.hip:1161-1270 `cgemm()` (row tile,
-split, in-launch combine or second launch), :1075-1122 launch_ev / launch_conv3 / launch_layout (the template instance) and
-csrc/conv3.hip:180-200 conv3x3_wgrad_halo with csrc/tile.h:87-94 wgrad_split.  It is used to name instances, never to
-compute a value.
+Which product an entry point launches, the row tile, the split and the second launch are never restated here: the GPU
+module asks the library (test_gpu_conv_kernels.dispatch).  What stays is layout arithmetic that bears on expected values
+(row_tiles, stat_ld, out_hw, rows_in / rows_out, the tap tables).
 """
 import zlib
 from collections import namedtuple
@@ -20,9 +19,10 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from scnattn import _lib as L
+
 U = 2.0 ** -24
-SROWS = 64                  # rows per statistics partial (csrc/cgemm.hip:60)
-COMBINE_MAX = 8             # option cgemm_combine_max
+SROWS = 64                  # rows per statistics partial (SROWS of csrc/cgemm.hip)
 OPTION_DEFAULTS = {"cgemm_combine": 1, "cgemm_mi": 0}
 
 
@@ -72,26 +72,6 @@ def rows_out(c):
     return c.N * Ho * Wo
 
 
-def product(c):
-    """csrc/api.cpp:145-262: the GEMM an entry point launches -> dict(tA, tB, M, N, K, c3, gather)"""
-    Ri, Ro = rows_in(c), rows_out(c)
-    if c.op == "f1":
-        return dict(tA=0, tB=1, M=Ro, N=c.Cout, K=c.Cin, c3=0, gather=c.s > 1)
-    if c.op == "d1":
-        return dict(tA=0, tB=int("t" in c.var), M=Ri, N=c.Cin, K=c.Cout, c3=0, gather=False)
-    if c.op == "w1":
-        return dict(tA=1, tB=0, M=c.Cout, N=c.Cin, K=Ro, c3=0, gather=c.s > 1)
-    if c.op == "f3":
-        return dict(tA=0, tB=1, M=Ro, N=c.Cout, K=9 * c.Cin, c3=1, gather=False)
-    if c.op == "d3":
-        return dict(tA=0, tB=0, M=Ri, N=c.Cin, K=9 * c.Cout, c3=2, gather=False)
-    if c.op == "s3":
-        return dict(tA=0, tB=0, M=Ro, N=c.Cin, K=9 * c.Cout, c3=4, gather=False)
-    if c.op == "w3":
-        return dict(tA=1, tB=0, M=c.Cout, N=9 * c.Cin, K=Ro, c3=3, gather=False)
-    raise ValueError(c.op)
-
-
 def out_shape(c):
     """(rows, columns) of the output map / weight gradient"""
     if c.op in ("f1", "f3"):
@@ -111,87 +91,21 @@ def ws_floats(c):
     return 16 * r * n if c.ws else 0
 
 
-# ==== the mirror of the host dispatch ====================================================================================
-def halo_lines(c):
-    """csrc/conv3.hip:183-187 -> (SEG, Q)"""
-    seg = 16 if c.Wi % 16 == 0 else 8
-    return seg, c.N * cdiv(c.Wi, seg) * c.Hi
+# ==== instance names, rendered from the launch plan of the real call (scnattn_plan_next) ===============================
+_SECOND = {L.SECOND_NONE: None, L.SECOND_CSTATS1: "cstats<1> from slabs", L.SECOND_CSTATS2_SLABS: "cstats<2> from slabs",
+           L.SECOND_CSTATS2_C: "cstats<2> from C", L.SECOND_CGEMM_REDUCE: "creduce<1>"}
 
 
-def mirror_halo(c):
-    """csrc/conv3.hip:180-200 + csrc/tile.h:87-94 -> (instance, second launch or None, S); ValueError where the host refuses"""
-    assert c.s == 1 and c.Cin % 32 == 0 and c.Cout % 32 == 0 and c.split >= 0
-    seg, Q = halo_lines(c)
-    ntiles = (c.Cout // 32) * (c.Cin // 32)
-    S = c.split if c.split > 0 else (512 + ntiles // 2) // ntiles
-    S = max(1, min(S, max(Q // 16, 1)))
-    while S > 1 and S * c.Cout * 9 * c.Cin > ws_floats(c):
-        S -= 1
-    if c.split > 0 and S != c.split:
-        raise ValueError("conv3x3_wgrad_halo: forced split does not fit")
-    return "conv3_wgrad<%d>" % seg, ("creduce<1>" if S > 1 else None), S
-
-
-def mirror(c):
-    """-> (instance, second launch or None, info).  csrc/cgemm.hip line numbers at each step."""
-    if c.op == "h3":
-        inst, second, S = mirror_halo(c)
-        return inst, second, dict(S=S)
-    o = dict(OPTION_DEFAULTS)
-    o.update(c.opts)
-    p = product(c)
-    tA, tB, M, N, K, c3, gather = (p[k] for k in ("tA", "tB", "M", "N", "K", "c3", "gather"))
-    pro, epi, wsf = c.pro, c.epi, ws_floats(c)
-    force_split = 0 if c.op in ("w3", "s3") else c.split          # api.cpp:242-262: no conv_extra on these entry points
-    force_mi = 0 if c.op in ("w3", "s3") else c.mi
-    assert N % 4 == 0                                             # :1161 vec: every output here takes 16-byte stores
-    mi = 2                                                        # :1165-1173
-    if cdiv(M, 128) * cdiv(N, 128) < 256 and M > 64 and c3 not in (1, 2, 4):
-        mi = 1
-    if c3 == 4 and cdiv(M, 128) * cdiv(N, 128) * 4 < 768:
-        mi = 1
-    if N <= 64 and M >= 128 and c3 != 3:
-        mi = 4
-    if o["cgemm_mi"] in (1, 2):
-        mi = o["cgemm_mi"]
-    if force_mi > 0:
-        mi = force_mi
-    assert mi in (1, 2) or (mi == 4 and c3 != 3)
-    tiles = cdiv(M, 128 if mi == 4 else 64 * mi) * cdiv(N, 64 if mi == 4 else 128)     # :1174-1176
-    S = 1
-    if wsf and tiles < 224 and K >= 256:                          # :1178-1194
-        target = 768 if c3 == 3 else (1100 if (not tA and K >= 4096 and not c3) else 512)
-        S = min(cdiv(target, tiles), K // 128, 128)
-        while S > 1 and S * M * N > wsf:
-            S -= 1
-        S = max(S, 1)
-    assert not (wsf and not c3 and S == 1 and 224 <= tiles < 768 and K >= 1536)        # :1199 not mirrored
-    if c3 == 4:                                                   # :1206
-        S = 1
-    if c3 in (1, 2) and wsf:                                      # :1207-1212
-        S = max(1, min(4, 512 // max(tiles, 1)))
-        while S > 1 and S * M * N > wsf:
-            S -= 1
-    if force_split > 0 and c3 != 4:                               # :1213-1216
-        S = force_split
-        if not (S == 1 or (wsf and S * M * N <= wsf and S <= 128)):
-            raise ValueError("cgemm: forced split does not fit")
-    if epi == 3 and S > 1:                                        # :1220-1223
-        S = min(S, COMBINE_MAX)
-        if not (o["cgemm_combine"] and S > 1):
-            S = 1
-    kper = cdiv(cdiv(K, S), 16) * 16                              # :1224-1226
-    S = cdiv(K, kper)
-    epi_in = epi != 2 or (not tA and not tB and pro == 0 and not gather and c3 == 0) or c3 == 2      # :1242
-    cnt = bool(S > 1 and o["cgemm_combine"] and S <= COMBINE_MAX and epi_in and (epi == 0 or not tA))  # :1244-1246
-    kepi = 0 if (S > 1 and not cnt) else (epi if epi_in else 0)                                      # :1249
-    lay = {(0, 1): "NT", (0, 0): "NN", (1, 0): "TN", (1, 1): "TT"}[(tA, tB)]
-    kpro = pro if ((lay == "NT" and pro == 1) or (lay == "TN" and pro == 2)) else 0
-    inst = "cgemm<MI%d %s PRO%d EPI%d G%d C3_%d>" % (mi, lay, kpro, kepi, int(gather), c3)           # :1075-1122
-    second = None
-    if (S > 1 and not cnt) or (epi == 2 and not epi_in):                                             # :1259-1268
-        second = "creduce<1>" if epi == 0 else "cstats<%d>%s" % (epi, " from C" if S == 1 else " from slabs")
-    return inst, second, dict(S=S, kper=kper, mi=mi, comb=cnt, tiles=tiles)
+def name(p):
+    """launch plan -> (instance, second launch or None, info): the kernel names of the parity report and the fields the
+    row selections read"""
+    if p.family == L.PLAN_CONV3_WGRAD:
+        return "conv3_wgrad<%d>" % p.seg, _SECOND[p.second], dict(S=p.S, Q=p.Q, ntiles=p.ntiles)
+    assert p.family == L.PLAN_CGEMM
+    lay = {(0, 1): "NT", (0, 0): "NN", (1, 0): "TN", (1, 1): "TT"}[(p.tA, p.tB)]
+    inst = "cgemm<MI%d %s PRO%d EPI%d G%d C3_%d>" % (p.mi, lay, p.pro, p.epi, p.gather, p.c3)
+    second = "creduce<%d>" % p.vec if p.second == L.SECOND_CREDUCE else _SECOND[p.second]
+    return inst, second, dict(S=p.S, kper=p.kper, mi=p.mi, comb=bool(p.in_launch), tiles=p.tiles)
 
 
 # ==== index tables =======================================================================================================
@@ -327,7 +241,7 @@ def mask_stats_ref(g, xhat):
 
 
 def bn_mask(z, mean, invstd, a, b, folded):
-    """The ReLU mask exactly as bn_relu_on (csrc/tile.h:56-59) decides it, and xhat as it computes it:
+    """The ReLU mask exactly as bn_relu_on (csrc/tile.h) decides it, and xhat as it computes it:
     xhat = fl32(fl32(z - mean) * invstd) in numpy float32 steps; the mask is the sign of fma(t, a, b), t = z (folded: a, b =
     scale, shift) or xhat (a, b = gamma, beta).  In fp64 the product of two fp32 numbers is exact and the sign of a sum
     survives its rounding, so `t * a + b > 0` in fp64 is the sign of the fp32 fma."""

@@ -1,4 +1,4 @@
-"""fp64 references, case table, inputs, judge and dispatch mirror of the eval BatchNorm epilogue on bf16 maps
+"""fp64 references, case table, inputs, judge and instance description of the eval BatchNorm epilogue on bf16 maps
 (include/scnattn.h scnattn_conv1x1_fwd_bn_eval16 / scnattn_conv3x3_fwd_bn_eval16; csrc/cgemm16.hip EPI 3 and the eval
 form of creduce16_kernel).  Shared by tests/test_eval16_refs.py (CPU) and tests/test_gpu_eval16_kernels.py.
 
@@ -14,10 +14,9 @@ the second term being the single round-to-nearest-even to bf16 of a value within
 roundoff 2^-8).  ReLU is 1-Lipschitz and commutes with the rounding, so the bound holds after the clamp and no element is
 excluded.
 
-The mirror is conv16_refs.mirror_cgemm16, the one mirror of csrc/cgemm16.hip `cgemm16()`, with epi = 3: row tile mi (1 when
-the 128-row grid has < 256 tiles and M > 64; force_mi), S (policy: tiles < 192 and K >= 512 with a workspace -> ceil(512 / tiles), at most K / 256, 16 and what the
-workspace holds; force_split), kper in whole 32s, and the epilogue: inside the product launch when S == 1 (EPI 3), else
-EPI 0 + the eval creduce16.  It names instances, it never computes a value."""
+`describe` reads the launch plan of a case's own call (scnattn_plan_next; test_gpu_eval16_kernels.dispatch) through
+conv16_refs.names: row tile mi, S, kper in whole 32s, and where the epilogue runs -- inside the product launch when S == 1
+(EPI 3), else EPI 0 + the eval creduce16.  The policy itself is cgemm16_plan (csrc/cgemm16.hip)."""
 from collections import namedtuple
 
 import torch
@@ -93,12 +92,12 @@ def mkn(c):
     return c.R, c.Cout, (9 if c.op == "f3" else 1) * c.Cin
 
 
-def mirror(c, ws_floats=WS_FLOATS):
-    """-> dict(mi, S, kper, inst = (MI, EPI, GATHER, C3) of the product launch, reduce = 'eval' | None, forced)"""
-    M, N, K = mkn(c)
-    d = C16.mirror_cgemm16(M, N, K, c3=1 if c.op == "f3" else 0, epi=3, gather=c.gather, obf=True, force_mi=c.mi, force_split=c.split,
-                           ws_floats=ws_floats)
-    mi, kepi, gather, _, c3 = d["inst"]
+def describe(c, plan):
+    """the launch plan of the case's call -> dict(mi, S, kper, inst = (MI, EPI, GATHER, C3) of the product launch,
+    reduce = 'eval' | None, forced = the case asks for its split)"""
+    d = C16.names(plan)
+    mi, kepi, gather, obf, c3 = d["inst"]
+    assert obf
     return dict(mi=mi, S=d["S"], kper=d["kper"], inst=(mi, kepi, gather, c3), reduce=d["reduce"], forced=c.split > 0)
 
 

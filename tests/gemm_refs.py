@@ -10,6 +10,8 @@ the terms of each element, and `x_n`, their number: what kernel_harness._sum_ok 
 """
 import torch
 
+from scnattn import _lib as L
+
 
 def cdiv(a, b):
     return -(-a // b)
@@ -53,12 +55,30 @@ def gemm(a, b, ta=False, tb=False, alpha=1.0, beta=0.0, c0=None, bias=None, rowm
     return {"c": c, "c_abs": c_abs, "c_n": n}
 
 
+# ---- instance names, rendered from the launch plan of the real call (scnattn_plan_next) -------------------------------
+def skinny_name(p):
+    """"nb<NB> c<chunks> v<XVEC> e<empty slices> z<grid.z>" of a skinny plan"""
+    assert p.family == L.PLAN_SKINNY and (p.wbf != 2 or p.nb % 2 == 0)
+    return "nb%d c%d v%d e%d z%d" % (p.nb, p.chunks, p.vec, p.empty, p.grid_z)
+
+
+def dense_name(p):
+    """"sgemm v<VEC> S<S>" or "cgemm mi<mi> S<S> <-|comb|red> <vst|sst>" of a plain dense product's plan"""
+    if p.family == L.PLAN_SGEMM:
+        assert (p.second == L.SECOND_SPLITK_REDUCE) == (p.S > 1)
+        return "sgemm v%d S%d" % (p.vec, p.S)
+    assert p.family == L.PLAN_CGEMM and (p.pro, p.epi, p.gather, p.c3) == (0, 0, 0, 0)
+    assert p.second in (L.SECOND_NONE, L.SECOND_CREDUCE)
+    assert p.S == 1 or bool(p.in_launch) != bool(p.second)
+    return "cgemm mi%d S%d %s %s" % (p.mi, p.S, "-" if p.S == 1 else "comb" if p.in_launch else "red", "vst" if p.vec else "sst")
+
+
 # ---- skinny -------------------------------------------------------------------------------------------------------------
-KW = 64     # csrc/skinny.hip:32, k per wave per chunk
+KW = 64     # KW of csrc/skinny.hip, k per wave per chunk
 
 
 def skinny_blocking(K, ksplit, form):
-    """csrc/skinny.hip:265-270: k per wave `per` = ceil(ceil(K / ksplit) / 4) in whole 8-k blocks (whole 16-k blocks for the
+    """skinny_plan of csrc/skinny.hip: k per wave `per` = ceil(ceil(K / ksplit) / 4) in whole 8-k blocks (whole 16-k blocks for the
     bf16 matrix instruction, form "bf16"), in whole 64-k chunks when above 64; kslice = 4 * per.
     -> (per, nb = 8-k blocks per wave per chunk, chunks, kslice)"""
     per = cdiv(cdiv(K, ksplit), 4)

@@ -144,11 +144,21 @@ class GBufI:
         return host[16:16 + self.n]
 
 
-def _call(name, dev, *args):
-    from scnattn._lib import call
+CPU = torch.device("cpu")
+
+
+def _call(name, dev, *args, arm=False):
+    """The C-ABI call on the GPU `dev`, synchronised.  With dev = CPU nothing runs: the same arguments (host windows of the
+    same alignment and leading dimensions) go through scnattn_plan_next and the launch plan of the call is returned -- what
+    the library would launch, from the library; a refusal raises the same RuntimeError either way.  arm: the same query with
+    the GPU's own windows and stream."""
+    from scnattn._lib import call, plan
+    if dev.type == "cpu":
+        return plan(name, None, *args)
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    call(name, st, *args)
+    got = plan(name, st, *args) if arm else call(name, st, *args)
     torch.cuda.synchronize()
+    return got
 
 
 # ---- judging ------------------------------------------------------------------------------------------------------------

@@ -4,14 +4,16 @@
   2. torch's own CPU fp32 evaluation passes every judge at every case -- the inputs keep the reference alone inside the
      derived bounds -- and its worst err / bound per kind of output goes to the run's parity report;
   3. every planted defect fails;
-  4. the dispatch mirror reaches every training instance of cgemm16_kernel (26), the four creduce16<OBF, STATS> and w9 / w1
-     with S = 1 and S > 1 -- asserted against a literal list;
-  5. the S / kper mirror and the wgrad_split mirror against rows worked by hand."""
+  4. the case table reaches every training instance of cgemm16_kernel (26), the four creduce16<OBF, STATS> and w9 / w1
+     with S = 1 and S > 1 -- asserted against a literal list, the instance of each case being what the library plans for
+     the case's own call (test_gpu_conv16_kernels.dispatch: scnattn_plan_next on host windows);
+  5. the library's S / kper and wave-split policy against rows worked by hand."""
 import pytest
 import torch
 
 import conv16_refs as R
 import conv_refs as CR
+import test_gpu_conv16_kernels as T
 
 _PRODUCTS = {}
 
@@ -141,15 +143,15 @@ WGRADS = ["wgrad16_w9 (S = 1)", "wgrad16_w9 (S > 1)", "wgrad16_w1 (S = 1)", "wgr
 
 def test_case_table_reaches_every_training_instance():
     assert len(TRAINING_INSTANCES) == 26 and len(set(TRAINING_INSTANCES)) == 26
-    m = [(c, R.mirror(c)) for c in R.CASES]
+    m = [(c, T.dispatch(c)) for c in R.CASES]
     reached = {n for _, d in m for n in d["names"]}
     assert reached == set(TRAINING_INSTANCES + REDUCERS + WGRADS), sorted(reached ^ set(TRAINING_INSTANCES + REDUCERS + WGRADS))
     gem = [(c, d) for c, d in m if c.op not in ("w9", "w1")]
     # the splits the table promises: forced 2 at K = 40 and K = 72, forced 2 / 4 at K = 1024, one the policy chose; a split
     # 3x3 and a split gather; beta = 1 through each plain reducer; both statistics reducers with and without a shift
     for K, S in ((40, 2), (72, 2), (1024, 2), (1024, 4)):
-        assert any(d["forced"] and d["S"] == S and R.gemm_of(c)["K"] == K for c, d in gem), (K, S)
-    assert any(not d["forced"] and d["S"] > 1 for c, d in gem)
+        assert any(c.split == S and d["S"] == S and R.gemm_of(c)["K"] == K for c, d in gem), (K, S)
+    assert any(c.split == 0 and d["S"] > 1 for c, d in gem)
     assert any(d["S"] > 1 and d["inst"][4] == 1 for c, d in gem) and any(d["S"] > 1 and d["inst"][2] for c, d in gem)
     for obf in (True, False):
         assert any(d["reduce"] == (obf, False) and "b" in c.var for c, d in gem)
@@ -164,8 +166,24 @@ def test_case_table_reaches_every_training_instance():
     assert all(c.Hi % 2 == 0 and c.Wi % 2 == 0 for c in R.CASES if c.op == "s3")
 
 
+def _plan_of(c, wsf=R.WS_FLOATS):
+    """the library's plan for a case outside the table, as conv16_refs.names renders it"""
+    return R.names(T._run(c, R.inputs(c), T.CPU, torch.empty(R.WS_FLOATS + 64), wsf=wsf))
+
+
 def test_policy_mirror_against_hand_worked_rows():
-    mc = R.mirror_cgemm16
+    def mc(M, N, K, c3=0, epi=0, obf=True, force_mi=0, force_split=0, ws_floats=R.WS_FLOATS):
+        """the plan of the M x N x K product: scnattn_cgemm16 (1x1 forward; the mask epilogue as a 1x1 d input), or with
+        c3 = 4 scnattn_conv3x3_dgrad16 at stride 2 on M maps of 2 x 2 (K = 9 * Cout)"""
+        if c3 == 4:
+            c = R.case("s3", M, 2, 2, N, K // 9, s=2, mi=force_mi, split=force_split)
+        elif epi == 2:
+            c = R.case("d1", M, 1, 1, N, K, epi=2, mi=force_mi, split=force_split)
+        else:
+            c = R.case("f1", M, 1, 1, K, N, epi=epi, mi=force_mi, split=force_split, obf=int(obf))
+        assert (R.gemm_of(c)["M"], R.gemm_of(c)["N"], R.gemm_of(c)["K"], R.gemm_of(c)["c3"]) == (M, N, K, c3)
+        return _plan_of(c, ws_floats)
+
     # K = 40 forced to 2 slabs: ceil(20 / 32) * 32 = 32 per slab, the second one 8 deep
     d = mc(65, 72, 40, force_split=2)
     assert (d["S"], d["kper"], 40 - d["kper"]) == (2, 32, 8)
@@ -176,7 +194,7 @@ def test_policy_mirror_against_hand_worked_rows():
     assert (mc(65, 72, 72, force_split=3)["S"], mc(65, 72, 64, force_split=4)["S"]) == (3, 2)
     # policy: 200 x 256 x 1024, M > 64 and 2 x 2 128-row tiles -> mi 1, 4 x 2 = 8 tiles, ceil(512 / 8) = 64 -> K / 256 = 4
     d = mc(200, 256, 1024)
-    assert (d["mi"], d["tiles"], d["S"], d["kper"], d["forced"], d["reduce"]) == (1, 8, 4, 256, False, (True, False))
+    assert (d["mi"], d["tiles"], d["S"], d["kper"], d["reduce"]) == (1, 8, 4, 256, (True, False))
     # the same without a workspace, and below K = 512: one launch
     assert mc(200, 256, 1024, ws_floats=0)["S"] == 1 and mc(200, 256, 480)["S"] == 1
     # M = 64 keeps the 128-row tile (M > 64 fails); force_mi wins
@@ -191,22 +209,35 @@ def test_policy_mirror_against_hand_worked_rows():
     assert (d["mi"], d["S"], d["inst"]) == (2, 1, (2, 0, False, True, 4))
     assert mc(65, 72, 576, c3=4)["mi"] == 1
     # a forced split the workspace cannot hold is refused
-    with pytest.raises(ValueError):
+    with pytest.raises(RuntimeError, match="cgemm16: forced split does not fit"):
         mc(64, 64, 64, force_split=2, ws_floats=16)
-    # ---- wgrad_split(ntiles, Q, target, mn, ws_floats, force) ----
-    ws = R.wgrad_split
-    assert ws(1, 36, 512, 32 * 9 * 32, R.WS_FLOATS, 0) == 2        # aim 512, at least 16 lines per slab: 36 // 16 = 2
-    assert ws(1, 31, 512, 9216, R.WS_FLOATS, 0) == 1               # fewer than 32 lines: no split
-    assert ws(1, 64, 512, 9216, R.WS_FLOATS, 3) == 3 and ws(1, 36, 512, 9216, R.WS_FLOATS, 3) == 2     # a force clamped
-    assert ws(1, 64, 512, 9216, 0, 0) == 1 and ws(1, 64, 512, 9216, 2 * 9216, 0) == 2                # what the workspace holds
-    assert ws(600, 64000, 512, 64, R.WS_FLOATS, 0) == 1            # (512 + 300) // 600 = 1
-    assert ws(400, 64000, 512, 64, R.WS_FLOATS, 0) == 1 and ws(300, 64000, 512, 64, R.WS_FLOATS, 0) == 2    # 712 // 400, 662 // 300
+
+    # ---- wgrad_split: aim 512 workgroups over ntiles blocks, at least 16 of the Q lines per slab, what the workspace holds.
+    # One 32 x 32 block (ntiles = 1, a slab of 32 * 9 * 32 = 9216 floats) is scnattn_wgrad16_3x3 on a 1 x Q x 16 map; many
+    # blocks are scnattn_wgrad16_rows on 16 * Q rows with Cin = 640 (10 blocks wide) and Cout = 64 * ntiles / 10 ----
+    def ws(ntiles, Q, ws_floats=R.WS_FLOATS, force=0):
+        if ntiles == 1:
+            c = R.case("w9", 1, Q, 16, 32, 32, split=force, obf=0)
+        else:
+            c = R.case("w1", 16 * Q, 1, 1, 640, 64 * (ntiles // 10), split=force, obf=0)
+        d = _plan_of(c, ws_floats)
+        assert (d["ntiles"], d["Q"]) == (ntiles, Q)
+        return d["S"]
+
+    assert ws(1, 36) == 2                                           # aim 512, at least 16 lines per slab: 36 // 16 = 2
+    assert ws(1, 31) == 1                                           # fewer than 32 lines: no split
+    assert ws(1, 64, force=3) == 3
+    with pytest.raises(RuntimeError, match="wgrad16_3x3: forced split does not fit"):
+        ws(1, 36, force=3)                                          # a force clamped to 2: the entry point refuses it
+    assert ws(1, 64, 0) == 1 and ws(1, 64, 2 * 9216) == 2           # what the workspace holds
+    assert ws(600, 64) == 1                                         # (512 + 300) // 600 = 1
+    assert ws(400, 64) == 1 and ws(300, 64) == 2                    # 712 // 400, 662 // 300 (two slabs of 1920 x 640 fit)
     # Q and ntiles as the two host functions form them
-    d = R.mirror_wgrad(R.case("w9", 2, 9, 20, 64, 96, obf=0))       # 2 segments of 16 per line: Q = 2 * 2 * 9, 3 x 2 blocks
+    d = _plan_of(R.case("w9", 2, 9, 20, 64, 96, obf=0))       # 2 segments of 16 per line: Q = 2 * 2 * 9, 3 x 2 blocks
     assert (d["Q"], d["ntiles"], d["S"]) == (36, 6, 2)
-    d = R.mirror_wgrad(R.case("w9", 1, 1, 3, 32, 32, obf=0))        # one line: three waves of the workgroup have none
+    d = _plan_of(R.case("w9", 1, 1, 3, 32, 32, obf=0))        # one line: three waves of the workgroup have none
     assert (d["Q"], d["S"]) == (1, 1)
-    d = R.mirror_wgrad(R.case("w1", 500, 1, 1, 128, 64, split=2, obf=0))    # 32 lines of 16 rows, the last one 4 deep
+    d = _plan_of(R.case("w1", 500, 1, 1, 128, 64, split=2, obf=0))    # 32 lines of 16 rows, the last one 4 deep
     assert (d["Q"], d["ntiles"], d["S"]) == (32, 2, 2)
-    with pytest.raises(ValueError):
-        R.mirror_wgrad(R.case("w1", 257, 1, 1, 64, 64, split=2, obf=0))     # 17 lines: the clamp reduces a forced 2
+    with pytest.raises(RuntimeError, match="wgrad16_rows: forced split does not fit"):
+        _plan_of(R.case("w1", 257, 1, 1, 64, 64, split=2, obf=0))     # 17 lines: the clamp reduces a forced 2

@@ -6,8 +6,8 @@ without a GPU:
     epilogue formed in fp32, passes every judge at every row (the worst err / bound is printed; 0.21 for the GEMM families);
   * the judges are sensitive: a copy of the reference with one planted defect fails at least one row, for each defect of
     DEFECTS;
-  * the Python mirror of the host dispatch (conv_refs.mirror, source lines cited there and in the GPU module's docstring) names
-    the instance and the second launch each row reaches; every instance of REQUIRED appears."""
+  * the library names the instance and the second launch each row reaches (test_gpu_conv_kernels.dispatch: the row's own
+    call through scnattn_plan_next on host windows, rendered by conv_refs.name); every instance of REQUIRED appears."""
 import numpy as np
 import pytest
 import torch
@@ -251,7 +251,7 @@ def test_planted_defect_fails(defect):
     assert applied and caught >= 1
 
 
-# ==== the mirror =========================================================================================================
+# ==== the dispatch, asked of the library ===============================================================================
 def _required():
     req = set()
     for mi in (1, 2, 4):
@@ -279,14 +279,14 @@ REQUIRED_ANY_MI = [
 
 
 def test_table_reaches_every_instance():
-    seen = {R.mirror(c)[:2] for c in R.CASES}
+    seen = {T.dispatch(c)[:2] for c in R.CASES}
     missing = sorted(_required() - seen, key=str)
     missing += [r for r in REQUIRED_ANY_MI if not any(r[0] in inst and r[1] == second for inst, second in seen)]
     assert not missing, missing
 
 
 def test_table_holds_the_edges_the_issue_names():
-    info = {R.case_id(c): (c, R.mirror(c)) for c in R.CASES}
+    info = {R.case_id(c): (c, T.dispatch(c)) for c in R.CASES}
     rows = list(info.values())
     # a 3x3 K-slice boundary inside a tap
     assert any(c.op == "f3" and m[2]["S"] > 1 and m[2]["kper"] % c.Cin for c, m in rows)
@@ -294,7 +294,7 @@ def test_table_holds_the_edges_the_issue_names():
     assert any(c.op == "f1" and c.pro == 1 and m[2]["S"] == 9 and not m[2]["comb"] for c, m in rows)
     assert any(c.op == "f1" and c.pro == 1 and c.epi == 1 and m[2]["S"] in (2, 3) and m[2]["comb"] for c, m in rows)
     # the halo kernel with fewer strip lines than waves, and every forced split legal
-    assert {R.halo_lines(c)[1] for c, m in rows if c.op == "h3"} >= {1, 2, 32, 54}
+    assert {m[2]["Q"] for c, m in rows if c.op == "h3"} >= {1, 2, 32, 54}
     assert {m[2]["S"] for c, m in rows if c.op == "h3"} == {1, 2, 3}
     # gathers on the non-square odd map, with both prologues; stat_shift NULL and given; both mask forms on each layout
     assert any(c.op == "f1" and c.s == 2 and c.pro == 1 and (c.Hi, c.Wi) == (7, 5) for c, m in rows)
@@ -310,7 +310,7 @@ def test_table_holds_the_edges_the_issue_names():
 
 
 def test_refusals_are_what_the_mirror_refuses():
+    """the library refuses every row of REFUSALS with the message the row names: the argument checks run on host windows"""
     for what, c, wsf, msg in T.REFUSALS:
-        if c.op == "h3" or "forced split" in what:
-            with pytest.raises(ValueError, match="forced split does not fit"):
-                R.mirror(c._replace(ws=0) if wsf else c)
+        with pytest.raises(RuntimeError, match=msg):
+            T._run(T.CPU, c, wsf=wsf)

@@ -1,10 +1,12 @@
 """CPU tests of tests/eval16_refs.py, the yardstick of tests/test_gpu_eval16_kernels.py: torch's own evaluation passes the
-derived per-element bound at every case, every planted defect fails it, and the dispatch mirror shows that the case table
-reaches every new kernel instance, the eval reducer, and both the forced and the policy-chosen split."""
+derived per-element bound at every case, every planted defect fails it, and the launch plans of the cases' own calls
+(test_gpu_eval16_kernels.dispatch: scnattn_plan_next on host windows) show that the case table reaches every new kernel
+instance, the eval reducer, and both the forced and the policy-chosen split."""
 import pytest
 import torch
 
 import eval16_refs as E
+import test_gpu_eval16_kernels as T
 
 _REFS = {}
 
@@ -64,7 +66,7 @@ def test_reference_is_the_fp64_module_arithmetic():
 
 
 def test_case_table_reaches_every_instance_and_both_splits():
-    m = [E.mirror(c) for c in E.CASES]
+    m = [T.dispatch(c) for c in E.CASES]
     insts = {d["inst"] for d in m}
     # cgemm16_kernel<MI, EPI 3, GATHER, OBF, C3>: plain and gathered 1x1, 3x3, each at both row tiles
     for want in [(mi, 3, gather, 0) for mi in (1, 2) for gather in (False, True)] + [(mi, 3, False, 1) for mi in (1, 2)]:
@@ -75,7 +77,7 @@ def test_case_table_reaches_every_instance_and_both_splits():
     assert any(not d["forced"] for d in split), "no case the policy splits by itself"
     assert any(d["inst"][3] == 1 for d in split) and any(d["inst"][2] for d in split)      # a split 3x3, a split gather
     # the shape the issue names: R = 128, 1024 -> 256 is split by the policy
-    d = E.mirror(E.f1(128, 1024, 256, True, True))
+    d = T.dispatch(E.f1(128, 1024, 256, True, True))
     assert (d["mi"], d["S"], d["kper"], d["forced"]) == (1, 4, 256, False)
     # kper in whole 32-k stages, every slab non-empty
     for c, d in zip(E.CASES, m):

@@ -3,8 +3,9 @@
   * the bound is attainable: the same product evaluated in fp32 on the CPU (torch.matmul; slice by slice for the skinny
     slabs) passes the judge at every table row -- the bound excludes nothing a correct fp32 evaluation produces;
   * the judge is sensitive: an fp32 result with one planted defect fails;
-  * a Python mirror of the host dispatch (source lines cited at each function) says that every row reaches the instance its
-    `inst` names and that every instance the GPU module lists is reached by a row.  The mirror is used for nothing else."""
+  * the library itself says which instance every row reaches: the row's own call goes through scnattn_plan_next on host
+    windows (test_gpu_gemm_kernels.skinny_plan / dense_plan), gemm_refs.skinny_name / dense_name render the plan; every
+    row reaches the instance its `inst` names and every instance the GPU module lists is reached by a row."""
 import pytest
 import torch
 
@@ -22,105 +23,40 @@ def _fails(kernel, name, got, ref):
         _sum_ok(kernel, name, got, ref)
 
 
-# ==== the mirror of the host dispatch ====================================================================================
-def pick_ksplit(rows, N, K, groups):
-    """csrc/skinny.hip:239-253 skinny_pick_ksplit"""
-    wgs = cdiv(N, 32) * groups * cdiv(max(rows, 1), 32)
-    ks = max(cdiv(K, 4 * 64), cdiv(256, wgs))
-    kmax = max(K // 32, 1)
-    ks = min(ks, kmax)
-    if 256 < wgs * ks < 384 and ks * 2 <= kmax:
-        ks *= 2
-    return max(1, min(ks, 16))
+# ==== the dispatch, asked of the library ===============================================================================
+_PLANS = {}
 
 
-def mirror_skinny(r):
-    """csrc/api.cpp:354-376 (ksplit <= 0 -> policy) and csrc/skinny.hip:265-273 -> (inst, causes of XVEC = false)"""
-    L = T.sk_layout(r)
-    ks = r.ks if r.ks > 0 else pick_ksplit(r.rows, r.N, r.K, r.groups)
-    per, nb, chunks, kslice = R.skinny_blocking(r.K, ks, r.form)
-    assert 1 <= nb <= 8 and per % (8 * nb) == 0 and (r.form != "bf16" or nb % 2 == 0)
-    causes = set()
-    if L["mis"]:
-        causes.add("mis")                       # GBuf: a 64-byte aligned allocation, 16 floats of margin, + mis
-    if L["ldx"] % 4:
-        causes.add("ldx")
-    if L["xg"] % 4:
-        causes.add("xg")
-    if r.K % 4 or r.K < 4:
-        causes.add("K")
-    empty = sum(1 for kb, ke in R.skinny_slices(r.K, ks, r.form) if kb == ke)
-    return "nb%d c%d v%d e%d z%d" % (nb, chunks, int(not causes), empty, cdiv(r.rows, 32)), causes, ks
+def skinny_dispatch(r):
+    """-> (inst, ksplit the call runs with, XVEC) from the launch plan of the row's own call"""
+    if r not in _PLANS:
+        p, ks = T.skinny_plan(r)
+        _PLANS[r] = (R.skinny_name(p), ks, bool(p.vec))
+    return _PLANS[r]
 
 
-def cgemm_supported(r, L):
-    """csrc/cgemm.hip:1060-1071"""
-    if L["misA"] or L["misB"] or L["lda"] % 4 or L["ldb"] % 4 or L["sA"] % 4 or L["sB"] % 4:
-        return False
-    if (r.M if r.ta else r.K) % 4 or (r.K if r.tb else r.N) % 4:
-        return False
-    return True
-
-
-def mirror_dense(r):
-    """csrc/sgemm.hip:220-273 sgemm_ws and csrc/cgemm.hip:1128-1272 cgemm (plain epilogue, no prologue / gather / 3x3)"""
-    L = T.dg_layout(r)
-    ws_floats = T.dg_ws_floats(r)
-    o = dict(T.OPTION_DEFAULTS)
-    o.update(r.opts)
-    M, N, K, batch = r.M, r.N, r.K, r.batch
-    if r.api == "cgemm":
-        assert cgemm_supported(r, L), "scnattn_cgemm would refuse this row"
-    if r.api == "cgemm" or (o["use_cgemm"] and cgemm_supported(r, L)):
-        vst = N % 4 == 0 and L["ldc"] % 4 == 0 and L["sC"] % 4 == 0 and not L["misC"]              # :1223
-        mi = 2                                                                                         # :1227-1234
-        if cdiv(M, 128) * cdiv(N, 128) * batch < 256 and M > 64:
-            mi = 1
-        if N <= 64 and M >= 128:
-            mi = 4
-        if o["cgemm_mi"] in (1, 2):
-            mi = o["cgemm_mi"]
-        if o.get("force_mi", 0) > 0:
-            mi = o["force_mi"]
-        tiles = cdiv(M, 128 if mi == 4 else 64 * mi) * cdiv(N, 64 if mi == 4 else 128) * batch         # :1236-1238
-        S = 1
-        if ws_floats and tiles < 224 and K >= 256:                                                      # :1240-1256
-            target = 1100 if (not r.ta and K >= 4096) else 512
-            S = min(cdiv(target, tiles), K // 128, 128)
-            while S > 1 and S * batch * M * N > ws_floats:
-                S -= 1
-            S = max(S, 1)
-        assert not (ws_floats and S == 1 and 224 <= tiles < 768 and K >= 1536)                          # :1261 not mirrored
-        if o.get("force_split", 0) > 0:                                                                 # :1275-1278
-            S = o["force_split"]
-            assert S == 1 or (ws_floats and S * batch * M * N <= ws_floats)
-        kper = cdiv(cdiv(K, S), 16) * 16                                                                # :1286-1288
-        S = cdiv(K, kper)
-        comb = S > 1 and o["cgemm_combine"] and S <= 8 and vst and tiles <= (1 << 16)                    # :1308-1310
-        how = "-" if S == 1 else ("comb" if comb else "red")
-        return "cgemm mi%d S%d %s %s" % (mi, S, how, "vst" if vst else "sst"), dict(S=S, kper=kper, K=K)
-    tiles = cdiv(N, 128) * cdiv(M, 128) * batch                                                         # sgemm.hip:238-251
-    S = 1
-    kmin = 128 if tiles <= 16 else 256
-    if ws_floats and tiles < 256 and K >= 2 * kmin:
-        S = min(cdiv(512, tiles), K // kmin, 16)
-        while S > 1 and S * batch * M * N > ws_floats:
-            S -= 1
-        S = max(S, 1)
-    kper = cdiv(cdiv(K, S), 16) * 16
-    S = cdiv(K, kper)
-    vec = not (L["misA"] or L["misB"] or L["lda"] % 4 or L["ldb"] % 4 or L["sA"] % 4 or L["sB"] % 4 or
-               (r.M if r.ta else r.K) % 4 or (r.K if r.tb else r.N) % 4)                                # :255-256
-    return "sgemm v%d S%d" % (int(vec), S), dict(S=S, kper=kper, K=K)
+def dense_dispatch(r):
+    """-> (inst, dict(S, kper, K)) from the launch plan of the row's own call"""
+    key = T._dense_id(r) + repr((r.lay, r.ws, sorted(r.opts.items())))
+    if key not in _PLANS:
+        p = T.dense_plan(r)
+        _PLANS[key] = (R.dense_name(p), dict(S=p.S, kper=p.kper, K=r.K))
+    return _PLANS[key]
 
 
 # ==== tables =============================================================================================================
 @pytest.mark.parametrize("r", T.SKINNY, ids=SKINNY_IDS)
 def test_skinny_rows_reach_the_instance_they_name(r):
-    inst, causes, ks = mirror_skinny(r)
+    inst, ks, xvec = skinny_dispatch(r)
     assert inst == r.inst
-    assert causes == ({r.x} if r.x else set()), "XVEC is false for %s, the row says %r" % (sorted(causes), r.x)
+    assert inst.startswith("nb%d c%d " % R.skinny_blocking(r.K, ks, r.form)[1:3])      # the slices the references are cut by
+    # XVEC is false for exactly the cause the row names: with that one cause taken away the same call loads 16 bytes
+    assert xvec == (not r.x), "XVEC is %s, the row says %r" % (xvec, r.x)
     L = T.sk_layout(r)
+    if r.x == "K":
+        assert (r.K % 4 or r.K < 4) and not L["mis"] and L["ldx"] % 4 == 0 and L["xg"] % 4 == 0
+    elif r.x:
+        assert r.K % 4 == 0 and r.K >= 4 and skinny_dispatch(r._replace(x=""))[2], "%r is not the only cause" % r.x
     assert L["xg"] > r.K and L["ldx"] > (r.groups - 1) * L["xg"] + r.K and L["ldw"] > r.N and L["wg"] > r.K * L["ldw"]
     assert L["ldy"] > r.N and L["yg"] > r.rows * L["ldy"] and L["yslab"] > r.groups * L["yg"]
 
@@ -128,8 +64,9 @@ def test_skinny_rows_reach_the_instance_they_name(r):
 def test_skinny_table_covers_every_instance():
     seen = {}
     for r in T.SKINNY:
-        inst, causes, ks = mirror_skinny(r)
+        inst, ks, xvec = skinny_dispatch(r)
         nb, chunks, v, e, z = (int(t[1 if t[0] in "cvez" else 2:]) for t in inst.split())
+        causes = {r.x} if r.x else set()            # test_skinny_rows_reach_the_instance_they_name holds the row to it
         seen.setdefault(r.form, []).append((nb, chunks, v, e, z, frozenset(causes), r))
     for form, nbs in (("f32", range(1, 9)), ("bf16w", range(1, 9)), ("bf16", (2, 4, 6, 8))):
         rows = seen[form]
@@ -152,13 +89,13 @@ def test_skinny_table_covers_every_instance():
     for K in (9, 33, 77, 128, 132, 192, 200, 256):
         assert {r.form for r in T.SKINNY if r.K == K and r.ks == 1} >= {"f32", "bf16w"}, K
     old = {(32, 128, 512, 1, 0), (32, 2048, 2048, 1, 0), (7, 45, 77, 1, 3), (32, 512, 1024, 4, 0), (5, 36, 40, 4, 2),
-           (1, 33, 9, 1, 1), (40, 64, 128, 1, 2), (32, 4608, 512, 1, 4), (32, 512, 4608, 1, 16)}     # test_gpu_parity.py:95-97
+           (1, 33, 9, 1, 1), (40, 64, 128, 1, 2), (32, 4608, 512, 1, 4), (32, 512, 4608, 1, 16)}     # the shapes of test_gpu_parity.py
     assert old <= {(r.rows, r.N, r.K, r.groups, r.ks) for r in T.SKINNY}
 
 
 @pytest.mark.parametrize("r", T.DENSE, ids=DENSE_IDS)
 def test_dense_rows_reach_the_instance_they_name(r):
-    inst, _ = mirror_dense(r)
+    inst, _ = dense_dispatch(r)
     assert inst == r.inst
     L = T.dg_layout(r)
     if "tn" not in r.lay:
@@ -167,7 +104,7 @@ def test_dense_rows_reach_the_instance_they_name(r):
 
 
 def test_dense_table_covers_every_instance():
-    rows = [(r, mirror_dense(r)) for r in T.DENSE]
+    rows = [(r, dense_dispatch(r)) for r in T.DENSE]
     inst = {r.inst for r in T.DENSE}
     lay = lambda r: (r.ta, r.tb)
     every = {(0, 0), (0, 1), (1, 0), (1, 1)}
@@ -258,7 +195,7 @@ def test_skinny_reference_equals_einsum_and_slices_follow_the_host():
         assert torch.allclose(r["sum_abs"], torch.einsum("rgk,gkn->grn", X.abs(), W.abs()), rtol=0, atol=1e-12)
         for s, (kb, ke) in enumerate(sl):
             assert torch.allclose(r["y"][s], torch.einsum("rgk,gkn->grn", X[:, :, kb:ke], W[:, kb:ke]), rtol=0, atol=1e-12)
-    # csrc/skinny.hip:265-270 at the sizes the comments of the GPU table quote
+    # skinny_plan (csrc/skinny.hip) at the sizes the comments of the GPU table quote
     assert R.skinny_blocking(33, 16, "f32") == (8, 1, 1, 32) and R.skinny_blocking(40, 2, "f32") == (8, 1, 1, 32)
     assert R.skinny_blocking(260, 1, "f32") == (128, 8, 2, 512) and R.skinny_blocking(1024, 1, "bf16") == (256, 8, 4, 1024)
     assert R.skinny_blocking(132, 1, "f32")[1] == 5 and R.skinny_blocking(132, 1, "bf16")[1] == 6
@@ -275,7 +212,7 @@ def _skinny_fp32(r, ks=None):
     """-> (slabs [ks, g, rows, N] evaluated slice by slice in fp32 on the CPU, the fp64 reference, the slices)"""
     X, W = T._skinny_inputs(r)
     Xo, Wo = R.skinny_operands(X, W, r.form)
-    ks = ks or mirror_skinny(r)[2]
+    ks = ks or skinny_dispatch(r)[1]
     slices = R.skinny_slices(r.K, ks, r.form)
     return R.skinny(Xo, Wo, slices)["y"], R.skinny(Xo.double(), Wo.double(), slices), slices
 

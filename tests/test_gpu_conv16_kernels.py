@@ -10,7 +10,8 @@ slots [row_tiles, stat_ld) of the partials and the tail of the split workspace. 
 fix dense rows; their maps are guarded in front and behind.  Every case runs twice and must give the same bits: slab order
 and the four-wave meet are fixed.  Every refusal returns -1 and leaves the output window as the sentinel.
 
-The worst err / bound per kernel instance (conv16_refs.mirror names it) and result goes to the run's parity report;
+The worst err / bound per kernel instance (conv16_refs.names renders it from the launch plan of the case's own call,
+scnattn_plan_next on host windows: `_run` on the CPU device) and result goes to the run's parity report;
 profiles/parity_report_conv16_kernels.txt keeps a copy."""
 import ctypes as C
 
@@ -19,7 +20,7 @@ import torch
 
 import conv16_refs as R
 import conv_refs as CR
-from kernel_harness import GBuf, GBuf16, SENT
+from kernel_harness import CPU, GBuf, GBuf16, SENT, _call
 
 pytestmark = pytest.mark.gpu
 
@@ -66,10 +67,12 @@ def _vec(dev, v):
     return GBuf(dev, v.shape, vals=v)
 
 
-def _run(c, I, dev, ws):
-    """one launch sequence of a case -> dict(out, part) read back through the guard checks"""
+def _run(c, I, dev, ws, wsf=R.WS_FLOATS):
+    """one launch sequence of a case -> dict(out, part) read back through the guard checks; on the CPU device nothing runs:
+    -> the launch plan of the same call (kernel_harness._call; the nine launches of a "t" case share one plan)"""
     from scnattn import _lib as L
-    h, st, cid = L.lib(), _stream(dev), R.case_id(c)
+    cid = R.case_id(c)
+    wsp = ws.data_ptr() if wsf else None
     rows, cols = R.out_shape(c)
     keep = []                                   # the guarded inputs stay alive until the synchronize
     part = None
@@ -78,23 +81,21 @@ def _run(c, I, dev, ws):
         x = GBuf16(dev, R.rows_in(c), c.Cin, vals=I["x"])
         if c.op == "w9":
             out = GBuf(dev, (rows, cols), out=True)
-            rc = h.scnattn_wgrad16_3x3(st, c.N, c.Hi, c.Wi, c.Cin, c.Cout, dy.ptr, x.ptr, out.ptr, ws.data_ptr(), R.WS_FLOATS, c.split)
+            plan = _call("scnattn_wgrad16_3x3", dev, c.N, c.Hi, c.Wi, c.Cin, c.Cout, dy.ptr, x.ptr, out.ptr, wsp, wsf, c.split)
         elif "t" in c.var:                      # nine launches into one [Cout][9][Cin] window
             out = GBuf(dev, (rows, cols), out=True)
             Ho, Wo = R.out_hw(c)
-            rc = 0
             for t in range(9):
-                rc = rc or h.scnattn_wgrad16_rows(st, R.rows_out(c), c.Cin, c.Cout, dy.ptr, x.ptr, R.rows_in(c), out.ptr.value + 4 * t * c.Cin,
-                                                  9 * c.Cin, c.s, c.Hi, c.Wi, Ho, Wo, t // 3 - 1, t % 3 - 1, ws.data_ptr(), R.WS_FLOATS, c.split)
+                plan = _call("scnattn_wgrad16_rows", dev, R.rows_out(c), c.Cin, c.Cout, dy.ptr, x.ptr, R.rows_in(c),
+                             out.ptr.value + 4 * t * c.Cin, 9 * c.Cin, c.s, c.Hi, c.Wi, Ho, Wo, t // 3 - 1, t % 3 - 1, wsp,
+                             wsf, c.split)
         else:
             out = GBuf(dev, (rows, cols), (c.Cin + 4, 1), out=True)
             Ho, Wo = R.out_hw(c)
             g = (c.s, c.Hi, c.Wi, Ho, Wo) if c.s > 1 else (0, 0, 0, 0, 0)
-            rc = h.scnattn_wgrad16_rows(st, R.rows_out(c), c.Cin, c.Cout, dy.ptr, x.ptr, R.rows_in(c), out.ptr, c.Cin + 4, *g, 0, 0,
-                                        ws.data_ptr(), R.WS_FLOATS, c.split)
-        L.check(rc, cid)
-        torch.cuda.synchronize()
-        return dict(out=out.read(cid), part=None)
+            plan = _call("scnattn_wgrad16_rows", dev, R.rows_out(c), c.Cin, c.Cout, dy.ptr, x.ptr, R.rows_in(c), out.ptr, c.Cin + 4, *g, 0, 0,
+                         wsp, wsf, c.split)
+        return plan if dev.type == "cpu" else dict(out=out.read(cid), part=None)
 
     ex = L.ConvExtra(epi=c.epi, force_split=c.split, force_mi=c.mi)
     if c.epi in (1, 2):
@@ -124,19 +125,30 @@ def _run(c, I, dev, ws):
         if p["gather"]:
             ex.stride, ex.Hi, ex.Wi = c.s, c.Hi, c.Wi
             ex.Ho, ex.Wo = R.out_hw(c)
-        rc = h.scnattn_cgemm16(st, p["M"], p["N"], p["K"], a.ptr, a.ld, b.ptr, b.ld, 1.0 if old is not None else 0.0, optr,
-                               cols + 8 if c.obf else cols + 4, c.obf, ws.data_ptr(), R.WS_FLOATS, C.byref(ex))
+        plan = _call("scnattn_cgemm16", dev, p["M"], p["N"], p["K"], a.ptr, a.ld, b.ptr, b.ld, 1.0 if old is not None else 0.0, optr,
+                               cols + 8 if c.obf else cols + 4, c.obf, wsp, wsf, C.byref(ex))
     elif c.op == "f3":
         a = GBuf16(dev, R.rows_in(c), c.Cin, vals=I["x"])
         b = GBuf16(dev, c.Cout, 9 * c.Cin, vals=I["w"])
-        rc = h.scnattn_conv3x3_fwd16(st, c.N, c.Hi, c.Wi, c.Cin, c.Cout, c.s, a.ptr, b.ptr, optr, C.byref(ex), ws.data_ptr(), R.WS_FLOATS)
+        plan = _call("scnattn_conv3x3_fwd16", dev, c.N, c.Hi, c.Wi, c.Cin, c.Cout, c.s, a.ptr, b.ptr, optr, C.byref(ex), wsp, wsf)
     else:
         a = GBuf16(dev, R.rows_out(c), c.Cout, vals=I["dy"])
         b = GBuf16(dev, c.Cin, 9 * c.Cout, vals=I["wt"])
-        rc = h.scnattn_conv3x3_dgrad16(st, c.N, c.Hi, c.Wi, c.Cin, c.Cout, c.s, a.ptr, b.ptr, optr, C.byref(ex), ws.data_ptr(), R.WS_FLOATS)
-    L.check(rc, cid)
-    torch.cuda.synchronize()
+        plan = _call("scnattn_conv3x3_dgrad16", dev, c.N, c.Hi, c.Wi, c.Cin, c.Cout, c.s, a.ptr, b.ptr, optr, C.byref(ex), wsp, wsf)
+    if dev.type == "cpu":
+        return plan
     return dict(out=out.read(cid), part=part.read(cid + " partials") if part is not None else None)
+
+
+_PLANS = {}
+
+
+def dispatch(c):
+    """-> conv16_refs.names of the case: its kernel instances in launch order and the plan fields, from the library"""
+    key = R.case_id(c)
+    if key not in _PLANS:
+        _PLANS[key] = R.names(_run(c, R.inputs(c), CPU, torch.empty(R.WS_FLOATS + 64)))
+    return _PLANS[key]
 
 
 def _bits(t):
@@ -147,7 +159,7 @@ def _bits(t):
 def test_conv16_case_vs_fp64(dev, ws, i):
     c = R.CASES[i]
     I = R.inputs(c)
-    names = " + ".join(R.mirror(c)["names"])
+    names = " + ".join(dispatch(c)["names"])
     got = _run(c, I, dev, ws)
     ok, ratios, fails = R.judge(c, I, got)
     for k, v in ratios.items():

@@ -25,20 +25,23 @@ How a case is judged (the harness of tests/kernel_harness.py; the j
 The worst err / bound per (instance, result) goes to the run's parity report; profiles/parity_report_conv_kernels.txt keeps a
 copy, profiles/conv_kernel_tests_kernel_coverage.txt the instances reached.  Wall time of the module on an MI355X: under 4 s.
 
-The dispatch the table mirrors (conv_refs.mirror; tests/test_conv_refs.py asserts without a GPU that every instance listed
-there is reached):
-  csrc/api.cpp:145-262       which product an entry point is (layout, M / N / K, the 3x3 mode, gather)
-  csrc/cgemm.hip:1161-1173   vector store; row tile mi (1 when the 128-row grid has < 256 tiles and M > 64, never for 3x3
+Which instance and which second launch a case reaches is asked of the library: `_run` on the CPU device sends the case's own
+call, on host windows of the same alignment and leading dimensions, through scnattn_plan_next (kernel_harness._call) and
+conv_refs.name renders the plan (`dispatch`); the row selections below are made from those plans at collection time, so the
+library is a prerequisite of this module.  tests/test_conv_refs.py asserts without a GPU that every instance is reached.
+The policy, for orientation (cgemm_plan of csrc/cgemm.hip states it):
+  api.cpp                    which product an entry point is (layout, M / N / K, the 3x3 mode, gather)
+  cgemm_plan                 vector store; row tile mi (1 when the 128-row grid has < 256 tiles and M > 64, never for 3x3
                              forward / d input; stride-2 d input: 1 below 768 class tiles; 4 when N <= 64 and M >= 128;
-                             option cgemm_mi, ex->force_mi)
-  :1178-1226                 S: policy (K >= 256), 3x3 forward / d input min(4, 512 / tiles), the stride-2 d input never,
-                             ex->force_split, epi 3 clamped to the in-launch combine; kper in whole 16s
-  :1242-1249                 epi_in (the mask epilogue runs in the launch only on NN without gather, or 3x3 d input);
-                             in-launch combine when S <= cgemm_combine_max and option cgemm_combine; kepi
-  :1075-1122                 launch_ev / launch_conv3 / launch_layout: the template instance
-  :1259-1268                 second launch: creduce_kernel<true> (epi 0), cstats_kernel<1> / <2> from slabs, or <2> reading C
+                             option cgemm_mi, ex->force_mi);
+                             S: policy (K >= 256), 3x3 forward / d input min(4, 512 / tiles), the stride-2 d input never,
+                             ex->force_split, epi 3 clamped to the in-launch combine; kper in whole 16s;
+                             epi_in (the mask epilogue runs in the launch only on NN without gather, or 3x3 d input);
+                             in-launch combine when S <= cgemm_combine_max and option cgemm_combine; kepi;
+                             second launch: creduce_kernel<true> (epi 0), cstats_kernel<1> / <2> from slabs, or <2> reading C
                              back (S = 0) for the mask epilogue on the NT layout (w_transposed)
-  csrc/conv3.hip:180-200     SEG 16 / 8, Q, wgrad_split (csrc/tile.h:87-94), cgemm_reduce when S > 1
+  launch_layout              launch_ev / launch_conv3: the template instance
+  conv3x3_wgrad_halo         SEG 16 / 8, Q, wgrad_split (csrc/tile.h), cgemm_reduce when S > 1
 """
 import ctypes as C
 
@@ -46,7 +49,7 @@ import pytest
 import torch
 
 import conv_refs as R
-from kernel_harness import GBuf, NAN, SENT, _bound_ok, _call, _write_report  # noqa: F401 (fixture)
+from kernel_harness import CPU, GBuf, NAN, SENT, _bound_ok, _call, _write_report  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -91,9 +94,10 @@ def _vec(dev, v):
     return GBuf(dev, v.shape, None, v)
 
 
-def _run(dev, c, opts=None, wsf=None, bufs=None):
+def _run(dev, c, opts=None, wsf=None, bufs=None, arm=False):
     """one call of the case's entry point -> (out [rows][cols], partials [2][C][row_tiles] or None, inputs); every guard word
-    of the output and of the partials is checked.  `bufs` receives the output GBuf before the call (refusals)."""
+    of the output and of the partials is checked.  `bufs` receives the output GBuf before the call (refusals).
+    On the CPU device, or with `arm` on the GPU, nothing runs: -> the launch plan of the same call (kernel_harness._call)."""
     from scnattn._lib import BnEval, ConvExtra, lib
     I = R.inputs(c)
     wide = "g" in c.var
@@ -111,7 +115,8 @@ def _run(dev, c, opts=None, wsf=None, bufs=None):
     if bufs is not None:
         bufs["out"] = b_out
     wsf = R.ws_floats(c) if wsf is None else wsf
-    ws = torch.full((wsf + 4,), NAN, device=dev) if wsf else None          # NaN: a slab read before it is written shows
+    # NaN: a slab read before it is written shows (a plan query touches no memory)
+    ws = (torch.empty(wsf + 4) if dev.type == "cpu" else torch.full((wsf + 4,), NAN, device=dev)) if wsf else None
     wsp = None if ws is None else C.c_void_p(ws.data_ptr())
     keep, b_part = [], None
     ex = ConvExtra()
@@ -150,35 +155,49 @@ def _run(dev, c, opts=None, wsf=None, bufs=None):
             bn.res, bn.ldres = keep[-1].ptr.value, c.Cout + 4
     exp = C.byref(ex)
     geo = (c.N, c.Hi, c.Wi, c.Cin, c.Cout)
+    if wide:        # scnattn_cgemm itself: the product of the 1x1 form, on rows wider than the matrices
+        A, B, tA, tB, K = {"f1": (b_x, b_w, 0, 1, c.Cin), "d1": (b_dy, b_w, 0, int("t" in c.var), c.Cout),
+                           "w1": (b_dy, b_x, 1, 0, Ro)}[c.op]
+        call = ("scnattn_cgemm", tA, tB, orows, ocols, K, 1.0, A.ptr, A.pos.shape[1] + 4, B.ptr, B.pos.shape[1] + 8, beta, b_out.ptr,
+                ocols + 4, None, None, 1, 0, 0, 0, wsp, wsf, exp)
+    elif c.op == "f1" and c.epi == 3:
+        call = ("scnattn_conv1x1_fwd_bn_eval", Ro, c.Cin, c.Cout, b_x.ptr, b_w.ptr, b_out.ptr, C.byref(bn), exp, wsp, wsf)
+    elif c.op == "f1":
+        call = ("scnattn_conv1x1_fwd", Ro, c.Cin, c.Cout, b_x.ptr, b_w.ptr, b_out.ptr, exp, wsp, wsf)
+    elif c.op == "d1":
+        call = ("scnattn_conv1x1_dgrad", Ri, c.Cin, c.Cout, b_dy.ptr, b_w.ptr, int("t" in c.var), beta, b_out.ptr, exp, wsp, wsf)
+    elif c.op == "w1":
+        call = ("scnattn_conv1x1_wgrad", Ro, c.Cin, c.Cout, b_dy.ptr, b_x.ptr, b_out.ptr, exp, wsp, wsf)
+    elif c.op == "f3" and c.epi == 3:
+        call = ("scnattn_conv3x3_fwd_bn_eval", *geo, c.s, b_x.ptr, b_w.ptr, b_out.ptr, C.byref(bn), exp, wsp, wsf)
+    elif c.op == "f3":
+        call = ("scnattn_conv3x3_fwd", *geo, c.s, b_x.ptr, b_w.ptr, b_out.ptr, exp, wsp, wsf)
+    elif c.op == "d3":
+        call = ("scnattn_conv3x3_dgrad", *geo, b_dy.ptr, b_w.ptr, b_out.ptr, exp, wsp, wsf)
+    elif c.op == "s3":
+        call = ("scnattn_conv3x3_dgrad_strided", *geo, c.s, b_dy.ptr, b_w.ptr, b_out.ptr, wsp, wsf)
+    else:
+        call = ("scnattn_conv3x3_wgrad", *geo, c.s, b_dy.ptr, b_x.ptr, b_out.ptr, wsp, wsf, c.split)
     with _Options(c.opts if opts is None else opts):
-        if wide:
-            p = R.product(c)
-            A, B = {"f1": (b_x, b_w), "d1": (b_dy, b_w), "w1": (b_dy, b_x)}[c.op]
-            _call("scnattn_cgemm", dev, p["tA"], p["tB"], p["M"], p["N"], p["K"], 1.0, A.ptr, A.pos.shape[1] + 4, B.ptr,
-                  B.pos.shape[1] + 8, beta, b_out.ptr, ocols + 4, None, None, 1, 0, 0, 0, wsp, wsf, exp)
-        elif c.op == "f1" and c.epi == 3:
-            _call("scnattn_conv1x1_fwd_bn_eval", dev, Ro, c.Cin, c.Cout, b_x.ptr, b_w.ptr, b_out.ptr, C.byref(bn), exp, wsp, wsf)
-        elif c.op == "f1":
-            _call("scnattn_conv1x1_fwd", dev, Ro, c.Cin, c.Cout, b_x.ptr, b_w.ptr, b_out.ptr, exp, wsp, wsf)
-        elif c.op == "d1":
-            _call("scnattn_conv1x1_dgrad", dev, Ri, c.Cin, c.Cout, b_dy.ptr, b_w.ptr, int("t" in c.var), beta, b_out.ptr, exp, wsp, wsf)
-        elif c.op == "w1":
-            _call("scnattn_conv1x1_wgrad", dev, Ro, c.Cin, c.Cout, b_dy.ptr, b_x.ptr, b_out.ptr, exp, wsp, wsf)
-        elif c.op == "f3" and c.epi == 3:
-            _call("scnattn_conv3x3_fwd_bn_eval", dev, *geo, c.s, b_x.ptr, b_w.ptr, b_out.ptr, C.byref(bn), exp, wsp, wsf)
-        elif c.op == "f3":
-            _call("scnattn_conv3x3_fwd", dev, *geo, c.s, b_x.ptr, b_w.ptr, b_out.ptr, exp, wsp, wsf)
-        elif c.op == "d3":
-            _call("scnattn_conv3x3_dgrad", dev, *geo, b_dy.ptr, b_w.ptr, b_out.ptr, exp, wsp, wsf)
-        elif c.op == "s3":
-            _call("scnattn_conv3x3_dgrad_strided", dev, *geo, c.s, b_dy.ptr, b_w.ptr, b_out.ptr, wsp, wsf)
-        else:
-            _call("scnattn_conv3x3_wgrad", dev, *geo, c.s, b_dy.ptr, b_x.ptr, b_out.ptr, wsp, wsf, c.split)
+        plan = _call(call[0], dev, *call[1:], arm=arm)
+    if dev.type == "cpu" or arm:
+        return plan
     return b_out.read("out"), (None if b_part is None else b_part.read("partials")), I
 
 
+_PLANS = {}
+
+
+def dispatch(c):
+    """-> (instance, second launch or None, info) of the case, from the launch plan of its own call"""
+    key = R.case_id(c)
+    if key not in _PLANS:
+        _PLANS[key] = R.name(_run(CPU, c))
+    return _PLANS[key]
+
+
 def _kernel(c):
-    inst, second, _ = R.mirror(c)
+    inst, second, _ = dispatch(c)
     return inst if second is None else "%s + %s" % (inst, second)
 
 
@@ -192,7 +211,7 @@ def test_conv_per_element(dev, c):
 def _split_rows(pred):
     rows = []
     for c in R.CASES:
-        if c.op != "h3" and not c.opts and R.mirror(c)[2]["S"] > 1 and R.mirror(c)[2]["comb"] and pred(c):
+        if c.op != "h3" and not c.opts and dispatch(c)[2]["S"] > 1 and dispatch(c)[2]["comb"] and pred(c):
             rows.append(c)
     return rows
 
@@ -212,7 +231,7 @@ def test_combine_modes_are_bit_identical(dev, c):
     """The reduce launch (cgemm_combine = 0), the write-through combine (1) and the release combine (2) sum the slabs in slab
     order and apply the same epilogue: the same bits in the product / the masked g.  The partials are compared between the two
     in-launch forms only (cstats_kernel adds a block's rows in another order).  The eval epilogue has no second-launch form --
-    with cgemm_combine = 0 it runs un-split (csrc/cgemm.hip:1217-1223), another order of the same sum -- so modes 1 and 2."""
+    with cgemm_combine = 0 it runs un-split (cgemm_plan), another order of the same sum -- so modes 1 and 2."""
     modes = (1, 2) if c.epi == 3 else (0, 1, 2)
     res = [_run(dev, c, {"cgemm_combine": m}) for m in modes]
     for r in res[1:]:
@@ -221,8 +240,8 @@ def test_combine_modes_are_bit_identical(dev, c):
         assert torch.equal(_bits(res[-2][1]), _bits(res[-1][1]))
 
 
-_TWICE_ROWS = _first_per(_split_rows(lambda c: True), lambda c: (c.op, c.epi, R.mirror(c)[2]["mi"])) + \
-    _first_per([c for c in R.CASES if c.op == "h3"], lambda c: (R.mirror(c)[0], R.mirror(c)[2]["S"]))
+_TWICE_ROWS = _first_per(_split_rows(lambda c: True), lambda c: (c.op, c.epi, dispatch(c)[2]["mi"])) + \
+    _first_per([c for c in R.CASES if c.op == "h3"], lambda c: (dispatch(c)[0], dispatch(c)[2]["S"]))
 
 
 @pytest.mark.parametrize("c", _TWICE_ROWS, ids=R.case_id)
@@ -231,6 +250,18 @@ def test_twice_is_bit_identical(dev, c):
     (o1, p1, _), (o2, p2, _) = _run(dev, c), _run(dev, c)
     assert torch.equal(_bits(o1), _bits(o2))
     assert p1 is None or torch.equal(_bits(p1), _bits(p2))
+
+
+def test_armed_call_launches_nothing(dev):
+    """scnattn_plan_next on the GPU's own buffers: the armed call returns its plan and leaves the sentinel-filled output
+    window and its guard words as they were; the same call right after, un-armed, is judged as usual"""
+    c = R.case("f1", 65, 1, 1, 16, 16)
+    bufs = {}
+    plan = _run(dev, c, bufs=bufs, arm=True)
+    assert R.name(plan) == dispatch(c) and plan.grid_x >= 1
+    assert bool((bufs["out"].flat.cpu().view(torch.int32) == SENT).all()), "an armed call wrote to its output"
+    out, part, I = _run(dev, c)
+    R.judge(c, I, out, part, _kernel(c), _bound_ok)
 
 
 # ==== helpers ============================================================================================================

@@ -16,10 +16,10 @@ How a case is judged:
 The worst error / bound ratio per kernel and result is appended to the run's parity report (test_gpu_parity._report);
 profiles/r05_parity_report_decoder_kernels.txt keeps a copy.
 
-The case tables mirror the dispatch of csrc/attention.hip: attn_scores :59-114 (early / loop / scalar) and :519;
-attn_context :556-569 (CU by ceil(P/8): <= 8 -> 8, 9..13 -> 13, 14..16 -> 8, > 16 -> 13; VEC by E % 4 and alignment);
-mean_pixels :637-644; attn_dalpha :667-675 (<8,2>: E >= 2048 and P <= 128; <4,4>: E >= 1024; <2,4>; scalar);
-attn_softmax_bwd :690-697; attn_datt1_post :826 (8 pixel rows per workgroup).  Picking: every value the sizes can take
+The case tables mirror the dispatch of csrc/attention.hip: attn_scores (early / loop / scalar);
+attn_context (CU by ceil(P/8): <= 8 -> 8, 9..13 -> 13, 14..16 -> 8, > 16 -> 13; VEC by E % 4 and alignment);
+mean_pixels; attn_dalpha (<8,2>: E >= 2048 and P <= 128; <4,4>: E >= 1024; <2,4>; scalar);
+attn_softmax_bwd; attn_datt1_post (8 pixel rows per workgroup).  Picking: every value the sizes can take
 appears at least once, and every (instance x optional pointer given / NULL) pair; sizes and options are otherwise paired
 round-robin instead of as a cross product.  Each row's comment names the instance or edge it is there for.
 """
@@ -510,7 +510,7 @@ def test_mul_bcast(dev, T, B, N):
 
 
 # ==== the sequence drivers and the stand-alone modules at sizes that are not multiples of 4 ==============================
-# The drivers carve `saved` / `scratch` in 256-byte granules (csrc/sequence.cpp:74-191), so every sub-buffer starts aligned,
+# The drivers carve `saved` / `scratch` in 256-byte granules (seq_workspace of csrc/sequence.cpp), so every sub-buffer starts aligned,
 # but with such sizes its rows and per-step slices do not: every kernel behind them has to take its scalar instance.  Construction of test_decoder_edge_batches
 # (fp64 oracle, TOL_OUT / TOL_GRAD, every parameter gradient, d encoder_out, d tags), no floors: the full-width case, where
 # a ReLU pre-activation within rounding of 0 is likely, uses the mask-unambiguous weights of

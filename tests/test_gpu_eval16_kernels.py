@@ -8,6 +8,8 @@ survive.  The two entries write dense rows (ldc = Cout), so there is no [Cout, l
 residual rows is where a column-range mistake of the epilogue would read.  Every case runs twice and must give the same
 bits (split sums are taken in slab order).  The refusals leave y as the sentinel.
 
+Which instance a case reaches is asked of the library: `_launch` on the CPU device sends the same call through
+scnattn_plan_next (kernel_harness._call) and eval16_refs.describe reads the plan.
 The worst err / bound per kernel instance goes to the run's parity report (test_gpu_parity._report);
 profiles/parity_report_eval16_kernels.txt keeps a copy."""
 import ctypes as C
@@ -16,7 +18,7 @@ import pytest
 import torch
 
 import eval16_refs as E
-from kernel_harness import GBuf16, SENT16  # noqa: F401
+from kernel_harness import CPU, GBuf16, SENT16, _call  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -60,10 +62,9 @@ def _inst_name(c, d):
     return s + (" + creduce16<eval> (%s S=%d)" % ("forced" if d["forced"] else "policy", d["S"]) if d["S"] > 1 else "")
 
 
-def _launch(c, I, dev, ws, y=None):
+def _launch(c, I, dev, ws, y=None, wsf=E.WS_FLOATS):
+    """the case's call -> the output window; on the CPU device nothing runs: -> the launch plan of the same call"""
     from scnattn import _lib as L
-    h = L.lib()
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     rows_in = I["x"].shape[0]
     xb = GBuf16(dev, rows_in, c.Cin, vals=I["x"])
     taps = I["w"].shape[1]
@@ -73,18 +74,21 @@ def _launch(c, I, dev, ws, y=None):
     vec = [I[k].to(dev) for k in ("gamma", "beta", "mean", "var")]
     bn = L.BnEval16(gamma=vec[0].data_ptr(), beta=vec[1].data_ptr(), mean=vec[2].data_ptr(), var=vec[3].data_ptr(), eps=c.eps,
                     res=rb.ptr if rb else None, ldres=c.Cout + 8 if rb else 0, relu=1 if c.relu else 0)
+    wsp = ws.data_ptr() if wsf else None
     if c.op == "f3":
         ex = L.ConvExtra(force_split=c.split, force_mi=c.mi)
-        rc = h.scnattn_conv3x3_fwd_bn_eval16(st, c.N, c.Hi, c.Hi, c.Cin, c.Cout, c.s, xb.ptr, wb.ptr, y.ptr, C.byref(bn), C.byref(ex),
-                                             ws.data_ptr(), E.WS_FLOATS)
+        plan = _call("scnattn_conv3x3_fwd_bn_eval16", dev, c.N, c.Hi, c.Hi, c.Cin, c.Cout, c.s, xb.ptr, wb.ptr, y.ptr, C.byref(bn),
+                     C.byref(ex), wsp, wsf)
     else:
         Ho = (c.Hi - 1) // c.s + 1 if c.gather else 0
         ex = L.ConvExtra(stride=c.s, Hi=c.Hi, Wi=c.Hi, Ho=Ho, Wo=Ho, force_split=c.split, force_mi=c.mi)
-        rc = h.scnattn_conv1x1_fwd_bn_eval16(st, c.R, c.Cin, c.Cout, xb.ptr, wb.ptr, y.ptr, C.byref(bn), C.byref(ex),
-                                             ws.data_ptr(), E.WS_FLOATS)
-    L.check(rc, "scnattn_conv%s_fwd_bn_eval16" % ("3x3" if c.op == "f3" else "1x1"))
-    torch.cuda.synchronize()
-    return y
+        plan = _call("scnattn_conv1x1_fwd_bn_eval16", dev, c.R, c.Cin, c.Cout, xb.ptr, wb.ptr, y.ptr, C.byref(bn), C.byref(ex), wsp, wsf)
+    return plan if dev.type == "cpu" else y
+
+
+def dispatch(c, wsf=E.WS_FLOATS):
+    """-> eval16_refs.describe of the case, from the launch plan of its own call"""
+    return E.describe(c, _launch(c, E.inputs(c), CPU, torch.empty(E.WS_FLOATS + 64), wsf=wsf))
 
 
 @pytest.mark.parametrize("i", range(len(E.CASES)), ids=[E.case_id(c) for c in E.CASES])
@@ -92,7 +96,7 @@ def test_bn_eval16_case_vs_fp64(dev, ws, i):
     c = E.CASES[i]
     I = E.inputs(c, i)
     ref = E.reference(c, I)
-    d = E.mirror(c)
+    d = dispatch(c)
     got = _launch(c, I, dev, ws).read(E.case_id(c))
     ok, ratio = E.judge(got, ref)
     name = _inst_name(c, d)

@@ -18,24 +18,23 @@ The worst err / bound per (instance, result) goes to the run's parity report; pr
 a copy, profiles/gemm_kernel_tests_kernel_coverage.txt the kernels a trace of this file saw launched (all 75 the dispatch
 below can pick).  Wall time of the module on an MI355X: under 4 s.
 
-The dispatch the tables mirror (tests/test_gemm_refs.py holds the Python mirror and asserts, without a GPU, that every
-row's `inst` is what the host code picks and that every instance below is reached):
-  skinny (csrc/skinny.hip)   :239-253 skinny_pick_ksplit (ksplit <= 0); :265-270 per / nb = 1..8 / chunks / kslice (the bf16
-                             matrix instruction: whole 16-k blocks, nb even); :271 XVEC = X 16-byte aligned, ldx % 4 == 0,
-                             xg % 4 == 0, K % 4 == 0, K >= 4; :273 grid = (ceil(N/32) * groups, ksplit, ceil(rows/32));
-                             :294-311 <NB, XVEC, WBF, BFM>.  inst = "nb<NB> c<chunks> v<XVEC> e<empty slices> z<grid.z>"
-  sgemm_ws (csrc/sgemm.hip)  :226 cgemm when use_cgemm and cgemm_supported (csrc/cgemm.hip:1060-1071: A, B 16-byte aligned,
-                             lda, ldb, sA, sB % 4 == 0, the contiguous extents % 4 == 0); :238-251 S (tiles < 256 and
-                             K >= 2 * kmin, kmin = 128 for <= 16 tiles else 256; target 512 workgroups; at most K / kmin, 16,
-                             and what fits ws), kper in whole 16s; :255-256 VEC; :269 splitk_reduce_kernel when S > 1.
-                             inst = "sgemm v<VEC> S<S>"
-  cgemm (csrc/cgemm.hip)     :1161 vector C store = N % 4 == 0, ldc % 4 == 0, sC % 4 == 0, C 16-byte aligned; :1165-1172 row
-                             tile mi (2: 128 rows; 1: 64 rows when the 128-row grid has < 256 tiles and M > 64; 4: 128 x 64
-                             when N <= 64 and M >= 128; option cgemm_mi, ex->force_mi); :1178-1194 S (tiles < 224 and
-                             K >= 256: 512 / tiles, at most K / 128 and what fits ws), :1213-1216 ex->force_split,
-                             :1224-1226 kper in whole 16s; :1244-1246 in-launch combine (finish_block) when S <= 8, vector
-                             store and option cgemm_combine, else :1259-1262 creduce_kernel<vector store>.
-                             inst = "cgemm mi<mi> S<S> <-|comb|red> <vst|sst>"
+Which instance a row reaches is asked of the library: the row's own call, built once (_skinny_call / _dense_call), goes
+through scnattn_plan_next on host windows of the same alignment and leading dimensions (kernel_harness._call with the CPU
+device) and gemm_refs.skinny_name / dense_name render the plan.  tests/test_gemm_refs.py asserts, without a GPU, that every
+row's `inst` is that name and that every instance below is reached:
+  skinny   the slice policy of the entry point (ksplit <= 0), skinny_plan: per / nb = 1..8 / chunks / kslice (the bf16 matrix instruction: whole
+           16-k blocks, nb even); XVEC = X 16-byte aligned, ldx % 4 == 0, xg % 4 == 0, K % 4 == 0, K >= 4; grid =
+           (ceil(N/32) * groups, ksplit, ceil(rows/32)); <NB, XVEC, WBF, BFM>.
+           inst = "nb<NB> c<chunks> v<XVEC> e<empty slices> z<grid.z>"
+  sgemm_ws cgemm when use_cgemm and cgemm_supported (A, B 16-byte aligned, lda, ldb, sA, sB % 4 == 0, the contiguous extents
+           % 4 == 0); sgemm_plan: S (tiles < 256 and K >= 2 * kmin, kmin = 128 for <= 16 tiles else 256; target 512 workgroups;
+           at most K / kmin, 16, and what fits ws), kper in whole 16s, VEC, splitk_reduce_kernel when S > 1.
+           inst = "sgemm v<VEC> S<S>"
+  cgemm    cgemm_plan: vector C store = N % 4 == 0, ldc % 4 == 0, sC % 4 == 0, C 16-byte aligned; row tile mi (2: 128 rows;
+           1: 64 rows when the 128-row grid has < 256 tiles and M > 64; 4: 128 x 64 when N <= 64 and M >= 128; option cgemm_mi,
+           ex->force_mi); S (tiles < 224 and K >= 256: 512 / tiles, at most K / 128 and what fits ws), ex->force_split, kper in
+           whole 16s; in-launch combine (finish_block) when S <= 8, vector store and option cgemm_combine, else
+           creduce_kernel<vector store>.  inst = "cgemm mi<mi> S<S> <-|comb|red> <vst|sst>"
 Picking: every value the sizes can take at an edge appears at least once and every instance; sizes and options are otherwise
 paired round-robin instead of as a cross product.  Each row's `why` names the instance or edge it is there for.
 """
@@ -46,7 +45,7 @@ import pytest
 import torch
 
 import gemm_refs as R
-from kernel_harness import GBuf, NAN, SENT, _call, _sum_ok, _write_report  # noqa: F401 (fixture)
+from kernel_harness import CPU, GBuf, NAN, SENT, _call, _sum_ok, _write_report  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -179,7 +178,7 @@ def _skinny_inputs(r):
 
 
 def _skinny_call(dev, r, X, W, ksplit=None):
-    """-> (Y [16, groups, rows, N] as read back, guards checked; ksplit_out)"""
+    """-> (Y [16, groups, rows, N] as read back, guards checked; ksplit_out); on the CPU device (the launch plan, ksplit_out)"""
     L = sk_layout(r)
     b_x = GBuf(dev, X.shape, (L["ldx"], L["xg"], 1), X, mis=L["mis"])
     if r.form == "f32":
@@ -189,12 +188,18 @@ def _skinny_call(dev, r, X, W, ksplit=None):
         b_w, wptr = _bf16_window(dev, W, L["wg"], L["ldw"])
     b_y = GBuf(dev, (R_MAX_KSPLIT, r.groups, r.rows, r.N), (L["yslab"], L["yg"], L["ldy"], 1), out=True)
     used = C.c_int(-1)
-    _call(SK_ENTRY[r.form], dev, r.rows, r.N, r.K, r.groups, b_x.ptr, L["ldx"], L["xg"], wptr, L["ldw"], L["wg"], b_y.ptr,
-          L["ldy"], L["yg"], L["yslab"], r.ks if ksplit is None else ksplit, C.byref(used))
-    return b_y.read("Y"), used.value
+    plan = _call(SK_ENTRY[r.form], dev, r.rows, r.N, r.K, r.groups, b_x.ptr, L["ldx"], L["xg"], wptr, L["ldw"], L["wg"], b_y.ptr,
+                 L["ldy"], L["yg"], L["yslab"], r.ks if ksplit is None else ksplit, C.byref(used))
+    return (plan if dev.type == "cpu" else b_y.read("Y")), used.value
 
 
-R_MAX_KSPLIT = 16       # SCN_MAX_KSPLIT (csrc/kernels.h:7)
+def skinny_plan(r):
+    """-> (the launch plan of the row's call, the ksplit it runs with)"""
+    X, W = _skinny_inputs(r)
+    return _skinny_call(CPU, r, X, W)
+
+
+R_MAX_KSPLIT = 16       # SCN_MAX_KSPLIT (csrc/kernels.h)
 
 
 @pytest.mark.parametrize("r", SKINNY, ids=lambda r: "%s-%dx%dx%d-g%d-ks%d%s" % (r.form, r.rows, r.N, r.K, r.groups, r.ks,
@@ -223,8 +228,8 @@ DG = namedtuple("DG", "api ta tb M N K batch epi lay ws opts inst why")
 # epi: a alpha = 2; b beta = 0.5 onto non-zero C; 1 beta = 1; B bias; m rowmask (zeros in the first row, the last row and the
 #      rows around the 64- and 128-row tile boundaries; C0 holds NaN there when beta != 0)
 # lay: A1 / B1 / C1 base one float off 16 bytes; lda1 / ldb1 / ldc1 leading dimension % 4 != 0; tn the drivers' batched TN
-#      product (csrc/sequence.cpp:707, :722: lda = batch * M, ldb = batch * N, sA = M, sB = N); colblk a column block of
-#      matrices four times as wide (:624: lda = 4 * D with N = F)
+#      product (csrc/sequence.cpp: lda = batch * M, ldb = batch * N, sA = M, sB = N); colblk a column block of
+#      matrices four times as wide (lda = 4 * D with N = F)
 # ws:  "full" room for every split the policy may pick; "null"; an int = room for that many slabs
 # opts: scnattn_set_option values, and force_mi / force_split of scnattn_conv_extra (api "cgemm")
 DENSE = [
@@ -361,7 +366,7 @@ class _Options:
 
 
 def _dense_call(dev, r, opts=None):
-    """-> (C [batch, M, N] as read back, guards checked; the fp64 reference)"""
+    """-> (C [batch, M, N] as read back, guards checked; the fp64 reference; the mask); on the CPU device the launch plan"""
     from scnattn._lib import ConvExtra
     a, b, alpha, beta, c0, bias, mask = dg_inputs(r)
     L = dg_layout(r)
@@ -371,7 +376,8 @@ def _dense_call(dev, r, opts=None):
     b_bias = None if bias is None else GBuf(dev, bias.shape, None, bias)
     b_mask = None if mask is None else GBuf(dev, mask.shape, None, mask)
     nws = dg_ws_floats(r)
-    ws = torch.full((nws + 4,), NAN, device=dev) if nws else None          # NaN: a slab read before it is written shows
+    # NaN: a slab read before it is written shows (a plan query touches no memory)
+    ws = (torch.empty(nws + 4) if dev.type == "cpu" else torch.full((nws + 4,), NAN, device=dev)) if nws else None
     opts = r.opts if opts is None else opts
     args = [int(r.ta), int(r.tb), r.M, r.N, r.K, C.c_float(alpha), b_a.ptr, L["lda"], b_b.ptr, L["ldb"], C.c_float(beta),
             b_c.ptr, L["ldc"], None if b_bias is None else b_bias.ptr, None if b_mask is None else b_mask.ptr, r.batch,
@@ -383,10 +389,16 @@ def _dense_call(dev, r, opts=None):
         ex.stride, ex.force_mi, ex.force_split = 1, opts.get("force_mi", 0), opts.get("force_split", 0)
         args.append(C.byref(ex))
     with _Options(opts):
-        _call({"ws": "scnattn_sgemm_ws", "sgemm": "scnattn_sgemm", "cgemm": "scnattn_cgemm"}[r.api], dev, *args)
+        plan = _call({"ws": "scnattn_sgemm_ws", "sgemm": "scnattn_sgemm", "cgemm": "scnattn_cgemm"}[r.api], dev, *args)
+    if dev.type == "cpu":
+        return plan
     ref = R.gemm(a.double(), b.double(), bool(r.ta), bool(r.tb), alpha, beta, None if c0 is None else c0.double(),
                  None if bias is None else bias.double(), mask)
     return b_c.read("C"), ref, mask
+
+
+def dense_plan(r, opts=None):
+    return _dense_call(CPU, r, opts)
 
 
 def _dense_id(r):
