@@ -26,6 +26,8 @@ extern "C" {
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
+                               + sampled rollouts and the reward-weighted loss for self-critical training (scnattn_rollout_*,
+                               scnattn_caption_loss_weighted_fwd/_bwd; new symbols only, the version stays);
                                0.1.8: + the tagger head (scnattn_tag_pool_fwd/_bwd, scnattn_bce_fwd/_bwd; new symbols only, the version stays), + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
                                new symbols only, the version stays), + batched beam search (scnattn_beam_*; new symbols only, the version stays), + eval-mode BatchNorm epilogue (scnattn_bn_eval, scnattn_conv1x1_fwd_bn_eval,
                                _conv3x3_fwd_bn_eval; new symbols only, the version stays), + bf16 trunk kernels (scnattn_cgemm16, _conv3x3_fwd16/_dgrad16, _wgrad16_*, _bf16_weights), split-K
@@ -181,6 +183,46 @@ int scnattn_beam_init(void* stream, const scnattn_dims* d, int K, int max_steps,
                       const float* tags, int start_token, float* ws);
 int scnattn_beam_steps(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                        int end_token, int t0, int n_steps, float* ws);
+/* ---- sampled rollouts for self-critical training (csrc/rollout.hip, the driver beside the search's) ---------------------
+ * The set-up and the decode step of the search above over the same N*K rows, but the K slots of an image are INDEPENDENT
+ * captions: nothing is compacted, the state carries over slot for slot, and after fc one token per open row is picked:
+ *   y_v = logits[row][v] * inv_temp,   key_v = y_v + noisy_j * g_v,   token = the first key under the TIE RULE (value
+ *   descending, index ascending, compared as the fp32 numbers the kernel computes)
+ *   noisy_j = 0 for slot 0 of every image when greedy_first != 0 (the arg-max caption), 1 otherwise
+ *   g_v = -log(-log(u_v)), u_v = ((bits_v >> 9) + 0.5) * 2^-23 (exact in fp32, inside (0, 1)): Gumbel noise, so the pick is
+ *   a draw from softmax(y)
+ * THE RNG CONTRACT: bits_v is word (v & 3) of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (v >> 2, row, t, draw): a token's noise depends on (seed, draw, row, t, v) alone -- not on N, K, the launch geometry or
+ * the chunking of the steps -- and numpy can restate it exactly.  draw is the caller's sequence number: one per rollout.
+ *   logp = y_token - logsumexp(y): the log-probability under the distribution that was sampled (temperature included).
+ * <end> closes a row: length[row] = t + 1 (0-based t), and the row's later records are token 0 (<pad>) / logp 0.0; a closed
+ * slot keeps computing on finite values and is ignored.  A row that never produced <end> within max_steps is CUT OFF there:
+ * its length stays 0 and all max_steps records are its tokens.  nsrc[n] for the attention kernels is K while any slot of
+ * image n is open and 0 afterwards; then no kernel reads or writes the image's rows.
+ * K in [1, 8], max_steps as for the search, inv_temp > 0 and finite, start / end tokens inside the vocabulary; a refusal
+ * returns -1 before anything is launched.  want_alpha != 0 keeps the attention maps (the largest buffer; training does not
+ * need them) and must be the same in the four calls.  fp32 only; dense encoder_out only.
+ *   scnattn_rollout_layout offsets (in 4-byte elements from ws), in this order:
+ *       0 open_rows int[1]   1 nsrc int[N]   2 nopen int[N] (open slots per image)   3 length int[N*K]   4 sum_logp f32[N*K]
+ *       5 token int[max_steps][N*K]   6 logp f32[max_steps][N*K]   7 alpha f32[max_steps][N*K][P] (-1 unless asked for)
+ *   scnattn_rollout_steps enqueues steps t0 .. t0+n_steps-1 (clipped to max_steps); steps on a finished batch are no-ops, so
+ *       the host enqueues chunks and reads `open_rows` (one int) in between.  Per step it launches the search's decode part,
+ *       then _pick and _advance: one launch fewer than a search step.
+ * The two kernels alone (state: the seven pointers 0..6 of the layout above, token / logp holding max_steps steps):
+ *   _pick     as above for step t; rows of an image with nsrc == 0 are neither read nor written
+ *   _advance  emb[row] = table[clamp(token_t[row], 0, V-1)] for every row; nsrc[n] = nopen[n] > 0 ? K : 0 */
+#define SCNATTN_ROLLOUT_NOFF 8
+int scnattn_rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
+int scnattn_rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* offsets);
+int scnattn_rollout_init(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                         const float* enc, const float* tags, int start_token, float* ws);
+int scnattn_rollout_steps(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                          const float* enc, int end_token, float inv_temp, uint64_t seed, uint32_t draw, int greedy_first,
+                          int t0, int n_steps, float* ws);
+int scnattn_rollout_pick(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, uint64_t seed,
+                         uint32_t draw, int t, int greedy_first, int end_token, int max_steps, void* const* state);
+int scnattn_rollout_advance(void* stream, int N, int K, int M, int V, const int32_t* token_t, const float* table, float* emb,
+                            const int32_t* nopen, int32_t* nsrc);
 /* The kernels of a step (csrc/beam.hip), one launch each; nsrc int[N] on the device.
  *   _attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0 for j < nsrc[n] (other rows untouched)
  *   _attn_context  alpha_out [N*K][P], awe [N*K][E] (either may be NULL), z = sigmoid(gpre + gate_bias) * awe (gpre NULL: awe)
@@ -377,6 +419,22 @@ int scnattn_caption_loss_metrics_fwd(void* stream, int B, int T, int V, int P, c
                                      long ldt, const int32_t* decode_lengths, long n_tokens, const float* alphas,
                                      float alpha_c, float* row_lse, float* row_loss, float* sm1, float* reg_part,
                                      float* loss, int k, int32_t* row_rank, int32_t* preds, long ldp, int32_t* hits);
+/* The reward-weighted loss of self-critical training: the pair above with row_weight [B] (device, fp32; the advantage of
+ * each sampled caption, a constant: no gradient flows to it):
+ *   loss = (1/n_tokens) * sum_b row_weight[b] * sum_{t < decode_lengths[b]} (logsumexp(scores[b,t,:]) - scores[b,t,tg])
+ *        + alpha_c * (the regulariser above, unweighted)
+ * The weight enters as ONE product per row -- row_loss[b,t] = nll * row_weight[b], and (grad_loss / n_tokens) *
+ * row_weight[b] in front of the softmax term -- so weights of 1.0 give loss, row_lse, row_loss, dscores and dalphas with the
+ * bits of the unweighted entry points (the same kernels; those pass no weights and multiply nothing).  row_lse is not
+ * weighted.  The weight of a row with decode length 0 is not read.  New symbols only, the version stays. */
+int scnattn_caption_loss_weighted_fwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
+                                      long ldt, const int32_t* decode_lengths, long n_tokens, const float* row_weight,
+                                      const float* alphas, float alpha_c, float* row_lse, float* row_loss, float* sm1,
+                                      float* reg_part, float* loss);
+int scnattn_caption_loss_weighted_bwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
+                                      long ldt, const int32_t* decode_lengths, long n_tokens, const float* row_weight,
+                                      const float* row_lse, const float* sm1, float alpha_c, const float* grad_loss,
+                                      float* dscores, float* dalphas);
 /* The head of the tagger step (models/encoders/tagger.py, trains/tagger.py:161-176) around its Linear layer.
  * The trunk map is addressed as x[b, q, c], q over the HW pixels, by ELEMENT strides sb / sp / sc; it holds fp32, or bf16
  * when bf16 != 0.  The channel-contiguous case (sc = 1, C and the other strides multiples of 16 bytes, aligned base) runs

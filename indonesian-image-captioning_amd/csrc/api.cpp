@@ -41,6 +41,13 @@ int beam_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const
               const float* tags, int start_token, float* ws);
 int beam_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                int end_token, int t0, int n_steps, float* ws);
+int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
+int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off);
+int rollout_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                 const float* enc, const float* tags, int start_token, float* ws);
+int rollout_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                  const float* enc, int end_token, float inv_temp, unsigned long long seed, unsigned draw, int greedy_first,
+                  int t0, int n_steps, float* ws);
 
 int pool_desc(const scnattn_pool* p, PoolDesc& out) {
     out = PoolDesc{0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -135,6 +142,35 @@ int scnattn_beam_advance(void* stream, int N, int K, int D, int M, int V, const 
                          const int32_t* parent_t, const int32_t* token_t, const float* table, float* hd, float* cd,
                          float* emb) {
     return beam_advance(ST(stream), N, K, D, M, V, hs, cs, parent_t, token_t, table, hd, cd, emb);
+}
+
+int scnattn_rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
+    return rollout_workspace(d, K, max_steps, want_alpha, bytes);
+}
+int scnattn_rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* offsets) {
+    return rollout_layout(d, K, max_steps, want_alpha, offsets);
+}
+int scnattn_rollout_init(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                         const float* enc, const float* tags, int start_token, float* ws) {
+    return rollout_init(ST(stream), d, K, max_steps, want_alpha, w, enc, tags, start_token, ws);
+}
+int scnattn_rollout_steps(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                          const float* enc, int end_token, float inv_temp, uint64_t seed, uint32_t draw, int greedy_first,
+                          int t0, int n_steps, float* ws) {
+    return rollout_steps(ST(stream), d, K, max_steps, want_alpha, w, enc, end_token, inv_temp, seed, draw, greedy_first, t0,
+                         n_steps, ws);
+}
+int scnattn_rollout_pick(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, uint64_t seed,
+                         uint32_t draw, int t, int greedy_first, int end_token, int max_steps, void* const* state) {
+    if (!state) { set_error("scnattn_rollout_pick: state is NULL"); return -1; }
+    if (N <= 0 || K < 1 || K > SCN_MAX_BEAM) { set_error("scnattn_rollout_pick: bad N / slot count"); return -1; }
+    const RolloutState s{N * K, max_steps, (int*)state[0], (int*)state[1], (int*)state[2], (int*)state[3], (float*)state[4],
+                         (int*)state[5], (float*)state[6]};
+    return rollout_pick(ST(stream), N, K, V, logits, ld, inv_temp, seed, draw, t, greedy_first, end_token, s);
+}
+int scnattn_rollout_advance(void* stream, int N, int K, int M, int V, const int32_t* token_t, const float* table, float* emb,
+                            const int32_t* nopen, int32_t* nsrc) {
+    return rollout_advance(ST(stream), N, K, M, V, token_t, table, emb, nopen, nsrc);
 }
 
 int scnattn_seq_workspace(const scnattn_dims* d, const scnattn_pool* pool, size_t* saved_bytes, size_t* scratch_bytes) {
@@ -710,6 +746,22 @@ int scnattn_caption_loss_bwd(void* stream, int B, int T, int V, int P, const flo
                              const float* sm1, float alpha_c, const float* grad_loss, float* dscores, float* dalphas) {
     return caption_loss_bwd(ST(stream), B, T, V, P, scores, (const long long*)targets, ldt, decode_lengths, n_tokens,
                             row_lse, sm1, alpha_c, grad_loss, dscores, dalphas);
+}
+
+int scnattn_caption_loss_weighted_fwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
+                                      long ldt, const int32_t* decode_lengths, long n_tokens, const float* row_weight,
+                                      const float* alphas, float alpha_c, float* row_lse, float* row_loss, float* sm1,
+                                      float* reg_part, float* loss) {
+    return caption_loss_weighted_fwd(ST(stream), B, T, V, P, scores, (const long long*)targets, ldt, decode_lengths,
+                                     n_tokens, row_weight, alphas, alpha_c, row_lse, row_loss, sm1, reg_part, loss);
+}
+
+int scnattn_caption_loss_weighted_bwd(void* stream, int B, int T, int V, int P, const float* scores, const int64_t* targets,
+                                      long ldt, const int32_t* decode_lengths, long n_tokens, const float* row_weight,
+                                      const float* row_lse, const float* sm1, float alpha_c, const float* grad_loss,
+                                      float* dscores, float* dalphas) {
+    return caption_loss_weighted_bwd(ST(stream), B, T, V, P, scores, (const long long*)targets, ldt, decode_lengths,
+                                     n_tokens, row_weight, row_lse, sm1, alpha_c, grad_loss, dscores, dalphas);
 }
 
 int scnattn_tag_pool_fwd(void* stream, int B, int HW, int C, const void* x, int bf16, long sb, long sp, long sc,

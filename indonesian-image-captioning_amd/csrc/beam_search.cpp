@@ -7,6 +7,9 @@
 // Launches per step (attention decoders): skinny h.[Wd^T|Wbeta^T|Ha], beam_attn_scores, beam_attn_context, skinny z.Wa[M:],
 // skinny emb.Wa[:M], scn_mix_fwd, skinny gates, lstm_fwd, fc (sgemm_ws: one or two launches), beam_row_topk, beam_merge,
 // beam_advance = 12-13; without attention 9-10.
+//
+// The rollout driver of self-critical training (scnattn_rollout_*, at the end of this file) shares the set-up and the decode
+// part of a step (decode_setup, decode_step) and ends a step with rollout_pick + rollout_advance (csrc/rollout.hip).
 #include <hip/hip_runtime.h>
 #include "../../include/scnattn.h"
 #include "common.h"
@@ -19,21 +22,67 @@ namespace {
 
 constexpr long BEAM_GEMM_WS_FLOATS = 8L << 20;     // 32 MiB of split-K partials (fc over N*K rows, the set-up products)
 
-struct BeamWs {
-    BeamState s;
+// what one decode step over R = N*K rows reads and writes (decode_step below): shared by the search and the rollout
+struct StepWs {
     // state: zero-filled by init, so that rows of dead slots that no kernel writes are finite
-    float *hA, *cA, *hB, *cB, *emb, *alpha, *z, *e, *candv, *qxr, *qhr, *pa, *phs, *xcat, *gates, *ex, *logits;
-    int* candi;
+    float *hA, *cA, *hB, *cB, *emb, *alpha, *z, *e, *qxr, *qhr, *pa, *phs, *xcat, *gates, *ex, *logits;
     size_t state_floats;
     // set-up results and scratch
     float *att1, *qx, *qh, *mean_enc, *h0, *c0, *WcatA, *WD, *slabA, *slabC, *slabD, *gws;
 };
 
+struct BeamWs : StepWs {
+    BeamState s;
+    float* candv;
+    int* candi;
+};
+
+struct RolloutWs : StepWs {
+    RolloutState s;
+};
+
 inline int* ints(float* p) { return reinterpret_cast<int*>(p); }
+
+// the two halves of a StepWs: what init zero-fills (rows of dead slots that no kernel writes stay finite), and the set-up
+// results and scratch
+void carve_step_state(Carver& c, const scnattn_dims& d, long R, StepWs& b) {
+    const int P = d.P, E = d.E, D = d.D, F = d.F, F4 = 4 * F;
+    b.hA = c.take(sz(R, D));
+    b.cA = c.take(sz(R, D));
+    b.hB = c.take(sz(R, D));
+    b.cB = c.take(sz(R, D));
+    b.emb = c.take(sz(R, d.M));
+    b.z = d.has_att ? c.take(sz(R, E)) : nullptr;
+    b.e = d.has_att ? c.take(sz(R, P)) : nullptr;
+    b.qxr = c.take(sz(R, F4));
+    b.qhr = c.take(sz(R, F4));
+    b.pa = c.take(sz(R, F4));
+    b.phs = c.take(sz(R, F4));
+    b.xcat = c.take(sz(R, 4, 2 * F));
+    b.gates = c.take(sz(R, 4 * D));
+    b.ex = c.take(sz(R, F4));
+    b.logits = c.take(sz(R, d.V));
+}
+
+void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b) {
+    const int N = d.B, P = d.P, E = d.E, A = d.A, D = d.D, F = d.F, F4 = 4 * F, NA = ncatA(d);
+    b.att1 = d.has_att ? c.take(sz(N, P, A)) : nullptr;
+    b.qx = c.take(sz(N, F4));
+    b.qh = c.take(sz(N, F4));
+    b.mean_enc = c.take(sz(N, E));
+    b.h0 = c.take(sz(N, D));
+    b.c0 = c.take(sz(N, D));
+    b.WcatA = c.take(sz(D, NA));
+    b.WD = c.take(sz(4, 2 * F, D));
+    b.slabA = c.take(sz(SCN_MAX_KSPLIT, R, NA));
+    b.slabC = d.has_att ? c.take(sz(SCN_MAX_KSPLIT, R, F4)) : nullptr;
+    b.slabD = c.take(sz(SCN_MAX_KSPLIT, 4, R, D));
+    b.gws = c.take(BEAM_GEMM_WS_FLOATS);
+}
 
 size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b) {
     Carver c(base);
-    const int N = d.B, P = d.P, E = d.E, A = d.A, D = d.D, F = d.F, F4 = 4 * F, NA = ncatA(d);
+    const int N = d.B, P = d.P;
     const long R = (long)N * K;
     b.s.R = (int)R;
     b.s.scores = c.take(R);
@@ -49,36 +98,11 @@ size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b) {
     b.s.token = ints(c.take(sz(T, R)));
     b.s.parent = ints(c.take(sz(T, R)));
     b.alpha = d.has_att ? c.take(sz(T, R, P)) : nullptr;
-    b.hA = c.take(sz(R, D));
-    b.cA = c.take(sz(R, D));
-    b.hB = c.take(sz(R, D));
-    b.cB = c.take(sz(R, D));
-    b.emb = c.take(sz(R, d.M));
-    b.z = d.has_att ? c.take(sz(R, E)) : nullptr;
-    b.e = d.has_att ? c.take(sz(R, P)) : nullptr;
+    carve_step_state(c, d, R, b);
     b.candv = c.take(sz(R, K));
     b.candi = ints(c.take(sz(R, K)));
-    b.qxr = c.take(sz(R, F4));
-    b.qhr = c.take(sz(R, F4));
-    b.pa = c.take(sz(R, F4));
-    b.phs = c.take(sz(R, F4));
-    b.xcat = c.take(sz(R, 4, 2 * F));
-    b.gates = c.take(sz(R, 4 * D));
-    b.ex = c.take(sz(R, F4));
-    b.logits = c.take(sz(R, d.V));
     b.state_floats = c.off;
-    b.att1 = d.has_att ? c.take(sz(N, P, A)) : nullptr;
-    b.qx = c.take(sz(N, F4));
-    b.qh = c.take(sz(N, F4));
-    b.mean_enc = c.take(sz(N, E));
-    b.h0 = c.take(sz(N, D));
-    b.c0 = c.take(sz(N, D));
-    b.WcatA = c.take(sz(D, NA));
-    b.WD = c.take(sz(4, 2 * F, D));
-    b.slabA = c.take(sz(SCN_MAX_KSPLIT, R, NA));
-    b.slabC = d.has_att ? c.take(sz(SCN_MAX_KSPLIT, R, F4)) : nullptr;
-    b.slabD = c.take(sz(SCN_MAX_KSPLIT, 4, R, D));
-    b.gws = c.take(BEAM_GEMM_WS_FLOATS);
+    carve_step_setup(c, d, R, b);
     return c.off * sizeof(float);
 }
 
@@ -91,6 +115,63 @@ int check_beam(const scnattn_dims* d, int K, int T) {
     SCN_ARG(d->V >= K, "vocab_size must be at least beam_size");
     SCN_ARG(T >= 1 && T <= 4096, "max_steps must be in [1, 4096]");
     SCN_ARG((long)d->B * K <= (1L << 20), "too many rows (images x beam_size)");
+    return 0;
+}
+
+// The set-up both drivers share: weight re-layout, att1 once per image, the tag factors, the initial state in every slot
+// and the <start> embedding in every row.
+int decode_setup(hipStream_t st, const scnattn_dims& d, int K, const scnattn_params* w, const float* enc, const float* tags,
+                 int start_token, const StepWs& b) {
+    const int N = d.B, P = d.P, E = d.E, A = d.A, D = d.D, F4 = 4 * d.F, M = d.M;
+    const GemmWs gws{b.gws, BEAM_GEMM_WS_FLOATS};
+    SCN_TRY(step_weight_layout(st, d, w, b.WcatA, b.WD));
+    if (d.has_att)      // once per image, not per beam
+        SCN_TRY(gemm(st, false, true, N * P, A, E, enc, E, w->attention_encoder_att_weight, E, 0.f, b.att1, A, gws,
+                     w->attention_encoder_att_bias));
+    SCN_TRY(gemm(st, false, false, N, F4, d.S, tags, d.S, w->decode_step_weight_ib, F4, 0.f, b.qx, F4, gws));
+    SCN_TRY(gemm(st, false, false, N, F4, d.S, tags, d.S, w->decode_step_weight_hb, F4, 0.f, b.qh, F4, gws));
+    SCN_TRY(beam_expand_rows(st, N, K, F4, b.qx, b.qxr));
+    SCN_TRY(beam_expand_rows(st, N, K, F4, b.qh, b.qhr));
+    SCN_TRY(mean_pixels(st, N, P, E, enc, b.mean_enc));
+    SCN_TRY(gemm(st, false, true, N, D, E, b.mean_enc, E, w->init_h_weight, E, 0.f, b.h0, D, gws, w->init_h_bias));
+    SCN_TRY(gemm(st, false, true, N, D, E, b.mean_enc, E, w->init_c_weight, E, 0.f, b.c0, D, gws, w->init_c_bias));
+    SCN_TRY(beam_expand_rows(st, N, K, D, b.h0, b.hA));     // slot 0 is the live one; the others hold finite copies
+    SCN_TRY(beam_expand_rows(st, N, K, D, b.c0, b.cA));
+    SCN_TRY(beam_expand_rows(st, 1, N * K, M, w->embedding_weight + (long)start_token * M, b.emb));
+    return 0;
+}
+
+// The decode part of one step over the R = N*K rows: (hin, cin, emb) -> (hout, cout, logits); the K rows of image n attend
+// over att1[n] / enc[n] for nsrc[n] live slots.  Launches: skinny h.[Wd^T|Wbeta^T|Ha], beam_attn_scores, beam_attn_context,
+// skinny z.Wa[M:], skinny emb.Wa[:M], scn_mix_fwd, skinny gates, lstm_fwd, fc (one or two launches).
+int decode_step(hipStream_t st, const scnattn_dims& d, int K, const scnattn_params* w, const float* enc, const StepWs& b,
+                const int* nsrc, float* alpha_t, const float* hin, const float* cin, float* hout, float* cout) {
+    const int N = d.B, P = d.P, E = d.E, A = d.A, D = d.D, F = d.F, F4 = 4 * F, M = d.M, V = d.V;
+    const int R = N * K, NA = ncatA(d), colph = d.has_att ? A + E : 0;
+    const long RD = (long)R * D;
+    const GemmWs gws{b.gws, BEAM_GEMM_WS_FLOATS};
+    const float* WaM = d.has_att ? w->decode_step_weight_ia + (long)M * F4 : nullptr;
+    const int ksA = pick(R, NA, D, 1);
+    SCN_TRY(skinny_gemm(st, R, NA, D, 1, hin, D, 0, b.WcatA, NA, 0, b.slabA, NA, 0, (long)R * NA, ksA));
+    const Slabs ph{b.slabA + colph, ksA, (long)R * NA, NA};
+    Slabs pz{nullptr, 0, 0, 0};
+    if (d.has_att) {
+        const Slabs att2{b.slabA, ksA, (long)R * NA, NA}, gpre{b.slabA + A, ksA, (long)R * NA, NA};
+        SCN_TRY(beam_attn_scores(st, N, K, P, A, b.att1, att2, w->attention_decoder_att_bias,
+                                 w->attention_full_att_weight, w->attention_full_att_bias, nsrc, b.e));
+        SCN_TRY(beam_attn_context(st, N, K, P, E, enc, b.e, gpre, w->f_beta_bias, nsrc,
+                                  alpha_t, nullptr, b.z));
+        const int ksC = pick(R, F4, E, 1);
+        SCN_TRY(skinny_gemm(st, R, F4, E, 1, b.z, E, 0, WaM, F4, 0, b.slabC, F4, 0, (long)R * F4, ksC));
+        pz = Slabs{b.slabC, ksC, (long)R * F4, F4};
+    }
+    SCN_TRY(skinny_gemm(st, R, F4, M, 1, b.emb, M, 0, w->decode_step_weight_ia, F4, 0, b.ex, F4, 0, (long)R * F4, 1));
+    SCN_TRY(scn_mix_fwd(st, R, F4, pz, b.ex, ph, b.qxr, b.qhr, b.pa, b.phs, b.xcat));
+    const int ksD = pick(R, D, 2 * F, 4);
+    SCN_TRY(skinny_gemm(st, R, D, 2 * F, 4, b.xcat, 8 * F, 2 * F, b.WD, D, (long)2 * F * D, b.slabD, D, RD, 4 * RD, ksD));
+    SCN_TRY(lstm_fwd(st, R, D, Slabs{b.slabD, ksD, 4 * RD, D}, RD, w->decode_step_bias_ih, w->decode_step_bias_hh, cin,
+                     b.gates, cout, hout, nullptr));
+    SCN_TRY(gemm(st, false, true, R, V, D, hout, D, w->fc_weight, D, 0.f, b.logits, V, gws, w->fc_bias));
     return 0;
 }
 
@@ -126,26 +207,11 @@ int beam_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, cons
     SCN_ARG(w && enc && tags && ws, "beam_init: null argument");
     SCN_ARG(start_token >= 0 && start_token < d.V, "beam_init: start token outside the vocabulary");
     SCN_ARG(aligned16(ws), "beam_init: the workspace must be 16-byte aligned");
-    const int N = d.B, P = d.P, E = d.E, A = d.A, D = d.D, F4 = 4 * d.F, M = d.M;
     BeamWs b;
     carve_beam(d, K, max_steps, ws, b);
-    const GemmWs gws{b.gws, BEAM_GEMM_WS_FLOATS};
     SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
-    SCN_TRY(beam_state_init(st, N, K, b.s));
-    SCN_TRY(step_weight_layout(st, d, w, b.WcatA, b.WD));
-    if (d.has_att)      // once per image, not per beam
-        SCN_TRY(gemm(st, false, true, N * P, A, E, enc, E, w->attention_encoder_att_weight, E, 0.f, b.att1, A, gws,
-                     w->attention_encoder_att_bias));
-    SCN_TRY(gemm(st, false, false, N, F4, d.S, tags, d.S, w->decode_step_weight_ib, F4, 0.f, b.qx, F4, gws));
-    SCN_TRY(gemm(st, false, false, N, F4, d.S, tags, d.S, w->decode_step_weight_hb, F4, 0.f, b.qh, F4, gws));
-    SCN_TRY(beam_expand_rows(st, N, K, F4, b.qx, b.qxr));
-    SCN_TRY(beam_expand_rows(st, N, K, F4, b.qh, b.qhr));
-    SCN_TRY(mean_pixels(st, N, P, E, enc, b.mean_enc));
-    SCN_TRY(gemm(st, false, true, N, D, E, b.mean_enc, E, w->init_h_weight, E, 0.f, b.h0, D, gws, w->init_h_bias));
-    SCN_TRY(gemm(st, false, true, N, D, E, b.mean_enc, E, w->init_c_weight, E, 0.f, b.c0, D, gws, w->init_c_bias));
-    SCN_TRY(beam_expand_rows(st, N, K, D, b.h0, b.hA));     // slot 0 is the live one; the others hold finite copies
-    SCN_TRY(beam_expand_rows(st, N, K, D, b.c0, b.cA));
-    SCN_TRY(beam_expand_rows(st, 1, N * K, M, w->embedding_weight + (long)start_token * M, b.emb));
+    SCN_TRY(beam_state_init(st, d.B, K, b.s));
+    SCN_TRY(decode_setup(st, d, K, w, enc, tags, start_token, b));
     return 0;
 }
 
@@ -156,41 +222,108 @@ int beam_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, con
     const scnattn_dims& d = *dp;
     SCN_ARG(w && enc && ws, "beam_steps: null argument");
     SCN_ARG(t0 >= 0 && n_steps >= 0, "beam_steps: negative step");
-    const int N = d.B, P = d.P, E = d.E, A = d.A, D = d.D, F = d.F, F4 = 4 * F, M = d.M, V = d.V;
-    const int R = N * K, NA = ncatA(d), colph = d.has_att ? A + E : 0;
-    const long RD = (long)R * D;
+    const int N = d.B, P = d.P, D = d.D, M = d.M, V = d.V, R = N * K;
     BeamWs b;
     carve_beam(d, K, max_steps, ws, b);
-    const GemmWs gws{b.gws, BEAM_GEMM_WS_FLOATS};
-    const float* WaM = d.has_att ? w->decode_step_weight_ia + (long)M * F4 : nullptr;
     const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
     for (int t = t0; t < t1; ++t) {
         int* token_t = b.s.token + (long)t * R;
         int* parent_t = b.s.parent + (long)t * R;
-        const int ksA = pick(R, NA, D, 1);
-        SCN_TRY(skinny_gemm(st, R, NA, D, 1, b.hA, D, 0, b.WcatA, NA, 0, b.slabA, NA, 0, (long)R * NA, ksA));
-        const Slabs ph{b.slabA + colph, ksA, (long)R * NA, NA};
-        Slabs pz{nullptr, 0, 0, 0};
-        if (d.has_att) {
-            const Slabs att2{b.slabA, ksA, (long)R * NA, NA}, gpre{b.slabA + A, ksA, (long)R * NA, NA};
-            SCN_TRY(beam_attn_scores(st, N, K, P, A, b.att1, att2, w->attention_decoder_att_bias,
-                                     w->attention_full_att_weight, w->attention_full_att_bias, b.s.nsrc, b.e));
-            SCN_TRY(beam_attn_context(st, N, K, P, E, enc, b.e, gpre, w->f_beta_bias, b.s.nsrc,
-                                      b.alpha + (long)t * R * P, nullptr, b.z));
-            const int ksC = pick(R, F4, E, 1);
-            SCN_TRY(skinny_gemm(st, R, F4, E, 1, b.z, E, 0, WaM, F4, 0, b.slabC, F4, 0, (long)R * F4, ksC));
-            pz = Slabs{b.slabC, ksC, (long)R * F4, F4};
-        }
-        SCN_TRY(skinny_gemm(st, R, F4, M, 1, b.emb, M, 0, w->decode_step_weight_ia, F4, 0, b.ex, F4, 0, (long)R * F4, 1));
-        SCN_TRY(scn_mix_fwd(st, R, F4, pz, b.ex, ph, b.qxr, b.qhr, b.pa, b.phs, b.xcat));
-        const int ksD = pick(R, D, 2 * F, 4);
-        SCN_TRY(skinny_gemm(st, R, D, 2 * F, 4, b.xcat, 8 * F, 2 * F, b.WD, D, (long)2 * F * D, b.slabD, D, RD, 4 * RD, ksD));
-        SCN_TRY(lstm_fwd(st, R, D, Slabs{b.slabD, ksD, 4 * RD, D}, RD, w->decode_step_bias_ih, w->decode_step_bias_hh, b.cA,
-                         b.gates, b.cB, b.hB, nullptr));
-        SCN_TRY(gemm(st, false, true, R, V, D, b.hB, D, w->fc_weight, D, 0.f, b.logits, V, gws, w->fc_bias));
+        SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, d.has_att ? b.alpha + (long)t * R * P : nullptr, b.hA, b.cA, b.hB,
+                            b.cB));
         SCN_TRY(beam_row_topk(st, N, K, V, b.logits, V, b.s.scores, b.s.nsrc, b.candv, b.candi, 0));
         SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
         SCN_TRY(beam_advance(st, N, K, D, M, V, b.hB, b.cB, parent_t, token_t, w->embedding_weight, b.hA, b.cA, b.emb));
+    }
+    return 0;
+}
+
+// ---- sampled rollouts (csrc/rollout.hip): the same set-up and decode step, K INDEPENDENT slots per image ------------------
+// After fc, rollout_pick replaces beam_row_topk + beam_merge and rollout_advance replaces beam_advance: the state carries
+// over slot for slot, so h / c are not gathered but alternate between the A and B buffers with the parity of the step, and
+// the advance only gathers the next embedding and refreshes nsrc.  One launch fewer per step than the search (11-12 with
+// attention, 8-9 without).  fp32 only.
+namespace {
+
+size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, float* base, RolloutWs& b) {
+    Carver c(base);
+    const int N = d.B, P = d.P;
+    const long R = (long)N * K;
+    b.s.R = (int)R;
+    b.s.T = T;
+    b.s.open_rows = ints(c.take(1));
+    b.s.nsrc = ints(c.take(N));
+    b.s.nopen = ints(c.take(N));
+    b.s.length = ints(c.take(R));
+    b.s.sum_logp = c.take(R);
+    b.s.token = ints(c.take(sz(T, R)));
+    b.s.logp = c.take(sz(T, R));
+    b.alpha = (d.has_att && want_alpha) ? c.take(sz(T, R, P)) : nullptr;
+    carve_step_state(c, d, R, b);
+    b.state_floats = c.off;
+    carve_step_setup(c, d, R, b);
+    return c.off * sizeof(float);
+}
+
+}  // namespace
+
+int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_ARG(bytes, "rollout_workspace: bytes is NULL");
+    RolloutWs b;
+    *bytes = carve_rollout(*d, K, max_steps, want_alpha, nullptr, b);
+    return 0;
+}
+
+// off[SCNATTN_ROLLOUT_NOFF]: where the results live in the workspace, in 4-byte elements (order: include/scnattn.h)
+int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_ARG(off, "rollout_layout: offsets is NULL");
+    RolloutWs b;
+    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
+    carve_rollout(*d, K, max_steps, want_alpha, base, b);
+    const void* p[SCNATTN_ROLLOUT_NOFF] = {b.s.open_rows, b.s.nsrc, b.s.nopen, b.s.length, b.s.sum_logp, b.s.token, b.s.logp,
+                                           b.alpha};
+    for (int i = 0; i < SCNATTN_ROLLOUT_NOFF; ++i)
+        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
+    return 0;
+}
+
+int rollout_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                 const float* enc, const float* tags, int start_token, float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    const scnattn_dims& d = *dp;
+    SCN_ARG(w && enc && tags && ws, "rollout_init: null argument");
+    SCN_ARG(start_token >= 0 && start_token < d.V, "rollout_init: start token outside the vocabulary");
+    SCN_ARG(aligned16(ws), "rollout_init: the workspace must be 16-byte aligned");
+    RolloutWs b;
+    carve_rollout(d, K, max_steps, want_alpha, ws, b);
+    SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));      // the records of closed rows: <pad> / 0.0
+    SCN_TRY(rollout_state_init(st, d.B, K, b.s));
+    SCN_TRY(decode_setup(st, d, K, w, enc, tags, start_token, b));
+    return 0;
+}
+
+// Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.
+int rollout_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                  const float* enc, int end_token, float inv_temp, unsigned long long seed, unsigned draw, int greedy_first,
+                  int t0, int n_steps, float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    const scnattn_dims& d = *dp;
+    SCN_ARG(w && enc && ws, "rollout_steps: null argument");
+    SCN_ARG(t0 >= 0 && n_steps >= 0, "rollout_steps: negative step");
+    SCN_ARG(inv_temp > 0.f && inv_temp < INFINITY, "rollout_steps: inv_temp must be positive and finite");
+    SCN_ARG(end_token >= 0 && end_token < d.V, "rollout_steps: end token outside the vocabulary");
+    const int N = d.B, P = d.P, M = d.M, V = d.V, R = N * K;
+    RolloutWs b;
+    carve_rollout(d, K, max_steps, want_alpha, ws, b);
+    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
+    for (int t = t0; t < t1; ++t) {
+        const bool even = (t & 1) == 0;         // the state of step t sits in A for even t, in B for odd t
+        SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, b.alpha ? b.alpha + (long)t * R * P : nullptr, even ? b.hA : b.hB,
+                            even ? b.cA : b.cB, even ? b.hB : b.hA, even ? b.cB : b.cA));
+        SCN_TRY(rollout_pick(st, N, K, V, b.logits, V, inv_temp, seed, draw, t, greedy_first, end_token, b.s));
+        SCN_TRY(rollout_advance(st, N, K, M, V, b.s.token + (long)t * R, w->embedding_weight, b.emb, b.s.nopen, b.s.nsrc));
     }
     return 0;
 }

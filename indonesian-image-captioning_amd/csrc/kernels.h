@@ -166,6 +166,26 @@ int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float*
 int beam_expand_rows(hipStream_t st, int N, int K, int W, const float* in, float* out);
 int beam_state_init(hipStream_t st, int N, int K, const BeamState& s);
 
+// ---- rollout.hip: sampled rollouts (K independent slots per image, rows n*K + j, nothing compacted) ------------------
+struct RolloutState {
+    int R, T;               // rows, steps the records hold
+    int* open_rows;         // [1]    rows that have not produced <end> (the host polls it)
+    int* nsrc;              // [N]    K while any slot of the image is open, 0 afterwards (what the attention kernels take)
+    int* nopen;             // [N]    open slots of the image
+    int* length;            // [R]    t + 1 of the step that produced <end>; 0: still open
+    float* sum_logp;        // [R]    running sum of the logp records
+    int* token;             // [T][R] token picked at step t (0 after the row closed)
+    float* logp;            // [T][R] its log-probability under softmax(logits * inv_temp) (0.0 after the row closed)
+};
+// One token per live row: arg-max of logits * inv_temp + Gumbel noise (Philox4x32-10 keyed by seed, counter
+// (v >> 2, row, t, draw)); slot 0 of every image takes the plain arg-max when greedy_first != 0.  Contract: rollout.hip.
+int rollout_pick(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp, unsigned long long seed,
+                 unsigned draw, int t, int greedy_first, int end_tok, const RolloutState& s);
+// emb[row] = table[clamp(token_t[row])]; nsrc[n] = nopen[n] > 0 ? K : 0
+int rollout_advance(hipStream_t st, int N, int K, int M, int V, const int* token_t, const float* table, float* emb,
+                    const int* nopen, int* nsrc);
+int rollout_state_init(hipStream_t st, int N, int K, const RolloutState& s);
+
 // ---- scn_cell.hip ----------------------------------------------------------------------------
 int scn_mix_fwd(hipStream_t st, int rows, int F4, Slabs pz, const float* ex, Slabs ph, const float* qx,
                 const float* qh, float* pa, float* phs, float* xcat);
@@ -205,6 +225,14 @@ int caption_loss_metrics_fwd(hipStream_t st, int B, int T, int V, int P, const f
 int caption_loss_bwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
                      const int* dl, long n_tokens, const float* row_lse, const float* sm1, float alpha_c,
                      const float* gout, float* dscores, float* dalphas);
+// the reward-weighted pair (self-critical training): row_loss[b,t] and d scores[b,t,:] times row_weight[b], ONE product per
+// row, so weights of 1.0 give the bits of the pair above; the attention regulariser is not weighted
+int caption_loss_weighted_fwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets,
+                              long ldt, const int* dl, long n_tokens, const float* row_weight, const float* alphas,
+                              float alpha_c, float* row_lse, float* row_loss, float* sm1, float* reg_part, float* loss);
+int caption_loss_weighted_bwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets,
+                              long ldt, const int* dl, long n_tokens, const float* row_weight, const float* row_lse,
+                              const float* sm1, float alpha_c, const float* gout, float* dscores, float* dalphas);
 // taghead.hip: the tagger's head around its Linear layer.  The map is x[b, q, c] (q over HW pixels) by element strides,
 // fp32 or bf16; pooled = sum_q x / HW * ks (ks: pre-scaled dropout keep mask [B][ldk], may be null); bce_*: sigmoid +
 // BCELoss (mean) + binary accuracy of the reference, rows: workspace [2][B], out: {loss, agreement count}

@@ -12,6 +12,9 @@
 // 4*B*T*V bytes once, backward reads them once more and writes as many.
 // The metrics of the caption loops (top-5 accuracy :255-257 / :338-339, arg-max hypotheses :366-372) are comparisons of the
 // same numbers: the metrics form of the forward counts them in that one read pass.
+// The reward-weighted form (self-critical training) is the same kernels with row_weight [B]: ONE product per
+// row, row_loss[r] * w[b] in the forward and (g / N) * w[b] in the backward, so weights of 1.0 leave every bit as it is;
+// row_weight == nullptr is the unweighted loss and multiplies nothing.  The regulariser is never weighted.
 #include <climits>
 
 #include "common.h"
@@ -62,7 +65,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(int T, int V, const float* 
                                                      const long long* __restrict__ targets, long ldt,
                                                      const int* __restrict__ dl, float* __restrict__ row_lse,
                                                      float* __restrict__ row_loss, int* __restrict__ row_rank,
-                                                     int* __restrict__ preds, long ldp) {
+                                                     int* __restrict__ preds, long ldp,
+                                                     const float* __restrict__ row_weight) {
     const int r = blockIdx.x, b = r / T, t = r - b * T;
     if (t >= dl[b]) {                         // not decoded: not part of the packed batch
         if (threadIdx.x == 0) {
@@ -118,7 +122,8 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(int T, int V, const float* 
         const float lse = m + logf(s);
         const long long tg = targets[(long)b * ldt + t];
         row_lse[r] = lse;
-        row_loss[r] = (tg >= 0 && tg < V) ? lse - x[tg] : __builtin_nanf("");   // bad label poisons the loss, no fault
+        const float nll = (tg >= 0 && tg < V) ? lse - x[tg] : __builtin_nanf("");   // bad label poisons the loss, no fault
+        row_loss[r] = row_weight ? nll * row_weight[b] : nll;
         if (MET) {
             first_of(q.bm, q.bi, qm[1], qi[1]); first_of(q.bm, q.bi, qm[2], qi[2]); first_of(q.bm, q.bi, qm[3], qi[3]);
             row_rank[r] = valid ? (qc[0] + qc[1]) + (qc[2] + qc[3]) : INT_MAX;
@@ -132,13 +137,15 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(int T, int V, const float* 
                                                      const long long* __restrict__ targets, long ldt,
                                                      const int* __restrict__ dl, const float* __restrict__ row_lse,
                                                      const float* __restrict__ gout, float inv_n,
+                                                     const float* __restrict__ row_weight,
                                                      float* __restrict__ dscores) {
     const int r = blockIdx.x, b = r / T, t = r - b * T;
     float* d = dscores + (long)r * V;
     const bool on = t < dl[b];
     const float* x = scores + (long)r * V;
     const float lse = on ? row_lse[r] : 0.f;
-    const float g = on ? gout[0] * inv_n : 0.f;
+    const float gn = on ? gout[0] * inv_n : 0.f;
+    const float g = (on && row_weight) ? gn * row_weight[b] : gn;
     const long long tl = on ? targets[(long)b * ldt + t] : -1;
     const int tg = (tl >= 0 && tl < V) ? (int)tl : -1;      // compared in 64 bits: 2^32 + 3 is a bad label, not label 3
     if (VEC) {
@@ -231,12 +238,13 @@ namespace {
 // the forward launches; row_rank == nullptr: the loss alone
 int loss_fwd_launch(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
                     const int* dl, long n_tokens, const float* alphas, float alpha_c, float* row_lse, float* row_loss,
-                    float* sm1, float* reg_part, float* loss, int k, int* row_rank, int* preds, long ldp, int* hits) {
+                    float* sm1, float* reg_part, float* loss, int k, int* row_rank, int* preds, long ldp, int* hits,
+                    const float* row_weight) {
     const bool vec = (V % 4 == 0) && aligned16(scores);
     const bool met = row_rank != nullptr;
 #define SCN_CE_FWD(VEC, MET)                                                                                                 \
     hipLaunchKernelGGL((ce_fwd_kernel<VEC, MET>), dim3(B * T), dim3(256), 0, st, T, V, scores, targets, ldt, dl, row_lse, \
-                       row_loss, row_rank, preds, ldp)
+                       row_loss, row_rank, preds, ldp, row_weight)
     if (met) { if (vec) SCN_CE_FWD(true, true); else SCN_CE_FWD(false, true); }
     else     { if (vec) SCN_CE_FWD(true, false); else SCN_CE_FWD(false, false); }
 #undef SCN_CE_FWD
@@ -265,7 +273,18 @@ int caption_loss_fwd(hipStream_t st, int B, int T, int V, int P, const float* sc
     SCN_ARG(scores && targets && dl && row_lse && row_loss && loss && ldt >= T, "caption_loss_fwd: bad argument");
     SCN_ARG(!alphas || (P > 0 && sm1 && reg_part), "caption_loss_fwd: alphas without workspace");
     return loss_fwd_launch(st, B, T, V, P, scores, targets, ldt, dl, n_tokens, alphas, alpha_c, row_lse, row_loss, sm1,
-                           reg_part, loss, 0, nullptr, nullptr, 0, nullptr);
+                           reg_part, loss, 0, nullptr, nullptr, 0, nullptr, nullptr);
+}
+
+int caption_loss_weighted_fwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets,
+                              long ldt, const int* dl, long n_tokens, const float* row_weight, const float* alphas,
+                              float alpha_c, float* row_lse, float* row_loss, float* sm1, float* reg_part, float* loss) {
+    SCN_ARG(B > 0 && T > 0 && V > 0 && n_tokens > 0, "caption_loss_weighted_fwd: bad shape");
+    SCN_ARG(scores && targets && dl && row_lse && row_loss && loss && ldt >= T, "caption_loss_weighted_fwd: bad argument");
+    SCN_ARG(row_weight, "caption_loss_weighted_fwd: row_weight is NULL");
+    SCN_ARG(!alphas || (P > 0 && sm1 && reg_part), "caption_loss_weighted_fwd: alphas without workspace");
+    return loss_fwd_launch(st, B, T, V, P, scores, targets, ldt, dl, n_tokens, alphas, alpha_c, row_lse, row_loss, sm1,
+                           reg_part, loss, 0, nullptr, nullptr, 0, nullptr, row_weight);
 }
 
 int caption_loss_metrics_fwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets,
@@ -278,19 +297,18 @@ int caption_loss_metrics_fwd(hipStream_t st, int B, int T, int V, int P, const f
     SCN_ARG(k >= 1, "caption_loss_metrics_fwd: k must be >= 1");
     SCN_ARG(row_rank && preds && hits && ldp >= T, "caption_loss_metrics_fwd: bad metrics output");
     return loss_fwd_launch(st, B, T, V, P, scores, targets, ldt, dl, n_tokens, alphas, alpha_c, row_lse, row_loss, sm1,
-                           reg_part, loss, k, row_rank, preds, ldp, hits);
+                           reg_part, loss, k, row_rank, preds, ldp, hits, nullptr);
 }
 
-int caption_loss_bwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
-                     const int* dl, long n_tokens, const float* row_lse, const float* sm1, float alpha_c,
-                     const float* gout, float* dscores, float* dalphas) {
-    SCN_ARG(B > 0 && T > 0 && V > 0 && n_tokens > 0, "caption_loss_bwd: bad shape");
-    SCN_ARG(scores && targets && dl && row_lse && gout && dscores && ldt >= T, "caption_loss_bwd: bad argument");
-    SCN_ARG(!dalphas || (P > 0 && sm1), "caption_loss_bwd: dalphas without sm1");
+namespace {
+
+int loss_bwd_launch(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
+                    const int* dl, long n_tokens, const float* row_lse, const float* sm1, float alpha_c, const float* gout,
+                    float* dscores, float* dalphas, const float* row_weight) {
     const bool vec = (V % 4 == 0) && aligned16(scores) && aligned16(dscores);
     const float inv_n = 1.f / (float)n_tokens;
-    if (vec) hipLaunchKernelGGL(ce_bwd_kernel<true>, dim3(B * T), dim3(256), 0, st, T, V, scores, targets, ldt, dl, row_lse, gout, inv_n, dscores);
-    else     hipLaunchKernelGGL(ce_bwd_kernel<false>, dim3(B * T), dim3(256), 0, st, T, V, scores, targets, ldt, dl, row_lse, gout, inv_n, dscores);
+    if (vec) hipLaunchKernelGGL(ce_bwd_kernel<true>, dim3(B * T), dim3(256), 0, st, T, V, scores, targets, ldt, dl, row_lse, gout, inv_n, row_weight, dscores);
+    else     hipLaunchKernelGGL(ce_bwd_kernel<false>, dim3(B * T), dim3(256), 0, st, T, V, scores, targets, ldt, dl, row_lse, gout, inv_n, row_weight, dscores);
     SCN_LAUNCH_CHECK();
     if (dalphas) {
         const long n = (long)B * T * P;
@@ -299,6 +317,29 @@ int caption_loss_bwd(hipStream_t st, int B, int T, int V, int P, const float* sc
         SCN_LAUNCH_CHECK();
     }
     return 0;
+}
+
+}  // namespace
+
+int caption_loss_bwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets, long ldt,
+                     const int* dl, long n_tokens, const float* row_lse, const float* sm1, float alpha_c,
+                     const float* gout, float* dscores, float* dalphas) {
+    SCN_ARG(B > 0 && T > 0 && V > 0 && n_tokens > 0, "caption_loss_bwd: bad shape");
+    SCN_ARG(scores && targets && dl && row_lse && gout && dscores && ldt >= T, "caption_loss_bwd: bad argument");
+    SCN_ARG(!dalphas || (P > 0 && sm1), "caption_loss_bwd: dalphas without sm1");
+    return loss_bwd_launch(st, B, T, V, P, scores, targets, ldt, dl, n_tokens, row_lse, sm1, alpha_c, gout, dscores, dalphas,
+                           nullptr);
+}
+
+int caption_loss_weighted_bwd(hipStream_t st, int B, int T, int V, int P, const float* scores, const long long* targets,
+                              long ldt, const int* dl, long n_tokens, const float* row_weight, const float* row_lse,
+                              const float* sm1, float alpha_c, const float* gout, float* dscores, float* dalphas) {
+    SCN_ARG(B > 0 && T > 0 && V > 0 && n_tokens > 0, "caption_loss_weighted_bwd: bad shape");
+    SCN_ARG(scores && targets && dl && row_lse && gout && dscores && ldt >= T, "caption_loss_weighted_bwd: bad argument");
+    SCN_ARG(row_weight, "caption_loss_weighted_bwd: row_weight is NULL");
+    SCN_ARG(!dalphas || (P > 0 && sm1), "caption_loss_weighted_bwd: dalphas without sm1");
+    return loss_bwd_launch(st, B, T, V, P, scores, targets, ldt, dl, n_tokens, row_lse, sm1, alpha_c, gout, dscores, dalphas,
+                           row_weight);
 }
 
 }  // namespace scn

@@ -5,7 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from scnattn import functional as SF
-from utils.token import start_token, end_token
+from utils.token import start_token, end_token, padding_token
 
 
 def sort_by_length(encoder_out, encoded_captions, caption_lengths, sort_ind=None, caplens_host=None):
@@ -175,6 +175,23 @@ def beam_search(decoder, beam_size, word_map, encoder_out, tag_out, use_attentio
     return out
 
 
+def _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags):
+    """(dims, weights, enc (N, P, E), tags (N, S)) as the device drivers of the search and of the rollout take them"""
+    N, hh, ww, E = encoder_out.shape
+    P = hh * ww
+    enc = encoder_out.reshape(N, P, E)
+    D = decoder.decoder_dim
+    if use_tags:
+        from models.decoders.attention_scn import _collect_weights
+        weights, Fd, S = _collect_weights(decoder), decoder.factored_dim, decoder.semantic_dim
+    else:       # PureAttention: the LSTM cell through its SCN view, one constant "tag" (pure_attention.py)
+        weights, Fd, S = decoder._scn_view_of_lstm(), D, 1
+        tag_out = torch.ones(N, 1, device=enc.device)
+    dims = (N, P, E, decoder.attention_dim if use_attention else 0, D, Fd, decoder.embed_dim, S, V, SF.BEAM_MAX_STEPS,
+            SF.BEAM_MAX_STEPS, int(use_attention))
+    return dims, weights, enc, tag_out
+
+
 def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_attention, use_tags, return_all=False):
     """``beam_search`` for N images at once, the search itself on the device (csrc/beam_search.cpp): encoder_out
     (N, h, w, E), tag_out (N, S).  Returns a list of N results, each what ``beam_search`` returns for that image --
@@ -194,17 +211,7 @@ def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_
         raise ValueError("sample_batch: vocab_size %d is smaller than beam_size %d" % (V, k))
     _lib.require_cuda(encoder_out, tag_out)
     N, hh, ww, E = encoder_out.shape
-    P = hh * ww
-    enc = encoder_out.reshape(N, P, E)
-    D = decoder.decoder_dim
-    if use_tags:
-        from models.decoders.attention_scn import _collect_weights
-        weights, Fd, S = _collect_weights(decoder), decoder.factored_dim, decoder.semantic_dim
-    else:       # PureAttention: the LSTM cell through its SCN view, one constant "tag" (pure_attention.py)
-        weights, Fd, S = decoder._scn_view_of_lstm(), D, 1
-        tag_out = torch.ones(N, 1, device=enc.device)
-    dims = (N, P, E, decoder.attention_dim if use_attention else 0, D, Fd, decoder.embed_dim, S, V, SF.BEAM_MAX_STEPS,
-            SF.BEAM_MAX_STEPS, int(use_attention))
+    dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
     start, end = word_map[start_token], word_map[end_token]
     res, steps = SF.beam_search_run(dims, k, weights, enc, tag_out, start, end)
     token, parent = res["token"].tolist(), res["parent"].tolist()
@@ -249,3 +256,47 @@ def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_
         one = (seq, alphas_of(rows)) if use_attention else seq
         out.append((one, [(s, sc) for s, _, sc in done]) if return_all else one)
     return out
+
+
+def check_rollout_args(samples, temperature, greedy_first=False, who="rollout_batch"):
+    """The host-side refusals of a rollout: K = samples (+ 1 with greedy_first) slots per image in [1, 8], temperature > 0"""
+    from scnattn import _lib
+    samples = int(samples)
+    K = samples + (1 if greedy_first else 0)
+    if samples < 1 or K > _lib.MAX_BEAM:
+        raise ValueError("%s: %d slots per image (samples%s) outside [1, %d]"
+                         % (who, K, " + the greedy slot" if greedy_first else "", _lib.MAX_BEAM))
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature < float("inf")):
+        raise ValueError("%s: temperature must be positive and finite (got %r)" % (who, temperature))
+    return K
+
+
+def rollout_batched(decoder, word_map, encoder_out, tag_out, use_attention, use_tags, samples=1, seed=0, draw=0,
+                    temperature=1.0, greedy_first=False):
+    """Sampled captions for N images, the whole rollout on the device (csrc/rollout.hip, SF.rollout_run): encoder_out
+    (N, h, w, E), tag_out (N, S).  K = samples (+ 1 with greedy_first: slot 0 of every image is then the arg-max caption)
+    slots per image, rows R = N*K ordered n*K + j.  Every token is a draw from softmax(logits / temperature); the noise
+    is a pure function of (seed, draw, row, step, word), so the same (seed, draw) repeats the captions and the next
+    `draw` gives fresh ones.  No dropout, like the search; fp32 only.
+    Returns (caps (R, L) int64, caplens (R, 1) int64, sum_logp (R,)) ON THE DEVICE, in the form ``decoder.forward`` takes
+    captions: caps = <start>, tokens ..., <end>, <pad> ...; caplens counts <start> and <end>, so decode_lengths =
+    caplens - 1 is the number of sampled tokens and sum_logp their log-likelihood at this temperature.  A row that
+    produced no <end> within the step limit is CUT OFF there: its caption is <start> and all `steps` tokens without an
+    <end>, caplens = steps + 1 (decode_lengths = steps).  L = steps + 1."""
+    K = check_rollout_args(samples, temperature, greedy_first)
+    from scnattn import _lib
+    _lib.require_cuda(encoder_out, tag_out)
+    V = len(word_map)
+    dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
+    start, end, pad = word_map[start_token], word_map[end_token], word_map[padding_token]
+    res, steps = SF.rollout_run(dims, K, weights, enc, tag_out, start, end, seed, draw, inv_temp=1.0 / float(temperature),
+                                greedy_first=greedy_first)
+    length = res["length"].to(torch.int64)
+    n_tok = torch.where(length > 0, length, torch.full_like(length, steps))      # a cut-off row keeps every step
+    R = length.numel()
+    pos = torch.arange(steps, device=length.device).unsqueeze(0)
+    caps = torch.full((R, steps + 1), pad, dtype=torch.int64, device=length.device)
+    caps[:, 0] = start
+    caps[:, 1:] = torch.where(pos < n_tok.unsqueeze(1), res["tokens"].to(torch.int64), caps[:, 1:])
+    return caps, (n_tok + 1).unsqueeze(1), res["sum_logp"].clone()

@@ -99,6 +99,14 @@ _SIGS = {
     "scnattn_beam_row_topk": ([vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, i32], i32),
     "scnattn_beam_merge": ([vp, i32, i32, i32, i32, i32, vp, vp, C.POINTER(vp)], i32),
     "scnattn_beam_advance": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+    "scnattn_rollout_workspace": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(sz)], i32),
+    "scnattn_rollout_layout": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(i64)], i32),
+    "scnattn_rollout_init": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, vp, i32, vp], i32),
+    "scnattn_rollout_steps": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, i32, f32, C.c_uint64, C.c_uint32,
+                               i32, i32, i32, vp], i32),
+    "scnattn_rollout_pick": ([vp, i32, i32, i32, vp, i64, f32, C.c_uint64, C.c_uint32, i32, i32, i32, i32,
+                              C.POINTER(vp)], i32),
+    "scnattn_rollout_advance": ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], i32),
     "scnattn_sgemm": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64], i32),
     "scnattn_sgemm_ws": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64,
                           vp, i64], i32),
@@ -185,6 +193,8 @@ _SIGS = {
     "scnattn_caption_loss_metrics_fwd": ([vp, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp, f32, vp, vp, vp, vp, vp,
                                           i32, vp, vp, i64, vp], i32),
     "scnattn_caption_loss_bwd": ([vp, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, f32, vp, vp, vp], i32),
+    "scnattn_caption_loss_weighted_fwd": ([vp, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, f32, vp, vp, vp, vp, vp], i32),
+    "scnattn_caption_loss_weighted_bwd": ([vp, i32, i32, i32, i32, vp, vp, i64, vp, i64, vp, vp, vp, f32, vp, vp, vp], i32),
     "scnattn_tag_pool_fwd": ([vp, i32, i32, i32, vp, i32, i64, i64, i64, vp, i64, vp, i64], i32),
     "scnattn_tag_pool_bwd": ([vp, i32, i32, i32, vp, i64, vp, i64, vp, i32, i64, i64, i64], i32),
     "scnattn_bce_fwd": ([vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp], i32),
@@ -216,6 +226,7 @@ _SIGS = {
 }
 
 BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
+ROLLOUT_NOFF = 8    # SCNATTN_ROLLOUT_NOFF
 MAX_BEAM = 8
 RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM
 OVERLAY_MAX_MAP, OVERLAY_MAX_OUT = 32, 1024      # SCNATTN_OVERLAY_MAX_MAP, SCNATTN_OVERLAY_MAX_OUT

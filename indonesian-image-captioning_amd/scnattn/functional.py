@@ -289,6 +289,84 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
 
 
 # ----------------------------------------------------------------------------------------------
+# sampled rollouts (include/scnattn.h: scnattn_rollout_*)
+# ----------------------------------------------------------------------------------------------
+_ROLLOUT_RESULTS = ("open_rows", "nsrc", "nopen", "length", "sum_logp", "token", "logp", "alpha")
+_ROLLOUT_FLOAT = ("sum_logp", "logp", "alpha")
+
+
+def rollout_run(dims, K, weights, enc, tags, start, end, seed, draw, inv_temp=1.0, greedy_first=False,
+                max_steps=BEAM_MAX_STEPS, want_alpha=False, guard=0, chunk=BEAM_CHUNK):
+    """K captions per image sampled from the decoder on the device (csrc/rollout.hip; the analogue of beam_search_run):
+    every step picks one token per open row from softmax(logits * inv_temp) by the Gumbel arg-max, the noise being
+    Philox4x32-10 of (seed, draw, row, step, word) -- the same (seed, draw) gives the same captions, another `draw` fresh
+    ones.  greedy_first: slot 0 of every image takes the arg-max instead (lowest index among equal logits).
+    dims / weights / enc / tags as for beam_search_run.  Returns (results, steps); the results stay ON THE DEVICE (views of
+    the workspace), only the open-row counter is downloaded between chunks:
+        tokens (R, steps) int32   the picks of row n*K + j, 0 (<pad>) after the row's <end>
+        logp (R, steps)           their log-probabilities under the sampled distribution, 0.0 after <end>
+        length (R,) int32         number of tokens up to and including <end>; 0 for a row that was CUT OFF: it produced no
+                                  <end> within max_steps, and all `steps` picks are its tokens
+        sum_logp (R,)             the sum of the row's logp
+        alpha (steps, R, P)       only with want_alpha (and attention), else None
+        open_rows, nsrc, nopen    the counters (scnattn_rollout_layout)
+    guard > 0 (tests): that many sentinel words behind the workspace, returned as results["guard"]."""
+    K = int(K)
+    if not 1 <= K <= _lib.MAX_BEAM:
+        raise ValueError("rollout_run: K must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, K))
+    inv_temp = float(inv_temp)
+    if not (inv_temp > 0.0 and inv_temp < float("inf")):
+        raise ValueError("rollout_run: inv_temp must be positive and finite (got %r)" % inv_temp)
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(draw) < 2 ** 32:
+        raise ValueError("rollout_run: seed must fit 64 bits and draw 32 bits, both unsigned")
+    d = Dims(*dims)
+    if not (0 <= int(start) < d.V and 0 <= int(end) < d.V):
+        raise ValueError("rollout_run: start / end token outside the vocabulary")
+    require_cuda(enc, tags, *weights)
+    dev = enc.device
+    enc, tags = f32c(enc), f32c(tags)
+    weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
+    w = _params_struct(weights)
+    N, wa = d.B, int(bool(want_alpha))
+    nbytes = C.c_size_t()
+    call("scnattn_rollout_workspace", C.byref(d), K, max_steps, wa, C.byref(nbytes))
+    off = (C.c_long * _lib.ROLLOUT_NOFF)()
+    call("scnattn_rollout_layout", C.byref(d), K, max_steps, wa, off)
+    nwords = nbytes.value // 4
+    ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_rollout_init zero-fills what needs it
+    wsi = ws.view(torch.int32)
+    if guard:
+        wsi[nwords:].fill_(0x7FC5A5A5)
+    st = stream_of(enc)
+    call("scnattn_rollout_init", st, C.byref(d), K, max_steps, wa, C.byref(w), ptr(enc), ptr(tags), int(start), ptr(ws))
+    t = 0
+    while t < max_steps:
+        n = min(chunk, max_steps - t)
+        call("scnattn_rollout_steps", st, C.byref(d), K, max_steps, wa, C.byref(w), ptr(enc), int(end), inv_temp, int(seed),
+             int(draw), int(bool(greedy_first)), t, n, ptr(ws))
+        t += n
+        if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
+            break
+    R = N * K
+    sizes = {"open_rows": 1, "nsrc": N, "nopen": N, "length": R, "sum_logp": R, "token": t * R, "logp": t * R,
+             "alpha": t * R * d.P}
+    out = {}
+    for i, name in enumerate(_ROLLOUT_RESULTS):
+        if off[i] < 0:
+            out[name] = None
+            continue
+        src = ws if name in _ROLLOUT_FLOAT else wsi
+        out[name] = src[off[i]:off[i] + sizes[name]]
+    out["tokens"] = out.pop("token").view(t, R).t()
+    out["logp"] = out["logp"].view(t, R).t()
+    if out["alpha"] is not None:
+        out["alpha"] = out["alpha"].view(t, R, d.P)
+    if guard:
+        out["guard"] = wsi[nwords:]
+    return out, t
+
+
+# ----------------------------------------------------------------------------------------------
 # stand-alone SCN cell (any batch size), split exactly where the reference splits it:
 #   scn_input      = SCNCell.forward's x side      (models/scn_cell.py:64-91)
 #   scn_recurrent  = SCNCell.recurrent_step        (models/scn_cell.py:112-154)
@@ -722,9 +800,10 @@ def bn_act(z, res, gamma, beta, run_mean, run_var, training, momentum, eps, relu
 # ----------------------------------------------------------------------------------------------
 # The train step's loss (trains/attention_scn.py:222-236) on the unpacked (B, T, V) scores
 # ----------------------------------------------------------------------------------------------
-def _caption_loss_fwd(ctx, scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_c, k=0):
-    """The forward launches of csrc/loss.hip; k >= 1: the metrics form, which also returns (hits, preds)."""
-    require_cuda(scores, alphas, caps_sorted, dl_dev)
+def _caption_loss_fwd(ctx, scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_c, k=0, row_weight=None):
+    """The forward launches of csrc/loss.hip; k >= 1: the metrics form, which also returns (hits, preds); row_weight: the
+    reward-weighted form."""
+    require_cuda(scores, alphas, caps_sorted, dl_dev, row_weight)
     scores = f32c(scores)
     alphas = None if alphas is None else f32c(alphas)
     B, T, V = scores.shape
@@ -745,8 +824,11 @@ def _caption_loss_fwd(ctx, scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_
     args = (stream_of(scores), B, T, V, P, ptr(scores), tgt, caps_sorted.stride(0),
             ptr(dl_dev), int(n_tokens), ptr(alphas), float(alpha_c), ptr(row_lse), ptr(row_loss),
             ptr(sm1) if P else None, ptr(reg_part) if P else None, ptr(loss))
-    ctx.save_for_backward(scores, caps_sorted, dl_dev, ws)
+    ctx.save_for_backward(scores, caps_sorted, dl_dev, ws, row_weight)
     ctx.meta = (B, T, V, P, int(n_tokens), float(alpha_c), alphas is not None)
+    if row_weight is not None:
+        call("scnattn_caption_loss_weighted_fwd", *args[:10], ptr(row_weight), *args[10:])
+        return loss.reshape(())
     if not k:
         call("scnattn_caption_loss_fwd", *args)
         return loss.reshape(())
@@ -758,7 +840,7 @@ def _caption_loss_fwd(ctx, scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_
 
 def _caption_loss_bwd(ctx, g):
     """(d scores, d alphas) through scnattn_caption_loss_bwd: the workspaces of either forward form"""
-    scores, caps_sorted, dl_dev, ws = ctx.saved_tensors
+    scores, caps_sorted, dl_dev, ws, row_weight = ctx.saved_tensors
     B, T, V, P, n_tokens, alpha_c, has_alpha = ctx.meta
     g = f32c(g).reshape(1)
     dscores = torch.empty_like(scores) if ctx.needs_input_grad[0] else None
@@ -768,9 +850,13 @@ def _caption_loss_bwd(ctx, g):
         dscores = torch.empty_like(scores)
     row_lse = ws[:B * T]
     sm1 = ws[2 * B * T:2 * B * T + B * P]
-    call("scnattn_caption_loss_bwd", stream_of(scores), B, T, V, P, ptr(scores),
-         C.c_void_p(caps_sorted.data_ptr() + 8), caps_sorted.stride(0), ptr(dl_dev), n_tokens, ptr(row_lse),
-         ptr(sm1) if dalphas is not None else None, alpha_c, ptr(g), ptr(dscores), ptr(dalphas))
+    head = (stream_of(scores), B, T, V, P, ptr(scores), C.c_void_p(caps_sorted.data_ptr() + 8), caps_sorted.stride(0),
+            ptr(dl_dev), n_tokens)
+    tail = (ptr(row_lse), ptr(sm1) if dalphas is not None else None, alpha_c, ptr(g), ptr(dscores), ptr(dalphas))
+    if row_weight is not None:
+        call("scnattn_caption_loss_weighted_bwd", *head, ptr(row_weight), *tail)
+    else:
+        call("scnattn_caption_loss_bwd", *head, *tail)
     return (dscores if ctx.needs_input_grad[0] else None), dalphas
 
 
@@ -796,6 +882,16 @@ class _CaptionLossMetrics(torch.autograd.Function):
         return _caption_loss_bwd(ctx, g) + (None, None, None, None, None)
 
 
+class _CaptionLossWeighted(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_c, row_weight):
+        return _caption_loss_fwd(ctx, scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_c, row_weight=row_weight)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _caption_loss_bwd(ctx, g) + (None, None, None, None, None)
+
+
 def _loss_lengths(scores, decode_lengths, dl_dev):
     T = scores.shape[1]
     n_tokens = sum(min(int(l), T) for l in decode_lengths)
@@ -811,6 +907,22 @@ def caption_loss(scores, caps_sorted, decode_lengths, alphas=None, alpha_c=1.0, 
     lengths as an int32 device vector (saves one small host-to-device copy)."""
     n_tokens, dl_dev = _loss_lengths(scores, decode_lengths, dl_dev)
     return _CaptionLoss.apply(scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_c)
+
+
+def caption_loss_weighted(scores, caps_sorted, decode_lengths, row_weight, alphas=None, alpha_c=0.0, dl_dev=None):
+    """The reward-weighted loss of self-critical training:
+        (1 / n_tokens) * sum_b row_weight[b] * sum_{t < decode_lengths[b]} (logsumexp(scores[b, t]) - scores[b, t, target])
+        + alpha_c * ((1 - alphas.sum(1))**2).mean()                      (the regulariser is not weighted)
+    row_weight (B,) on the device, fp32: the advantage of each caption, a constant -- it gets no gradient.  The same kernels
+    as caption_loss with one product per row, so weights of 1.0 give caption_loss's bits, forward and backward."""
+    B = scores.shape[0]
+    if row_weight.dim() != 1 or row_weight.numel() != B:
+        raise RuntimeError("caption_loss_weighted: row_weight must be a vector of B = %d entries (got %s)"
+                           % (B, tuple(row_weight.shape)))
+    if row_weight.requires_grad:
+        raise RuntimeError("caption_loss_weighted: row_weight is a constant and must not require grad")
+    n_tokens, dl_dev = _loss_lengths(scores, decode_lengths, dl_dev)
+    return _CaptionLossWeighted.apply(scores, alphas, caps_sorted, dl_dev, n_tokens, alpha_c, f32c(row_weight))
 
 
 def caption_loss_metrics(scores, caps_sorted, decode_lengths, alphas=None, alpha_c=1.0, dl_dev=None, k=5):

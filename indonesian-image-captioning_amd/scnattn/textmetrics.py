@@ -201,3 +201,37 @@ class CaptionScorer:
         if per_image:
             out.update(stats=stats, lcs=lcs, rouge_l=rouge, cider=cider)
         return out
+
+    def score_rows(self, image_index, hyp, hyp_len, skip_hyp=()):
+        """Per-row CIDEr-D of any number of captions, each against the references of the image `image_index[row]` names:
+        the reward of self-critical training.  hyp int32 [rows, Lh] / hyp_len int32 [rows] packed on the device,
+        image_index an integer vector of `rows` entries in [0, N) (device, or host: then it is uploaded).  The document
+        frequencies and the document count are the CORPUS's (the fitted tables, self.N), whatever the number of rows, so
+        image_index = arange(N) gives the bits of score(per_image=True)['cider'].  Returns (cider fp64 [rows], flag int32
+        [1]: non-zero when a token lay outside 0..65534) as device tensors: no download, no synchronisation.  An index
+        outside [0, N) is refused when image_index is given on the host; a device index is clamped into range by the
+        gather, so a wrong one scores against the wrong image instead of faulting."""
+        dev = self.ref.device
+        if hyp.dim() != 2 or hyp_len.dim() != 1 or hyp_len.numel() != hyp.shape[0]:
+            raise ValueError("CaptionScorer.score_rows: hyp must be [rows, Lh] and hyp_len [rows]")
+        rows = hyp.shape[0]
+        image_index = torch.as_tensor(image_index)
+        if image_index.dim() != 1 or image_index.numel() != rows or image_index.dtype.is_floating_point:
+            raise ValueError("CaptionScorer.score_rows: image_index must be an integer vector of %d entries (got %s)"
+                             % (rows, tuple(image_index.shape)))
+        if not image_index.is_cuda and rows and (int(image_index.min()) < 0 or int(image_index.max()) >= self.N):
+            raise ValueError("CaptionScorer.score_rows: image_index outside [0, %d)" % self.N)
+        _lib.require_cuda(hyp, hyp_len)
+        hyp = hyp.to(device=dev, dtype=torch.int32).contiguous()
+        hyp_len = hyp_len.to(device=dev, dtype=torch.int32).contiguous()
+        idx = image_index.to(device=dev, dtype=torch.int64).clamp(0, self.N - 1)
+        ref, ref_len = self.ref.index_select(0, idx), self.ref_len.index_select(0, idx)
+        sh, nh = _skip(skip_hyp)
+        sr, nr = _skip(self.skip_ref)
+        cider = torch.empty(rows, dtype=torch.float64, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        if rows:
+            _lib.call("scnattn_text_cider", _lib.stream_of(hyp), rows, self.R, _lib.ptr(hyp), hyp.shape[1], _lib.ptr(hyp_len),
+                      _lib.ptr(ref), self.Lr, _lib.ptr(ref_len), sh, nh, sr, nr, _lib.ptr(self.table_keys),
+                      _lib.ptr(self.table_df), self._off_c, self.N, _lib.ptr(cider), None, _lib.ptr(flag))
+        return cider, flag

@@ -50,15 +50,16 @@ def synthetic_batch(batch_size, vocab_size, max_len, image_size, semantic_dim, d
 
 
 def build_decoder(kind, cfg):
+    extra = {"encoder_dim": cfg["encoder_dim"]} if "encoder_dim" in cfg else {}      # default: the trunk's 2048 channels
     if kind == "attention_scn":
         return AttentionSCN(cfg["attention_dim"], cfg["emb_dim"], cfg["decoder_dim"], cfg["factored_dim"],
-                            cfg["semantic_dim"], cfg["vocab_size"], dropout=cfg["dropout"])
+                            cfg["semantic_dim"], cfg["vocab_size"], dropout=cfg["dropout"], **extra)
     if kind == "pure_scn":
         return PureSCN(cfg["emb_dim"], cfg["decoder_dim"], cfg["factored_dim"], cfg["semantic_dim"],
-                       cfg["vocab_size"], dropout=cfg["dropout"])
+                       cfg["vocab_size"], dropout=cfg["dropout"], **extra)
     if kind == "pure_attention":
         return PureAttention(cfg["attention_dim"], cfg["emb_dim"], cfg["decoder_dim"], cfg["vocab_size"],
-                             dropout=cfg["dropout"])
+                             dropout=cfg["dropout"], **extra)
     raise ValueError("Error model type not found!")
 
 
@@ -248,6 +249,137 @@ class TrainStep:
         if self.last_metrics is None:
             raise RuntimeError("TrainStep.topk_percent: no step has run with metrics=True")
         return topk_percent(self.last_metrics[1], self.last_metrics[2])
+
+
+class SyntheticWordMap:
+    """The word map of synthetic_batch without its V entries: <pad> = 0, <unk> = V-3, <start> = V-2, <end> = V-1"""
+
+    def __init__(self, vocab_size):
+        self.ids = {"<pad>": 0, "<unk>": vocab_size - 3, "<start>": vocab_size - 2, "<end>": vocab_size - 1}
+        self.vocab_size = vocab_size
+
+    def __len__(self):
+        return self.vocab_size
+
+    def __getitem__(self, word):
+        return self.ids[word]
+
+
+class SCSTTrainStep(TrainStep):
+    """Self-critical sequence training (Rennie et al. 2017) on the TrainStep's models and optimizers: the decoder is
+    rewarded with the CIDEr-D of the captions it samples itself.  One ``step(imgs, tags, image_index)`` =
+        encoder fwd (and the tagger's tags, when there is a tagger)
+        -> under no_grad one rollout of K = samples (+ 1 with baseline="greedy": slot 0 is the arg-max caption) captions
+           per image on the device (decoder.rollout_batch), at `temperature`
+        -> rewards = scorer.score_rows(image of each row, the captions)          CIDEr-D against that image's references
+        -> advantage = reward - baseline:  "greedy": the reward of the image's arg-max caption;
+                                           "mean":   the mean reward of the image's OTHER samples (samples >= 2)
+        -> the teacher-forced decoder.forward on the sampled rows (encoder rows repeated per sample; the attached
+           pre-pool map when there is one), SF.caption_loss_weighted with row_weight = advantage (fp32, a constant)
+        -> backward, clamp + Adam as in TrainStep.
+    The rollout runs WITHOUT dropout, as the search does; the teacher-forced pass runs in whatever mode the decoder
+    module is in (train() after construction: dropout as configured), so its log-likelihood is not bit for bit the
+    rollout's.  Every step draws fresh noise: the rollout's `draw` is the number of steps taken so far, `rollout_seed`
+    (default: `seed`) stays.  The arg-max rows get no gradient (their advantage is 0 by construction) and are left out of
+    the teacher-forced pass.  `last` keeps what the step did, on the device: caps / caplens / advantage / reward of the
+    trained rows (n*samples + s), reward_all (N, K), mean_reward / mean_baseline / mean_advantage over the trained rows
+    as 0-dim tensors, flag (a token outside CIDEr-D's range).  Nothing of it is downloaded; the step waits for the device
+    only in the rollout's counter polls and where decoder.forward learns its loop bounds (the caption lengths)."""
+
+    def __init__(self, scorer=None, samples=5, baseline="greedy", temperature=1.0, word_map=None, rollout_seed=None,
+                 seed=1234, **kw):
+        if baseline not in ("greedy", "mean"):
+            raise ValueError("SCSTTrainStep: baseline must be 'greedy' or 'mean' (got %r)" % (baseline,))
+        if baseline == "mean" and int(samples) < 2:
+            raise ValueError("SCSTTrainStep: baseline='mean' is the mean of an image's other samples and needs samples >= 2")
+        from models.decoders._common import check_rollout_args
+        self.K = check_rollout_args(samples, temperature, baseline == "greedy", who="SCSTTrainStep")
+        if scorer is None or not hasattr(scorer, "score_rows"):
+            raise ValueError("SCSTTrainStep: scorer must be a CaptionScorer (score_rows gives the rewards)")
+        if kw.get("metrics"):
+            raise ValueError("SCSTTrainStep: metrics=True belongs to the cross-entropy step")
+        super().__init__(seed=seed, **kw)
+        self.scorer, self.samples, self.baseline, self.temperature = scorer, int(samples), baseline, float(temperature)
+        self.word_map = word_map if word_map is not None else SyntheticWordMap(self.cfg["vocab_size"])
+        if len(self.word_map) != self.cfg["vocab_size"]:
+            raise ValueError("SCSTTrainStep: word_map has %d entries, vocab_size is %d" % (len(self.word_map), self.cfg["vocab_size"]))
+        self.rollout_seed = int(seed if rollout_seed is None else rollout_seed)
+        self.draw = 0
+        self.last = None
+
+    def step(self, imgs, tags, image_index, encoder_out=None):
+        """imgs (N, 3, H, W) (ignored without an encoder: then encoder_out (N, h, w, E) is given), tags (N, S) (replaced
+        by the tagger's when there is one), image_index (N,): the scorer's image behind each batch row."""
+        N = imgs.shape[0] if encoder_out is None else encoder_out.shape[0]
+        image_index = torch.as_tensor(image_index)
+        if image_index.dim() != 1 or image_index.numel() != N:
+            raise ValueError("SCSTTrainStep.step: image_index must name one image per batch row (%d), got %s"
+                             % (N, tuple(image_index.shape)))
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.encoder_bf16):
+            if self.encoder is not None:
+                encoder_out = self.encoder_call(imgs)
+            if self.tagger is not None:
+                with torch.no_grad():
+                    tags = self.tagger(imgs)
+        if encoder_out is None:
+            raise RuntimeError("SCSTTrainStep.step: no encoder and no encoder_out")
+        if self.tagger is not None:
+            tags = tags.float()
+        S, K, greedy = self.samples, self.K, self.baseline == "greedy"
+        from models.decoders._common import attached_prepool
+        from utils.token import start_token, end_token, padding_token
+        pre = attached_prepool(encoder_out)
+        with torch.no_grad():
+            caps, caplens, _ = self.decoder.rollout_batch(self.word_map, encoder_out.detach(), tags, samples=S,
+                                                          seed=self.rollout_seed, draw=self.draw,
+                                                          temperature=self.temperature, greedy_first=greedy)
+            self.draw += 1
+            dev = caps.device
+            rows_image = image_index.to(dev).repeat_interleave(K)
+            skip = tuple(self.word_map[w] for w in (start_token, end_token, padding_token))
+            reward, flag = self.scorer.score_rows(rows_image, caps[:, 1:].to(torch.int32),
+                                                  (caplens.reshape(-1) - 1).to(torch.int32), skip_hyp=skip)
+            reward_all = reward.view(N, K)
+            sampled = reward_all[:, 1:] if greedy else reward_all
+            if greedy:
+                base = reward_all[:, :1].expand(N, S)
+            else:
+                base = (sampled.sum(dim=1, keepdim=True) - sampled) / (S - 1)
+            advantage = (sampled - base).reshape(-1)
+            keep = torch.arange(N * K, device=dev).view(N, K)[:, K - S:].reshape(-1)      # the sampled rows n*K + j
+            caps_s, caplens_s = caps[keep], caplens[keep]
+        rep = lambda x: None if x is None else x.repeat_interleave(S, dim=0)      # noqa: E731
+        enc_rep, pre_rep = (None, rep(pre)) if pre is not None else (rep(encoder_out), None)
+        pool = self.encoder.enc_image_size if self.encoder is not None else encoder_out.shape[1]
+        if self.kind == "attention_scn":
+            scores, caps_sorted, decode_lengths, alphas, sort_ind = self.decoder(enc_rep, rep(tags), caps_s, caplens_s,
+                                                                                 prepool=pre_rep, pool_size=pool)
+        elif self.kind == "pure_scn":
+            scores, caps_sorted, decode_lengths, sort_ind = self.decoder(enc_rep, rep(tags), caps_s, caplens_s,
+                                                                         prepool=pre_rep, pool_size=pool)
+            alphas = None
+        else:
+            scores, caps_sorted, decode_lengths, alphas, sort_ind = self.decoder(enc_rep, caps_s, caplens_s, prepool=pre_rep,
+                                                                                 pool_size=pool)
+        dl_dev = (caplens_s.reshape(-1)[sort_ind] - 1).to(torch.int32)
+        weight = advantage[sort_ind].to(torch.float32)
+        loss = SF.caption_loss_weighted(scores, caps_sorted, decode_lengths, weight, alphas, self.cfg["alpha_c"], dl_dev)
+        self.last = dict(caps=caps_s, caplens=caplens_s, advantage=advantage, reward=sampled.reshape(-1),
+                         reward_all=reward_all, mean_reward=sampled.mean(), mean_baseline=base.mean(),
+                         mean_advantage=advantage.mean(), flag=flag, loss=loss.detach())
+        self.decoder_optimizer.zero_grad()
+        if self.encoder_optimizer is not None:
+            self.encoder_optimizer.zero_grad()
+        for r in self.reducers:
+            r.reset()
+        loss.backward()
+        scale = 1.0
+        for r in self.reducers:
+            scale = r.finish()
+        self.decoder_optimizer.step(scale)
+        if self.encoder_optimizer is not None:
+            self.encoder_optimizer.step(scale)
+        return loss
 
 
 def topk_percent(hits, n_tokens):
