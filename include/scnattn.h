@@ -26,6 +26,7 @@ extern "C" {
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
+                               + ensemble beam search (scnattn_ensemble_*, scnattn_beam_row_topk_ens; new symbols only, the version stays);
                                + sampled rollouts and the reward-weighted loss for self-critical training (scnattn_rollout_*,
                                scnattn_caption_loss_weighted_fwd/_bwd; new symbols only, the version stays);
                                0.1.8: + the tagger head (scnattn_tag_pool_fwd/_bwd, scnattn_bce_fwd/_bwd; new symbols only, the version stays), + eval-mode BatchNorm epilogue on bf16 maps (scnattn_bn_eval16, scnattn_conv1x1_fwd_bn_eval16, _conv3x3_fwd_bn_eval16;
@@ -183,6 +184,40 @@ int scnattn_beam_init(void* stream, const scnattn_dims* d, int K, int max_steps,
                       const float* tags, int start_token, float* ws);
 int scnattn_beam_steps(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                        int end_token, int t0, int n_steps, float* ws);
+/* ---- ensemble beam search: up to SCNATTN_MAX_ENSEMBLE decoders under ONE search state -----------------------------------
+ * Published caption scores are reported for an ensemble of the trained models; the three decoders read the same encoder map
+ * and share one vocabulary.  The search above, with the candidates of a step ranked by a COMBINED distribution.  With
+ * l_mv = log_softmax(fc_m(h_mj))[v] of member m:
+ *   mode 0 ("logprob", weighted geometric mean of the probabilities)   c_v = sum_m w_m l_mv, summed in member order
+ *   mode 1 ("prob", weighted arithmetic mean of the probabilities)     c_v = a_v + log(sum_m w_m exp(l_mv - a_v)),
+ *                                                                      a_v = max_m l_mv (finite when every exp underflows)
+ * and a step takes the top kk of score[j] + c_v under the TIE RULE.  Every member keeps its own recurrent state, gathered by
+ * the same parents.  M = 1, mode 0, w = 1 is, bit for bit, the search above.
+ *   dims / w   arrays of M structs.  Members may differ in has_att, A, D, F, M (embed_dim) and S; they must agree in B, P, E
+ *              and V (refused otherwise).
+ *   enc [N,P,E] one map for all members; tags: HOST array of M device pointers, tags[m] [N,S_m]
+ *   member_w   HOST array of M fp32 weights, each positive and finite, summing to 1 (normalise in double, then round)
+ *   alpha_member  the member whose attention maps are recorded (-1, or a member without attention: none)
+ *   scnattn_ensemble_layout  the 13 offsets of scnattn_beam_layout, in the same order (12: the maps of alpha_member or -1)
+ *   ws: scnattn_ensemble_workspace bytes, 16-byte aligned: one search state, one step workspace per member, ONE split-K
+ *   scratch for all of them -- everything runs on the caller's stream, in order.
+ * A step launches the decode part of every member (9-10 launches with attention, 6-7 without), one _row_topk_ens, one
+ * _merge and one _advance per member.  alpha_member, M, K and max_steps must be the same in the four calls.
+ * fp32 only: option "decoder_bf16" is ignored here.  Dense encoder_out only (no scnattn_pool).
+ *   scnattn_beam_row_topk_ens  the selection kernel alone: logits / ld / w are HOST arrays of M entries (row r of member m at
+ *   logits[m] + r*ld[m], ld[m] >= V); refuses (-1) M outside [1, 4], K outside [1, 8], V < K, a null row, ld < V, a
+ *   weight that is not positive and finite, mode outside {0, 1}.  Rows of dead slots are neither read nor written. */
+#define SCNATTN_MAX_ENSEMBLE 4
+int scnattn_ensemble_workspace(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, size_t* bytes);
+int scnattn_ensemble_layout(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, long* offsets);
+int scnattn_ensemble_init(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                          const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws);
+int scnattn_ensemble_steps(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                           const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
+                           int n_steps, float* ws);
+int scnattn_beam_row_topk_ens(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
+                              const float* w, int mode, const float* scores, const int32_t* nsrc, float* outv, int32_t* outi,
+                              int force_passes);
 /* ---- sampled rollouts for self-critical training (csrc/rollout.hip, the driver beside the search's) ---------------------
  * The set-up and the decode step of the search above over the same N*K rows, but the K slots of an image are INDEPENDENT
  * captions: nothing is compacted, the state carries over slot for slot, and after fc one token per open row is picked:

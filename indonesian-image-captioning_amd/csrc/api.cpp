@@ -41,6 +41,13 @@ int beam_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const
               const float* tags, int start_token, float* ws);
 int beam_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                int end_token, int t0, int n_steps, float* ws);
+int ensemble_workspace(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, size_t* bytes);
+int ensemble_layout(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, long* off);
+int ensemble_init(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                  const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws);
+int ensemble_steps(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                   const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
+                   int n_steps, float* ws);
 int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
 int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off);
 int rollout_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
@@ -128,6 +135,30 @@ int scnattn_beam_attn_context(void* stream, int N, int K, int P, int E, const fl
 int scnattn_beam_row_topk(void* stream, int N, int K, int V, const float* logits, long ld, const float* scores,
                           const int32_t* nsrc, float* outv, int32_t* outi, int force_passes) {
     return beam_row_topk(ST(stream), N, K, V, logits, ld, scores, nsrc, outv, outi, force_passes);
+}
+int scnattn_beam_row_topk_ens(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
+                              const float* w, int mode, const float* scores, const int32_t* nsrc, float* outv, int32_t* outi,
+                              int force_passes) {
+    if (M < 1 || M > SCN_MAX_ENSEMBLE) { set_error("scnattn_beam_row_topk_ens: need 1 <= members <= 4"); return -1; }
+    if (!logits || !ld || !w) { set_error("scnattn_beam_row_topk_ens: null member arrays"); return -1; }
+    EnsRows e{};
+    for (int m = 0; m < M; ++m) { e.p[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; }
+    return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, outv, outi, force_passes);
+}
+int scnattn_ensemble_workspace(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, size_t* bytes) {
+    return ensemble_workspace(M, dims, K, max_steps, alpha_member, bytes);
+}
+int scnattn_ensemble_layout(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, long* offsets) {
+    return ensemble_layout(M, dims, K, max_steps, alpha_member, offsets);
+}
+int scnattn_ensemble_init(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                          const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
+    return ensemble_init(ST(stream), M, dims, K, max_steps, alpha_member, w, enc, tags, start_token, ws);
+}
+int scnattn_ensemble_steps(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                           const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
+                           int n_steps, float* ws) {
+    return ensemble_steps(ST(stream), M, dims, K, max_steps, alpha_member, w, enc, member_w, mode, end_token, t0, n_steps, ws);
 }
 int scnattn_beam_merge(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
                        void* const* state) {

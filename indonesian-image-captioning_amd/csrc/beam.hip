@@ -6,6 +6,9 @@
 //   beam_attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0      (attn_scores_kernel's pixel-row layout)
 //   beam_attn_context  K softmaxes over P, awe / z for the K rows from one pass over enc[n] (attn_context_kernel's tiles)
 //   beam_row_topk      per live row: log-softmax statistics and the row's top K of  score + logit - lse
+//   beam_row_topk_ens  the same selection for an ensemble: M logits rows per live row, top K of score + c_v, where c_v is
+//                      the weighted mean of the members' log-probabilities (mode 0) or the log of the weighted mean of
+//                      their probabilities (mode 1)
 //   beam_merge         per image: the top kk of the nsrc x K row candidates, <end> picks recorded, the rest compacted
 //   beam_advance       h / c gathered from the parent slot, next input embedding gathered from the table
 // ORDER (the tie rule): candidates are ranked by (value descending, flat index j*V + v ascending), values compared as the
@@ -275,6 +278,144 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(int K, int V, const 
     }
 }
 
+// ---- the row selection of an ENSEMBLE: M decoders, one search state ------------------------------------
+// elements v0 .. v0+3 of a member's row: one 16-byte load where the row allows it, scalar loads otherwise and for the tail
+__device__ __forceinline__ void ens_load4(const float* __restrict__ g, int v0, int V, bool vec, float x[4]) {
+    if (vec && v0 + 3 < V) {
+        const f32x4 l = ld4(g + v0);
+        x[0] = l[0]; x[1] = l[1]; x[2] = l[2]; x[3] = l[3];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) x[c] = v0 + c < V ? g[v0 + c] : 0.f;
+    }
+}
+
+// c_v from the members' l_mv = x_mv - lse_m.  Products and sums are spelled out (one rounded product, then fused
+// multiply-adds in member order), so that the staged and the unstaged kernel compute the same bits.
+//   mode 0: sum_m w_m l_mv                                 (weighted geometric mean of the probabilities)
+//   mode 1: a + log(sum_m w_m exp(l_mv - a)), a = max_m l_mv      (weighted arithmetic mean; finite when exp(l_mv) underflows)
+__device__ __forceinline__ float ens_combine(int M, int mode, const float l[SCN_MAX_ENSEMBLE], const EnsRows& e) {
+    if (mode == 0) {
+        float c = __fmul_rn(e.w[0], l[0]);
+#pragma unroll
+        for (int m = 1; m < SCN_MAX_ENSEMBLE; ++m)
+            if (m < M) c = fmaf(e.w[m], l[m], c);
+        return c;
+    }
+    float a = l[0];
+#pragma unroll
+    for (int m = 1; m < SCN_MAX_ENSEMBLE; ++m)
+        if (m < M) a = fmaxf(a, l[m]);
+    float s = __fmul_rn(e.w[0], expf(l[0] - a));
+#pragma unroll
+    for (int m = 1; m < SCN_MAX_ENSEMBLE; ++m)
+        if (m < M) s = fmaf(e.w[m], expf(l[m] - a), s);
+    return a + logf(s);
+}
+
+// One workgroup per live row, as beam_row_topk_kernel.  Per member the log-sum-exp of its row with that kernel's
+// reductions (the sum runs over v = tid, tid + 256, ... in every path, so lse_m has that kernel's bits; the maximum does not
+// depend on the order it is taken in).  STAGED: a member's row passes through LDS for its statistics, then c_v of the whole
+// row is written there once and the K rounds run over it.  Otherwise every round recomputes c_v from the M global rows.
+template <bool STAGED>
+__global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int V, int M, int mode, EnsRows e, unsigned vecmask,
+                                                                const float* __restrict__ scores,
+                                                                const int* __restrict__ nsrc, float* __restrict__ outv,
+                                                                int* __restrict__ outi) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* redv = sm;                               // [4]
+    int* redi = reinterpret_cast<int*>(sm + 8);     // [4]
+    float* buf = sm + 16;                           // [V] when STAGED
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    const int n = (int)(row / K), j = (int)(row - (long)n * K);
+    if (j >= nsrc[n]) return;
+    const int groups = (V + 3) >> 2;
+    const float* g[SCN_MAX_ENSEMBLE];
+    float lse[SCN_MAX_ENSEMBLE];
+#pragma unroll
+    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) {
+        g[m] = nullptr;
+        lse[m] = 0.f;
+        if (m < M) {                                // uniform over the workgroup
+            g[m] = e.p[m] + row * e.ld[m];
+            const bool vec = (vecmask >> m) & 1u;
+            float mx = -INFINITY;
+            for (int q = tid; q < groups; q += 256) {
+                float x[4];
+                ens_load4(g[m], q * 4, V, vec, x);
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (q * 4 + c < V) {
+                        if (STAGED) buf[q * 4 + c] = x[c];
+                        mx = fmaxf(mx, x[c]);
+                    }
+            }
+            mx = block_sum_max(mx, redv, true);     // its barriers also publish buf
+            const float* src = STAGED ? buf : g[m];
+            float s = 0.f;
+            for (int v = tid; v < V; v += 256) s += expf(src[v] - mx);
+            s = block_sum_max(s, redv, false);      // ... and every thread is done with buf before it is written again
+            lse[m] = mx + logf(s);
+        }
+    }
+    if (STAGED) {
+        for (int q = tid; q < groups; q += 256) {
+            float x[SCN_MAX_ENSEMBLE][4];
+#pragma unroll
+            for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
+                if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, x[m]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (q * 4 + c < V) {
+                    float l[SCN_MAX_ENSEMBLE];
+#pragma unroll
+                    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? x[m][c] - lse[m] : 0.f;
+                    buf[q * 4 + c] = ens_combine(M, mode, l, e);
+                }
+        }
+        __syncthreads();
+    }
+    const float sc = scores[row];
+    float pv = INFINITY;
+    int pi = -1;
+    for (int r = 0; r < K; ++r) {
+        float bv = -INFINITY;
+        int bi = INT_MAX;
+        if (STAGED) {
+            for (int v = tid; v < V; v += 256) {
+                const float val = sc + buf[v];
+                if (before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
+            }
+        } else {
+            for (int q = tid; q < groups; q += 256) {
+                float x[SCN_MAX_ENSEMBLE][4];
+#pragma unroll
+                for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
+                    if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, x[m]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int v = q * 4 + c;
+                    if (v < V) {
+                        float l[SCN_MAX_ENSEMBLE];
+#pragma unroll
+                        for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? x[m][c] - lse[m] : 0.f;
+                        const float val = sc + ens_combine(M, mode, l, e);
+                        if (before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
+                    }
+                }
+            }
+        }
+        block_best(bv, bi, redv, redi);
+        if (tid == 0) {
+            outv[row * K + r] = bv;
+            outi[row * K + r] = bi;
+        }
+        pv = bv;
+        pi = bi;
+    }
+}
+
 __global__ __launch_bounds__(64) void beam_merge_kernel(int K, int V, int end_tok, int t, const float* __restrict__ candv,
                                                         const int* __restrict__ candi, BeamState s) {
     __shared__ float sv[8];
@@ -435,6 +576,31 @@ int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long
     else
         hipLaunchKernelGGL(beam_row_topk_kernel<false>, grid, block, 16 * sizeof(float), st, K, V, logits, ld, scores, nsrc,
                            outv, outi);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
+                      const int* nsrc, float* outv, int* outi, int force_passes) {
+    if (N <= 0) return 0;
+    SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "beam_row_topk_ens: need 1 <= members <= 4");
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk_ens: need 1 <= beam size <= 8 and vocab_size >= beam size");
+    SCN_ARG(mode == 0 || mode == 1, "beam_row_topk_ens: mode must be 0 (logprob) or 1 (prob)");
+    SCN_ARG(scores && nsrc && outv && outi, "beam_row_topk_ens: null argument");
+    unsigned vecmask = 0;
+    for (int m = 0; m < M; ++m) {
+        SCN_ARG(e.p[m] && e.ld[m] >= V, "beam_row_topk_ens: a member's logits are null or its leading dimension < vocab_size");
+        SCN_ARG(e.w[m] > 0.f && e.w[m] < INFINITY, "beam_row_topk_ens: member weights must be positive and finite");
+        if (aligned16(e.p[m]) && e.ld[m] % 4 == 0) vecmask |= 1u << m;
+    }
+    const size_t staged = (size_t)(16 + V) * sizeof(float);
+    dim3 grid(N * K), block(256);
+    if (staged <= 64 * 1024 && !force_passes)
+        hipLaunchKernelGGL(beam_row_topk_ens_kernel<true>, grid, block, staged, st, K, V, M, mode, e, vecmask, scores, nsrc,
+                           outv, outi);
+    else
+        hipLaunchKernelGGL(beam_row_topk_ens_kernel<false>, grid, block, 16 * sizeof(float), st, K, V, M, mode, e, vecmask,
+                           scores, nsrc, outv, outi);
     SCN_LAUNCH_CHECK();
     return 0;
 }

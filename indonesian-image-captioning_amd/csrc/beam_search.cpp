@@ -10,6 +10,9 @@
 //
 // The rollout driver of self-critical training (scnattn_rollout_*, at the end of this file) shares the set-up and the decode
 // part of a step (decode_setup, decode_step) and ends a step with rollout_pick + rollout_advance (csrc/rollout.hip).
+//
+// The ensemble driver (scnattn_ensemble_*, between the two) steps up to four decoders under one search state: the decode
+// part per member, one beam_row_topk_ens over their logits, one beam_merge, beam_advance per member.
 #include <hip/hip_runtime.h>
 #include "../../include/scnattn.h"
 #include "common.h"
@@ -64,7 +67,8 @@ void carve_step_state(Carver& c, const scnattn_dims& d, long R, StepWs& b) {
     b.logits = c.take(sz(R, d.V));
 }
 
-void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b) {
+// shared_gws: the split-K scratch of another StepWs on the same stream (an ensemble's members run one after the other)
+void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b, const StepWs* shared_gws = nullptr) {
     const int N = d.B, P = d.P, E = d.E, A = d.A, D = d.D, F = d.F, F4 = 4 * F, NA = ncatA(d);
     b.att1 = d.has_att ? c.take(sz(N, P, A)) : nullptr;
     b.qx = c.take(sz(N, F4));
@@ -77,7 +81,7 @@ void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b) {
     b.slabA = c.take(sz(SCN_MAX_KSPLIT, R, NA));
     b.slabC = d.has_att ? c.take(sz(SCN_MAX_KSPLIT, R, F4)) : nullptr;
     b.slabD = c.take(sz(SCN_MAX_KSPLIT, 4, R, D));
-    b.gws = c.take(BEAM_GEMM_WS_FLOATS);
+    b.gws = shared_gws ? shared_gws->gws : c.take(BEAM_GEMM_WS_FLOATS);
 }
 
 size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b) {
@@ -234,6 +238,147 @@ int beam_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, con
         SCN_TRY(beam_row_topk(st, N, K, V, b.logits, V, b.s.scores, b.s.nsrc, b.candv, b.candi, 0));
         SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
         SCN_TRY(beam_advance(st, N, K, D, M, V, b.hB, b.cB, parent_t, token_t, w->embedding_weight, b.hA, b.cA, b.emb));
+    }
+    return 0;
+}
+
+// ---- ensemble search: M decoders under ONE search state ---------------------------------------------------
+// The members read the same enc [N,P,E] and share the vocabulary; each keeps its own StepWs (state, set-up results) and
+// they share the split-K scratch, since everything runs on one stream in order.  A step is, per member, decode_step with
+// that member's hA/cA -> hB/cB, then ONE beam_row_topk_ens over the M logits buffers, ONE beam_merge, and per member
+// beam_advance with its own table and state: (decode launches of the members) + 2 + M.  The attention maps of one member
+// (alpha_member) are recorded; the other attention members pass a null alpha_t, as the rollout does.  fp32 only.
+namespace {
+
+struct EnsembleWs {
+    BeamState s;
+    float* candv;
+    int* candi;
+    float* alpha;       // [T][R][P] of alpha_member, or null
+    size_t state_floats;
+    StepWs m[SCN_MAX_ENSEMBLE];
+};
+
+bool ens_alpha(int M, const scnattn_dims* d, int alpha_member) {
+    return alpha_member >= 0 && alpha_member < M && d[alpha_member].has_att;
+}
+
+size_t carve_ensemble(int M, const scnattn_dims* d, int K, int T, int alpha_member, float* base, EnsembleWs& b) {
+    Carver c(base);
+    const int N = d[0].B, P = d[0].P;
+    const long R = (long)N * K;
+    b.s.R = (int)R;
+    b.s.scores = c.take(R);
+    b.s.nsrc = ints(c.take(N));
+    b.s.kk = ints(c.take(N));
+    b.s.ncomp = ints(c.take(N));
+    b.s.best_idx = ints(c.take(N));
+    b.s.best_score = c.take(N);
+    b.s.open_images = ints(c.take(1));
+    b.s.comp_score = c.take(R);
+    b.s.comp_step = ints(c.take(R));
+    b.s.comp_parent = ints(c.take(R));
+    b.s.token = ints(c.take(sz(T, R)));
+    b.s.parent = ints(c.take(sz(T, R)));
+    b.alpha = ens_alpha(M, d, alpha_member) ? c.take(sz(T, R, P)) : nullptr;
+    for (int m = 0; m < M; ++m) {
+        b.m[m].alpha = m == alpha_member ? b.alpha : nullptr;
+        carve_step_state(c, d[m], R, b.m[m]);
+    }
+    b.candv = c.take(sz(R, K));
+    b.candi = ints(c.take(sz(R, K)));
+    b.state_floats = c.off;
+    for (int m = 0; m < M; ++m) {
+        b.m[m].state_floats = b.state_floats;
+        carve_step_setup(c, d[m], R, b.m[m], m ? &b.m[0] : nullptr);
+    }
+    return c.off * sizeof(float);
+}
+
+int check_ensemble(int M, const scnattn_dims* d, int K, int T, int alpha_member) {
+    SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "an ensemble has 1 to 4 members");
+    SCN_ARG(d, "dims is NULL");
+    for (int m = 0; m < M; ++m) {
+        SCN_TRY(check_beam(d + m, K, T));
+        SCN_ARG(d[m].B == d[0].B && d[m].P == d[0].P && d[m].E == d[0].E && d[m].V == d[0].V,
+                "the members of an ensemble must agree in B, P, E and V");
+    }
+    SCN_ARG(alpha_member >= -1 && alpha_member < M, "alpha_member must be -1 or a member index");
+    return 0;
+}
+
+}  // namespace
+
+int ensemble_workspace(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, size_t* bytes) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_ARG(bytes, "ensemble_workspace: bytes is NULL");
+    EnsembleWs b;
+    *bytes = carve_ensemble(M, d, K, max_steps, alpha_member, nullptr, b);
+    return 0;
+}
+
+// off[SCNATTN_BEAM_NOFF]: the offsets of scnattn_beam_layout, in the same order
+int ensemble_layout(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, long* off) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_ARG(off, "ensemble_layout: offsets is NULL");
+    EnsembleWs b;
+    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
+    carve_ensemble(M, d, K, max_steps, alpha_member, base, b);
+    const void* p[SCNATTN_BEAM_NOFF] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
+                                        b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
+                                        b.s.parent, b.alpha};
+    for (int i = 0; i < SCNATTN_BEAM_NOFF; ++i)
+        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
+    return 0;
+}
+
+int ensemble_init(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                  const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_ARG(w && enc && tags && ws, "ensemble_init: null argument");
+    for (int m = 0; m < M; ++m) SCN_ARG(tags[m], "ensemble_init: a member's tags are NULL");
+    SCN_ARG(start_token >= 0 && start_token < d[0].V, "ensemble_init: start token outside the vocabulary");
+    SCN_ARG(aligned16(ws), "ensemble_init: the workspace must be 16-byte aligned");
+    EnsembleWs b;
+    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b);
+    SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
+    SCN_TRY(beam_state_init(st, d[0].B, K, b.s));
+    for (int m = 0; m < M; ++m) SCN_TRY(decode_setup(st, d[m], K, w + m, enc, tags[m], start_token, b.m[m]));
+    return 0;
+}
+
+// Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.
+int ensemble_steps(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                   const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
+                   int n_steps, float* ws) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_ARG(w && enc && member_w && ws, "ensemble_steps: null argument");
+    SCN_ARG(t0 >= 0 && n_steps >= 0, "ensemble_steps: negative step");
+    const int N = d[0].B, P = d[0].P, V = d[0].V, R = N * K;
+    EnsembleWs b;
+    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b);
+    EnsRows rows{};
+    for (int m = 0; m < M; ++m) {
+        rows.p[m] = b.m[m].logits;
+        rows.ld[m] = V;
+        rows.w[m] = member_w[m];
+    }
+    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
+    for (int t = t0; t < t1; ++t) {
+        int* token_t = b.s.token + (long)t * R;
+        int* parent_t = b.s.parent + (long)t * R;
+        for (int m = 0; m < M; ++m) {
+            const StepWs& s = b.m[m];
+            SCN_TRY(decode_step(st, d[m], K, w + m, enc, s, b.s.nsrc, s.alpha ? s.alpha + (long)t * R * P : nullptr, s.hA, s.cA,
+                                s.hB, s.cB));
+        }
+        SCN_TRY(beam_row_topk_ens(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, b.candv, b.candi, 0));
+        SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
+        for (int m = 0; m < M; ++m) {
+            const StepWs& s = b.m[m];
+            SCN_TRY(beam_advance(st, N, K, d[m].D, d[m].M, V, s.hB, s.cB, parent_t, token_t, w[m].embedding_weight, s.hA, s.cA,
+                                 s.emb));
+        }
     }
     return 0;
 }

@@ -159,6 +159,18 @@ int beam_attn_context(hipStream_t st, int N, int K, int P, int E, const float* e
 // force_passes != 0 (tests): read the row from global memory in every pass even when it fits the LDS.
 int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
                   float* outv, int* outi, int force_passes);
+// The M logits rows an ensemble's selection reads per live row r: p[m] + r * ld[m], weights w[m] > 0 that sum to 1.
+#define SCN_MAX_ENSEMBLE 4
+struct EnsRows {
+    const float* p[SCN_MAX_ENSEMBLE];
+    long ld[SCN_MAX_ENSEMBLE];
+    float w[SCN_MAX_ENSEMBLE];
+};
+// beam_row_topk over a combined distribution: the top K of scores[row] + c_v with l_mv = logits_m[row][v] - lse_m(row),
+// mode 0: c_v = sum_m w_m l_mv;  mode 1: c_v = a_v + log(sum_m w_m exp(l_mv - a_v)), a_v = max_m l_mv.
+// mode 0 with M = 1, w = 1 writes the bits of beam_row_topk.
+int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
+                      const int* nsrc, float* outv, int* outi, int force_passes);
 int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
                const BeamState& s);
 int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,

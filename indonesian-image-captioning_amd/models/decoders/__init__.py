@@ -1,0 +1,1 @@
+from .ensemble import DecoderEnsemble  # noqa: F401

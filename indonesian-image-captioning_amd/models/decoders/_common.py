@@ -214,6 +214,14 @@ def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_
     dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
     start, end = word_map[start_token], word_map[end_token]
     res, steps = SF.beam_search_run(dims, k, weights, enc, tag_out, start, end)
+    return trace_back(res, steps, N, k, start, end, (hh, ww), use_attention, return_all)
+
+
+def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=False):
+    """The results of a device search (SF.beam_search_run / SF.ensemble_search_run) -> the list of N results that
+    ``beam_search_batched`` documents: the parent chains read off the token / parent records, the all-ones first alpha map
+    (``use_attention``: the search kept maps), the fallback to the best open beam."""
+    hh, ww = map_hw
     token, parent = res["token"].tolist(), res["parent"].tolist()
     alpha = res["alpha"]
     ones = torch.ones(1, hh, ww)

@@ -1,0 +1,98 @@
+"""An ensemble of caption decoders under ONE beam search (csrc/beam_search.cpp: scnattn_ensemble_*).
+
+Published caption scores are normally those of an ensemble of the trained models.  The three decoders read the same
+EncoderCaption features and the same tag vector and share one vocabulary, so the search state is one per image, not one
+per model: every step runs the decode part of each member, ranks the candidates by the COMBINED distribution and advances
+every member's recurrent state by the same parents."""
+import torch
+from torch import nn
+
+from scnattn import functional as SF
+from utils.token import start_token, end_token
+from . import _common
+
+COMBINE = ("logprob", "prob")
+
+
+def _kind(decoder):
+    """(use_attention, use_tags) of a member, as the three decoders pass them to the search"""
+    from .attention_scn import AttentionSCN
+    from .pure_attention import PureAttention
+    from .pure_scn import PureSCN
+    if isinstance(decoder, PureAttention):
+        return True, False
+    if isinstance(decoder, PureSCN):
+        return False, True
+    if isinstance(decoder, AttentionSCN):
+        return True, True
+    raise ValueError("DecoderEnsemble: %s is not one of AttentionSCN, PureSCN, PureAttention" % type(decoder).__name__)
+
+
+class DecoderEnsemble(nn.Module):
+    """``DecoderEnsemble(decoders, weights=None, combine="logprob", alpha_member=None)``
+
+    decoders      1 to 4 of AttentionSCN / PureSCN / PureAttention with one ``vocab_size``
+    weights       one positive number per member (None: equal); normalised to sum 1
+    combine       "logprob": candidates are ranked by the weighted mean of the members' log-probabilities (the weighted
+                  geometric mean of the probabilities); "prob": by the log of the weighted mean of their probabilities
+    alpha_member  index of the member whose attention maps ``sample_batch`` returns (None: the first member with attention)
+
+    ``sample_batch`` returns what a single decoder's ``sample_batch`` returns, so `scnattn.inference.Captioner` and
+    `trains.harness.evaluate_captions` take an ensemble wherever they take a decoder.  fp32 only, like the search."""
+
+    def __init__(self, decoders, weights=None, combine="logprob", alpha_member=None):
+        super().__init__()
+        decoders = list(decoders)
+        if not 1 <= len(decoders) <= SF._lib.MAX_ENSEMBLE:
+            raise ValueError("DecoderEnsemble: 1 to %d members (got %d)" % (SF._lib.MAX_ENSEMBLE, len(decoders)))
+        self.kinds = [_kind(d) for d in decoders]
+        if len({d.vocab_size for d in decoders}) != 1:
+            raise ValueError("DecoderEnsemble: the members' vocab_size differ: %s" % [d.vocab_size for d in decoders])
+        if combine not in COMBINE:
+            raise ValueError("DecoderEnsemble: combine must be one of %s (got %r)" % (COMBINE, combine))
+        self.member_weights = SF.normalise_member_weights(weights, len(decoders))
+        with_att = [i for i, (att, _) in enumerate(self.kinds) if att]
+        if alpha_member is None:
+            alpha_member = with_att[0] if with_att else None
+        elif alpha_member not in with_att:
+            raise ValueError("DecoderEnsemble: alpha_member %r is not a member with attention" % (alpha_member,))
+        self.decoders = nn.ModuleList(decoders)
+        self.combine, self.alpha_member = combine, alpha_member
+        self.vocab_size = decoders[0].vocab_size
+
+    @property
+    def needs_tags(self):
+        return any(tags for _, tags in self.kinds)
+
+    @property
+    def has_alphas(self):
+        return self.alpha_member is not None
+
+    def sample_batch(self, beam_size, word_map, encoder_out, tags=None, return_all=False):
+        """encoder_out (N, h, w, E), tags (N, S) (may be None when no member uses tags) -> list of N results in the form
+        ``_common.beam_search_batched`` returns them: the sequence with the leading <start>, paired with the attention maps
+        of ``alpha_member`` (the all-ones first map included) when there is one; the best open beam where nothing
+        completed; with ``return_all`` each result paired with the image's completed (sequence, score) list."""
+        k = int(beam_size)
+        if not 1 <= k <= SF._lib.MAX_BEAM:
+            raise ValueError("sample_batch: beam_size must be in [1, %d] (got %d)" % (SF._lib.MAX_BEAM, k))
+        V = len(word_map)
+        if V != self.vocab_size:
+            raise ValueError("sample_batch: the word map has %d words, the members' vocab_size is %d" % (V, self.vocab_size))
+        if V < k:
+            raise ValueError("sample_batch: vocab_size %d is smaller than beam_size %d" % (V, k))
+        if self.needs_tags and tags is None:
+            raise ValueError("sample_batch: a member of the ensemble uses tags and none were given")
+        SF._lib.require_cuda(encoder_out, tags)
+        N, hh, ww, _ = encoder_out.shape
+        dims_list, weights_list, tags_list = [], [], []
+        for dec, (use_att, use_tags) in zip(self.decoders, self.kinds):
+            dims, weights, enc, tg = _common._search_operands(dec, V, encoder_out, tags if use_tags else None, use_att,
+                                                              use_tags)
+            dims_list.append(dims)
+            weights_list.append(weights)
+            tags_list.append(tg)
+        start, end = word_map[start_token], word_map[end_token]
+        res, steps = SF.ensemble_search_run(dims_list, k, weights_list, enc, tags_list, self.member_weights, self.combine,
+                                            start, end, self.alpha_member)
+        return _common.trace_back(res, steps, N, k, start, end, (hh, ww), self.has_alphas, return_all)

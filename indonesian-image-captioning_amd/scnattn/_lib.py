@@ -99,6 +99,13 @@ _SIGS = {
     "scnattn_beam_row_topk": ([vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, i32], i32),
     "scnattn_beam_merge": ([vp, i32, i32, i32, i32, i32, vp, vp, C.POINTER(vp)], i32),
     "scnattn_beam_advance": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+    "scnattn_beam_row_topk_ens": ([vp, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(f32), i32, vp, vp, vp, vp,
+                                   i32], i32),
+    "scnattn_ensemble_workspace": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(sz)], i32),
+    "scnattn_ensemble_layout": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(i64)], i32),
+    "scnattn_ensemble_init": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, C.POINTER(vp), i32, vp], i32),
+    "scnattn_ensemble_steps": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, C.POINTER(f32), i32, i32, i32,
+                                i32, vp], i32),
     "scnattn_rollout_workspace": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(sz)], i32),
     "scnattn_rollout_layout": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(i64)], i32),
     "scnattn_rollout_init": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, vp, i32, vp], i32),
@@ -228,6 +235,7 @@ _SIGS = {
 BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
 ROLLOUT_NOFF = 8    # SCNATTN_ROLLOUT_NOFF
 MAX_BEAM = 8
+MAX_ENSEMBLE = 4    # SCNATTN_MAX_ENSEMBLE
 RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM
 OVERLAY_MAX_MAP, OVERLAY_MAX_OUT = 32, 1024      # SCNATTN_OVERLAY_MAX_MAP, SCNATTN_OVERLAY_MAX_OUT
 TEXT_MAX_LEN, TEXT_MAX_REFS, TEXT_CIDER_MAX_TOKEN = 128, 32, 65534      # SCNATTN_TEXT_MAX_LEN, _MAX_REFS, _CIDER_MAX_TOKEN

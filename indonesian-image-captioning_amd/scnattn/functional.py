@@ -270,9 +270,15 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
         t += n
         if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
             break
+    return _beam_results(ws, off, N, K, d.P, t, nwords, guard), t
+
+
+def _beam_results(ws, off, N, K, P, t, nwords, guard):
+    """the host tensors of a finished search (t steps ran), by the names of scnattn_beam_layout"""
+    wsi = ws.view(torch.int32)
     R = N * K
     sizes = {"open_images": 1, "nsrc": N, "kk": N, "ncomp": N, "best_idx": N, "best_score": N, "scores": R,
-             "comp_score": R, "comp_step": R, "comp_parent": R, "token": t * R, "parent": t * R, "alpha": t * R * d.P}
+             "comp_score": R, "comp_step": R, "comp_parent": R, "token": t * R, "parent": t * R, "alpha": t * R * P}
     out = {}
     for i, name in enumerate(_BEAM_RESULTS):
         if off[i] < 0:
@@ -282,10 +288,91 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
         out[name] = src[off[i]:off[i] + sizes[name]].cpu()
     out["token"], out["parent"] = out["token"].view(t, R), out["parent"].view(t, R)
     if out["alpha"] is not None:
-        out["alpha"] = out["alpha"].view(t, R, d.P)
+        out["alpha"] = out["alpha"].view(t, R, P)
     if guard:
         out["guard"] = wsi[nwords:].cpu()
-    return out, t
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# ensemble beam search (include/scnattn.h: scnattn_ensemble_*)
+# ----------------------------------------------------------------------------------------------
+ENSEMBLE_MODES = {"logprob": 0, "prob": 1}
+
+
+def normalise_member_weights(weights, M):
+    """M positive finite weights -> the fp32 values the kernel takes: normalised to sum 1 in fp64, then rounded.
+    None: equal weights."""
+    import math
+    if weights is None:
+        weights = [1.0] * M
+    weights = [float(x) for x in weights]
+    if len(weights) != M:
+        raise ValueError("ensemble: %d weights for %d members" % (len(weights), M))
+    if not all(math.isfinite(x) and x > 0.0 for x in weights):
+        raise ValueError("ensemble: member weights must be positive and finite (got %r)" % (weights,))
+    total = math.fsum(weights)
+    out = [C.c_float(x / total).value for x in weights]
+    if not all(math.isfinite(x) and x > 0.0 for x in out):
+        raise ValueError("ensemble: a member weight vanishes in fp32 after normalisation (got %r)" % (weights,))
+    return out
+
+
+def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, member_weights, mode, start, end, alpha_member,
+                        max_steps=BEAM_MAX_STEPS, chunk=BEAM_CHUNK, guard=0):
+    """beam_search_run for an ensemble of M <= 4 decoders under one search state (csrc/beam_search.cpp:
+    scnattn_ensemble_*): dims_list / weights_list / tags_list hold one entry per member, as beam_search_run takes them;
+    enc (N, P, E) is shared.  member_weights: M positive numbers (None: equal), normalised here; mode: "logprob" / 0 (the
+    weighted mean of the members' log-probabilities) or "prob" / 1 (the log of the weighted mean of their probabilities).
+    alpha_member: the member whose attention maps are kept (-1 or None: none).  Returns (results, steps) exactly as
+    beam_search_run does; `guard` has the same meaning."""
+    M = len(dims_list)
+    if not 1 <= M <= _lib.MAX_ENSEMBLE:
+        raise ValueError("an ensemble has 1 to %d members (got %d)" % (_lib.MAX_ENSEMBLE, M))
+    if len(weights_list) != M or len(tags_list) != M:
+        raise ValueError("ensemble_search_run: dims, weights and tags must have one entry per member")
+    if not 1 <= beam_size <= _lib.MAX_BEAM:
+        raise ValueError("beam_size must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, beam_size))
+    mode = ENSEMBLE_MODES.get(mode, mode)
+    if mode not in (0, 1):
+        raise ValueError("ensemble_search_run: mode must be one of %s (got %r)" % (sorted(ENSEMBLE_MODES), mode))
+    mw = normalise_member_weights(member_weights, M)
+    alpha_member = -1 if alpha_member is None else int(alpha_member)
+    if not -1 <= alpha_member < M:
+        raise ValueError("ensemble_search_run: alpha_member %d is not a member" % alpha_member)
+    d = (Dims * M)(*[Dims(*x) for x in dims_list])
+    if any(x.V < beam_size for x in d):
+        raise ValueError("vocab_size %d is smaller than beam_size %d" % (d[0].V, beam_size))
+    if any((x.B, x.P, x.E, x.V) != (d[0].B, d[0].P, d[0].E, d[0].V) for x in d):
+        raise ValueError("the members of an ensemble must agree in batch, pixels, encoder_dim and vocab_size")
+    require_cuda(enc, *tags_list, *[t for ws_ in weights_list for t in ws_])
+    dev = enc.device
+    enc = f32c(enc)
+    tags_list = [f32c(t) for t in tags_list]
+    weights_list = [tuple(None if x is None else f32c(x.detach()) for x in ws_) for ws_ in weights_list]
+    w = (Params * M)(*[_params_struct(ws_) for ws_ in weights_list])
+    tg = (C.c_void_p * M)(*[t.data_ptr() for t in tags_list])
+    cw = (C.c_float * M)(*mw)
+    K, N = beam_size, d[0].B
+    nbytes = C.c_size_t()
+    call("scnattn_ensemble_workspace", M, d, K, max_steps, alpha_member, C.byref(nbytes))
+    off = (C.c_long * _lib.BEAM_NOFF)()
+    call("scnattn_ensemble_layout", M, d, K, max_steps, alpha_member, off)
+    nwords = nbytes.value // 4
+    ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_ensemble_init zero-fills what needs it
+    wsi = ws.view(torch.int32)
+    if guard:
+        wsi[nwords:].fill_(0x7FC5A5A5)
+    st = stream_of(enc)
+    call("scnattn_ensemble_init", st, M, d, K, max_steps, alpha_member, w, ptr(enc), tg, int(start), ptr(ws))
+    t = 0
+    while t < max_steps:
+        n = min(chunk, max_steps - t)
+        call("scnattn_ensemble_steps", st, M, d, K, max_steps, alpha_member, w, ptr(enc), cw, mode, int(end), t, n, ptr(ws))
+        t += n
+        if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
+            break
+    return _beam_results(ws, off, N, K, d[0].P, t, nwords, guard), t
 
 
 # ----------------------------------------------------------------------------------------------

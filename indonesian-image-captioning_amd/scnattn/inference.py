@@ -40,8 +40,9 @@ class Captioner:
         from models.decoders.pure_scn import PureSCN
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("Captioner: dtype must be float32 or bfloat16")
-        self.needs_tags = not isinstance(decoder, PureAttention)          # inference.py:73-74 (scn_based_model)
-        self.has_alphas = not isinstance(decoder, PureSCN)                # att_based_model
+        # a DecoderEnsemble states both itself (any member with tags / the member whose maps it returns)
+        self.needs_tags = getattr(decoder, "needs_tags", not isinstance(decoder, PureAttention))   # inference.py:73-74 (scn_based_model)
+        self.has_alphas = getattr(decoder, "has_alphas", not isinstance(decoder, PureSCN))         # att_based_model
         if self.needs_tags and tagger is None:
             raise ValueError("Captioner: a %s decoder needs a tagger" % type(decoder).__name__)
         for tok in _SPECIAL:

@@ -522,7 +522,7 @@ def evaluate_captions(batches, encoder, encoder_tagger, decoder, word_map, beam_
     with torch.no_grad():
         for imgs, allcaps in batches:
             encoder_out = encoder(imgs)
-            if isinstance(decoder, PureAttention):
+            if isinstance(decoder, PureAttention) or not getattr(decoder, "needs_tags", True):     # or an ensemble of them
                 results = decoder.sample_batch(beam_size, word_map, encoder_out)
             else:
                 results = decoder.sample_batch(beam_size, word_map, encoder_out, encoder_tagger(imgs))
