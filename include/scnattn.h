@@ -26,6 +26,8 @@ extern "C" {
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
+                               + search options: n-gram blocking, minimum length, banned tokens (scnattn_search_options, scnattn_beam_*_opt,
+                               scnattn_ensemble_*_opt; new symbols only, the version stays);
                                + ensemble beam search (scnattn_ensemble_*, scnattn_beam_row_topk_ens; new symbols only, the version stays);
                                + sampled rollouts and the reward-weighted loss for self-critical training (scnattn_rollout_*,
                                scnattn_caption_loss_weighted_fwd/_bwd; new symbols only, the version stays);
@@ -218,6 +220,69 @@ int scnattn_ensemble_steps(void* stream, int M, const scnattn_dims* dims, int K,
 int scnattn_beam_row_topk_ens(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
                               const float* w, int mode, const float* scores, const int32_t* nsrc, float* outv, int32_t* outi,
                               int force_passes);
+/* ---- search OPTIONS: n-gram blocking, a minimum length, banned tokens (both searches above) ----------------
+ * The reference's search has none of these; the semantics are this library's.  Let w_0 .. w_{t-1} be the words the open beam
+ * in slot j has emitted before 0-based step t (<start> is not among them).  At step t candidate (j, v) is EXCLUDED when
+ *   1. v is one of the n_banned <= 64 tokens of `banned` (<end> may not be among them), or
+ *   2. v == <end> and t < min_length                                (0 <= min_length <= max_steps - 1), or
+ *   3. g = no_repeat_ngram in [1, 8], t >= g, and there is an i in [0, t - g] with w_i .. w_{i+g-2} == w_{t-g+1} .. w_{t-1}
+ *      and w_{i+g-1} == v: picking v would repeat an n-gram of g words (g = 1: v occurs in the history).  <end> is never
+ *      in a history, so this rule never excludes it.  g = 0: the rule is off.
+ * An excluded candidate is not a candidate -- NOTHING IS RENORMALISED: the log-sum-exp runs over all V logits, scores stay
+ * sums of the model's log-probabilities, and a step that excludes nothing picks what the plain kernel picks, with its fp32
+ * values.  Order, tie rule, dead slots, nsrc / kk, completion records and the open-beam fallback are those of the search
+ * above.  Every live row must still offer K candidates: a call is REFUSED (-1) unless
+ *       V - n_banned - 1 - (no_repeat_ngram >= 1 ? max_steps : 0) >= K
+ * (sufficient: at most n_banned + 1 + t words can be excluded), as are options out of range, a banned token outside the
+ * vocabulary and a banned <end> (checked where the call knows <end>: _steps_opt).
+ * The per-beam history lives in the workspace as int32 [2][N*K][max_steps]: the selection of step t reads buffer t & 1
+ * (t entries per row), the advance gathers the parent slot's entries into the other buffer and appends the step's word;
+ * dead slots get slot 0's copy.  After `steps` steps the current buffer is steps & 1.  The launches per step are those of
+ * the plain search: the selection and the advance run in their _opt form.
+ *   _workspace_opt / _layout_opt / _init_opt / _steps_opt   the four calls of each search with the options after max_steps
+ *       (the ensemble: after alpha_member); the same options in all four.  _layout_opt writes SCNATTN_BEAM_NOFF_OPT
+ *       offsets: the 13 of scnattn_beam_layout, then 13 history int[2][N*K][max_steps].
+ *   scnattn_beam_row_topk_opt / _row_topk_ens_opt   the selection alone for step t: hist int32 [N*K][max_steps] holds t
+ *       entries per row (may be NULL when no_repeat_ngram == 0); <end> = end_token is excluded while t < min_length.
+ *       outv / outi as _row_topk; rows of dead slots are neither read nor written.  _row_topk_opt is _row_topk_ens_opt
+ *       with one member of weight 1 in mode 0, which writes the bits of _row_topk when nothing is excluded.
+ *   scnattn_beam_advance_opt   _advance, and hist_dst[row][0..t-1] = hist_src[n*K + parent_t[row]][0..t-1],
+ *       hist_dst[row][t] = token_t[row] (0 <= t < max_steps, hist_src != hist_dst). */
+#define SCNATTN_MAX_BANNED 64
+#define SCNATTN_MAX_NGRAM 8
+#define SCNATTN_BEAM_NOFF_OPT 14
+typedef struct {
+    int32_t min_length;
+    int32_t no_repeat_ngram;
+    int32_t n_banned;
+    int32_t banned[SCNATTN_MAX_BANNED];
+} scnattn_search_options;
+int scnattn_beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, size_t* bytes);
+int scnattn_beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, long* offsets);
+int scnattn_beam_init_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                          const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws);
+int scnattn_beam_steps_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                           const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws);
+int scnattn_ensemble_workspace_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                   const scnattn_search_options* opt, size_t* bytes);
+int scnattn_ensemble_layout_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                const scnattn_search_options* opt, long* offsets);
+int scnattn_ensemble_init_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                              const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
+                              const float* const* tags, int start_token, float* ws);
+int scnattn_ensemble_steps_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                               const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
+                               const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws);
+int scnattn_beam_row_topk_opt(void* stream, int N, int K, int V, const float* logits, long ld, const float* scores,
+                              const int32_t* nsrc, const scnattn_search_options* opt, int end_token, int t,
+                              const int32_t* hist, int max_steps, float* outv, int32_t* outi, int force_passes);
+int scnattn_beam_row_topk_ens_opt(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
+                                  const float* w, int mode, const float* scores, const int32_t* nsrc,
+                                  const scnattn_search_options* opt, int end_token, int t, const int32_t* hist,
+                                  int max_steps, float* outv, int32_t* outi, int force_passes);
+int scnattn_beam_advance_opt(void* stream, int N, int K, int D, int M, int V, int t, int max_steps, const float* hs,
+                             const float* cs, const int32_t* parent_t, const int32_t* token_t, const float* table,
+                             const int32_t* hist_src, int32_t* hist_dst, float* hd, float* cd, float* emb);
 /* ---- sampled rollouts for self-critical training (csrc/rollout.hip, the driver beside the search's) ---------------------
  * The set-up and the decode step of the search above over the same N*K rows, but the K slots of an image are INDEPENDENT
  * captions: nothing is compacted, the state carries over slot for slot, and after fc one token per open row is picked:

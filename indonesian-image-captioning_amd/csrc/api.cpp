@@ -48,6 +48,22 @@ int ensemble_init(hipStream_t st, int M, const scnattn_dims* d, int K, int max_s
 int ensemble_steps(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
                    const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
                    int n_steps, float* ws);
+int beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, size_t* bytes);
+int beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, long* off);
+int beam_init_opt(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o,
+                  const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws);
+int beam_steps_opt(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o,
+                   const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws);
+int ensemble_workspace_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                           const scnattn_search_options* o, size_t* bytes);
+int ensemble_layout_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                        const scnattn_search_options* o, long* off);
+int ensemble_init_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                      const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* const* tags,
+                      int start_token, float* ws);
+int ensemble_steps_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                       const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* member_w,
+                       int mode, int end_token, int t0, int n_steps, float* ws);
 int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
 int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off);
 int rollout_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
@@ -173,6 +189,87 @@ int scnattn_beam_advance(void* stream, int N, int K, int D, int M, int V, const 
                          const int32_t* parent_t, const int32_t* token_t, const float* table, float* hd, float* cd,
                          float* emb) {
     return beam_advance(ST(stream), N, K, D, M, V, hs, cs, parent_t, token_t, table, hd, cd, emb);
+}
+
+int scnattn_beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, size_t* bytes) {
+    return beam_workspace_opt(d, K, max_steps, opt, bytes);
+}
+int scnattn_beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, long* offsets) {
+    return beam_layout_opt(d, K, max_steps, opt, offsets);
+}
+int scnattn_beam_init_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                          const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws) {
+    return beam_init_opt(ST(stream), d, K, max_steps, opt, w, enc, tags, start_token, ws);
+}
+int scnattn_beam_steps_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                           const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws) {
+    return beam_steps_opt(ST(stream), d, K, max_steps, opt, w, enc, end_token, t0, n_steps, ws);
+}
+int scnattn_ensemble_workspace_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                   const scnattn_search_options* opt, size_t* bytes) {
+    return ensemble_workspace_opt(M, dims, K, max_steps, alpha_member, opt, bytes);
+}
+int scnattn_ensemble_layout_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                const scnattn_search_options* opt, long* offsets) {
+    return ensemble_layout_opt(M, dims, K, max_steps, alpha_member, opt, offsets);
+}
+int scnattn_ensemble_init_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                              const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
+                              const float* const* tags, int start_token, float* ws) {
+    return ensemble_init_opt(ST(stream), M, dims, K, max_steps, alpha_member, opt, w, enc, tags, start_token, ws);
+}
+int scnattn_ensemble_steps_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                               const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
+                               const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws) {
+    return ensemble_steps_opt(ST(stream), M, dims, K, max_steps, alpha_member, opt, w, enc, member_w, mode, end_token, t0,
+                              n_steps, ws);
+}
+// what step t of a search with `opt` excludes, for the selection kernel alone; the launcher checks the ranges
+static int excl_of(const scnattn_search_options* opt, int end_token, int t, const int32_t* hist, int max_steps, BeamExcl& x) {
+    SCN_ARG(opt, "search options are NULL");
+    SCN_ARG(opt->n_banned >= 0 && opt->n_banned <= SCN_MAX_BANNED, "at most 64 banned tokens");
+    SCN_ARG(end_token >= 0, "end token outside the vocabulary");
+    SCN_ARG(opt->min_length >= 0 && opt->min_length <= max_steps - 1, "min_length must be in [0, max_steps - 1]");
+    x = BeamExcl{};
+    x.t = t;
+    x.T = max_steps;
+    x.g = opt->no_repeat_ngram;
+    x.end_excl = t < opt->min_length ? end_token : -1;
+    x.n_banned = opt->n_banned;
+    x.hist = hist;
+    for (int i = 0; i < opt->n_banned; ++i) {
+        SCN_ARG(opt->banned[i] != end_token, "the end token may not be banned");
+        x.banned[i] = opt->banned[i];
+    }
+    return 0;
+}
+int scnattn_beam_row_topk_opt(void* stream, int N, int K, int V, const float* logits, long ld, const float* scores,
+                              const int32_t* nsrc, const scnattn_search_options* opt, int end_token, int t,
+                              const int32_t* hist, int max_steps, float* outv, int32_t* outi, int force_passes) {
+    BeamExcl x;
+    SCN_TRY(excl_of(opt, end_token, t, hist, max_steps, x));
+    SCN_ARG(end_token < V, "end token outside the vocabulary");
+    const EnsRows e{{logits}, {ld}, {1.f}};
+    return beam_row_topk_ens_opt(ST(stream), N, K, V, 1, e, 0, scores, nsrc, x, outv, outi, force_passes);
+}
+int scnattn_beam_row_topk_ens_opt(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
+                                  const float* w, int mode, const float* scores, const int32_t* nsrc,
+                                  const scnattn_search_options* opt, int end_token, int t, const int32_t* hist,
+                                  int max_steps, float* outv, int32_t* outi, int force_passes) {
+    if (M < 1 || M > SCN_MAX_ENSEMBLE) { set_error("scnattn_beam_row_topk_ens_opt: need 1 <= members <= 4"); return -1; }
+    if (!logits || !ld || !w) { set_error("scnattn_beam_row_topk_ens_opt: null member arrays"); return -1; }
+    BeamExcl x;
+    SCN_TRY(excl_of(opt, end_token, t, hist, max_steps, x));
+    SCN_ARG(end_token < V, "end token outside the vocabulary");
+    EnsRows e{};
+    for (int m = 0; m < M; ++m) { e.p[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; }
+    return beam_row_topk_ens_opt(ST(stream), N, K, V, M, e, mode, scores, nsrc, x, outv, outi, force_passes);
+}
+int scnattn_beam_advance_opt(void* stream, int N, int K, int D, int M, int V, int t, int max_steps, const float* hs,
+                             const float* cs, const int32_t* parent_t, const int32_t* token_t, const float* table,
+                             const int32_t* hist_src, int32_t* hist_dst, float* hd, float* cd, float* emb) {
+    return beam_advance_opt(ST(stream), N, K, D, M, V, t, max_steps, hs, cs, parent_t, token_t, table, hist_src, hist_dst, hd,
+                            cd, emb);
 }
 
 int scnattn_rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {

@@ -9,8 +9,12 @@
 //   beam_row_topk_ens  the same selection for an ensemble: M logits rows per live row, top K of score + c_v, where c_v is
 //                      the weighted mean of the members' log-probabilities (mode 0) or the log of the weighted mean of
 //                      their probabilities (mode 1)
+//   beam_row_topk_ens_opt  that selection with EXCLUSIONS (search options): banned words, <end> before
+//                      min_length and words that would repeat an n-gram of the row's history are not candidates (a bitmap
+//                      in LDS); one member of weight 1 serves the single decoder
 //   beam_merge         per image: the top kk of the nsrc x K row candidates, <end> picks recorded, the rest compacted
 //   beam_advance       h / c gathered from the parent slot, next input embedding gathered from the table
+//   beam_advance_opt   ... and the per-beam word history int32 [N*K][max_steps], gathered from the parent slot and extended
 // ORDER (the tie rule): candidates are ranked by (value descending, flat index j*V + v ascending), values compared as the
 // fp32 numbers the kernel computes.  Dead slots (j >= nsrc) are never read as candidates and never written by the first
 // three kernels; beam_merge / beam_advance fill them with a copy of slot 0 (or zeros), so every row stays finite.
@@ -416,6 +420,139 @@ __global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int V, in
     }
 }
 
+// ---- the selection with EXCLUSIONS (search options) ------------------------------------------------------
+// LDS words behind the 16 of the reductions: the bitmap of excluded words, then the row's history, both padded to 4
+__host__ __device__ inline int excl_bitmap_words(int V) { return (((V + 31) >> 5) + 3) & ~3; }
+__host__ __device__ inline int excl_hist_words(int T) { return (T + 3) & ~3; }
+
+__device__ __forceinline__ void excl_set(unsigned* bits, int v, int V) {
+    if (v >= 0 && v < V) atomicOr(&bits[v >> 5], 1u << (v & 31));
+}
+__device__ __forceinline__ bool excl_test(const unsigned* bits, int v) { return (bits[v >> 5] >> (v & 31)) & 1u; }
+
+// beam_row_topk_ens_kernel with a bitmap of the row's excluded words between the statistics and the K rounds: zeroed, then
+// set from the banned list, <end> before min_length, and -- thread i comparing the g-1 words at i with the last g-1 of the
+// history in LDS -- the word that followed every earlier occurrence of the open n-gram.  The rounds skip set bits; nothing
+// else differs, so with an empty bitmap the outputs are that kernel's bits (and with M = 1, mode 0, w = 1 beam_row_topk's).
+// The staged and the unstaged path read the same bitmap.
+template <bool STAGED>
+__global__ __launch_bounds__(256) void beam_row_topk_ens_opt_kernel(int K, int V, int M, int mode, EnsRows e,
+                                                                    unsigned vecmask, BeamExcl x,
+                                                                    const float* __restrict__ scores,
+                                                                    const int* __restrict__ nsrc, float* __restrict__ outv,
+                                                                    int* __restrict__ outi) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* redv = sm;                               // [4]
+    int* redi = reinterpret_cast<int*>(sm + 8);     // [4]
+    unsigned* bits = reinterpret_cast<unsigned*>(sm + 16);                      // [excl_bitmap_words(V)]
+    int* hs = reinterpret_cast<int*>(sm + 16 + excl_bitmap_words(V));           // [excl_hist_words(T)]
+    float* buf = sm + 16 + excl_bitmap_words(V) + excl_hist_words(x.T);         // [V] when STAGED
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    const int n = (int)(row / K), j = (int)(row - (long)n * K);
+    if (j >= nsrc[n]) return;
+    const int groups = (V + 3) >> 2;
+    const float* g[SCN_MAX_ENSEMBLE];
+    float lse[SCN_MAX_ENSEMBLE];
+#pragma unroll
+    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) {
+        g[m] = nullptr;
+        lse[m] = 0.f;
+        if (m < M) {                                // uniform over the workgroup
+            g[m] = e.p[m] + row * e.ld[m];
+            const bool vec = (vecmask >> m) & 1u;
+            float mx = -INFINITY;
+            for (int q = tid; q < groups; q += 256) {
+                float xv[4];
+                ens_load4(g[m], q * 4, V, vec, xv);
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (q * 4 + c < V) {
+                        if (STAGED) buf[q * 4 + c] = xv[c];
+                        mx = fmaxf(mx, xv[c]);
+                    }
+            }
+            mx = block_sum_max(mx, redv, true);     // its barriers also publish buf
+            const float* src = STAGED ? buf : g[m];
+            float s = 0.f;
+            for (int v = tid; v < V; v += 256) s += expf(src[v] - mx);
+            s = block_sum_max(s, redv, false);      // ... and every thread is done with buf before it is written again
+            lse[m] = mx + logf(s);
+        }
+    }
+    // the exclusions of this row
+    const bool ngram = x.g >= 1 && x.t >= x.g;
+    for (int w = tid; w < ((V + 31) >> 5); w += 256) bits[w] = 0u;
+    if (ngram)
+        for (int i = tid; i < x.t; i += 256) hs[i] = x.hist[row * x.T + i];
+    __syncthreads();
+    for (int i = tid; i < x.n_banned; i += 256) excl_set(bits, x.banned[i], V);
+    if (tid == 0) excl_set(bits, x.end_excl, V);
+    if (ngram) {
+        const int tail = x.t - x.g + 1;             // the open n-gram: hs[tail .. t-1], g-1 words
+        for (int i = tid; i <= x.t - x.g; i += 256) {
+            bool same = true;
+            for (int q = 0; q < x.g - 1; ++q) same = same && hs[i + q] == hs[tail + q];
+            if (same) excl_set(bits, hs[i + x.g - 1], V);
+        }
+    }
+    if (STAGED) {
+        for (int q = tid; q < groups; q += 256) {
+            float xv[SCN_MAX_ENSEMBLE][4];
+#pragma unroll
+            for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
+                if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, xv[m]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (q * 4 + c < V) {
+                    float l[SCN_MAX_ENSEMBLE];
+#pragma unroll
+                    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? xv[m][c] - lse[m] : 0.f;
+                    buf[q * 4 + c] = ens_combine(M, mode, l, e);
+                }
+        }
+    }
+    __syncthreads();                                // the bitmap (and buf) are complete
+    const float sc = scores[row];
+    float pv = INFINITY;
+    int pi = -1;
+    for (int r = 0; r < K; ++r) {
+        float bv = -INFINITY;
+        int bi = INT_MAX;
+        if (STAGED) {
+            for (int v = tid; v < V; v += 256) {
+                const float val = sc + buf[v];
+                if (!excl_test(bits, v) && before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
+            }
+        } else {
+            for (int q = tid; q < groups; q += 256) {
+                float xv[SCN_MAX_ENSEMBLE][4];
+#pragma unroll
+                for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
+                    if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, xv[m]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int v = q * 4 + c;
+                    if (v < V) {
+                        float l[SCN_MAX_ENSEMBLE];
+#pragma unroll
+                        for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? xv[m][c] - lse[m] : 0.f;
+                        const float val = sc + ens_combine(M, mode, l, e);
+                        if (!excl_test(bits, v) && before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
+                    }
+                }
+            }
+        }
+        block_best(bv, bi, redv, redi);
+        if (tid == 0) {
+            outv[row * K + r] = bv;
+            outi[row * K + r] = bi;
+        }
+        pv = bv;
+        pi = bi;
+    }
+}
+
 __global__ __launch_bounds__(64) void beam_merge_kernel(int K, int V, int end_tok, int t, const float* __restrict__ candv,
                                                         const int* __restrict__ candi, BeamState s) {
     __shared__ float sv[8];
@@ -489,6 +626,29 @@ __global__ __launch_bounds__(256) void beam_advance_kernel(int K, int D, int M, 
         cd[row * D + d] = cs[src * D + d];
     }
     for (int m = threadIdx.x; m < M; m += 256) emb[row * M + m] = table[tok * M + m];
+}
+
+// beam_advance_kernel, and the row's history for step t+1: the parent slot's t words, then this step's word.  A dead slot
+// carries slot 0's parent / token records, so it gets slot 0's history.
+__global__ __launch_bounds__(256) void beam_advance_opt_kernel(int K, int D, int M, int V, int t, int T,
+                                                               const float* __restrict__ hs, const float* __restrict__ cs,
+                                                               const int* __restrict__ parent_t,
+                                                               const int* __restrict__ token_t,
+                                                               const float* __restrict__ table,
+                                                               const int* __restrict__ hist_s, int* __restrict__ hist_d,
+                                                               float* __restrict__ hd, float* __restrict__ cd,
+                                                               float* __restrict__ emb) {
+    const long row = blockIdx.x;
+    const long n = row / K;
+    const long src = n * K + min(max(parent_t[row], 0), K - 1);     // an index outside the image's slots cannot leave them
+    const long tok = min(max(token_t[row], 0), V - 1);
+    for (int d = threadIdx.x; d < D; d += 256) {
+        hd[row * D + d] = hs[src * D + d];
+        cd[row * D + d] = cs[src * D + d];
+    }
+    for (int m = threadIdx.x; m < M; m += 256) emb[row * M + m] = table[tok * M + m];
+    for (int i = threadIdx.x; i < t; i += 256) hist_d[row * T + i] = hist_s[src * T + i];
+    if (threadIdx.x == 0) hist_d[row * T + t] = (int)tok;
 }
 
 // out[n*K + j][:] = in[n][:]
@@ -601,6 +761,57 @@ int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows&
     else
         hipLaunchKernelGGL(beam_row_topk_ens_kernel<false>, grid, block, 16 * sizeof(float), st, K, V, M, mode, e, vecmask,
                            scores, nsrc, outv, outi);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_row_topk_ens_opt(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
+                          const int* nsrc, const BeamExcl& x, float* outv, int* outi, int force_passes) {
+    if (N <= 0) return 0;
+    SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "beam_row_topk_opt: need 1 <= members <= 4");
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk_opt: need 1 <= beam size <= 8 and vocab_size >= beam size");
+    SCN_ARG(mode == 0 || mode == 1, "beam_row_topk_opt: mode must be 0 (logprob) or 1 (prob)");
+    SCN_ARG(scores && nsrc && outv && outi, "beam_row_topk_opt: null argument");
+    SCN_ARG(x.T >= 1 && x.T <= 4096 && x.t >= 0 && x.t <= x.T, "beam_row_topk_opt: need 0 <= t <= max_steps <= 4096");
+    SCN_ARG(x.g >= 0 && x.g <= SCN_MAX_NGRAM, "beam_row_topk_opt: no_repeat_ngram must be in [0, 8]");
+    SCN_ARG(x.n_banned >= 0 && x.n_banned <= SCN_MAX_BANNED, "beam_row_topk_opt: at most 64 banned tokens");
+    for (int i = 0; i < x.n_banned; ++i)
+        SCN_ARG(x.banned[i] >= 0 && x.banned[i] < V, "beam_row_topk_opt: a banned token lies outside the vocabulary");
+    SCN_ARG(x.end_excl >= -1 && x.end_excl < V, "beam_row_topk_opt: the end token lies outside the vocabulary");
+    SCN_ARG(x.g == 0 || x.hist, "beam_row_topk_opt: no_repeat_ngram needs the history");
+    SCN_ARG((long)V - x.n_banned - 1 - (x.g >= 1 ? x.T : 0) >= K,
+            "beam_row_topk_opt: the options may leave a row fewer than beam_size candidates "
+            "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) >= beam_size)");
+    unsigned vecmask = 0;
+    for (int m = 0; m < M; ++m) {
+        SCN_ARG(e.p[m] && e.ld[m] >= V, "beam_row_topk_opt: a member's logits are null or its leading dimension < vocab_size");
+        SCN_ARG(e.w[m] > 0.f && e.w[m] < INFINITY, "beam_row_topk_opt: member weights must be positive and finite");
+        if (aligned16(e.p[m]) && e.ld[m] % 4 == 0) vecmask |= 1u << m;
+    }
+    const size_t fixed = (size_t)(16 + excl_bitmap_words(V) + excl_hist_words(x.T)) * sizeof(float);
+    const size_t staged = fixed + (size_t)V * sizeof(float);
+    SCN_ARG(fixed <= 64 * 1024, "beam_row_topk_opt: vocab_size too large for the exclusion bitmap in LDS");
+    dim3 grid(N * K), block(256);
+    if (staged <= 64 * 1024 && !force_passes)
+        hipLaunchKernelGGL(beam_row_topk_ens_opt_kernel<true>, grid, block, staged, st, K, V, M, mode, e, vecmask, x, scores,
+                           nsrc, outv, outi);
+    else
+        hipLaunchKernelGGL(beam_row_topk_ens_opt_kernel<false>, grid, block, fixed, st, K, V, M, mode, e, vecmask, x, scores,
+                           nsrc, outv, outi);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_advance_opt(hipStream_t st, int N, int K, int D, int M, int V, int t, int T, const float* hs, const float* cs,
+                     const int* parent_t, const int* token_t, const float* table, const int* hist_s, int* hist_d, float* hd,
+                     float* cd, float* emb) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && D > 0 && M > 0 && V > 0, "beam_advance_opt: bad dims");
+    SCN_ARG(T >= 1 && t >= 0 && t < T, "beam_advance_opt: need 0 <= t < max_steps");
+    SCN_ARG(hs && cs && parent_t && token_t && table && hist_s && hist_d && hist_s != hist_d && hd && cd && emb,
+            "beam_advance_opt: null operand (or the history gathered in place)");
+    hipLaunchKernelGGL(beam_advance_opt_kernel, dim3(N * K), dim3(256), 0, st, K, D, M, V, t, T, hs, cs, parent_t, token_t,
+                       table, hist_s, hist_d, hd, cd, emb);
     SCN_LAUNCH_CHECK();
     return 0;
 }

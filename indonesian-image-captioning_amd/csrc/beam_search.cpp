@@ -13,6 +13,10 @@
 //
 // The ensemble driver (scnattn_ensemble_*, between the two) steps up to four decoders under one search state: the decode
 // part per member, one beam_row_topk_ens over their logits, one beam_merge, beam_advance per member.
+//
+// Search options (scnattn_beam_*_opt, scnattn_ensemble_*_opt): the same steps with beam_row_topk_ens_opt in
+// place of the selection and beam_advance_opt in place of the (first member's) advance; the workspace gains the per-beam
+// word history.  No launch is added per step.
 #include <hip/hip_runtime.h>
 #include "../../include/scnattn.h"
 #include "common.h"
@@ -38,6 +42,7 @@ struct BeamWs : StepWs {
     BeamState s;
     float* candv;
     int* candi;
+    int* hist;          // [2][R][T] with search options, else null
 };
 
 struct RolloutWs : StepWs {
@@ -84,7 +89,7 @@ void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b, const
     b.gws = shared_gws ? shared_gws->gws : c.take(BEAM_GEMM_WS_FLOATS);
 }
 
-size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b) {
+size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b, bool hist = false) {
     Carver c(base);
     const int N = d.B, P = d.P;
     const long R = (long)N * K;
@@ -105,9 +110,40 @@ size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b) {
     carve_step_state(c, d, R, b);
     b.candv = c.take(sz(R, K));
     b.candi = ints(c.take(sz(R, K)));
+    b.hist = hist ? ints(c.take(sz(2, R, T))) : nullptr;
     b.state_floats = c.off;
     carve_step_setup(c, d, R, b);
     return c.off * sizeof(float);
+}
+
+// The refusals of a search with options (include/scnattn.h); end_token < 0: not known to this call.
+int check_options(const scnattn_search_options* o, int V, int K, int T, int end_token) {
+    SCN_ARG(o, "search options are NULL");
+    SCN_ARG(o->min_length >= 0 && o->min_length <= T - 1, "min_length must be in [0, max_steps - 1]");
+    SCN_ARG(o->no_repeat_ngram >= 0 && o->no_repeat_ngram <= SCN_MAX_NGRAM, "no_repeat_ngram must be in [0, 8]");
+    SCN_ARG(o->n_banned >= 0 && o->n_banned <= SCN_MAX_BANNED, "at most 64 banned tokens");
+    for (int i = 0; i < o->n_banned; ++i) {
+        SCN_ARG(o->banned[i] >= 0 && o->banned[i] < V, "a banned token lies outside the vocabulary");
+        SCN_ARG(o->banned[i] != end_token, "the end token may not be banned");
+    }
+    SCN_ARG(end_token < V, "end token outside the vocabulary");
+    SCN_ARG((long)V - o->n_banned - 1 - (o->no_repeat_ngram >= 1 ? T : 0) >= K,
+            "the options may leave a row fewer than beam_size candidates "
+            "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) >= beam_size)");
+    return 0;
+}
+
+// what step t excludes; hist: the [2][R][T] buffers, step t reads buffer t & 1 and its advance writes the other
+BeamExcl step_excl(const scnattn_search_options& o, int t, int T, long R, int end_token, const int* hist) {
+    BeamExcl x{};
+    x.t = t;
+    x.T = T;
+    x.g = o.no_repeat_ngram;
+    x.end_excl = t < o.min_length ? end_token : -1;
+    x.n_banned = o.n_banned;
+    x.hist = hist + (long)(t & 1) * R * T;
+    for (int i = 0; i < o.n_banned; ++i) x.banned[i] = o.banned[i];
+    return x;
 }
 
 int check_beam(const scnattn_dims* d, int K, int T) {
@@ -204,19 +240,28 @@ int beam_layout(const scnattn_dims* d, int K, int max_steps, long* off) {
     return 0;
 }
 
-int beam_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_params* w, const float* enc,
-              const float* tags, int start_token, float* ws) {
+namespace {
+
+int beam_init_impl(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_params* w, const float* enc,
+                   const float* tags, int start_token, float* ws, bool hist) {
     SCN_TRY(check_beam(dp, K, max_steps));
     const scnattn_dims& d = *dp;
     SCN_ARG(w && enc && tags && ws, "beam_init: null argument");
     SCN_ARG(start_token >= 0 && start_token < d.V, "beam_init: start token outside the vocabulary");
     SCN_ARG(aligned16(ws), "beam_init: the workspace must be 16-byte aligned");
     BeamWs b;
-    carve_beam(d, K, max_steps, ws, b);
+    carve_beam(d, K, max_steps, ws, b, hist);
     SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
     SCN_TRY(beam_state_init(st, d.B, K, b.s));
     SCN_TRY(decode_setup(st, d, K, w, enc, tags, start_token, b));
     return 0;
+}
+
+}  // namespace
+
+int beam_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_params* w, const float* enc,
+              const float* tags, int start_token, float* ws) {
+    return beam_init_impl(st, dp, K, max_steps, w, enc, tags, start_token, ws, false);
 }
 
 // Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.
@@ -242,6 +287,67 @@ int beam_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, con
     return 0;
 }
 
+// ---- the search with OPTIONS: the same steps, the selection and the advance in their _opt form -----------
+// The workspace gains the history int32 [2][R][max_steps] (zero-filled by init); the launches per step are those above.
+int beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, size_t* bytes) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_TRY(check_options(o, d->V, K, max_steps, -1));
+    SCN_ARG(bytes, "beam_workspace_opt: bytes is NULL");
+    BeamWs b;
+    *bytes = carve_beam(*d, K, max_steps, nullptr, b, true);
+    return 0;
+}
+
+// off[SCNATTN_BEAM_NOFF_OPT]: the 13 offsets of beam_layout, then the history's
+int beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, long* off) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_TRY(check_options(o, d->V, K, max_steps, -1));
+    SCN_ARG(off, "beam_layout_opt: offsets is NULL");
+    BeamWs b;
+    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
+    carve_beam(*d, K, max_steps, base, b, true);
+    const void* p[SCNATTN_BEAM_NOFF_OPT] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
+                                            b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
+                                            b.s.parent, b.alpha, b.hist};
+    for (int i = 0; i < SCNATTN_BEAM_NOFF_OPT; ++i)
+        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
+    return 0;
+}
+
+int beam_init_opt(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_search_options* o,
+                  const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    SCN_TRY(check_options(o, dp->V, K, max_steps, -1));
+    return beam_init_impl(st, dp, K, max_steps, w, enc, tags, start_token, ws, true);
+}
+
+int beam_steps_opt(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_search_options* o,
+                   const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    const scnattn_dims& d = *dp;
+    SCN_ARG(end_token >= 0, "beam_steps_opt: end token outside the vocabulary");
+    SCN_TRY(check_options(o, d.V, K, max_steps, end_token));
+    SCN_ARG(w && enc && ws, "beam_steps_opt: null argument");
+    SCN_ARG(t0 >= 0 && n_steps >= 0, "beam_steps_opt: negative step");
+    const int N = d.B, P = d.P, D = d.D, M = d.M, V = d.V, R = N * K, T = max_steps;
+    BeamWs b;
+    carve_beam(d, K, max_steps, ws, b, true);
+    const EnsRows rows{{b.logits}, {V}, {1.f}};     // one member, weight 1: the bits of beam_row_topk
+    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
+    for (int t = t0; t < t1; ++t) {
+        int* token_t = b.s.token + (long)t * R;
+        int* parent_t = b.s.parent + (long)t * R;
+        SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, d.has_att ? b.alpha + (long)t * R * P : nullptr, b.hA, b.cA, b.hB,
+                            b.cB));
+        const BeamExcl x = step_excl(*o, t, T, R, end_token, b.hist);
+        SCN_TRY(beam_row_topk_ens_opt(st, N, K, V, 1, rows, 0, b.s.scores, b.s.nsrc, x, b.candv, b.candi, 0));
+        SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
+        SCN_TRY(beam_advance_opt(st, N, K, D, M, V, t, T, b.hB, b.cB, parent_t, token_t, w->embedding_weight, x.hist,
+                                 b.hist + (long)((t + 1) & 1) * R * T, b.hA, b.cA, b.emb));
+    }
+    return 0;
+}
+
 // ---- ensemble search: M decoders under ONE search state ---------------------------------------------------
 // The members read the same enc [N,P,E] and share the vocabulary; each keeps its own StepWs (state, set-up results) and
 // they share the split-K scratch, since everything runs on one stream in order.  A step is, per member, decode_step with
@@ -255,6 +361,7 @@ struct EnsembleWs {
     float* candv;
     int* candi;
     float* alpha;       // [T][R][P] of alpha_member, or null
+    int* hist;          // [2][R][T] with search options, else null
     size_t state_floats;
     StepWs m[SCN_MAX_ENSEMBLE];
 };
@@ -263,7 +370,8 @@ bool ens_alpha(int M, const scnattn_dims* d, int alpha_member) {
     return alpha_member >= 0 && alpha_member < M && d[alpha_member].has_att;
 }
 
-size_t carve_ensemble(int M, const scnattn_dims* d, int K, int T, int alpha_member, float* base, EnsembleWs& b) {
+size_t carve_ensemble(int M, const scnattn_dims* d, int K, int T, int alpha_member, float* base, EnsembleWs& b,
+                      bool hist = false) {
     Carver c(base);
     const int N = d[0].B, P = d[0].P;
     const long R = (long)N * K;
@@ -287,6 +395,7 @@ size_t carve_ensemble(int M, const scnattn_dims* d, int K, int T, int alpha_memb
     }
     b.candv = c.take(sz(R, K));
     b.candi = ints(c.take(sz(R, K)));
+    b.hist = hist ? ints(c.take(sz(2, R, T))) : nullptr;
     b.state_floats = c.off;
     for (int m = 0; m < M; ++m) {
         b.m[m].state_floats = b.state_floats;
@@ -332,19 +441,29 @@ int ensemble_layout(int M, const scnattn_dims* d, int K, int max_steps, int alph
     return 0;
 }
 
-int ensemble_init(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                  const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
+namespace {
+
+int ensemble_init_impl(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                       const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws,
+                       bool hist) {
     SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
     SCN_ARG(w && enc && tags && ws, "ensemble_init: null argument");
     for (int m = 0; m < M; ++m) SCN_ARG(tags[m], "ensemble_init: a member's tags are NULL");
     SCN_ARG(start_token >= 0 && start_token < d[0].V, "ensemble_init: start token outside the vocabulary");
     SCN_ARG(aligned16(ws), "ensemble_init: the workspace must be 16-byte aligned");
     EnsembleWs b;
-    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b);
+    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b, hist);
     SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
     SCN_TRY(beam_state_init(st, d[0].B, K, b.s));
     for (int m = 0; m < M; ++m) SCN_TRY(decode_setup(st, d[m], K, w + m, enc, tags[m], start_token, b.m[m]));
     return 0;
+}
+
+}  // namespace
+
+int ensemble_init(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                  const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
+    return ensemble_init_impl(st, M, d, K, max_steps, alpha_member, w, enc, tags, start_token, ws, false);
 }
 
 // Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.
@@ -378,6 +497,85 @@ int ensemble_steps(hipStream_t st, int M, const scnattn_dims* d, int K, int max_
             const StepWs& s = b.m[m];
             SCN_TRY(beam_advance(st, N, K, d[m].D, d[m].M, V, s.hB, s.cB, parent_t, token_t, w[m].embedding_weight, s.hA, s.cA,
                                  s.emb));
+        }
+    }
+    return 0;
+}
+
+// ---- the ensemble search with OPTIONS ---------------------------------------------------------------------
+int ensemble_workspace_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                           const scnattn_search_options* o, size_t* bytes) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    SCN_ARG(bytes, "ensemble_workspace_opt: bytes is NULL");
+    EnsembleWs b;
+    *bytes = carve_ensemble(M, d, K, max_steps, alpha_member, nullptr, b, true);
+    return 0;
+}
+
+int ensemble_layout_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                        const scnattn_search_options* o, long* off) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    SCN_ARG(off, "ensemble_layout_opt: offsets is NULL");
+    EnsembleWs b;
+    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
+    carve_ensemble(M, d, K, max_steps, alpha_member, base, b, true);
+    const void* p[SCNATTN_BEAM_NOFF_OPT] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
+                                            b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
+                                            b.s.parent, b.alpha, b.hist};
+    for (int i = 0; i < SCNATTN_BEAM_NOFF_OPT; ++i)
+        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
+    return 0;
+}
+
+int ensemble_init_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                      const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* const* tags,
+                      int start_token, float* ws) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    return ensemble_init_impl(st, M, d, K, max_steps, alpha_member, w, enc, tags, start_token, ws, true);
+}
+
+// One history serves all members: the first member's advance writes it, the others run the plain advance.
+int ensemble_steps_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
+                       const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* member_w,
+                       int mode, int end_token, int t0, int n_steps, float* ws) {
+    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
+    SCN_ARG(end_token >= 0, "ensemble_steps_opt: end token outside the vocabulary");
+    SCN_TRY(check_options(o, d[0].V, K, max_steps, end_token));
+    SCN_ARG(w && enc && member_w && ws, "ensemble_steps_opt: null argument");
+    SCN_ARG(t0 >= 0 && n_steps >= 0, "ensemble_steps_opt: negative step");
+    const int N = d[0].B, P = d[0].P, V = d[0].V, R = N * K, T = max_steps;
+    EnsembleWs b;
+    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b, true);
+    EnsRows rows{};
+    for (int m = 0; m < M; ++m) {
+        rows.p[m] = b.m[m].logits;
+        rows.ld[m] = V;
+        rows.w[m] = member_w[m];
+    }
+    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
+    for (int t = t0; t < t1; ++t) {
+        int* token_t = b.s.token + (long)t * R;
+        int* parent_t = b.s.parent + (long)t * R;
+        for (int m = 0; m < M; ++m) {
+            const StepWs& s = b.m[m];
+            SCN_TRY(decode_step(st, d[m], K, w + m, enc, s, b.s.nsrc, s.alpha ? s.alpha + (long)t * R * P : nullptr, s.hA, s.cA,
+                                s.hB, s.cB));
+        }
+        const BeamExcl x = step_excl(*o, t, T, R, end_token, b.hist);
+        SCN_TRY(beam_row_topk_ens_opt(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, x, b.candv, b.candi, 0));
+        SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
+        for (int m = 0; m < M; ++m) {
+            const StepWs& s = b.m[m];
+            if (m == 0)
+                SCN_TRY(beam_advance_opt(st, N, K, d[m].D, d[m].M, V, t, T, s.hB, s.cB, parent_t, token_t,
+                                         w[m].embedding_weight, x.hist, b.hist + (long)((t + 1) & 1) * R * T, s.hA, s.cA,
+                                         s.emb));
+            else
+                SCN_TRY(beam_advance(st, N, K, d[m].D, d[m].M, V, s.hB, s.cB, parent_t, token_t, w[m].embedding_weight, s.hA,
+                                     s.cA, s.emb));
         }
     }
     return 0;

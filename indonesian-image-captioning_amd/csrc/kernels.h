@@ -175,6 +175,24 @@ int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const fl
                const BeamState& s);
 int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,
                  const int* token_t, const float* table, float* hd, float* cd, float* emb);
+// ---- the search OPTIONS: candidates a step may not pick -------------------------------------------------
+#define SCN_MAX_BANNED 64
+#define SCN_MAX_NGRAM 8
+// What the selection of step t excludes, per live row: the banned words, `end_excl` (<end> while t < min_length; -1: none)
+// and, for g >= 1, every word that would close an n-gram of g words the row's history hist[row*T .. +t-1] already holds.
+struct BeamExcl {
+    int t, T, g, end_excl, n_banned;
+    const int* hist;        // [N*K][T] (may be null when g == 0)
+    int banned[SCN_MAX_BANNED];
+};
+// beam_row_topk_ens with the candidates of `x` left out of the K rounds (the log-sum-exp still runs over all V logits);
+// with nothing excluded it writes the bits of beam_row_topk_ens.  Refuses unless V - n_banned - 1 - (g >= 1 ? T : 0) >= K.
+int beam_row_topk_ens_opt(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
+                          const int* nsrc, const BeamExcl& x, float* outv, int* outi, int force_passes);
+// beam_advance, and the history of row n*K+s for step t+1: the parent slot's first t entries of hist_s, then token_t[row]
+int beam_advance_opt(hipStream_t st, int N, int K, int D, int M, int V, int t, int T, const float* hs, const float* cs,
+                     const int* parent_t, const int* token_t, const float* table, const int* hist_s, int* hist_d, float* hd,
+                     float* cd, float* emb);
 int beam_expand_rows(hipStream_t st, int N, int K, int W, const float* in, float* out);
 int beam_state_init(hipStream_t st, int N, int K, const BeamState& s);
 

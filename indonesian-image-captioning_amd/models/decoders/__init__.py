@@ -1,1 +1,2 @@
 from .ensemble import DecoderEnsemble  # noqa: F401
+from .search_options import SearchOptions  # noqa: F401

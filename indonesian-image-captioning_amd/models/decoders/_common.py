@@ -192,7 +192,16 @@ def _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags):
     return dims, weights, enc, tag_out
 
 
-def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_attention, use_tags, return_all=False):
+def device_options(options):
+    """(what the device search gets, length_penalty): None for the device when there is nothing to exclude -- ``None`` or
+    an all-default object takes the plain search, launch for launch"""
+    if options is None:
+        return None, 0.0
+    return (options if options.on_device else None), options.length_penalty
+
+
+def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_attention, use_tags, return_all=False,
+                        options=None):
     """``beam_search`` for N images at once, the search itself on the device (csrc/beam_search.cpp): encoder_out
     (N, h, w, E), tag_out (N, S).  Returns a list of N results, each what ``beam_search`` returns for that image --
     the leading <start>, the all-ones first alpha map and this build's fallback to the best open beam included; with
@@ -201,7 +210,9 @@ def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_
     K = beam_size slots per image; a step takes the top candidates of score + log_softmax ordered by (value
     descending, flat index beam * vocab_size + word ascending): among EQUAL values the lower flat index wins, where the
     reference leaves the choice to ``topk``.  Per step only token / parent / alpha records are kept; the sequences
-    that are returned are read off the parent chain here.  1 <= beam_size <= 8 <= vocab_size; fp32 only."""
+    that are returned are read off the parent chain here.  1 <= beam_size <= 8 <= vocab_size; fp32 only.
+    ``options``: a ``models.decoders.SearchOptions`` (n-gram blocking, minimum length, banned tokens inside the
+    selection kernel, a length penalty in ``trace_back``); None or an all-default object: the search above, untouched."""
     from scnattn import _lib
     k = beam_size
     if not 1 <= k <= _lib.MAX_BEAM:
@@ -209,18 +220,30 @@ def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_
     V = len(word_map)
     if V < k:
         raise ValueError("sample_batch: vocab_size %d is smaller than beam_size %d" % (V, k))
+    start, end = word_map[start_token], word_map[end_token]
+    dev_options, alpha = device_options(options)
+    if dev_options is not None:
+        dev_options.check(V, k, SF.BEAM_MAX_STEPS, end)       # before anything touches the GPU
     _lib.require_cuda(encoder_out, tag_out)
     N, hh, ww, E = encoder_out.shape
     dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
-    start, end = word_map[start_token], word_map[end_token]
-    res, steps = SF.beam_search_run(dims, k, weights, enc, tag_out, start, end)
-    return trace_back(res, steps, N, k, start, end, (hh, ww), use_attention, return_all)
+    res, steps = SF.beam_search_run(dims, k, weights, enc, tag_out, start, end, options=dev_options)
+    return trace_back(res, steps, N, k, start, end, (hh, ww), use_attention, return_all, length_penalty=alpha)
 
 
-def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=False):
+def pick_best(done_scores, lengths, length_penalty):
+    """index of the first maximum of score / L**alpha over the beams, in the order given (Python floats)"""
+    norm = [s / float(L) ** length_penalty for s, L in zip(done_scores, lengths)]
+    return norm.index(max(norm))
+
+
+def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=False, length_penalty=0.0):
     """The results of a device search (SF.beam_search_run / SF.ensemble_search_run) -> the list of N results that
     ``beam_search_batched`` documents: the parent chains read off the token / parent records, the all-ones first alpha map
-    (``use_attention``: the search kept maps), the fallback to the best open beam."""
+    (``use_attention``: the search kept maps), the fallback to the best open beam.
+    ``length_penalty`` alpha != 0: the returned caption is the first maximum, in completion order (the open beams: slot
+    order), of score / L**alpha with L = len(sequence) - 1, the decoded tokens with <end>; the (sequence, score) lists of
+    ``return_all`` keep raw scores.  alpha == 0: the device's best_idx decides, as without options."""
     hh, ww = map_hw
     token, parent = res["token"].tolist(), res["parent"].tolist()
     alpha = res["alpha"]
@@ -260,6 +283,8 @@ def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=F
                 done.append((words, rows, float(res["scores"][n * k + s])))
             scores = [x[2] for x in done]
             i = scores.index(max(scores))
+        if length_penalty != 0.0:
+            i = pick_best([x[2] for x in done], [len(x[0]) - 1 for x in done], length_penalty)
         seq, rows, _ = done[i]
         one = (seq, alphas_of(rows)) if use_attention else seq
         out.append((one, [(s, sc) for s, _, sc in done]) if return_all else one)

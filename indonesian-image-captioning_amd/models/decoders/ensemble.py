@@ -68,11 +68,12 @@ class DecoderEnsemble(nn.Module):
     def has_alphas(self):
         return self.alpha_member is not None
 
-    def sample_batch(self, beam_size, word_map, encoder_out, tags=None, return_all=False):
+    def sample_batch(self, beam_size, word_map, encoder_out, tags=None, return_all=False, options=None):
         """encoder_out (N, h, w, E), tags (N, S) (may be None when no member uses tags) -> list of N results in the form
         ``_common.beam_search_batched`` returns them: the sequence with the leading <start>, paired with the attention maps
         of ``alpha_member`` (the all-ones first map included) when there is one; the best open beam where nothing
-        completed; with ``return_all`` each result paired with the image's completed (sequence, score) list."""
+        completed; with ``return_all`` each result paired with the image's completed (sequence, score) list.
+        ``options``: a ``SearchOptions`` as a single decoder's ``sample_batch`` takes it (None / all-default: untouched)."""
         k = int(beam_size)
         if not 1 <= k <= SF._lib.MAX_BEAM:
             raise ValueError("sample_batch: beam_size must be in [1, %d] (got %d)" % (SF._lib.MAX_BEAM, k))
@@ -83,6 +84,10 @@ class DecoderEnsemble(nn.Module):
             raise ValueError("sample_batch: vocab_size %d is smaller than beam_size %d" % (V, k))
         if self.needs_tags and tags is None:
             raise ValueError("sample_batch: a member of the ensemble uses tags and none were given")
+        start, end = word_map[start_token], word_map[end_token]
+        dev_options, alpha = _common.device_options(options)
+        if dev_options is not None:
+            dev_options.check(V, k, SF.BEAM_MAX_STEPS, end)       # before anything touches the GPU
         SF._lib.require_cuda(encoder_out, tags)
         N, hh, ww, _ = encoder_out.shape
         dims_list, weights_list, tags_list = [], [], []
@@ -92,7 +97,6 @@ class DecoderEnsemble(nn.Module):
             dims_list.append(dims)
             weights_list.append(weights)
             tags_list.append(tg)
-        start, end = word_map[start_token], word_map[end_token]
         res, steps = SF.ensemble_search_run(dims_list, k, weights_list, enc, tags_list, self.member_weights, self.combine,
-                                            start, end, self.alpha_member)
-        return _common.trace_back(res, steps, N, k, start, end, (hh, ww), self.has_alphas, return_all)
+                                            start, end, self.alpha_member, options=dev_options)
+        return _common.trace_back(res, steps, N, k, start, end, (hh, ww), self.has_alphas, return_all, length_penalty=alpha)

@@ -115,11 +115,12 @@ class PureAttention(nn.Module):
     def sample(self, beam_size, word_map, encoder_out):
         return _common.beam_search(self, beam_size, word_map, encoder_out, None, use_attention=True, use_tags=False)
 
-    def sample_batch(self, beam_size, word_map, encoder_out):
+    def sample_batch(self, beam_size, word_map, encoder_out, options=None):
         """``sample`` for a batch: encoder_out (N, h, w, E) -> list of N (seq, alphas); the LSTM cell runs through its
-        SCN view with the single constant tag, the whole search on the device (_common.beam_search_batched)."""
+        SCN view with the single constant tag, the whole search on the device (_common.beam_search_batched); ``options``:
+        a SearchOptions or None."""
         return _common.beam_search_batched(self, beam_size, word_map, encoder_out, None, use_attention=True,
-                                           use_tags=False)
+                                           use_tags=False, options=options)
 
     def rollout_batch(self, word_map, encoder_out, tags=None, samples=1, seed=0, draw=0, temperature=1.0,
                       greedy_first=False):

@@ -64,11 +64,11 @@ class PureSCN(nn.Module):
     def sample(self, beam_size, word_map, encoder_out, tag_out):
         return _common.beam_search(self, beam_size, word_map, encoder_out, tag_out, use_attention=False, use_tags=True)
 
-    def sample_batch(self, beam_size, word_map, encoder_out, tag_out):
+    def sample_batch(self, beam_size, word_map, encoder_out, tag_out, options=None):
         """``sample`` for a batch: encoder_out (N, h, w, E), tag_out (N, S) -> list of N sequences, the whole search on
-        the device (_common.beam_search_batched)."""
+        the device (_common.beam_search_batched); ``options``: a SearchOptions or None."""
         return _common.beam_search_batched(self, beam_size, word_map, encoder_out, tag_out, use_attention=False,
-                                           use_tags=True)
+                                           use_tags=True, options=options)
 
     def rollout_batch(self, word_map, encoder_out, tags=None, samples=1, seed=0, draw=0, temperature=1.0,
                       greedy_first=False):

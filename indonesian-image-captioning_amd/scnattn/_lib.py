@@ -80,6 +80,14 @@ class ImageDesc(C.Structure):      # scnattn_image_desc
                 ("tab_v", C.c_int32), ("reserved", C.c_int32)]
 
 
+MAX_BANNED, MAX_NGRAM = 64, 8      # SCNATTN_MAX_BANNED, SCNATTN_MAX_NGRAM
+
+
+class SearchOpts(C.Structure):     # scnattn_search_options
+    _fields_ = [("min_length", C.c_int32), ("no_repeat_ngram", C.c_int32), ("n_banned", C.c_int32),
+                ("banned", C.c_int32 * MAX_BANNED)]
+
+
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
@@ -106,6 +114,22 @@ _SIGS = {
     "scnattn_ensemble_init": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, C.POINTER(vp), i32, vp], i32),
     "scnattn_ensemble_steps": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, C.POINTER(f32), i32, i32, i32,
                                 i32, vp], i32),
+    "scnattn_beam_workspace_opt": ([C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(sz)], i32),
+    "scnattn_beam_layout_opt": ([C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(i64)], i32),
+    "scnattn_beam_init_opt": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Params), vp, vp, i32, vp], i32),
+    "scnattn_beam_steps_opt": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Params), vp, i32, i32, i32,
+                                vp], i32),
+    "scnattn_ensemble_workspace_opt": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(sz)], i32),
+    "scnattn_ensemble_layout_opt": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(i64)], i32),
+    "scnattn_ensemble_init_opt": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Params), vp,
+                                   C.POINTER(vp), i32, vp], i32),
+    "scnattn_ensemble_steps_opt": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Params), vp,
+                                    C.POINTER(f32), i32, i32, i32, i32, vp], i32),
+    "scnattn_beam_row_topk_opt": ([vp, i32, i32, i32, vp, i64, vp, vp, C.POINTER(SearchOpts), i32, i32, vp, i32, vp, vp,
+                                   i32], i32),
+    "scnattn_beam_row_topk_ens_opt": ([vp, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(f32), i32, vp, vp,
+                                       C.POINTER(SearchOpts), i32, i32, vp, i32, vp, vp, i32], i32),
+    "scnattn_beam_advance_opt": ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
     "scnattn_rollout_workspace": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(sz)], i32),
     "scnattn_rollout_layout": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(i64)], i32),
     "scnattn_rollout_init": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, vp, i32, vp], i32),
@@ -233,6 +257,7 @@ _SIGS = {
 }
 
 BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
+BEAM_NOFF_OPT = 14  # SCNATTN_BEAM_NOFF_OPT
 ROLLOUT_NOFF = 8    # SCNATTN_ROLLOUT_NOFF
 MAX_BEAM = 8
 MAX_ENSEMBLE = 4    # SCNATTN_MAX_ENSEMBLE

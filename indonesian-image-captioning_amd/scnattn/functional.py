@@ -234,49 +234,71 @@ _BEAM_RESULTS = ("open_images", "nsrc", "kk", "ncomp", "best_idx", "best_score",
 _BEAM_FLOAT = ("best_score", "scores", "comp_score", "alpha")
 
 
+def search_options_struct(options, vocab_size, beam_size, max_steps, end_token):
+    """a models.decoders.SearchOptions -> scnattn_search_options, after its refusals for this search (ValueError)"""
+    options.check(vocab_size, beam_size, max_steps, end_token)
+    o = _lib.SearchOpts(min_length=options.min_length, no_repeat_ngram=options.no_repeat_ngram,
+                        n_banned=len(options.banned_tokens))
+    for i, tok in enumerate(options.banned_tokens):
+        o.banned[i] = tok
+    return o
+
+
 def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token, max_steps=BEAM_MAX_STEPS,
-                    chunk=BEAM_CHUNK, guard=0):
+                    chunk=BEAM_CHUNK, guard=0, options=None):
     """The whole search of N images on the device.  dims: 12-tuple in scnattn_dims order with B = N (T, L unused);
     enc (N, P, E) as the caller has it (no copy per beam), tags (N, S) un-expanded; weights in PARAM_FIELDS order.
     Returns (results, steps): host tensors by the names of scnattn_beam_layout -- token / parent (steps, N*K),
     alpha (steps, N*K, P) or None -- and the number of steps that ran.  guard > 0 (tests): that many sentinel words
-    behind the workspace, returned as results["guard"] (host int32)."""
+    behind the workspace, returned as results["guard"] (host int32).
+    options: a models.decoders.SearchOptions runs the scnattn_beam_*_opt calls (its length_penalty is the caller's
+    business: trace_back) and adds results["history"] (N*K, steps) int32, the words of the beam in every slot; None: the
+    plain search, and results["history"] is None."""
     require_cuda(enc, tags, *weights)
     if not 1 <= beam_size <= _lib.MAX_BEAM:
         raise ValueError("beam_size must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, beam_size))
     d = Dims(*dims)
     if d.V < beam_size:
         raise ValueError("vocab_size %d is smaller than beam_size %d" % (d.V, beam_size))
+    # with options: the same four calls in their _opt form, the options struct after max_steps
+    sfx, opt = "", ()
+    if options is not None:
+        sfx, opt = "_opt", (C.byref(search_options_struct(options, d.V, beam_size, max_steps, end_token)),)
     dev = enc.device
     enc, tags = f32c(enc), f32c(tags)
     weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
     w = _params_struct(weights)
     K, N = beam_size, d.B
     nbytes = C.c_size_t()
-    call("scnattn_beam_workspace", C.byref(d), K, max_steps, C.byref(nbytes))
-    off = (C.c_long * _lib.BEAM_NOFF)()
-    call("scnattn_beam_layout", C.byref(d), K, max_steps, off)
+    call("scnattn_beam_workspace" + sfx, C.byref(d), K, max_steps, *opt, C.byref(nbytes))
+    off = (C.c_long * (_lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF))()
+    call("scnattn_beam_layout" + sfx, C.byref(d), K, max_steps, *opt, off)
     nwords = nbytes.value // 4
     ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_beam_init zero-fills what needs it
     wsi = ws.view(torch.int32)
     if guard:
         wsi[nwords:].fill_(0x7FC5A5A5)
     st = stream_of(enc)
-    call("scnattn_beam_init", st, C.byref(d), K, max_steps, C.byref(w), ptr(enc), ptr(tags), start_token, ptr(ws))
+    call("scnattn_beam_init" + sfx, st, C.byref(d), K, max_steps, *opt, C.byref(w), ptr(enc), ptr(tags), start_token, ptr(ws))
     t = 0
     while t < max_steps:
         n = min(chunk, max_steps - t)
-        call("scnattn_beam_steps", st, C.byref(d), K, max_steps, C.byref(w), ptr(enc), end_token, t, n, ptr(ws))
+        call("scnattn_beam_steps" + sfx, st, C.byref(d), K, max_steps, *opt, C.byref(w), ptr(enc), end_token, t, n, ptr(ws))
         t += n
         if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
             break
-    return _beam_results(ws, off, N, K, d.P, t, nwords, guard), t
+    return _beam_results(ws, off, N, K, d.P, t, nwords, guard, max_steps), t
 
 
-def _beam_results(ws, off, N, K, P, t, nwords, guard):
-    """the host tensors of a finished search (t steps ran), by the names of scnattn_beam_layout"""
+def _beam_results(ws, off, N, K, P, t, nwords, guard, max_steps=BEAM_MAX_STEPS):
+    """the host tensors of a finished search (t steps ran), by the names of scnattn_beam_layout; "history" (N*K, t): the
+    current one of the two history buffers of a search with options (scnattn_beam_layout_opt), None without"""
     wsi = ws.view(torch.int32)
     R = N * K
+    hist = None
+    if len(off) > _lib.BEAM_NOFF:
+        cur = off[_lib.BEAM_NOFF] + (t & 1) * R * max_steps
+        hist = wsi[cur:cur + R * max_steps].view(R, max_steps)[:, :t].cpu()
     sizes = {"open_images": 1, "nsrc": N, "kk": N, "ncomp": N, "best_idx": N, "best_score": N, "scores": R,
              "comp_score": R, "comp_step": R, "comp_parent": R, "token": t * R, "parent": t * R, "alpha": t * R * P}
     out = {}
@@ -289,6 +311,7 @@ def _beam_results(ws, off, N, K, P, t, nwords, guard):
     out["token"], out["parent"] = out["token"].view(t, R), out["parent"].view(t, R)
     if out["alpha"] is not None:
         out["alpha"] = out["alpha"].view(t, R, P)
+    out["history"] = hist
     if guard:
         out["guard"] = wsi[nwords:].cpu()
     return out
@@ -319,13 +342,13 @@ def normalise_member_weights(weights, M):
 
 
 def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, member_weights, mode, start, end, alpha_member,
-                        max_steps=BEAM_MAX_STEPS, chunk=BEAM_CHUNK, guard=0):
+                        max_steps=BEAM_MAX_STEPS, chunk=BEAM_CHUNK, guard=0, options=None):
     """beam_search_run for an ensemble of M <= 4 decoders under one search state (csrc/beam_search.cpp:
     scnattn_ensemble_*): dims_list / weights_list / tags_list hold one entry per member, as beam_search_run takes them;
     enc (N, P, E) is shared.  member_weights: M positive numbers (None: equal), normalised here; mode: "logprob" / 0 (the
     weighted mean of the members' log-probabilities) or "prob" / 1 (the log of the weighted mean of their probabilities).
     alpha_member: the member whose attention maps are kept (-1 or None: none).  Returns (results, steps) exactly as
-    beam_search_run does; `guard` has the same meaning."""
+    beam_search_run does; `guard` and `options` have the same meaning."""
     M = len(dims_list)
     if not 1 <= M <= _lib.MAX_ENSEMBLE:
         raise ValueError("an ensemble has 1 to %d members (got %d)" % (_lib.MAX_ENSEMBLE, M))
@@ -354,25 +377,29 @@ def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, memb
     tg = (C.c_void_p * M)(*[t.data_ptr() for t in tags_list])
     cw = (C.c_float * M)(*mw)
     K, N = beam_size, d[0].B
+    sfx, opt = "", ()       # with options: the _opt form of the four calls, the options struct after alpha_member
+    if options is not None:
+        sfx, opt = "_opt", (C.byref(search_options_struct(options, d[0].V, beam_size, max_steps, int(end))),)
     nbytes = C.c_size_t()
-    call("scnattn_ensemble_workspace", M, d, K, max_steps, alpha_member, C.byref(nbytes))
-    off = (C.c_long * _lib.BEAM_NOFF)()
-    call("scnattn_ensemble_layout", M, d, K, max_steps, alpha_member, off)
+    call("scnattn_ensemble_workspace" + sfx, M, d, K, max_steps, alpha_member, *opt, C.byref(nbytes))
+    off = (C.c_long * (_lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF))()
+    call("scnattn_ensemble_layout" + sfx, M, d, K, max_steps, alpha_member, *opt, off)
     nwords = nbytes.value // 4
     ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_ensemble_init zero-fills what needs it
     wsi = ws.view(torch.int32)
     if guard:
         wsi[nwords:].fill_(0x7FC5A5A5)
     st = stream_of(enc)
-    call("scnattn_ensemble_init", st, M, d, K, max_steps, alpha_member, w, ptr(enc), tg, int(start), ptr(ws))
+    call("scnattn_ensemble_init" + sfx, st, M, d, K, max_steps, alpha_member, *opt, w, ptr(enc), tg, int(start), ptr(ws))
     t = 0
     while t < max_steps:
         n = min(chunk, max_steps - t)
-        call("scnattn_ensemble_steps", st, M, d, K, max_steps, alpha_member, w, ptr(enc), cw, mode, int(end), t, n, ptr(ws))
+        call("scnattn_ensemble_steps" + sfx, st, M, d, K, max_steps, alpha_member, *opt, w, ptr(enc), cw, mode, int(end), t, n,
+             ptr(ws))
         t += n
         if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
             break
-    return _beam_results(ws, off, N, K, d[0].P, t, nwords, guard), t
+    return _beam_results(ws, off, N, K, d[0].P, t, nwords, guard, max_steps), t
 
 
 # ----------------------------------------------------------------------------------------------

@@ -31,11 +31,12 @@ class Captioner:
     input size (default: the module's `input_size` attribute, else 256 x 256).  The batch is produced in the layout and
     type a `DeviceBatchLoader` hands the same encoder: channels-last when the encoder asks for it, fp32 values
     (`image_dtype`; the fused stem reads fp32 images in both modes).  `dtype` bf16 runs the trunks under bf16 autocast, as
-    `TrainStep` runs them; the decoder stays fp32."""
+    `TrainStep` runs them; the decoder stays fp32.  `search_options`: a `models.decoders.SearchOptions` handed to
+    `sample_batch` (n-gram blocking, minimum length, banned tokens, length penalty); None: the reference's search."""
 
     def __init__(self, encoder, decoder, word_map, tagger=None, beam_size=5, dtype=torch.float32,
                  mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD, size=None, image_dtype=torch.float32,
-                 overlay_size=(336, 336), overlay_sigma=8, overlay_weight=0.8):
+                 overlay_size=(336, 336), overlay_sigma=8, overlay_weight=0.8, search_options=None):
         from models.decoders.pure_attention import PureAttention
         from models.decoders.pure_scn import PureSCN
         if dtype not in (torch.float32, torch.bfloat16):
@@ -58,6 +59,7 @@ class Captioner:
         self.channels_last = bool(getattr(encoder, "channels_last", False))
         self.overlay_size = (int(overlay_size[0]), int(overlay_size[1]))       # utils/vizualize.py:26, 40-48
         self.overlay_sigma, self.overlay_weight = overlay_sigma, overlay_weight
+        self.search_options = search_options        # a models.decoders.SearchOptions for sample_batch, or None
         p = next(decoder.parameters())
         require_cuda(p)
         self.device = p.device
@@ -83,10 +85,11 @@ class Captioner:
             encoder_out = encoder_out.float()
             if tags is not None:
                 tags = tags.float()
+            kw = {} if self.search_options is None else {"options": self.search_options}
             if self.needs_tags:
-                results = self.decoder.sample_batch(self.beam_size, self.word_map, encoder_out, tags)
+                results = self.decoder.sample_batch(self.beam_size, self.word_map, encoder_out, tags, **kw)
             else:
-                results = self.decoder.sample_batch(self.beam_size, self.word_map, encoder_out)
+                results = self.decoder.sample_batch(self.beam_size, self.word_map, encoder_out, **kw)
         tags_host = tags.cpu().numpy() if tags is not None and tag_count > 0 else None
         records = []
         for i, res in enumerate(results):

@@ -504,15 +504,17 @@ def _validate_fused(batches, encoder, encoder_tagger, decoder, word_map, alpha_c
     return corpus_bleu(references, hypotheses), losses.avg, top5accs.avg
 
 
-def evaluate_captions(batches, encoder, encoder_tagger, decoder, word_map, beam_size=5):
+def evaluate_captions(batches, encoder, encoder_tagger, decoder, word_map, beam_size=5, search_options=None):
     """The reference's eval_caption.py:95-165, batched: per batch (imgs, allcaps) on the device both trunks in eval mode, the
     batched beam search (sample_batch), then BLEU-1..4, ROUGE-L and CIDEr-D of the whole split from ONE
     scnattn.textmetrics.CaptionScorer.score with <start>, <end> and <pad> dropped on both sides inside the kernels -- what the
     reference strips in Python before it hands words to NLGEval.  The references never leave the device; each batch uploads
     its hypotheses once.  Returns the scorer's dict (NLGEval's key names, plus 'bleu4_nltk'; no METEOR); writing the JSON files
-    of the reference is the caller's business."""
+    of the reference is the caller's business.  `search_options`: a models.decoders.SearchOptions handed to sample_batch
+    (None: the reference's search)."""
     import torch.nn.functional as F
     from scnattn import textmetrics as TM
+    kw = {} if search_options is None else {"options": search_options}
     decoder.eval()
     encoder.eval()
     if hasattr(encoder_tagger, "eval"):
@@ -523,9 +525,9 @@ def evaluate_captions(batches, encoder, encoder_tagger, decoder, word_map, beam_
         for imgs, allcaps in batches:
             encoder_out = encoder(imgs)
             if isinstance(decoder, PureAttention) or not getattr(decoder, "needs_tags", True):     # or an ensemble of them
-                results = decoder.sample_batch(beam_size, word_map, encoder_out)
+                results = decoder.sample_batch(beam_size, word_map, encoder_out, **kw)
             else:
-                results = decoder.sample_batch(beam_size, word_map, encoder_out, encoder_tagger(imgs))
+                results = decoder.sample_batch(beam_size, word_map, encoder_out, encoder_tagger(imgs), **kw)
             seqs = [r[0] if isinstance(r, tuple) else r for r in results]
             tok, n = TM.pack_captions(seqs, allcaps.device)
             hyps.append(tok)

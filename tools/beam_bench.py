@@ -6,7 +6,12 @@ Both sides get the same random weights (one seed) at the train step's widths (P=
 V=10000), with the <end> bias raised so that searches end at mixed lengths.  Each side runs in a FRESH process
 (`--side batched|loop`, started from here): a warm-up pass over the whole batch, then `--repeats` timed passes, each
 bracketed by device events around the whole batch (the searches synchronise inside, so the events see host time too);
-the median is reported.  Prints one JSON line per side and one for the ratio.  Not part of bench.py."""
+the median is reported.  Prints one JSON line per side and one for the ratio.  Not part of bench.py.
+
+    python tools/beam_bench.py --side batched --end-bias -30 [--no-repeat-ngram 3 --ban-unk] [--min-length N]
+
+One side alone; with --end-bias -30 nothing completes and every search runs all 51 steps, which makes the plain search
+and the search with options comparable per step."""
 import argparse
 import json
 import os
@@ -42,11 +47,16 @@ def side(args):
     enc = torch.rand(args.images, 14, 14, E).to(dev)
     tags = torch.rand(args.images, S).to(dev)
     wm = word_map(V)
+    kw = {}
+    if args.no_repeat_ngram or args.min_length or args.ban_unk:
+        from models.decoders import SearchOptions
+        kw["options"] = SearchOptions(min_length=args.min_length, no_repeat_ngram=args.no_repeat_ngram,
+                                      banned_tokens=(wm["<unk>"],) if args.ban_unk else ())
 
     def run():
         with torch.no_grad():
             if args.side == "batched":
-                return [r[0] for r in m.sample_batch(args.beam, wm, enc, tags)]
+                return [r[0] for r in m.sample_batch(args.beam, wm, enc, tags, **kw)]
             return [m.sample(args.beam, wm, enc[i:i + 1], tags[i:i + 1])[0] for i in range(args.images)]
 
     seqs = run()                                    # warm-up: code objects, allocator, workspaces
@@ -63,6 +73,7 @@ def side(args):
     lens = [len(s) for s in seqs]
     print(json.dumps({"side": args.side, "images": args.images, "beam": args.beam, "median_ms": round(med, 3),
                       "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "captions_per_s": round(args.images * 1e3 / med, 2),
+                      "options": repr(kw.get("options")), "ms_per_step_of_longest": round(med / (max(lens) - 1), 4),
                       "steps_longest": max(lens) - 1, "lengths": sorted(lens), "digest": hash(tuple(map(tuple, seqs))) & 0xffffffff}))
 
 
@@ -75,6 +86,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--sharpen", type=float, default=10.0)
     ap.add_argument("--end-bias", type=float, default=2.0)
+    ap.add_argument("--no-repeat-ngram", type=int, default=0)      # search options (batched side only)
+    ap.add_argument("--min-length", type=int, default=0)
+    ap.add_argument("--ban-unk", action="store_true")
     ap.add_argument("--side", choices=["batched", "loop"])
     ap.add_argument("--out")
     args = ap.parse_args()
