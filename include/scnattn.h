@@ -128,9 +128,11 @@ typedef struct scnattn_pool {
 } scnattn_pool;
 
 /* Bytes of the two workspaces of the sequence drivers (pool may be NULL).  `saved` carries forward state to
- * the backward pass; `scratch` is free after each call.  Both must be zero-filled by the caller before
- * scnattn_seq_fwd (saved) / each call (scratch) unless every caption decodes at every step (bt_host[T-1] == B),
- * in which case every element is written before it is read. */
+ * the backward pass; `scratch` is free after each call and may be re-used, as may `saved` once its backward has run.
+ * Zero-fill `saved` before scnattn_seq_fwd and `scratch` before scnattn_seq_bwd, unless every caption decodes at
+ * every step (bt_host[T-1] == B), in which case every element is written before it is read.  The scratch of
+ * scnattn_seq_fwd needs no fill in either case: the forward writes every word of it before reading it.
+ * (tests/test_gpu_seq_driver.py holds the drivers to this with NaN-filled workspaces.) */
 int scnattn_seq_workspace(const scnattn_dims* d, const scnattn_pool* pool, size_t* saved_bytes, size_t* scratch_bytes);
 
 /* Teacher-forced decoder forward over all T steps: replaces the loop of
@@ -151,7 +153,10 @@ int scnattn_seq_fwd(void* stream, const scnattn_dims* d, const scnattn_params* w
 
 /* Gradient of scnattn_seq_fwd (what autograd derives for the reference's loop).  `g` receives
  * d loss / d parameter (fields may be NULL to skip; embedding_weight must be zero-filled: rows
- * are accumulated).  denc [B,P,E] ([B,Q,E] = d x when pool != NULL) and dtags [B,S] may be NULL. */
+ * are accumulated -- it is the ONE accumulated output: every other one is overwritten, so a second call on the
+ * same `saved` gives the same bits once embedding_weight is zeroed again).  denc [B,P,E] ([B,Q,E] = d x when
+ * pool != NULL) and dtags [B,S] may be NULL; an omitted output changes no other.  dalphas may be NULL (= zeros).
+ * Finite values in the dpreds / dalphas cells at t >= decode length change no result. */
 int scnattn_seq_bwd(void* stream, const scnattn_dims* d, const scnattn_params* w, const float* enc,
                     const float* tags, const int64_t* caps, const int32_t* dl_dev, const int32_t* bt_host,
                     const float* drop_mask, const float* saved, float* scratch, const float* dpreds,

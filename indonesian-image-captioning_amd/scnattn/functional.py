@@ -168,7 +168,8 @@ class _DecoderSeq(torch.autograd.Function):
         # skipped.  `_POISON` (tests) fills with NaN instead to prove exactly that.
         full = min(bt_host) == d.B
         saved = _workspace(sv.value // 4, dev, full)
-        scratch = torch.empty(sc.value // 4, device=dev, dtype=torch.float32)
+        # the forward's scratch needs no fill, ragged or not (include/scnattn.h): every word is written before it is read
+        scratch = _workspace(sc.value // 4, dev, True)
         preds = torch.empty((d.B, d.T, d.V), device=dev, dtype=torch.float32)
         alphas = _workspace(d.B * d.T * d.P, dev, full).view(d.B, d.T, d.P) if d.has_att else None
         bt = (C.c_int32 * d.T)(*bt_host)

@@ -1,6 +1,6 @@
 """What the per-kernel GPU test modules share (tests/test_gpu_decoder_kernels.py, tests/test_gpu_attn_variant_kernels.py,
 tests/test_gpu_gemm_kernels.py,
-tests/test_gpu_bn_kernels.py, tests/test_gpu_stem_kernels.py, and for the bf16 windows tests/test_gpu_eval16_kernels.py,
+tests/test_gpu_bn_kernels.py, tests/test_gpu_stem_kernels.py, tests/test_gpu_seq_driver.py, and for the bf16 windows tests/test_gpu_eval16_kernels.py,
 tests/test_gpu_conv16_kernels.py): guarded buffers, the C-ABI call, the
 per-element sum judge and the parity-report fixture.  How a case is judged: DESIGN.md 3.
 A plain module (tests/ is on sys.path, like decoder_kernel_refs); a test module imports `_write_report` by name to get
@@ -41,7 +41,10 @@ def _write_report(request):
     for (kern, name), (ratio, kind, yard, n) in sorted(_STATS.items()):
         how = kind[1:] if kind.startswith("=") else "(n+8)*2^-24*sum|terms|" if kind == "sum" else \
             "(n+16)*2^-24*(sum|terms|*|scale|+|mean*scale|+|beta|+|res|)" \
-            if kind == "eval" else "min(4 x CPU-fp32 worst element error [worst seen %.3e], %s x row max)" % (yard, kind)
+            if kind == "eval" else \
+            "4 x rho x row max, rho = CPU-fp32 worst row-relative error [%.3e]; rows below 1e-6 x tensor max: 4 x CPU-fp32 " \
+            "worst element error" % yard if kind == "row" else \
+            "min(4 x CPU-fp32 worst element error [worst seen %.3e], %s x row max)" % (yard, kind)
         lines.append(fmt.replace("%-9s %-6s", "%-9.3f %-6d") % (kern, name, ratio, n, how))
     _report(lines, getattr(request.module, "REPORT_TITLE",
                            "decode-step primitives vs fp64: worst |got - ref| / bound over all cases"))
@@ -87,6 +90,31 @@ class GBuf:
         assert bad.numel() == 0, "%s: %d guard words overwritten (first at window offset %d)" % (
             what, bad.numel(), int(guard.nonzero().reshape(-1)[bad[0]]) - self.base)
         return host[self.pos]
+
+
+class GBig:
+    """GBuf for a dense window of `n` floats that is too large to build and compare on the host (a workspace with its GEMM
+    partials): filled and checked on the device.  16 sentinel floats in front, `tail` behind, the window filled with `fill`
+    (a float, NaN included) or left in the sentinel; read() proves the margins intact and returns the window (host)."""
+
+    def __init__(self, dev, n, fill=None, tail=64):
+        self.base, self.n = 16, int(n)
+        self.flat = torch.empty(self.base + self.n + int(tail), dtype=torch.float32, device=dev)
+        self.flat.view(torch.int32).fill_(SENT)
+        assert self.flat.data_ptr() % 64 == 0
+        self.ptr = C.c_void_p(self.flat.data_ptr() + 4 * self.base)
+        self.window = self.flat[self.base:self.base + self.n]
+        if fill is not None:
+            self.window.fill_(fill)
+
+    def check(self, what):
+        words = self.flat.view(torch.int32)
+        bad = int((words[:self.base] != SENT).sum()) + int((words[self.base + self.n:] != SENT).sum())
+        assert bad == 0, "%s: %d guard words overwritten" % (what, bad)
+
+    def read(self, what):
+        self.check(what)
+        return self.window.cpu()
 
 
 class GBuf16:
