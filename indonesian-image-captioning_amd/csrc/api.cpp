@@ -35,35 +35,17 @@ int seq_bwd(hipStream_t st, const scnattn_dims* d, const scnattn_params* w, cons
             const int64_t* caps, const int32_t* dl_dev, const int32_t* bt, const float* drop_mask,
             const float* saved, float* scratch, const float* dpreds, const float* dalphas, const scnattn_params* g,
             float* denc, float* dtags, const scnattn_pool* pool);
-int beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes);
-int beam_layout(const scnattn_dims* d, int K, int max_steps, long* off);
-int beam_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
-              const float* tags, int start_token, float* ws);
-int beam_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
-               int end_token, int t0, int n_steps, float* ws);
-int ensemble_workspace(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, size_t* bytes);
-int ensemble_layout(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, long* off);
-int ensemble_init(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                  const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws);
-int ensemble_steps(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                   const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
-                   int n_steps, float* ws);
-int beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, size_t* bytes);
-int beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, long* off);
-int beam_init_opt(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o,
-                  const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws);
-int beam_steps_opt(hipStream_t st, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o,
-                   const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws);
-int ensemble_workspace_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                           const scnattn_search_options* o, size_t* bytes);
-int ensemble_layout_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                        const scnattn_search_options* o, long* off);
-int ensemble_init_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                      const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* const* tags,
-                      int start_token, float* ws);
-int ensemble_steps_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                       const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* member_w,
-                       int mode, int end_token, int t0, int n_steps, float* ws);
+// the one search driver (beam_search.cpp); o: the search options, null for a search without
+int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
+                     size_t* bytes);
+int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
+                  long* off);
+int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
+                int max_steps, const scnattn_params* w, const float* enc, const float* const* tags, int start_token,
+                float* ws);
+int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
+                 int max_steps, const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token,
+                 int t0, int n_steps, float* ws);
 int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
 int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off);
 int rollout_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
@@ -123,19 +105,25 @@ int scnattn_profile_collect(double* out6) {
     return profile_collect(out6);
 }
 
+// The sixteen search entry points over the one driver.  The single search is the one-member ensemble of weight 1 in mode 0
+// that records its attention maps when it has any; the _opt forms are the calls whose options may not be NULL.
+static int alpha_of(const scnattn_dims* d) { return d && d->has_att ? 0 : -1; }
+static const float k_one[1] = {1.f};
+static int no_options() { SCN_ARG(false, "search options are NULL"); return -1; }
+
 int scnattn_beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes) {
-    return beam_workspace(d, K, max_steps, bytes);
+    return search_workspace(1, d, alpha_of(d), nullptr, K, max_steps, bytes);
 }
 int scnattn_beam_layout(const scnattn_dims* d, int K, int max_steps, long* offsets) {
-    return beam_layout(d, K, max_steps, offsets);
+    return search_layout(1, d, alpha_of(d), nullptr, K, max_steps, offsets);
 }
 int scnattn_beam_init(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                       const float* tags, int start_token, float* ws) {
-    return beam_init(ST(stream), d, K, max_steps, w, enc, tags, start_token, ws);
+    return search_init(ST(stream), 1, d, alpha_of(d), nullptr, K, max_steps, w, enc, tags ? &tags : nullptr, start_token, ws);
 }
 int scnattn_beam_steps(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                        int end_token, int t0, int n_steps, float* ws) {
-    return beam_steps(ST(stream), d, K, max_steps, w, enc, end_token, t0, n_steps, ws);
+    return search_steps(ST(stream), 1, d, alpha_of(d), nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0, n_steps, ws);
 }
 int scnattn_beam_attn_scores(void* stream, int N, int K, int P, int A, const float* att1, const float* att2, int nslab,
                              long slab_stride, long att2_ld, const float* dec_bias, const float* w, const float* b0,
@@ -152,29 +140,36 @@ int scnattn_beam_row_topk(void* stream, int N, int K, int V, const float* logits
                           const int32_t* nsrc, float* outv, int32_t* outi, int force_passes) {
     return beam_row_topk(ST(stream), N, K, V, logits, ld, scores, nsrc, outv, outi, force_passes);
 }
+// the member arrays of the two ensemble selection calls -> EnsRows
+static int rows_of(int M, const float* const* logits, const long* ld, const float* w, EnsRows& e) {
+    SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "scnattn_beam_row_topk_ens: need 1 <= members <= 4");
+    SCN_ARG(logits && ld && w, "scnattn_beam_row_topk_ens: null member arrays");
+    e = EnsRows{};
+    for (int m = 0; m < M; ++m) { e.p[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; }
+    return 0;
+}
 int scnattn_beam_row_topk_ens(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
                               const float* w, int mode, const float* scores, const int32_t* nsrc, float* outv, int32_t* outi,
                               int force_passes) {
-    if (M < 1 || M > SCN_MAX_ENSEMBLE) { set_error("scnattn_beam_row_topk_ens: need 1 <= members <= 4"); return -1; }
-    if (!logits || !ld || !w) { set_error("scnattn_beam_row_topk_ens: null member arrays"); return -1; }
-    EnsRows e{};
-    for (int m = 0; m < M; ++m) { e.p[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; }
-    return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, outv, outi, force_passes);
+    EnsRows e;
+    SCN_TRY(rows_of(M, logits, ld, w, e));
+    return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, nullptr, outv, outi, force_passes);
 }
 int scnattn_ensemble_workspace(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, size_t* bytes) {
-    return ensemble_workspace(M, dims, K, max_steps, alpha_member, bytes);
+    return search_workspace(M, dims, alpha_member, nullptr, K, max_steps, bytes);
 }
 int scnattn_ensemble_layout(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, long* offsets) {
-    return ensemble_layout(M, dims, K, max_steps, alpha_member, offsets);
+    return search_layout(M, dims, alpha_member, nullptr, K, max_steps, offsets);
 }
 int scnattn_ensemble_init(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                           const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
-    return ensemble_init(ST(stream), M, dims, K, max_steps, alpha_member, w, enc, tags, start_token, ws);
+    return search_init(ST(stream), M, dims, alpha_member, nullptr, K, max_steps, w, enc, tags, start_token, ws);
 }
 int scnattn_ensemble_steps(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                            const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
                            int n_steps, float* ws) {
-    return ensemble_steps(ST(stream), M, dims, K, max_steps, alpha_member, w, enc, member_w, mode, end_token, t0, n_steps, ws);
+    return search_steps(ST(stream), M, dims, alpha_member, nullptr, K, max_steps, w, enc, member_w, mode, end_token, t0,
+                        n_steps, ws);
 }
 int scnattn_beam_merge(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
                        void* const* state) {
@@ -192,37 +187,40 @@ int scnattn_beam_advance(void* stream, int N, int K, int D, int M, int V, const 
 }
 
 int scnattn_beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, size_t* bytes) {
-    return beam_workspace_opt(d, K, max_steps, opt, bytes);
+    return opt ? search_workspace(1, d, alpha_of(d), opt, K, max_steps, bytes) : no_options();
 }
 int scnattn_beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, long* offsets) {
-    return beam_layout_opt(d, K, max_steps, opt, offsets);
+    return opt ? search_layout(1, d, alpha_of(d), opt, K, max_steps, offsets) : no_options();
 }
 int scnattn_beam_init_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                           const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws) {
-    return beam_init_opt(ST(stream), d, K, max_steps, opt, w, enc, tags, start_token, ws);
+    return opt ? search_init(ST(stream), 1, d, alpha_of(d), opt, K, max_steps, w, enc, tags ? &tags : nullptr, start_token, ws)
+               : no_options();
 }
 int scnattn_beam_steps_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                            const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws) {
-    return beam_steps_opt(ST(stream), d, K, max_steps, opt, w, enc, end_token, t0, n_steps, ws);
+    return opt ? search_steps(ST(stream), 1, d, alpha_of(d), opt, K, max_steps, w, enc, k_one, 0, end_token, t0, n_steps, ws)
+               : no_options();
 }
 int scnattn_ensemble_workspace_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                    const scnattn_search_options* opt, size_t* bytes) {
-    return ensemble_workspace_opt(M, dims, K, max_steps, alpha_member, opt, bytes);
+    return opt ? search_workspace(M, dims, alpha_member, opt, K, max_steps, bytes) : no_options();
 }
 int scnattn_ensemble_layout_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                 const scnattn_search_options* opt, long* offsets) {
-    return ensemble_layout_opt(M, dims, K, max_steps, alpha_member, opt, offsets);
+    return opt ? search_layout(M, dims, alpha_member, opt, K, max_steps, offsets) : no_options();
 }
 int scnattn_ensemble_init_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                               const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
                               const float* const* tags, int start_token, float* ws) {
-    return ensemble_init_opt(ST(stream), M, dims, K, max_steps, alpha_member, opt, w, enc, tags, start_token, ws);
+    return opt ? search_init(ST(stream), M, dims, alpha_member, opt, K, max_steps, w, enc, tags, start_token, ws) : no_options();
 }
 int scnattn_ensemble_steps_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
                                const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws) {
-    return ensemble_steps_opt(ST(stream), M, dims, K, max_steps, alpha_member, opt, w, enc, member_w, mode, end_token, t0,
-                              n_steps, ws);
+    return opt ? search_steps(ST(stream), M, dims, alpha_member, opt, K, max_steps, w, enc, member_w, mode, end_token, t0,
+                              n_steps, ws)
+               : no_options();
 }
 // what step t of a search with `opt` excludes, for the selection kernel alone; the launcher checks the ranges
 static int excl_of(const scnattn_search_options* opt, int end_token, int t, const int32_t* hist, int max_steps, BeamExcl& x) {
@@ -250,20 +248,18 @@ int scnattn_beam_row_topk_opt(void* stream, int N, int K, int V, const float* lo
     SCN_TRY(excl_of(opt, end_token, t, hist, max_steps, x));
     SCN_ARG(end_token < V, "end token outside the vocabulary");
     const EnsRows e{{logits}, {ld}, {1.f}};
-    return beam_row_topk_ens_opt(ST(stream), N, K, V, 1, e, 0, scores, nsrc, x, outv, outi, force_passes);
+    return beam_row_topk_ens(ST(stream), N, K, V, 1, e, 0, scores, nsrc, &x, outv, outi, force_passes);
 }
 int scnattn_beam_row_topk_ens_opt(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
                                   const float* w, int mode, const float* scores, const int32_t* nsrc,
                                   const scnattn_search_options* opt, int end_token, int t, const int32_t* hist,
                                   int max_steps, float* outv, int32_t* outi, int force_passes) {
-    if (M < 1 || M > SCN_MAX_ENSEMBLE) { set_error("scnattn_beam_row_topk_ens_opt: need 1 <= members <= 4"); return -1; }
-    if (!logits || !ld || !w) { set_error("scnattn_beam_row_topk_ens_opt: null member arrays"); return -1; }
+    EnsRows e;
+    SCN_TRY(rows_of(M, logits, ld, w, e));
     BeamExcl x;
     SCN_TRY(excl_of(opt, end_token, t, hist, max_steps, x));
     SCN_ARG(end_token < V, "end token outside the vocabulary");
-    EnsRows e{};
-    for (int m = 0; m < M; ++m) { e.p[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; }
-    return beam_row_topk_ens_opt(ST(stream), N, K, V, M, e, mode, scores, nsrc, x, outv, outi, force_passes);
+    return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, &x, outv, outi, force_passes);
 }
 int scnattn_beam_advance_opt(void* stream, int N, int K, int D, int M, int V, int t, int max_steps, const float* hs,
                              const float* cs, const int32_t* parent_t, const int32_t* token_t, const float* table,

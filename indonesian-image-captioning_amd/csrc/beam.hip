@@ -5,21 +5,22 @@
 // image and feed K accumulators from every loaded fragment, where the per-image search keeps k materialised copies:
 //   beam_attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0      (attn_scores_kernel's pixel-row layout)
 //   beam_attn_context  K softmaxes over P, awe / z for the K rows from one pass over enc[n] (attn_context_kernel's tiles)
-//   beam_row_topk      per live row: log-softmax statistics and the row's top K of  score + logit - lse
-//   beam_row_topk_ens  the same selection for an ensemble: M logits rows per live row, top K of score + c_v, where c_v is
-//                      the weighted mean of the members' log-probabilities (mode 0) or the log of the weighted mean of
-//                      their probabilities (mode 1)
-//   beam_row_topk_ens_opt  that selection with EXCLUSIONS (search options): banned words, <end> before
-//                      min_length and words that would repeat an n-gram of the row's history are not candidates (a bitmap
-//                      in LDS); one member of weight 1 serves the single decoder
+//   beam_row_topk_ens  per live row: per member the log-softmax statistics of its logits row, then the row's top K of
+//                      score + c_v, where c_v is the weighted mean of the members' log-probabilities (mode 0) or the log of
+//                      the weighted mean of their probabilities (mode 1).  ONE kernel template serves every search: the
+//                      single decoder is one member of weight 1 in mode 0 (beam_row_topk, c_v = logit - lse to the bit), and
+//                      with EXCLUSIONS (search options) banned words, <end> before min_length and words that
+//                      would repeat an n-gram of the row's history are not candidates (a bitmap in LDS)
 //   beam_merge         per image: the top kk of the nsrc x K row candidates, <end> picks recorded, the rest compacted
-//   beam_advance       h / c gathered from the parent slot, next input embedding gathered from the table
-//   beam_advance_opt   ... and the per-beam word history int32 [N*K][max_steps], gathered from the parent slot and extended
+//   beam_advance       h / c gathered from the parent slot, next input embedding gathered from the table; with search
+//                      options (beam_advance_opt, the same kernel) also the per-beam word history int32 [N*K][max_steps],
+//                      gathered from the parent slot and extended
 // ORDER (the tie rule): candidates are ranked by (value descending, flat index j*V + v ascending), values compared as the
 // fp32 numbers the kernel computes.  Dead slots (j >= nsrc) are never read as candidates and never written by the first
 // three kernels; beam_merge / beam_advance fill them with a copy of slot 0 (or zeros), so every row stays finite.
 // Plain vector stores only; no kernel waits for another workgroup.
 #include <climits>
+#include <type_traits>
 #include "common.h"
 #include "kernels.h"
 
@@ -235,54 +236,7 @@ __device__ __forceinline__ float block_sum_max(float v, float* red, bool is_max)
     return r;
 }
 
-// One workgroup per row.  STAGED: the row's V logits sit in LDS after the first pass; otherwise every pass re-reads them
-// from global memory.  Round r takes the best candidate that comes strictly after round r-1's pick in the search order,
-// which is the knock-out without a store (and exact on ties: equal values leave in index order).
-template <bool STAGED>
-__global__ __launch_bounds__(256) void beam_row_topk_kernel(int K, int V, const float* __restrict__ logits, long ld,
-                                                            const float* __restrict__ scores, const int* __restrict__ nsrc,
-                                                            float* __restrict__ outv, int* __restrict__ outi) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* redv = sm;                               // [4]
-    int* redi = reinterpret_cast<int*>(sm + 8);     // [4]
-    float* buf = sm + 16;                           // [V] when STAGED
-    const int tid = threadIdx.x;
-    const long row = blockIdx.x;
-    const int n = (int)(row / K), j = (int)(row - (long)n * K);
-    if (j >= nsrc[n]) return;
-    const float* g = logits + row * ld;
-    float m = -INFINITY;
-    for (int v = tid; v < V; v += 256) {
-        const float x = g[v];
-        if (STAGED) buf[v] = x;
-        m = fmaxf(m, x);
-    }
-    m = block_sum_max(m, redv, true);               // its barriers also publish buf
-    const float* src = STAGED ? buf : g;
-    float s = 0.f;
-    for (int v = tid; v < V; v += 256) s += expf(src[v] - m);
-    s = block_sum_max(s, redv, false);
-    const float lse = m + logf(s), sc = scores[row];
-    float pv = INFINITY;
-    int pi = -1;
-    for (int r = 0; r < K; ++r) {
-        float bv = -INFINITY;
-        int bi = INT_MAX;
-        for (int v = tid; v < V; v += 256) {
-            const float val = sc + (src[v] - lse);
-            if (before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
-        }
-        block_best(bv, bi, redv, redi);
-        if (tid == 0) {
-            outv[row * K + r] = bv;
-            outi[row * K + r] = bi;
-        }
-        pv = bv;
-        pi = bi;
-    }
-}
-
-// ---- the row selection of an ENSEMBLE: M decoders, one search state ------------------------------------
+// ---- the row selection: M decoders, one search state; the single decoder is M = 1, mode 0, w = 1 --------
 // elements v0 .. v0+3 of a member's row: one 16-byte load where the row allows it, scalar loads otherwise and for the tail
 __device__ __forceinline__ void ens_load4(const float* __restrict__ g, int v0, int V, bool vec, float x[4]) {
     if (vec && v0 + 3 < V) {
@@ -294,8 +248,35 @@ __device__ __forceinline__ void ens_load4(const float* __restrict__ g, int v0, i
     }
 }
 
+// The log-sum-exp of one member's row g[0 .. V-1]: the maximum over groups of four, the sum over v = tid, tid + 256, ...
+// (from LDS when STAGED, else from global memory; that order fixes the bits of lse, the maximum does not depend on its
+// order).  STAGED leaves the row in buf; the barriers of the reductions publish it, and the last one also says that every
+// thread is done with buf before it is written again.
+template <bool STAGED>
+__device__ __forceinline__ float ens_row_lse(const float* __restrict__ g, int V, bool vec, float* buf, float* red) {
+    const int tid = threadIdx.x, groups = (V + 3) >> 2;
+    float mx = -INFINITY;
+    for (int q = tid; q < groups; q += 256) {
+        float x[4];
+        ens_load4(g, q * 4, V, vec, x);
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (q * 4 + c < V) {
+                if (STAGED) buf[q * 4 + c] = x[c];
+                mx = fmaxf(mx, x[c]);
+            }
+    }
+    mx = block_sum_max(mx, red, true);
+    const float* src = STAGED ? buf : g;
+    float s = 0.f;
+    for (int v = tid; v < V; v += 256) s += expf(src[v] - mx);
+    s = block_sum_max(s, red, false);
+    return mx + logf(s);
+}
+
 // c_v from the members' l_mv = x_mv - lse_m.  Products and sums are spelled out (one rounded product, then fused
-// multiply-adds in member order), so that the staged and the unstaged kernel compute the same bits.
+// multiply-adds in member order), so that the staged and the unstaged kernel compute the same bits -- and, with one member
+// of weight 1 in mode 0, exactly x_v - lse.
 //   mode 0: sum_m w_m l_mv                                 (weighted geometric mean of the probabilities)
 //   mode 1: a + log(sum_m w_m exp(l_mv - a)), a = max_m l_mv      (weighted arithmetic mean; finite when exp(l_mv) underflows)
 __device__ __forceinline__ float ens_combine(int M, int mode, const float l[SCN_MAX_ENSEMBLE], const EnsRows& e) {
@@ -317,110 +298,23 @@ __device__ __forceinline__ float ens_combine(int M, int mode, const float l[SCN_
     return a + logf(s);
 }
 
-// One workgroup per live row, as beam_row_topk_kernel.  Per member the log-sum-exp of its row with that kernel's
-// reductions (the sum runs over v = tid, tid + 256, ... in every path, so lse_m has that kernel's bits; the maximum does not
-// depend on the order it is taken in).  STAGED: a member's row passes through LDS for its statistics, then c_v of the whole
-// row is written there once and the K rounds run over it.  Otherwise every round recomputes c_v from the M global rows.
-template <bool STAGED>
-__global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int V, int M, int mode, EnsRows e, unsigned vecmask,
-                                                                const float* __restrict__ scores,
-                                                                const int* __restrict__ nsrc, float* __restrict__ outv,
-                                                                int* __restrict__ outi) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* redv = sm;                               // [4]
-    int* redi = reinterpret_cast<int*>(sm + 8);     // [4]
-    float* buf = sm + 16;                           // [V] when STAGED
-    const int tid = threadIdx.x;
-    const long row = blockIdx.x;
-    const int n = (int)(row / K), j = (int)(row - (long)n * K);
-    if (j >= nsrc[n]) return;
-    const int groups = (V + 3) >> 2;
-    const float* g[SCN_MAX_ENSEMBLE];
-    float lse[SCN_MAX_ENSEMBLE];
+// The M members at the four words of group q: the loads, then c_v of word q*4 + c from them.
+struct EnsGroup {
+    float x[SCN_MAX_ENSEMBLE][4];
+    __device__ __forceinline__ void load(int M, const float* const g[SCN_MAX_ENSEMBLE], int q, int V, unsigned vecmask) {
 #pragma unroll
-    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) {
-        g[m] = nullptr;
-        lse[m] = 0.f;
-        if (m < M) {                                // uniform over the workgroup
-            g[m] = e.p[m] + row * e.ld[m];
-            const bool vec = (vecmask >> m) & 1u;
-            float mx = -INFINITY;
-            for (int q = tid; q < groups; q += 256) {
-                float x[4];
-                ens_load4(g[m], q * 4, V, vec, x);
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (q * 4 + c < V) {
-                        if (STAGED) buf[q * 4 + c] = x[c];
-                        mx = fmaxf(mx, x[c]);
-                    }
-            }
-            mx = block_sum_max(mx, redv, true);     // its barriers also publish buf
-            const float* src = STAGED ? buf : g[m];
-            float s = 0.f;
-            for (int v = tid; v < V; v += 256) s += expf(src[v] - mx);
-            s = block_sum_max(s, redv, false);      // ... and every thread is done with buf before it is written again
-            lse[m] = mx + logf(s);
-        }
+        for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
+            if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, x[m]);
     }
-    if (STAGED) {
-        for (int q = tid; q < groups; q += 256) {
-            float x[SCN_MAX_ENSEMBLE][4];
+    __device__ __forceinline__ float combine(int M, int mode, int c, const float lse[SCN_MAX_ENSEMBLE], const EnsRows& e) const {
+        float l[SCN_MAX_ENSEMBLE];
 #pragma unroll
-            for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
-                if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, x[m]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (q * 4 + c < V) {
-                    float l[SCN_MAX_ENSEMBLE];
-#pragma unroll
-                    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? x[m][c] - lse[m] : 0.f;
-                    buf[q * 4 + c] = ens_combine(M, mode, l, e);
-                }
-        }
-        __syncthreads();
+        for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? x[m][c] - lse[m] : 0.f;
+        return ens_combine(M, mode, l, e);
     }
-    const float sc = scores[row];
-    float pv = INFINITY;
-    int pi = -1;
-    for (int r = 0; r < K; ++r) {
-        float bv = -INFINITY;
-        int bi = INT_MAX;
-        if (STAGED) {
-            for (int v = tid; v < V; v += 256) {
-                const float val = sc + buf[v];
-                if (before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
-            }
-        } else {
-            for (int q = tid; q < groups; q += 256) {
-                float x[SCN_MAX_ENSEMBLE][4];
-#pragma unroll
-                for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
-                    if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, x[m]);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int v = q * 4 + c;
-                    if (v < V) {
-                        float l[SCN_MAX_ENSEMBLE];
-#pragma unroll
-                        for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? x[m][c] - lse[m] : 0.f;
-                        const float val = sc + ens_combine(M, mode, l, e);
-                        if (before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
-                    }
-                }
-            }
-        }
-        block_best(bv, bi, redv, redi);
-        if (tid == 0) {
-            outv[row * K + r] = bv;
-            outi[row * K + r] = bi;
-        }
-        pv = bv;
-        pi = bi;
-    }
-}
+};
 
-// ---- the selection with EXCLUSIONS (search options) ------------------------------------------------------
+// ---- EXCLUSIONS (search options) ----------------------------------------------------------------------------
 // LDS words behind the 16 of the reductions: the bitmap of excluded words, then the row's history, both padded to 4
 __host__ __device__ inline int excl_bitmap_words(int V) { return (((V + 31) >> 5) + 3) & ~3; }
 __host__ __device__ inline int excl_hist_words(int T) { return (T + 3) & ~3; }
@@ -430,57 +324,11 @@ __device__ __forceinline__ void excl_set(unsigned* bits, int v, int V) {
 }
 __device__ __forceinline__ bool excl_test(const unsigned* bits, int v) { return (bits[v >> 5] >> (v & 31)) & 1u; }
 
-// beam_row_topk_ens_kernel with a bitmap of the row's excluded words between the statistics and the K rounds: zeroed, then
-// set from the banned list, <end> before min_length, and -- thread i comparing the g-1 words at i with the last g-1 of the
-// history in LDS -- the word that followed every earlier occurrence of the open n-gram.  The rounds skip set bits; nothing
-// else differs, so with an empty bitmap the outputs are that kernel's bits (and with M = 1, mode 0, w = 1 beam_row_topk's).
-// The staged and the unstaged path read the same bitmap.
-template <bool STAGED>
-__global__ __launch_bounds__(256) void beam_row_topk_ens_opt_kernel(int K, int V, int M, int mode, EnsRows e,
-                                                                    unsigned vecmask, BeamExcl x,
-                                                                    const float* __restrict__ scores,
-                                                                    const int* __restrict__ nsrc, float* __restrict__ outv,
-                                                                    int* __restrict__ outi) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* redv = sm;                               // [4]
-    int* redi = reinterpret_cast<int*>(sm + 8);     // [4]
-    unsigned* bits = reinterpret_cast<unsigned*>(sm + 16);                      // [excl_bitmap_words(V)]
-    int* hs = reinterpret_cast<int*>(sm + 16 + excl_bitmap_words(V));           // [excl_hist_words(T)]
-    float* buf = sm + 16 + excl_bitmap_words(V) + excl_hist_words(x.T);         // [V] when STAGED
+// The bitmap of the row's excluded words: zeroed, then set from the banned list, <end> before min_length, and -- thread i
+// comparing the g-1 words at i with the last g-1 of the history in LDS -- the word that followed every earlier occurrence
+// of the open n-gram.  The caller's next barrier completes it.
+__device__ __forceinline__ void excl_fill(const BeamExcl& x, long row, int V, unsigned* bits, int* hs) {
     const int tid = threadIdx.x;
-    const long row = blockIdx.x;
-    const int n = (int)(row / K), j = (int)(row - (long)n * K);
-    if (j >= nsrc[n]) return;
-    const int groups = (V + 3) >> 2;
-    const float* g[SCN_MAX_ENSEMBLE];
-    float lse[SCN_MAX_ENSEMBLE];
-#pragma unroll
-    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) {
-        g[m] = nullptr;
-        lse[m] = 0.f;
-        if (m < M) {                                // uniform over the workgroup
-            g[m] = e.p[m] + row * e.ld[m];
-            const bool vec = (vecmask >> m) & 1u;
-            float mx = -INFINITY;
-            for (int q = tid; q < groups; q += 256) {
-                float xv[4];
-                ens_load4(g[m], q * 4, V, vec, xv);
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (q * 4 + c < V) {
-                        if (STAGED) buf[q * 4 + c] = xv[c];
-                        mx = fmaxf(mx, xv[c]);
-                    }
-            }
-            mx = block_sum_max(mx, redv, true);     // its barriers also publish buf
-            const float* src = STAGED ? buf : g[m];
-            float s = 0.f;
-            for (int v = tid; v < V; v += 256) s += expf(src[v] - mx);
-            s = block_sum_max(s, redv, false);      // ... and every thread is done with buf before it is written again
-            lse[m] = mx + logf(s);
-        }
-    }
-    // the exclusions of this row
     const bool ngram = x.g >= 1 && x.t >= x.g;
     for (int w = tid; w < ((V + 31) >> 5); w += 256) bits[w] = 0u;
     if (ngram)
@@ -496,51 +344,78 @@ __global__ __launch_bounds__(256) void beam_row_topk_ens_opt_kernel(int K, int V
             if (same) excl_set(bits, hs[i + x.g - 1], V);
         }
     }
-    if (STAGED) {
-        for (int q = tid; q < groups; q += 256) {
-            float xv[SCN_MAX_ENSEMBLE][4];
+}
+
+struct NoExcl {};       // what the kernel without exclusions takes in place of a BeamExcl: nothing
+
+// One workgroup per live row: per member the log-sum-exp of its row, then K rounds over the candidates score + c_v.  Round r
+// takes the best candidate that comes strictly after round r-1's pick in the search order, which is the knock-out without a
+// store (and exact on ties: equal values leave in index order).
+// STAGED: a member's row passes through LDS for its statistics, then c_v of the whole row is written there once and the K
+// rounds run over it.  Otherwise every round recomputes c_v from the M global rows.
+// EXCL: the rounds skip the words of the row's bitmap (excl_fill); nothing else differs, so with an empty bitmap the outputs
+// are the bits of EXCL = false.  The staged and the unstaged path read the same bitmap.  Without EXCL neither the bitmap nor
+// the history takes LDS.
+template <bool STAGED, bool EXCL>
+__global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int V, int M, int mode, EnsRows e, unsigned vecmask,
+                                                                std::conditional_t<EXCL, BeamExcl, NoExcl> x,
+                                                                const float* __restrict__ scores,
+                                                                const int* __restrict__ nsrc, float* __restrict__ outv,
+                                                                int* __restrict__ outi) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* redv = sm;                               // [4]
+    int* redi = reinterpret_cast<int*>(sm + 8);     // [4]
+    unsigned* bits = nullptr;                       // [excl_bitmap_words(V)] when EXCL
+    float* buf = sm + 16;                           // [V] when STAGED, behind the bitmap and the history [excl_hist_words(T)]
+    if constexpr (EXCL) {
+        bits = reinterpret_cast<unsigned*>(sm + 16);
+        buf += excl_bitmap_words(V) + excl_hist_words(x.T);
+    }
+    const int tid = threadIdx.x;
+    const long row = blockIdx.x;
+    const int n = (int)(row / K), j = (int)(row - (long)n * K);
+    if (j >= nsrc[n]) return;
+    const int groups = (V + 3) >> 2;
+    const float* g[SCN_MAX_ENSEMBLE];
+    float lse[SCN_MAX_ENSEMBLE];
 #pragma unroll
-            for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
-                if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, xv[m]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (q * 4 + c < V) {
-                    float l[SCN_MAX_ENSEMBLE];
-#pragma unroll
-                    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? xv[m][c] - lse[m] : 0.f;
-                    buf[q * 4 + c] = ens_combine(M, mode, l, e);
-                }
+    for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) {
+        g[m] = nullptr;
+        lse[m] = 0.f;
+        if (m < M) {                                // uniform over the workgroup
+            g[m] = e.p[m] + row * e.ld[m];
+            lse[m] = ens_row_lse<STAGED>(g[m], V, (vecmask >> m) & 1u, buf, redv);
         }
     }
-    __syncthreads();                                // the bitmap (and buf) are complete
+    if constexpr (EXCL) excl_fill(x, row, V, bits, reinterpret_cast<int*>(sm + 16 + excl_bitmap_words(V)));
+    if (STAGED) {
+        for (int q = tid; q < groups; q += 256) {
+            EnsGroup eg;
+            eg.load(M, g, q, V, vecmask);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (q * 4 + c < V) buf[q * 4 + c] = eg.combine(M, mode, c, lse, e);
+        }
+    }
+    if (STAGED || EXCL) __syncthreads();            // buf and the bitmap are complete; uniform over the workgroup
     const float sc = scores[row];
     float pv = INFINITY;
     int pi = -1;
     for (int r = 0; r < K; ++r) {
         float bv = -INFINITY;
         int bi = INT_MAX;
+        const auto offer = [&](float val, int v) {
+            if ((!EXCL || !excl_test(bits, v)) && before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
+        };
         if (STAGED) {
-            for (int v = tid; v < V; v += 256) {
-                const float val = sc + buf[v];
-                if (!excl_test(bits, v) && before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
-            }
+            for (int v = tid; v < V; v += 256) offer(sc + buf[v], v);
         } else {
             for (int q = tid; q < groups; q += 256) {
-                float xv[SCN_MAX_ENSEMBLE][4];
+                EnsGroup eg;
+                eg.load(M, g, q, V, vecmask);
 #pragma unroll
-                for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m)
-                    if (m < M) ens_load4(g[m], q * 4, V, (vecmask >> m) & 1u, xv[m]);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int v = q * 4 + c;
-                    if (v < V) {
-                        float l[SCN_MAX_ENSEMBLE];
-#pragma unroll
-                        for (int m = 0; m < SCN_MAX_ENSEMBLE; ++m) l[m] = m < M ? xv[m][c] - lse[m] : 0.f;
-                        const float val = sc + ens_combine(M, mode, l, e);
-                        if (!excl_test(bits, v) && before(pv, pi, val, v) && before(val, v, bv, bi)) { bv = val; bi = v; }
-                    }
-                }
+                for (int c = 0; c < 4; ++c)
+                    if (q * 4 + c < V) offer(sc + eg.combine(M, mode, c, lse, e), q * 4 + c);
             }
         }
         block_best(bv, bi, redv, redi);
@@ -612,11 +487,15 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(int K, int V, int end_to
     if (nopen == 0) atomicAdd(s.open_images, -1);
 }
 
-__global__ __launch_bounds__(256) void beam_advance_kernel(int K, int D, int M, int V, const float* __restrict__ hs,
-                                                           const float* __restrict__ cs, const int* __restrict__ parent_t,
-                                                           const int* __restrict__ token_t, const float* __restrict__ table,
-                                                           float* __restrict__ hd, float* __restrict__ cd,
-                                                           float* __restrict__ emb) {
+// h / c gathered from the parent slot, the next input embedding from the table.  With hist_d (search options): also the
+// row's history for step t+1, the parent slot's t words of hist_s, then this step's word.  A dead slot carries slot 0's
+// parent / token records, so it gets slot 0's history.
+__global__ __launch_bounds__(256) void beam_advance_kernel(int K, int D, int M, int V, int t, int T,
+                                                           const float* __restrict__ hs, const float* __restrict__ cs,
+                                                           const int* __restrict__ parent_t, const int* __restrict__ token_t,
+                                                           const float* __restrict__ table, const int* __restrict__ hist_s,
+                                                           int* __restrict__ hist_d, float* __restrict__ hd,
+                                                           float* __restrict__ cd, float* __restrict__ emb) {
     const long row = blockIdx.x;
     const long n = row / K;
     const long src = n * K + min(max(parent_t[row], 0), K - 1);     // an index outside the image's slots cannot leave them
@@ -626,27 +505,7 @@ __global__ __launch_bounds__(256) void beam_advance_kernel(int K, int D, int M, 
         cd[row * D + d] = cs[src * D + d];
     }
     for (int m = threadIdx.x; m < M; m += 256) emb[row * M + m] = table[tok * M + m];
-}
-
-// beam_advance_kernel, and the row's history for step t+1: the parent slot's t words, then this step's word.  A dead slot
-// carries slot 0's parent / token records, so it gets slot 0's history.
-__global__ __launch_bounds__(256) void beam_advance_opt_kernel(int K, int D, int M, int V, int t, int T,
-                                                               const float* __restrict__ hs, const float* __restrict__ cs,
-                                                               const int* __restrict__ parent_t,
-                                                               const int* __restrict__ token_t,
-                                                               const float* __restrict__ table,
-                                                               const int* __restrict__ hist_s, int* __restrict__ hist_d,
-                                                               float* __restrict__ hd, float* __restrict__ cd,
-                                                               float* __restrict__ emb) {
-    const long row = blockIdx.x;
-    const long n = row / K;
-    const long src = n * K + min(max(parent_t[row], 0), K - 1);     // an index outside the image's slots cannot leave them
-    const long tok = min(max(token_t[row], 0), V - 1);
-    for (int d = threadIdx.x; d < D; d += 256) {
-        hd[row * D + d] = hs[src * D + d];
-        cd[row * D + d] = cs[src * D + d];
-    }
-    for (int m = threadIdx.x; m < M; m += 256) emb[row * M + m] = table[tok * M + m];
+    if (!hist_d) return;                            // uniform over the grid
     for (int i = threadIdx.x; i < t; i += 256) hist_d[row * T + i] = hist_s[src * T + i];
     if (threadIdx.x == 0) hist_d[row * T + t] = (int)tok;
 }
@@ -724,96 +583,57 @@ int beam_attn_context(hipStream_t st, int N, int K, int P, int E, const float* e
     return 0;
 }
 
-int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
-                  float* outv, int* outi, int force_passes) {
-    if (N <= 0) return 0;
-    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk: need 1 <= beam size <= 8 and vocab_size >= beam size");
-    SCN_ARG(logits && scores && nsrc && outv && outi && ld >= V, "beam_row_topk: bad argument");
-    const size_t staged = (size_t)(16 + V) * sizeof(float);
-    dim3 grid(N * K), block(256);
-    if (staged <= 64 * 1024 && !force_passes)
-        hipLaunchKernelGGL(beam_row_topk_kernel<true>, grid, block, staged, st, K, V, logits, ld, scores, nsrc, outv, outi);
-    else
-        hipLaunchKernelGGL(beam_row_topk_kernel<false>, grid, block, 16 * sizeof(float), st, K, V, logits, ld, scores, nsrc,
-                           outv, outi);
-    SCN_LAUNCH_CHECK();
-    return 0;
-}
-
+// The one launcher of the selection; x: what the step excludes, null: nothing.
 int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                      const int* nsrc, float* outv, int* outi, int force_passes) {
+                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes) {
     if (N <= 0) return 0;
     SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "beam_row_topk_ens: need 1 <= members <= 4");
     SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk_ens: need 1 <= beam size <= 8 and vocab_size >= beam size");
     SCN_ARG(mode == 0 || mode == 1, "beam_row_topk_ens: mode must be 0 (logprob) or 1 (prob)");
     SCN_ARG(scores && nsrc && outv && outi, "beam_row_topk_ens: null argument");
+    if (x) {
+        SCN_ARG(x->T >= 1 && x->T <= 4096 && x->t >= 0 && x->t <= x->T, "beam_row_topk_ens: need 0 <= t <= max_steps <= 4096");
+        SCN_ARG(x->g >= 0 && x->g <= SCN_MAX_NGRAM, "beam_row_topk_ens: no_repeat_ngram must be in [0, 8]");
+        SCN_ARG(x->n_banned >= 0 && x->n_banned <= SCN_MAX_BANNED, "beam_row_topk_ens: at most 64 banned tokens");
+        for (int i = 0; i < x->n_banned; ++i)
+            SCN_ARG(x->banned[i] >= 0 && x->banned[i] < V, "beam_row_topk_ens: a banned token lies outside the vocabulary");
+        SCN_ARG(x->end_excl >= -1 && x->end_excl < V, "beam_row_topk_ens: the end token lies outside the vocabulary");
+        SCN_ARG(x->g == 0 || x->hist, "beam_row_topk_ens: no_repeat_ngram needs the history");
+        SCN_ARG((long)V - x->n_banned - 1 - (x->g >= 1 ? x->T : 0) >= K,
+                "beam_row_topk_ens: the options may leave a row fewer than beam_size candidates "
+                "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) >= beam_size)");
+    }
     unsigned vecmask = 0;
     for (int m = 0; m < M; ++m) {
         SCN_ARG(e.p[m] && e.ld[m] >= V, "beam_row_topk_ens: a member's logits are null or its leading dimension < vocab_size");
         SCN_ARG(e.w[m] > 0.f && e.w[m] < INFINITY, "beam_row_topk_ens: member weights must be positive and finite");
         if (aligned16(e.p[m]) && e.ld[m] % 4 == 0) vecmask |= 1u << m;
     }
-    const size_t staged = (size_t)(16 + V) * sizeof(float);
-    dim3 grid(N * K), block(256);
-    if (staged <= 64 * 1024 && !force_passes)
-        hipLaunchKernelGGL(beam_row_topk_ens_kernel<true>, grid, block, staged, st, K, V, M, mode, e, vecmask, scores, nsrc,
-                           outv, outi);
-    else
-        hipLaunchKernelGGL(beam_row_topk_ens_kernel<false>, grid, block, 16 * sizeof(float), st, K, V, M, mode, e, vecmask,
-                           scores, nsrc, outv, outi);
-    SCN_LAUNCH_CHECK();
-    return 0;
-}
-
-int beam_row_topk_ens_opt(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                          const int* nsrc, const BeamExcl& x, float* outv, int* outi, int force_passes) {
-    if (N <= 0) return 0;
-    SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "beam_row_topk_opt: need 1 <= members <= 4");
-    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk_opt: need 1 <= beam size <= 8 and vocab_size >= beam size");
-    SCN_ARG(mode == 0 || mode == 1, "beam_row_topk_opt: mode must be 0 (logprob) or 1 (prob)");
-    SCN_ARG(scores && nsrc && outv && outi, "beam_row_topk_opt: null argument");
-    SCN_ARG(x.T >= 1 && x.T <= 4096 && x.t >= 0 && x.t <= x.T, "beam_row_topk_opt: need 0 <= t <= max_steps <= 4096");
-    SCN_ARG(x.g >= 0 && x.g <= SCN_MAX_NGRAM, "beam_row_topk_opt: no_repeat_ngram must be in [0, 8]");
-    SCN_ARG(x.n_banned >= 0 && x.n_banned <= SCN_MAX_BANNED, "beam_row_topk_opt: at most 64 banned tokens");
-    for (int i = 0; i < x.n_banned; ++i)
-        SCN_ARG(x.banned[i] >= 0 && x.banned[i] < V, "beam_row_topk_opt: a banned token lies outside the vocabulary");
-    SCN_ARG(x.end_excl >= -1 && x.end_excl < V, "beam_row_topk_opt: the end token lies outside the vocabulary");
-    SCN_ARG(x.g == 0 || x.hist, "beam_row_topk_opt: no_repeat_ngram needs the history");
-    SCN_ARG((long)V - x.n_banned - 1 - (x.g >= 1 ? x.T : 0) >= K,
-            "beam_row_topk_opt: the options may leave a row fewer than beam_size candidates "
-            "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) >= beam_size)");
-    unsigned vecmask = 0;
-    for (int m = 0; m < M; ++m) {
-        SCN_ARG(e.p[m] && e.ld[m] >= V, "beam_row_topk_opt: a member's logits are null or its leading dimension < vocab_size");
-        SCN_ARG(e.w[m] > 0.f && e.w[m] < INFINITY, "beam_row_topk_opt: member weights must be positive and finite");
-        if (aligned16(e.p[m]) && e.ld[m] % 4 == 0) vecmask |= 1u << m;
-    }
-    const size_t fixed = (size_t)(16 + excl_bitmap_words(V) + excl_hist_words(x.T)) * sizeof(float);
+    // LDS: the reductions, with exclusions the bitmap and the history, and the row itself when that still fits (STAGED)
+    const size_t fixed = (size_t)(16 + (x ? excl_bitmap_words(V) + excl_hist_words(x->T) : 0)) * sizeof(float);
     const size_t staged = fixed + (size_t)V * sizeof(float);
-    SCN_ARG(fixed <= 64 * 1024, "beam_row_topk_opt: vocab_size too large for the exclusion bitmap in LDS");
+    SCN_ARG(fixed <= 64 * 1024, "beam_row_topk_ens: vocab_size too large for the exclusion bitmap in LDS");
+    const bool stage = staged <= 64 * 1024 && !force_passes;
+    const size_t lds = stage ? staged : fixed;
     dim3 grid(N * K), block(256);
-    if (staged <= 64 * 1024 && !force_passes)
-        hipLaunchKernelGGL(beam_row_topk_ens_opt_kernel<true>, grid, block, staged, st, K, V, M, mode, e, vecmask, x, scores,
-                           nsrc, outv, outi);
-    else
-        hipLaunchKernelGGL(beam_row_topk_ens_opt_kernel<false>, grid, block, fixed, st, K, V, M, mode, e, vecmask, x, scores,
-                           nsrc, outv, outi);
+#define L(STAGED)                                                                                                             \
+    if (x) hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, true>), grid, block, lds, st, K, V, M, mode, e, vecmask, *x,   \
+                              scores, nsrc, outv, outi);                                                                      \
+    else   hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, false>), grid, block, lds, st, K, V, M, mode, e, vecmask,      \
+                              NoExcl{}, scores, nsrc, outv, outi);
+    if (stage) { L(true) } else { L(false) }
+#undef L
     SCN_LAUNCH_CHECK();
     return 0;
 }
 
-int beam_advance_opt(hipStream_t st, int N, int K, int D, int M, int V, int t, int T, const float* hs, const float* cs,
-                     const int* parent_t, const int* token_t, const float* table, const int* hist_s, int* hist_d, float* hd,
-                     float* cd, float* emb) {
+// The single decoder's selection: one member of weight 1 in mode 0, whose c_v is logits[row][v] - lse(row) to the bit.
+int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
+                  float* outv, int* outi, int force_passes) {
     if (N <= 0) return 0;
-    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && D > 0 && M > 0 && V > 0, "beam_advance_opt: bad dims");
-    SCN_ARG(T >= 1 && t >= 0 && t < T, "beam_advance_opt: need 0 <= t < max_steps");
-    SCN_ARG(hs && cs && parent_t && token_t && table && hist_s && hist_d && hist_s != hist_d && hd && cd && emb,
-            "beam_advance_opt: null operand (or the history gathered in place)");
-    hipLaunchKernelGGL(beam_advance_opt_kernel, dim3(N * K), dim3(256), 0, st, K, D, M, V, t, T, hs, cs, parent_t, token_t,
-                       table, hist_s, hist_d, hd, cd, emb);
-    SCN_LAUNCH_CHECK();
-    return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk: need 1 <= beam size <= 8 and vocab_size >= beam size");
+    SCN_ARG(logits && scores && nsrc && outv && outi && ld >= V, "beam_row_topk: bad argument");
+    return beam_row_topk_ens(st, N, K, V, 1, EnsRows{{logits}, {ld}, {1.f}}, 0, scores, nsrc, nullptr, outv, outi, force_passes);
 }
 
 int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
@@ -834,8 +654,22 @@ int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float*
     if (N <= 0) return 0;
     SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && D > 0 && M > 0 && V > 0, "beam_advance: bad dims");
     SCN_ARG(hs && cs && parent_t && token_t && table && hd && cd && emb, "beam_advance: null operand");
-    hipLaunchKernelGGL(beam_advance_kernel, dim3(N * K), dim3(256), 0, st, K, D, M, V, hs, cs, parent_t, token_t, table, hd,
-                       cd, emb);
+    hipLaunchKernelGGL(beam_advance_kernel, dim3(N * K), dim3(256), 0, st, K, D, M, V, 0, 0, hs, cs, parent_t, token_t, table,
+                       nullptr, nullptr, hd, cd, emb);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_advance_opt(hipStream_t st, int N, int K, int D, int M, int V, int t, int T, const float* hs, const float* cs,
+                     const int* parent_t, const int* token_t, const float* table, const int* hist_s, int* hist_d, float* hd,
+                     float* cd, float* emb) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && D > 0 && M > 0 && V > 0, "beam_advance_opt: bad dims");
+    SCN_ARG(T >= 1 && t >= 0 && t < T, "beam_advance_opt: need 0 <= t < max_steps");
+    SCN_ARG(hs && cs && parent_t && token_t && table && hist_s && hist_d && hist_s != hist_d && hd && cd && emb,
+            "beam_advance_opt: null operand (or the history gathered in place)");
+    hipLaunchKernelGGL(beam_advance_kernel, dim3(N * K), dim3(256), 0, st, K, D, M, V, t, T, hs, cs, parent_t, token_t, table,
+                       hist_s, hist_d, hd, cd, emb);
     SCN_LAUNCH_CHECK();
     return 0;
 }

@@ -1,22 +1,23 @@
 // Batched beam search driver: the decode step of sequence.cpp's forward loop over a FIXED N*K rows (K slots per image),
-// followed by the selection kernels of beam.hip.  scnattn_beam_init does the teacher-forced driver's set-up (weight
-// re-layout, att1 once per IMAGE, qx / qh from the tags, the initial state), scnattn_beam_steps enqueues whole steps; the
-// host only reads `open_images` between chunks of steps and the token / parent / alpha records at the end.
+// followed by the selection kernels of beam.hip.  init does the teacher-forced driver's set-up (weight re-layout, att1 once
+// per IMAGE, qx / qh from the tags, the initial state), steps enqueues whole steps; the host only reads `open_images`
+// between chunks of steps and the token / parent / alpha records at the end.
 // fp32 only: option "decoder_bf16" is not looked at here.
 //
-// Launches per step (attention decoders): skinny h.[Wd^T|Wbeta^T|Ha], beam_attn_scores, beam_attn_context, skinny z.Wa[M:],
-// skinny emb.Wa[:M], scn_mix_fwd, skinny gates, lstm_fwd, fc (sgemm_ws: one or two launches), beam_row_topk, beam_merge,
-// beam_advance = 12-13; without attention 9-10.
+// ONE driver (search_workspace / search_layout / search_init / search_steps) serves the sixteen entry points
+// scnattn_beam_*, scnattn_ensemble_* and their _opt forms (csrc/api.cpp): M decoders step under one search state
+// (DESIGN.md 5m), the single search being M = 1 with weight 1 in mode 0, and search options are a pointer
+// that is null without them.
+//
+// Launches per step, all in search_steps: per member the decode part (decode_step; with attention skinny
+// h.[Wd^T|Wbeta^T|Ha], beam_attn_scores, beam_attn_context, skinny z.Wa[M:], skinny emb.Wa[:M], scn_mix_fwd, skinny gates,
+// lstm_fwd, fc (sgemm_ws: one or two launches) = 9-10; without attention 6-7), then ONE beam_row_topk_ens, ONE beam_merge
+// and beam_advance per member: (decode launches) + 2 + M, which for the single search is 12-13 with attention and 9-10
+// without.  Options add no launch: the selection takes the step's exclusions and the first member's advance also writes the
+// per-beam word history, which the workspace gains.
 //
 // The rollout driver of self-critical training (scnattn_rollout_*, at the end of this file) shares the set-up and the decode
 // part of a step (decode_setup, decode_step) and ends a step with rollout_pick + rollout_advance (csrc/rollout.hip).
-//
-// The ensemble driver (scnattn_ensemble_*, between the two) steps up to four decoders under one search state: the decode
-// part per member, one beam_row_topk_ens over their logits, one beam_merge, beam_advance per member.
-//
-// Search options (scnattn_beam_*_opt, scnattn_ensemble_*_opt): the same steps with beam_row_topk_ens_opt in
-// place of the selection and beam_advance_opt in place of the (first member's) advance; the workspace gains the per-beam
-// word history.  No launch is added per step.
 #include <hip/hip_runtime.h>
 #include "../../include/scnattn.h"
 #include "common.h"
@@ -38,11 +39,18 @@ struct StepWs {
     float *att1, *qx, *qh, *mean_enc, *h0, *c0, *WcatA, *WD, *slabA, *slabC, *slabD, *gws;
 };
 
-struct BeamWs : StepWs {
+// The workspace of one search: M decoders (the single search: one) under ONE search state.  The members read the same enc
+// [N,P,E] and share the vocabulary; each keeps its own StepWs (state, set-up results) and they share the split-K scratch,
+// since everything runs on one stream in order.  The attention maps of one member (alpha_member) are recorded; the other
+// attention members pass a null alpha_t, as the rollout does.
+struct SearchWs {
     BeamState s;
     float* candv;
     int* candi;
+    float* alpha;       // [T][R][P] of alpha_member, or null
     int* hist;          // [2][R][T] with search options, else null
+    size_t state_floats;
+    StepWs m[SCN_MAX_ENSEMBLE];
 };
 
 struct RolloutWs : StepWs {
@@ -89,9 +97,11 @@ void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b, const
     b.gws = shared_gws ? shared_gws->gws : c.take(BEAM_GEMM_WS_FLOATS);
 }
 
-size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b, bool hist = false) {
+// In this order: the BeamState fields, alpha, the members' step state, candv / candi, the history -- all of which init
+// zero-fills (state_floats) -- then the members' set-up results with the shared split-K scratch.
+size_t carve_search(int M, const scnattn_dims* d, int K, int T, int alpha_member, bool hist, float* base, SearchWs& b) {
     Carver c(base);
-    const int N = d.B, P = d.P;
+    const int N = d[0].B, P = d[0].P;
     const long R = (long)N * K;
     b.s.R = (int)R;
     b.s.scores = c.take(R);
@@ -106,14 +116,29 @@ size_t carve_beam(const scnattn_dims& d, int K, int T, float* base, BeamWs& b, b
     b.s.comp_parent = ints(c.take(R));
     b.s.token = ints(c.take(sz(T, R)));
     b.s.parent = ints(c.take(sz(T, R)));
-    b.alpha = d.has_att ? c.take(sz(T, R, P)) : nullptr;
-    carve_step_state(c, d, R, b);
+    const bool alpha = alpha_member >= 0 && alpha_member < M && d[alpha_member].has_att;
+    b.alpha = alpha ? c.take(sz(T, R, P)) : nullptr;
+    for (int m = 0; m < M; ++m) {
+        b.m[m].alpha = m == alpha_member ? b.alpha : nullptr;
+        carve_step_state(c, d[m], R, b.m[m]);
+    }
     b.candv = c.take(sz(R, K));
     b.candi = ints(c.take(sz(R, K)));
     b.hist = hist ? ints(c.take(sz(2, R, T))) : nullptr;
     b.state_floats = c.off;
-    carve_step_setup(c, d, R, b);
+    for (int m = 0; m < M; ++m) {
+        b.m[m].state_floats = b.state_floats;
+        carve_step_setup(c, d[m], R, b.m[m], m ? &b.m[0] : nullptr);
+    }
     return c.off * sizeof(float);
+}
+
+// Where results live in a workspace: off[i] = p[i] - base in 4-byte elements, -1 for a null p[i].  A layout query carves
+// from layout_base(), which is never dereferenced: only differences are taken.
+inline float* layout_base() { return reinterpret_cast<float*>(uintptr_t(1) << 40); }
+
+void offsets_from(const float* base, const void* const* p, int n, long* off) {
+    for (int i = 0; i < n; ++i) off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
 }
 
 // The refusals of a search with options (include/scnattn.h); end_token < 0: not known to this call.
@@ -155,6 +180,18 @@ int check_beam(const scnattn_dims* d, int K, int T) {
     SCN_ARG(d->V >= K, "vocab_size must be at least beam_size");
     SCN_ARG(T >= 1 && T <= 4096, "max_steps must be in [1, 4096]");
     SCN_ARG((long)d->B * K <= (1L << 20), "too many rows (images x beam_size)");
+    return 0;
+}
+
+int check_search(int M, const scnattn_dims* d, int K, int T, int alpha_member) {
+    SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "an ensemble has 1 to 4 members");
+    SCN_ARG(d, "dims is NULL");
+    for (int m = 0; m < M; ++m) {
+        SCN_TRY(check_beam(d + m, K, T));
+        SCN_ARG(d[m].B == d[0].B && d[m].P == d[0].P && d[m].E == d[0].E && d[m].V == d[0].V,
+                "the members of an ensemble must agree in B, P, E and V");
+    }
+    SCN_ARG(alpha_member >= -1 && alpha_member < M, "alpha_member must be -1 or a member index");
     return 0;
 }
 
@@ -217,345 +254,75 @@ int decode_step(hipStream_t st, const scnattn_dims& d, int K, const scnattn_para
 
 }  // namespace
 
-int beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes) {
-    SCN_TRY(check_beam(d, K, max_steps));
-    SCN_ARG(bytes, "beam_workspace: bytes is NULL");
-    BeamWs b;
-    *bytes = carve_beam(*d, K, max_steps, nullptr, b);
+// ---- the search: M decoders under ONE search state; o: the search options, null without ------------
+int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
+                     size_t* bytes) {
+    SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
+    if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    SCN_ARG(bytes, "search_workspace: bytes is NULL");
+    SearchWs b;
+    *bytes = carve_search(M, d, K, max_steps, alpha_member, o != nullptr, nullptr, b);
     return 0;
 }
 
-// off[SCNATTN_BEAM_NOFF]: where the results live in the workspace, in 4-byte elements (order: include/scnattn.h)
-int beam_layout(const scnattn_dims* d, int K, int max_steps, long* off) {
-    SCN_TRY(check_beam(d, K, max_steps));
-    SCN_ARG(off, "beam_layout: offsets is NULL");
-    BeamWs b;
-    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
-    carve_beam(*d, K, max_steps, base, b);
-    const void* p[SCNATTN_BEAM_NOFF] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
-                                        b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
-                                        b.s.parent, b.alpha};
-    for (int i = 0; i < SCNATTN_BEAM_NOFF; ++i)
-        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
-    return 0;
-}
-
-namespace {
-
-int beam_init_impl(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_params* w, const float* enc,
-                   const float* tags, int start_token, float* ws, bool hist) {
-    SCN_TRY(check_beam(dp, K, max_steps));
-    const scnattn_dims& d = *dp;
-    SCN_ARG(w && enc && tags && ws, "beam_init: null argument");
-    SCN_ARG(start_token >= 0 && start_token < d.V, "beam_init: start token outside the vocabulary");
-    SCN_ARG(aligned16(ws), "beam_init: the workspace must be 16-byte aligned");
-    BeamWs b;
-    carve_beam(d, K, max_steps, ws, b, hist);
-    SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
-    SCN_TRY(beam_state_init(st, d.B, K, b.s));
-    SCN_TRY(decode_setup(st, d, K, w, enc, tags, start_token, b));
-    return 0;
-}
-
-}  // namespace
-
-int beam_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_params* w, const float* enc,
-              const float* tags, int start_token, float* ws) {
-    return beam_init_impl(st, dp, K, max_steps, w, enc, tags, start_token, ws, false);
-}
-
-// Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.
-int beam_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_params* w, const float* enc,
-               int end_token, int t0, int n_steps, float* ws) {
-    SCN_TRY(check_beam(dp, K, max_steps));
-    const scnattn_dims& d = *dp;
-    SCN_ARG(w && enc && ws, "beam_steps: null argument");
-    SCN_ARG(t0 >= 0 && n_steps >= 0, "beam_steps: negative step");
-    const int N = d.B, P = d.P, D = d.D, M = d.M, V = d.V, R = N * K;
-    BeamWs b;
-    carve_beam(d, K, max_steps, ws, b);
-    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
-    for (int t = t0; t < t1; ++t) {
-        int* token_t = b.s.token + (long)t * R;
-        int* parent_t = b.s.parent + (long)t * R;
-        SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, d.has_att ? b.alpha + (long)t * R * P : nullptr, b.hA, b.cA, b.hB,
-                            b.cB));
-        SCN_TRY(beam_row_topk(st, N, K, V, b.logits, V, b.s.scores, b.s.nsrc, b.candv, b.candi, 0));
-        SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
-        SCN_TRY(beam_advance(st, N, K, D, M, V, b.hB, b.cB, parent_t, token_t, w->embedding_weight, b.hA, b.cA, b.emb));
-    }
-    return 0;
-}
-
-// ---- the search with OPTIONS: the same steps, the selection and the advance in their _opt form -----------
-// The workspace gains the history int32 [2][R][max_steps] (zero-filled by init); the launches per step are those above.
-int beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, size_t* bytes) {
-    SCN_TRY(check_beam(d, K, max_steps));
-    SCN_TRY(check_options(o, d->V, K, max_steps, -1));
-    SCN_ARG(bytes, "beam_workspace_opt: bytes is NULL");
-    BeamWs b;
-    *bytes = carve_beam(*d, K, max_steps, nullptr, b, true);
-    return 0;
-}
-
-// off[SCNATTN_BEAM_NOFF_OPT]: the 13 offsets of beam_layout, then the history's
-int beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* o, long* off) {
-    SCN_TRY(check_beam(d, K, max_steps));
-    SCN_TRY(check_options(o, d->V, K, max_steps, -1));
-    SCN_ARG(off, "beam_layout_opt: offsets is NULL");
-    BeamWs b;
-    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
-    carve_beam(*d, K, max_steps, base, b, true);
+// off[SCNATTN_BEAM_NOFF]: where the results live in the workspace, in 4-byte elements (order: include/scnattn.h); with
+// options off[SCNATTN_BEAM_NOFF_OPT], the history's offset behind them
+int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
+                  long* off) {
+    SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
+    if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    SCN_ARG(off, "search_layout: offsets is NULL");
+    SearchWs b;
+    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, layout_base(), b);
     const void* p[SCNATTN_BEAM_NOFF_OPT] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
                                             b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
                                             b.s.parent, b.alpha, b.hist};
-    for (int i = 0; i < SCNATTN_BEAM_NOFF_OPT; ++i)
-        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
+    offsets_from(layout_base(), p, o ? SCNATTN_BEAM_NOFF_OPT : SCNATTN_BEAM_NOFF, off);
     return 0;
 }
 
-int beam_init_opt(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_search_options* o,
-                  const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws) {
-    SCN_TRY(check_beam(dp, K, max_steps));
-    SCN_TRY(check_options(o, dp->V, K, max_steps, -1));
-    return beam_init_impl(st, dp, K, max_steps, w, enc, tags, start_token, ws, true);
-}
-
-int beam_steps_opt(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, const scnattn_search_options* o,
-                   const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws) {
-    SCN_TRY(check_beam(dp, K, max_steps));
-    const scnattn_dims& d = *dp;
-    SCN_ARG(end_token >= 0, "beam_steps_opt: end token outside the vocabulary");
-    SCN_TRY(check_options(o, d.V, K, max_steps, end_token));
-    SCN_ARG(w && enc && ws, "beam_steps_opt: null argument");
-    SCN_ARG(t0 >= 0 && n_steps >= 0, "beam_steps_opt: negative step");
-    const int N = d.B, P = d.P, D = d.D, M = d.M, V = d.V, R = N * K, T = max_steps;
-    BeamWs b;
-    carve_beam(d, K, max_steps, ws, b, true);
-    const EnsRows rows{{b.logits}, {V}, {1.f}};     // one member, weight 1: the bits of beam_row_topk
-    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
-    for (int t = t0; t < t1; ++t) {
-        int* token_t = b.s.token + (long)t * R;
-        int* parent_t = b.s.parent + (long)t * R;
-        SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, d.has_att ? b.alpha + (long)t * R * P : nullptr, b.hA, b.cA, b.hB,
-                            b.cB));
-        const BeamExcl x = step_excl(*o, t, T, R, end_token, b.hist);
-        SCN_TRY(beam_row_topk_ens_opt(st, N, K, V, 1, rows, 0, b.s.scores, b.s.nsrc, x, b.candv, b.candi, 0));
-        SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
-        SCN_TRY(beam_advance_opt(st, N, K, D, M, V, t, T, b.hB, b.cB, parent_t, token_t, w->embedding_weight, x.hist,
-                                 b.hist + (long)((t + 1) & 1) * R * T, b.hA, b.cA, b.emb));
-    }
-    return 0;
-}
-
-// ---- ensemble search: M decoders under ONE search state ---------------------------------------------------
-// The members read the same enc [N,P,E] and share the vocabulary; each keeps its own StepWs (state, set-up results) and
-// they share the split-K scratch, since everything runs on one stream in order.  A step is, per member, decode_step with
-// that member's hA/cA -> hB/cB, then ONE beam_row_topk_ens over the M logits buffers, ONE beam_merge, and per member
-// beam_advance with its own table and state: (decode launches of the members) + 2 + M.  The attention maps of one member
-// (alpha_member) are recorded; the other attention members pass a null alpha_t, as the rollout does.  fp32 only.
-namespace {
-
-struct EnsembleWs {
-    BeamState s;
-    float* candv;
-    int* candi;
-    float* alpha;       // [T][R][P] of alpha_member, or null
-    int* hist;          // [2][R][T] with search options, else null
-    size_t state_floats;
-    StepWs m[SCN_MAX_ENSEMBLE];
-};
-
-bool ens_alpha(int M, const scnattn_dims* d, int alpha_member) {
-    return alpha_member >= 0 && alpha_member < M && d[alpha_member].has_att;
-}
-
-size_t carve_ensemble(int M, const scnattn_dims* d, int K, int T, int alpha_member, float* base, EnsembleWs& b,
-                      bool hist = false) {
-    Carver c(base);
-    const int N = d[0].B, P = d[0].P;
-    const long R = (long)N * K;
-    b.s.R = (int)R;
-    b.s.scores = c.take(R);
-    b.s.nsrc = ints(c.take(N));
-    b.s.kk = ints(c.take(N));
-    b.s.ncomp = ints(c.take(N));
-    b.s.best_idx = ints(c.take(N));
-    b.s.best_score = c.take(N);
-    b.s.open_images = ints(c.take(1));
-    b.s.comp_score = c.take(R);
-    b.s.comp_step = ints(c.take(R));
-    b.s.comp_parent = ints(c.take(R));
-    b.s.token = ints(c.take(sz(T, R)));
-    b.s.parent = ints(c.take(sz(T, R)));
-    b.alpha = ens_alpha(M, d, alpha_member) ? c.take(sz(T, R, P)) : nullptr;
-    for (int m = 0; m < M; ++m) {
-        b.m[m].alpha = m == alpha_member ? b.alpha : nullptr;
-        carve_step_state(c, d[m], R, b.m[m]);
-    }
-    b.candv = c.take(sz(R, K));
-    b.candi = ints(c.take(sz(R, K)));
-    b.hist = hist ? ints(c.take(sz(2, R, T))) : nullptr;
-    b.state_floats = c.off;
-    for (int m = 0; m < M; ++m) {
-        b.m[m].state_floats = b.state_floats;
-        carve_step_setup(c, d[m], R, b.m[m], m ? &b.m[0] : nullptr);
-    }
-    return c.off * sizeof(float);
-}
-
-int check_ensemble(int M, const scnattn_dims* d, int K, int T, int alpha_member) {
-    SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "an ensemble has 1 to 4 members");
-    SCN_ARG(d, "dims is NULL");
-    for (int m = 0; m < M; ++m) {
-        SCN_TRY(check_beam(d + m, K, T));
-        SCN_ARG(d[m].B == d[0].B && d[m].P == d[0].P && d[m].E == d[0].E && d[m].V == d[0].V,
-                "the members of an ensemble must agree in B, P, E and V");
-    }
-    SCN_ARG(alpha_member >= -1 && alpha_member < M, "alpha_member must be -1 or a member index");
-    return 0;
-}
-
-}  // namespace
-
-int ensemble_workspace(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, size_t* bytes) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_ARG(bytes, "ensemble_workspace: bytes is NULL");
-    EnsembleWs b;
-    *bytes = carve_ensemble(M, d, K, max_steps, alpha_member, nullptr, b);
-    return 0;
-}
-
-// off[SCNATTN_BEAM_NOFF]: the offsets of scnattn_beam_layout, in the same order
-int ensemble_layout(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member, long* off) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_ARG(off, "ensemble_layout: offsets is NULL");
-    EnsembleWs b;
-    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
-    carve_ensemble(M, d, K, max_steps, alpha_member, base, b);
-    const void* p[SCNATTN_BEAM_NOFF] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
-                                        b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
-                                        b.s.parent, b.alpha};
-    for (int i = 0; i < SCNATTN_BEAM_NOFF; ++i)
-        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
-    return 0;
-}
-
-namespace {
-
-int ensemble_init_impl(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                       const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws,
-                       bool hist) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_ARG(w && enc && tags && ws, "ensemble_init: null argument");
-    for (int m = 0; m < M; ++m) SCN_ARG(tags[m], "ensemble_init: a member's tags are NULL");
-    SCN_ARG(start_token >= 0 && start_token < d[0].V, "ensemble_init: start token outside the vocabulary");
-    SCN_ARG(aligned16(ws), "ensemble_init: the workspace must be 16-byte aligned");
-    EnsembleWs b;
-    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b, hist);
+// The history int32 [2][R][max_steps] of a search with options is zero-filled with the rest of the state.
+int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
+                int max_steps, const scnattn_params* w, const float* enc, const float* const* tags, int start_token,
+                float* ws) {
+    SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
+    if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    SCN_ARG(w && enc && tags && ws, "search_init: null argument");
+    for (int m = 0; m < M; ++m) SCN_ARG(tags[m], "search_init: a member's tags are NULL");
+    SCN_ARG(start_token >= 0 && start_token < d[0].V, "search_init: start token outside the vocabulary");
+    SCN_ARG(aligned16(ws), "search_init: the workspace must be 16-byte aligned");
+    SearchWs b;
+    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, ws, b);
     SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
     SCN_TRY(beam_state_init(st, d[0].B, K, b.s));
     for (int m = 0; m < M; ++m) SCN_TRY(decode_setup(st, d[m], K, w + m, enc, tags[m], start_token, b.m[m]));
     return 0;
 }
 
-}  // namespace
-
-int ensemble_init(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                  const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
-    return ensemble_init_impl(st, M, d, K, max_steps, alpha_member, w, enc, tags, start_token, ws, false);
-}
-
-// Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.
-int ensemble_steps(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                   const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
-                   int n_steps, float* ws) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_ARG(w && enc && member_w && ws, "ensemble_steps: null argument");
-    SCN_ARG(t0 >= 0 && n_steps >= 0, "ensemble_steps: negative step");
-    const int N = d[0].B, P = d[0].P, V = d[0].V, R = N * K;
-    EnsembleWs b;
-    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b);
-    EnsRows rows{};
-    for (int m = 0; m < M; ++m) {
-        rows.p[m] = b.m[m].logits;
-        rows.ld[m] = V;
-        rows.w[m] = member_w[m];
+// Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.  A step is, per
+// member, decode_step with that member's hA/cA -> hB/cB, then ONE selection over the M logits buffers, ONE beam_merge, and
+// per member beam_advance with its own table and state.  With options the selection takes what step t excludes, and one
+// history serves all members: step t reads buffer t & 1, the first member's advance writes buffer (t + 1) & 1.
+int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
+                 int max_steps, const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token,
+                 int t0, int n_steps, float* ws) {
+    SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
+    if (o) {    // only a search with options needs to know <end>: min_length keeps it out, and it may not be banned
+        SCN_ARG(end_token >= 0, "search_steps: end token outside the vocabulary");
+        SCN_TRY(check_options(o, d[0].V, K, max_steps, end_token));
     }
-    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
-    for (int t = t0; t < t1; ++t) {
-        int* token_t = b.s.token + (long)t * R;
-        int* parent_t = b.s.parent + (long)t * R;
-        for (int m = 0; m < M; ++m) {
-            const StepWs& s = b.m[m];
-            SCN_TRY(decode_step(st, d[m], K, w + m, enc, s, b.s.nsrc, s.alpha ? s.alpha + (long)t * R * P : nullptr, s.hA, s.cA,
-                                s.hB, s.cB));
-        }
-        SCN_TRY(beam_row_topk_ens(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, b.candv, b.candi, 0));
-        SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
-        for (int m = 0; m < M; ++m) {
-            const StepWs& s = b.m[m];
-            SCN_TRY(beam_advance(st, N, K, d[m].D, d[m].M, V, s.hB, s.cB, parent_t, token_t, w[m].embedding_weight, s.hA, s.cA,
-                                 s.emb));
-        }
-    }
-    return 0;
-}
-
-// ---- the ensemble search with OPTIONS ---------------------------------------------------------------------
-int ensemble_workspace_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                           const scnattn_search_options* o, size_t* bytes) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
-    SCN_ARG(bytes, "ensemble_workspace_opt: bytes is NULL");
-    EnsembleWs b;
-    *bytes = carve_ensemble(M, d, K, max_steps, alpha_member, nullptr, b, true);
-    return 0;
-}
-
-int ensemble_layout_opt(int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                        const scnattn_search_options* o, long* off) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
-    SCN_ARG(off, "ensemble_layout_opt: offsets is NULL");
-    EnsembleWs b;
-    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
-    carve_ensemble(M, d, K, max_steps, alpha_member, base, b, true);
-    const void* p[SCNATTN_BEAM_NOFF_OPT] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
-                                            b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
-                                            b.s.parent, b.alpha, b.hist};
-    for (int i = 0; i < SCNATTN_BEAM_NOFF_OPT; ++i)
-        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
-    return 0;
-}
-
-int ensemble_init_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                      const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* const* tags,
-                      int start_token, float* ws) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
-    return ensemble_init_impl(st, M, d, K, max_steps, alpha_member, w, enc, tags, start_token, ws, true);
-}
-
-// One history serves all members: the first member's advance writes it, the others run the plain advance.
-int ensemble_steps_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int max_steps, int alpha_member,
-                       const scnattn_search_options* o, const scnattn_params* w, const float* enc, const float* member_w,
-                       int mode, int end_token, int t0, int n_steps, float* ws) {
-    SCN_TRY(check_ensemble(M, d, K, max_steps, alpha_member));
-    SCN_ARG(end_token >= 0, "ensemble_steps_opt: end token outside the vocabulary");
-    SCN_TRY(check_options(o, d[0].V, K, max_steps, end_token));
-    SCN_ARG(w && enc && member_w && ws, "ensemble_steps_opt: null argument");
-    SCN_ARG(t0 >= 0 && n_steps >= 0, "ensemble_steps_opt: negative step");
+    SCN_ARG(w && enc && member_w && ws, "search_steps: null argument");
+    SCN_ARG(t0 >= 0 && n_steps >= 0, "search_steps: negative step");
     const int N = d[0].B, P = d[0].P, V = d[0].V, R = N * K, T = max_steps;
-    EnsembleWs b;
-    carve_ensemble(M, d, K, max_steps, alpha_member, ws, b, true);
+    SearchWs b;
+    carve_search(M, d, K, T, alpha_member, o != nullptr, ws, b);
     EnsRows rows{};
     for (int m = 0; m < M; ++m) {
         rows.p[m] = b.m[m].logits;
         rows.ld[m] = V;
         rows.w[m] = member_w[m];
     }
-    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
+    const int t1 = t0 + n_steps < T ? t0 + n_steps : T;
     for (int t = t0; t < t1; ++t) {
         int* token_t = b.s.token + (long)t * R;
         int* parent_t = b.s.parent + (long)t * R;
@@ -564,12 +331,13 @@ int ensemble_steps_opt(hipStream_t st, int M, const scnattn_dims* d, int K, int 
             SCN_TRY(decode_step(st, d[m], K, w + m, enc, s, b.s.nsrc, s.alpha ? s.alpha + (long)t * R * P : nullptr, s.hA, s.cA,
                                 s.hB, s.cB));
         }
-        const BeamExcl x = step_excl(*o, t, T, R, end_token, b.hist);
-        SCN_TRY(beam_row_topk_ens_opt(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, x, b.candv, b.candi, 0));
+        BeamExcl x{};
+        if (o) x = step_excl(*o, t, T, R, end_token, b.hist);
+        SCN_TRY(beam_row_topk_ens(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, o ? &x : nullptr, b.candv, b.candi, 0));
         SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
         for (int m = 0; m < M; ++m) {
             const StepWs& s = b.m[m];
-            if (m == 0)
+            if (o && m == 0)
                 SCN_TRY(beam_advance_opt(st, N, K, d[m].D, d[m].M, V, t, T, s.hB, s.cB, parent_t, token_t,
                                          w[m].embedding_weight, x.hist, b.hist + (long)((t + 1) & 1) * R * T, s.hA, s.cA,
                                          s.emb));
@@ -623,12 +391,10 @@ int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, 
     SCN_TRY(check_beam(d, K, max_steps));
     SCN_ARG(off, "rollout_layout: offsets is NULL");
     RolloutWs b;
-    float* base = reinterpret_cast<float*>(uintptr_t(1) << 40);     // never dereferenced: only differences are taken
-    carve_rollout(*d, K, max_steps, want_alpha, base, b);
+    carve_rollout(*d, K, max_steps, want_alpha, layout_base(), b);
     const void* p[SCNATTN_ROLLOUT_NOFF] = {b.s.open_rows, b.s.nsrc, b.s.nopen, b.s.length, b.s.sum_logp, b.s.token, b.s.logp,
                                            b.alpha};
-    for (int i = 0; i < SCNATTN_ROLLOUT_NOFF; ++i)
-        off[i] = p[i] ? (long)(reinterpret_cast<const float*>(p[i]) - base) : -1;
+    offsets_from(layout_base(), p, SCNATTN_ROLLOUT_NOFF, off);
     return 0;
 }
 

@@ -155,26 +155,13 @@ int beam_attn_scores(hipStream_t st, int N, int K, int P, int A, const float* at
 // alpha_out [N*K][P] (may be NULL), awe [N*K][E] (may be NULL), z = sigmoid(gpre + bbeta) * awe (gpre.p == nullptr: z = awe)
 int beam_attn_context(hipStream_t st, int N, int K, int P, int E, const float* enc, const float* e, Slabs gpre,
                       const float* bbeta, const int* nsrc, float* alpha_out, float* awe, float* z);
-// outv / outi [N*K][K]: per live row the top K of scores[row] + logits[row][v] - lse(row), best first.
-// force_passes != 0 (tests): read the row from global memory in every pass even when it fits the LDS.
-int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
-                  float* outv, int* outi, int force_passes);
-// The M logits rows an ensemble's selection reads per live row r: p[m] + r * ld[m], weights w[m] > 0 that sum to 1.
+// The M logits rows the selection reads per live row r: p[m] + r * ld[m], weights w[m] > 0 that sum to 1.
 #define SCN_MAX_ENSEMBLE 4
 struct EnsRows {
     const float* p[SCN_MAX_ENSEMBLE];
     long ld[SCN_MAX_ENSEMBLE];
     float w[SCN_MAX_ENSEMBLE];
 };
-// beam_row_topk over a combined distribution: the top K of scores[row] + c_v with l_mv = logits_m[row][v] - lse_m(row),
-// mode 0: c_v = sum_m w_m l_mv;  mode 1: c_v = a_v + log(sum_m w_m exp(l_mv - a_v)), a_v = max_m l_mv.
-// mode 0 with M = 1, w = 1 writes the bits of beam_row_topk.
-int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                      const int* nsrc, float* outv, int* outi, int force_passes);
-int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
-               const BeamState& s);
-int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,
-                 const int* token_t, const float* table, float* hd, float* cd, float* emb);
 // ---- the search OPTIONS: candidates a step may not pick -------------------------------------------------
 #define SCN_MAX_BANNED 64
 #define SCN_MAX_NGRAM 8
@@ -185,11 +172,24 @@ struct BeamExcl {
     const int* hist;        // [N*K][T] (may be null when g == 0)
     int banned[SCN_MAX_BANNED];
 };
-// beam_row_topk_ens with the candidates of `x` left out of the K rounds (the log-sum-exp still runs over all V logits);
-// with nothing excluded it writes the bits of beam_row_topk_ens.  Refuses unless V - n_banned - 1 - (g >= 1 ? T : 0) >= K.
-int beam_row_topk_ens_opt(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                          const int* nsrc, const BeamExcl& x, float* outv, int* outi, int force_passes);
-// beam_advance, and the history of row n*K+s for step t+1: the parent slot's first t entries of hist_s, then token_t[row]
+// THE selection (one kernel template, one launcher).  outv / outi [N*K][K]: per live row the top K of scores[row] + c_v,
+// best first, with l_mv = logits_m[row][v] - lse_m(row) and
+// mode 0: c_v = sum_m w_m l_mv;  mode 1: c_v = a_v + log(sum_m w_m exp(l_mv - a_v)), a_v = max_m l_mv.
+// x: the candidates left out of the K rounds (the log-sum-exp still runs over all V logits); null: none, which writes the
+// bits of an `x` that excludes nothing.  With x it refuses unless V - n_banned - 1 - (g >= 1 ? T : 0) >= K.
+// force_passes != 0 (tests): read the rows from global memory in every pass even when a row fits the LDS.
+int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
+                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes);
+// The single decoder's selection, the top K of scores[row] + logits[row][v] - lse(row): beam_row_topk_ens with M = 1,
+// mode 0, w = 1, nothing excluded.
+int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
+                  float* outv, int* outi, int force_passes);
+int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
+               const BeamState& s);
+// One kernel behind both: h / c of row n*K+s gathered from its parent slot, emb from the table; the _opt form also writes
+// the row's history for step t+1, the parent slot's first t entries of hist_s, then token_t[row] (hist_s != hist_d)
+int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,
+                 const int* token_t, const float* table, float* hd, float* cd, float* emb);
 int beam_advance_opt(hipStream_t st, int N, int K, int D, int M, int V, int t, int T, const float* hs, const float* cs,
                      const int* parent_t, const int* token_t, const float* table, const int* hist_s, int* hist_d, float* hd,
                      float* cd, float* emb);

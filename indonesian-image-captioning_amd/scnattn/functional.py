@@ -235,6 +235,35 @@ _BEAM_RESULTS = ("open_images", "nsrc", "kk", "ncomp", "best_idx", "best_score",
 _BEAM_FLOAT = ("best_score", "scores", "comp_score", "alpha")
 
 
+def _run_on_device(fmt, head, noff, init_tail, steps_tail, st, dev, max_steps, chunk, guard):
+    """What beam_search_run, ensemble_search_run and rollout_run share.  fmt % "workspace" / "layout" / "init" / "steps" name
+    the four calls of one driver and `head` is what all four take first (dims, K, max_steps, ...):
+        workspace(*head, &bytes), layout(*head, off[noff])
+        the allocation; guard > 0 (tests): that many sentinel words behind the workspace
+        init(stream, *head, *init_tail, ws)         zero-fills what needs it
+        steps(stream, *head, *steps_tail, t, n, ws) in chunks of `chunk` steps, with one 4-byte copy (and sync) per chunk:
+                                                    the driver's open counter at off[0]
+    Returns (ws, off, nwords, t): the workspace (float32, nwords + guard words), the offsets, and the steps that ran."""
+    nbytes = C.c_size_t()
+    call(fmt % "workspace", *head, C.byref(nbytes))
+    off = (C.c_long * noff)()
+    call(fmt % "layout", *head, off)
+    nwords = nbytes.value // 4
+    ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)
+    wsi = ws.view(torch.int32)
+    if guard:
+        wsi[nwords:].fill_(0x7FC5A5A5)
+    call(fmt % "init", st, *head, *init_tail, ptr(ws))
+    t = 0
+    while t < max_steps:
+        n = min(chunk, max_steps - t)
+        call(fmt % "steps", st, *head, *steps_tail, t, n, ptr(ws))
+        t += n
+        if int(wsi[off[0]]) == 0:
+            break
+    return ws, off, nwords, t
+
+
 def search_options_struct(options, vocab_size, beam_size, max_steps, end_token):
     """a models.decoders.SearchOptions -> scnattn_search_options, after its refusals for this search (ValueError)"""
     options.check(vocab_size, beam_size, max_steps, end_token)
@@ -270,24 +299,10 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
     weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
     w = _params_struct(weights)
     K, N = beam_size, d.B
-    nbytes = C.c_size_t()
-    call("scnattn_beam_workspace" + sfx, C.byref(d), K, max_steps, *opt, C.byref(nbytes))
-    off = (C.c_long * (_lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF))()
-    call("scnattn_beam_layout" + sfx, C.byref(d), K, max_steps, *opt, off)
-    nwords = nbytes.value // 4
-    ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_beam_init zero-fills what needs it
-    wsi = ws.view(torch.int32)
-    if guard:
-        wsi[nwords:].fill_(0x7FC5A5A5)
-    st = stream_of(enc)
-    call("scnattn_beam_init" + sfx, st, C.byref(d), K, max_steps, *opt, C.byref(w), ptr(enc), ptr(tags), start_token, ptr(ws))
-    t = 0
-    while t < max_steps:
-        n = min(chunk, max_steps - t)
-        call("scnattn_beam_steps" + sfx, st, C.byref(d), K, max_steps, *opt, C.byref(w), ptr(enc), end_token, t, n, ptr(ws))
-        t += n
-        if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
-            break
+    ws, off, nwords, t = _run_on_device("scnattn_beam_%s" + sfx, (C.byref(d), K, max_steps, *opt),
+                                        _lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF,
+                                        (C.byref(w), ptr(enc), ptr(tags), start_token), (C.byref(w), ptr(enc), end_token),
+                                        stream_of(enc), dev, max_steps, chunk, guard)
     return _beam_results(ws, off, N, K, d.P, t, nwords, guard, max_steps), t
 
 
@@ -381,25 +396,9 @@ def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, memb
     sfx, opt = "", ()       # with options: the _opt form of the four calls, the options struct after alpha_member
     if options is not None:
         sfx, opt = "_opt", (C.byref(search_options_struct(options, d[0].V, beam_size, max_steps, int(end))),)
-    nbytes = C.c_size_t()
-    call("scnattn_ensemble_workspace" + sfx, M, d, K, max_steps, alpha_member, *opt, C.byref(nbytes))
-    off = (C.c_long * (_lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF))()
-    call("scnattn_ensemble_layout" + sfx, M, d, K, max_steps, alpha_member, *opt, off)
-    nwords = nbytes.value // 4
-    ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_ensemble_init zero-fills what needs it
-    wsi = ws.view(torch.int32)
-    if guard:
-        wsi[nwords:].fill_(0x7FC5A5A5)
-    st = stream_of(enc)
-    call("scnattn_ensemble_init" + sfx, st, M, d, K, max_steps, alpha_member, *opt, w, ptr(enc), tg, int(start), ptr(ws))
-    t = 0
-    while t < max_steps:
-        n = min(chunk, max_steps - t)
-        call("scnattn_ensemble_steps" + sfx, st, M, d, K, max_steps, alpha_member, *opt, w, ptr(enc), cw, mode, int(end), t, n,
-             ptr(ws))
-        t += n
-        if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
-            break
+    ws, off, nwords, t = _run_on_device("scnattn_ensemble_%s" + sfx, (M, d, K, max_steps, alpha_member, *opt),
+                                        _lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF, (w, ptr(enc), tg, int(start)),
+                                        (w, ptr(enc), cw, mode, int(end)), stream_of(enc), dev, max_steps, chunk, guard)
     return _beam_results(ws, off, N, K, d[0].P, t, nwords, guard, max_steps), t
 
 
@@ -443,25 +442,11 @@ def rollout_run(dims, K, weights, enc, tags, start, end, seed, draw, inv_temp=1.
     weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
     w = _params_struct(weights)
     N, wa = d.B, int(bool(want_alpha))
-    nbytes = C.c_size_t()
-    call("scnattn_rollout_workspace", C.byref(d), K, max_steps, wa, C.byref(nbytes))
-    off = (C.c_long * _lib.ROLLOUT_NOFF)()
-    call("scnattn_rollout_layout", C.byref(d), K, max_steps, wa, off)
-    nwords = nbytes.value // 4
-    ws = torch.empty(nwords + guard, device=dev, dtype=torch.float32)      # scnattn_rollout_init zero-fills what needs it
+    ws, off, nwords, t = _run_on_device("scnattn_rollout_%s", (C.byref(d), K, max_steps, wa), _lib.ROLLOUT_NOFF,
+                                        (C.byref(w), ptr(enc), ptr(tags), int(start)),
+                                        (C.byref(w), ptr(enc), int(end), inv_temp, int(seed), int(draw),
+                                         int(bool(greedy_first))), stream_of(enc), dev, max_steps, chunk, guard)
     wsi = ws.view(torch.int32)
-    if guard:
-        wsi[nwords:].fill_(0x7FC5A5A5)
-    st = stream_of(enc)
-    call("scnattn_rollout_init", st, C.byref(d), K, max_steps, wa, C.byref(w), ptr(enc), ptr(tags), int(start), ptr(ws))
-    t = 0
-    while t < max_steps:
-        n = min(chunk, max_steps - t)
-        call("scnattn_rollout_steps", st, C.byref(d), K, max_steps, wa, C.byref(w), ptr(enc), int(end), inv_temp, int(seed),
-             int(draw), int(bool(greedy_first)), t, n, ptr(ws))
-        t += n
-        if int(wsi[off[0]]) == 0:       # the one 4-byte copy (and sync) per chunk
-            break
     R = N * K
     sizes = {"open_rows": 1, "nsrc": N, "nopen": N, "length": R, "sum_logp": R, "token": t * R, "logp": t * R,
              "alpha": t * R * d.P}

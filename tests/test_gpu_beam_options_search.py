@@ -161,6 +161,43 @@ def test_history_is_the_parent_chain_and_the_guard_is_intact(dev, kind, seed):
                 assert len(grams) == len(set(grams)) and V - 1 not in words
 
 
+def test_chunking_does_not_change_a_search_with_options(dev):
+    """no_repeat_ngram = 2, min_length = 3 with chunk = 1 and with chunk = max_steps, for the single decoder and for a
+    two-member ensemble: every entry of the two result dicts EQUAL, the history included.  Which of the two history buffers
+    a step reads depends on t alone, so a step loop that counted from its chunk's start would differ here.
+    The fixtures are the smallest of BR.FIXTURES (4 images, 3x3 pixels, E = 32, V = 23; the attention and the tags-only
+    decoder share these shapes, so they also make the ensemble).  V = 23 bounds max_steps by the candidate rule
+    (23 - 1 - 16 >= 3), and <end> is biased away so that every beam is open at every step: both runs then execute the same
+    16 steps -- a chunk of 1 would otherwise stop at the first look after the last image closed, which the other run never
+    takes -- and every row's history is a live one."""
+    from models.decoders import SearchOptions, _common
+    from scnattn import functional as SF
+    from test_gpu_parity import _build_decoder
+    k, T, o = 3, 16, SearchOptions(no_repeat_ngram=2, min_length=3)
+    ops, V = [], None
+    for name, kind in (BR.FIXTURES[1], BR.FIXTURES[2]):
+        d, V = BR.sharpened(name)
+        d["p.fc.bias"] = d["p.fc.bias"].copy()
+        d["p.fc.bias"][V - 1] -= 30.0
+        m = _build_decoder(kind, d, dev).eval()
+        ops.append(_common._search_operands(m, V, t(d["enc"]).to(dev), t(d["tags"]).to(dev), kind != "pure_scn", True))
+    (dims, weights, enc, tags), _ = ops
+
+    def single(chunk):
+        return SF.beam_search_run(dims, k, weights, enc, tags, V - 2, V - 1, max_steps=T, chunk=chunk, options=o)
+
+    def pair(chunk):
+        return SF.ensemble_search_run([x[0] for x in ops], k, [x[1] for x in ops], enc, [x[3] for x in ops], (0.6, 0.4),
+                                      "prob", V - 2, V - 1, 0, max_steps=T, chunk=chunk, options=o)
+
+    for run in (single, pair):
+        (one, steps1), (whole, steps) = run(1), run(T)
+        assert steps1 == steps == T and int(whole["open_images"]) == enc.shape[0]
+        assert sorted(one) == sorted(whole) and whole["history"].shape == (enc.shape[0] * k, T)
+        for key in whole:
+            assert torch.equal(one[key], whole[key]), (run.__name__, key)
+
+
 # ---- (d) the ensemble -----------------------------------------------------------------------------------------------------
 def _ensemble(dev, members, **kw):
     from models.decoders import DecoderEnsemble
