@@ -26,6 +26,8 @@ extern "C" {
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
+                               + truncated sampling: top-k / nucleus rollouts (scnattn_sample_filter, scnattn_rollout_*_f; new symbols only,
+                               the version stays);
                                + search options: n-gram blocking, minimum length, banned tokens (scnattn_search_options, scnattn_beam_*_opt,
                                scnattn_ensemble_*_opt; new symbols only, the version stays);
                                + ensemble beam search (scnattn_ensemble_*, scnattn_beam_row_topk_ens; new symbols only, the version stays);
@@ -328,6 +330,64 @@ int scnattn_rollout_pick(void* stream, int N, int K, int V, const float* logits,
                          uint32_t draw, int t, int greedy_first, int end_token, int max_steps, void* const* state);
 int scnattn_rollout_advance(void* stream, int N, int K, int M, int V, const int32_t* token_t, const float* table, float* emb,
                             const int32_t* nopen, int32_t* nsrc);
+/* ---- TRUNCATED sampling: top-k and nucleus (top-p) rollouts (csrc/rollout.hip: rollout_pick_filtered) ------
+ * The reference has none of this; the semantics are this library's.  For an open row at step t, with y_v =
+ * fl(logits[row][v] * inv_temp) (the fp32 number _pick forms) and the ORDER of the project (y descending, index ascending,
+ * compared as fp32 numbers, so -0 == +0):
+ *   THE FILTER   top_k >= 0 (0 or >= V: off), 0 < top_p <= 1 (1: off).  Anything else, NaN included, is refused (-1) before
+ *                any launch.
+ *   THE KEPT SET the first nkeep = min(L_k, L_p) words of the ORDER, where
+ *                  L_k = top_k when 1 <= top_k < V, else V
+ *                  L_p = the smallest L >= 1 with sum_{i<L} e_(i) >= top_p * sum_all e      ((i): along the ORDER)
+ *                  e_v = expf(fl(y_v - m)), m = max y; a -inf logit has e_v = 0 exactly and sorts last
+ *                top_p == 1 gives L_p = V without computing anything.  Both limits are measured on the FULL distribution
+ *                (top-p is not re-applied to a renormalised top-k), and ties at the cut are broken by index.
+ *                WHERE fp64 BEGINS: the terms e_v are fp32 (one fp32 subtraction, one expf); every sum of them, the product
+ *                top_p * sum_all (top_p widened exactly), and the comparison are fp64.  The sums are taken in one fixed order
+ *                that does not follow the ORDER (thread i of 256 adds its groups of four words q = i, i + 256, ..., words
+ *                4q .. 4q + 3; lanes, then waves, are added in a fixed tree); among the words EQUAL to the value at the cut, which all carry the same e, the mass of
+ *                the first j is A + j * e in fp64 (A: the fp64 mass of the words above that value).  An fp64 sum of at most
+ *                2^20 fp32 terms is exact to 2^-32 relative, so the choice of order is invisible next to the terms' own error.
+ *   THE DRAW     token = the first key in the ORDER among the kept words, key_v = y_v + noisy_j * g_v with exactly the noise
+ *                of _pick (counter (v >> 2, row, t, draw)): the noise of word v does not depend on the filter, (seed, draw)
+ *                repeats a rollout, and the Gumbel arg-max over the kept set is a draw from the truncated, renormalised
+ *                softmax.  The arg-max slot (greedy_first, slot 0) picks the first word of the ORDER, inside every kept set.
+ *   logp         = y_token - (m + log(sum_kept e)): the log-probability under the distribution that was sampled.
+ *                WHERE fp64 ENDS: sum_kept (fp64 sum of the fp32 terms), its log, m + log(.) and the difference from y_token
+ *                are fp64 (y_token and m widened exactly); the difference is rounded ONCE to fp32 and is the record.
+ *                sum_logp accumulates the fp32 records in fp32, as _pick does.  top_k == 1 gives logp = +0.0 exactly.
+ *   nkeep        a NEW RECORD int[max_steps][N*K]: nkeep of every open row and step; 0 for the records of a closed row of an
+ *                open image (as token and logp get 0).
+ *   DETERMINISM  the same inputs give the same bits from run to run and for any chunking of the steps: the reductions have a
+ *                fixed order and no floating-point atomics.
+ * Closed images, closed rows, <end> book-keeping, cut-off rows and the read-only nsrc are exactly those of _pick.  A row that
+ * holds a NaN is OUTSIDE this contract (its nkeep, token and logp are unspecified); it still writes only its own records.
+ * FILTER OFF (both limits off): the bits of the plain entry points in every buffer they share -- the plain kernel is
+ * launched -- and nothing writes nkeep, which keeps the zeros _init_f put there.
+ *   _workspace_f / _layout_f / _init_f / _steps_f   the four calls with the filter after want_alpha; the same filter in all
+ *       four.  _layout_f writes SCNATTN_ROLLOUT_NOFF_F offsets: the 8 of scnattn_rollout_layout, then 8 nkeep
+ *       int[max_steps][N*K].  The launches per step are those of the plain rollout: the pick runs in its filtered form.
+ *   scnattn_rollout_pick_f   _pick with the filter; nkeep_t int[N*K] is the record of step t (refused when NULL while the
+ *       filter is on); force_passes != 0 re-reads the row from global memory in every pass even when it fits the
+ *       registers (the path of a V beyond 10240); both paths add the same numbers in the same order: the same bits. */
+#define SCNATTN_ROLLOUT_NOFF_F 9
+typedef struct {
+    int32_t top_k;
+    float top_p;
+} scnattn_sample_filter;
+int scnattn_rollout_workspace_f(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* filter,
+                                size_t* bytes);
+int scnattn_rollout_layout_f(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* filter,
+                             long* offsets);
+int scnattn_rollout_init_f(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha,
+                           const scnattn_sample_filter* filter, const scnattn_params* w, const float* enc, const float* tags,
+                           int start_token, float* ws);
+int scnattn_rollout_steps_f(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha,
+                            const scnattn_sample_filter* filter, const scnattn_params* w, const float* enc, int end_token,
+                            float inv_temp, uint64_t seed, uint32_t draw, int greedy_first, int t0, int n_steps, float* ws);
+int scnattn_rollout_pick_f(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, uint64_t seed,
+                           uint32_t draw, int t, int greedy_first, int end_token, int max_steps, void* const* state,
+                           const scnattn_sample_filter* filter, int32_t* nkeep_t, int force_passes);
 /* The kernels of a step (csrc/beam.hip), one launch each; nsrc int[N] on the device.
  *   _attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0 for j < nsrc[n] (other rows untouched)
  *   _attn_context  alpha_out [N*K][P], awe [N*K][E] (either may be NULL), z = sigmoid(gpre + gate_bias) * awe (gpre NULL: awe)

@@ -46,13 +46,16 @@ int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, 
 int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
                  int max_steps, const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token,
                  int t0, int n_steps, float* ws);
-int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
-int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off);
-int rollout_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
-                 const float* enc, const float* tags, int start_token, float* ws);
-int rollout_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
-                  const float* enc, int end_token, float inv_temp, unsigned long long seed, unsigned draw, int greedy_first,
-                  int t0, int n_steps, float* ws);
+// filtered: the _f form (f is then checked and the workspace holds the nkeep records); else f is ignored
+int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
+                      bool filtered, size_t* bytes);
+int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f, bool filtered,
+                   long* off);
+int rollout_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
+                 bool filtered, const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws);
+int rollout_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
+                  bool filtered, const scnattn_params* w, const float* enc, int end_token, float inv_temp,
+                  unsigned long long seed, unsigned draw, int greedy_first, int t0, int n_steps, float* ws);
 
 int pool_desc(const scnattn_pool* p, PoolDesc& out) {
     out = PoolDesc{0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -269,28 +272,61 @@ int scnattn_beam_advance_opt(void* stream, int N, int K, int D, int M, int V, in
 }
 
 int scnattn_rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
-    return rollout_workspace(d, K, max_steps, want_alpha, bytes);
+    return rollout_workspace(d, K, max_steps, want_alpha, nullptr, false, bytes);
 }
 int scnattn_rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* offsets) {
-    return rollout_layout(d, K, max_steps, want_alpha, offsets);
+    return rollout_layout(d, K, max_steps, want_alpha, nullptr, false, offsets);
 }
 int scnattn_rollout_init(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
                          const float* enc, const float* tags, int start_token, float* ws) {
-    return rollout_init(ST(stream), d, K, max_steps, want_alpha, w, enc, tags, start_token, ws);
+    return rollout_init(ST(stream), d, K, max_steps, want_alpha, nullptr, false, w, enc, tags, start_token, ws);
 }
 int scnattn_rollout_steps(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
                           const float* enc, int end_token, float inv_temp, uint64_t seed, uint32_t draw, int greedy_first,
                           int t0, int n_steps, float* ws) {
-    return rollout_steps(ST(stream), d, K, max_steps, want_alpha, w, enc, end_token, inv_temp, seed, draw, greedy_first, t0,
-                         n_steps, ws);
+    return rollout_steps(ST(stream), d, K, max_steps, want_alpha, nullptr, false, w, enc, end_token, inv_temp, seed, draw,
+                         greedy_first, t0, n_steps, ws);
+}
+int scnattn_rollout_workspace_f(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* filter,
+                                size_t* bytes) {
+    return rollout_workspace(d, K, max_steps, want_alpha, filter, true, bytes);
+}
+int scnattn_rollout_layout_f(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* filter,
+                             long* offsets) {
+    return rollout_layout(d, K, max_steps, want_alpha, filter, true, offsets);
+}
+int scnattn_rollout_init_f(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha,
+                           const scnattn_sample_filter* filter, const scnattn_params* w, const float* enc, const float* tags,
+                           int start_token, float* ws) {
+    return rollout_init(ST(stream), d, K, max_steps, want_alpha, filter, true, w, enc, tags, start_token, ws);
+}
+int scnattn_rollout_steps_f(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha,
+                            const scnattn_sample_filter* filter, const scnattn_params* w, const float* enc, int end_token,
+                            float inv_temp, uint64_t seed, uint32_t draw, int greedy_first, int t0, int n_steps, float* ws) {
+    return rollout_steps(ST(stream), d, K, max_steps, want_alpha, filter, true, w, enc, end_token, inv_temp, seed, draw,
+                         greedy_first, t0, n_steps, ws);
+}
+static int rollout_state_of(const char* who, int N, int K, int max_steps, void* const* state, RolloutState& s) {
+    if (!state) { set_error("%s: state is NULL", who); return -1; }
+    if (N <= 0 || K < 1 || K > SCN_MAX_BEAM) { set_error("%s: bad N / slot count", who); return -1; }
+    s = RolloutState{N * K, max_steps, (int*)state[0], (int*)state[1], (int*)state[2], (int*)state[3], (float*)state[4],
+                     (int*)state[5], (float*)state[6]};
+    return 0;
 }
 int scnattn_rollout_pick(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, uint64_t seed,
                          uint32_t draw, int t, int greedy_first, int end_token, int max_steps, void* const* state) {
-    if (!state) { set_error("scnattn_rollout_pick: state is NULL"); return -1; }
-    if (N <= 0 || K < 1 || K > SCN_MAX_BEAM) { set_error("scnattn_rollout_pick: bad N / slot count"); return -1; }
-    const RolloutState s{N * K, max_steps, (int*)state[0], (int*)state[1], (int*)state[2], (int*)state[3], (float*)state[4],
-                         (int*)state[5], (float*)state[6]};
+    RolloutState s;
+    SCN_TRY(rollout_state_of("scnattn_rollout_pick", N, K, max_steps, state, s));
     return rollout_pick(ST(stream), N, K, V, logits, ld, inv_temp, seed, draw, t, greedy_first, end_token, s);
+}
+int scnattn_rollout_pick_f(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, uint64_t seed,
+                           uint32_t draw, int t, int greedy_first, int end_token, int max_steps, void* const* state,
+                           const scnattn_sample_filter* filter, int32_t* nkeep_t, int force_passes) {
+    SCN_ARG(filter, "scnattn_rollout_pick_f: the sample filter is NULL");
+    RolloutState s;
+    SCN_TRY(rollout_state_of("scnattn_rollout_pick_f", N, K, max_steps, state, s));
+    return rollout_pick_filtered(ST(stream), N, K, V, logits, ld, inv_temp, seed, draw, t, greedy_first, end_token,
+                                 filter->top_k, filter->top_p, nkeep_t, force_passes, s);
 }
 int scnattn_rollout_advance(void* stream, int N, int K, int M, int V, const int32_t* token_t, const float* table, float* emb,
                             const int32_t* nopen, int32_t* nsrc) {

@@ -55,6 +55,7 @@ struct SearchWs {
 
 struct RolloutWs : StepWs {
     RolloutState s;
+    int* nkeep;             // [T][R] words kept by the sample filter (the _f form of the driver), else null
 };
 
 inline int* ints(float* p) { return reinterpret_cast<int*>(p); }
@@ -356,7 +357,8 @@ int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member,
 // attention, 8-9 without).  fp32 only.
 namespace {
 
-size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, float* base, RolloutWs& b) {
+// filtered: the _f form of the four calls, whose workspace also holds the nkeep records (behind alpha, zero-filled by init)
+size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, bool filtered, float* base, RolloutWs& b) {
     Carver c(base);
     const int N = d.B, P = d.P;
     const long R = (long)N * K;
@@ -370,54 +372,71 @@ size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, float*
     b.s.token = ints(c.take(sz(T, R)));
     b.s.logp = c.take(sz(T, R));
     b.alpha = (d.has_att && want_alpha) ? c.take(sz(T, R, P)) : nullptr;
+    b.nkeep = filtered ? ints(c.take(sz(T, R))) : nullptr;
     carve_step_state(c, d, R, b);
     b.state_floats = c.off;
     carve_step_setup(c, d, R, b);
     return c.off * sizeof(float);
 }
 
+// f: the filter of the _f form (null: the plain form), refused when out of range
+int check_filter(const scnattn_sample_filter* f, bool given) {
+    if (!given) return 0;
+    SCN_ARG(f, "rollout: the sample filter is NULL");
+    SCN_ARG(rollout_filter_ok(f->top_k, f->top_p), "rollout: the sample filter needs top_k >= 0 and 0 < top_p <= 1");
+    return 0;
+}
+
 }  // namespace
 
-int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
+int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
+                      bool filtered, size_t* bytes) {
     SCN_TRY(check_beam(d, K, max_steps));
+    SCN_TRY(check_filter(f, filtered));
     SCN_ARG(bytes, "rollout_workspace: bytes is NULL");
     RolloutWs b;
-    *bytes = carve_rollout(*d, K, max_steps, want_alpha, nullptr, b);
+    *bytes = carve_rollout(*d, K, max_steps, want_alpha, filtered, nullptr, b);
     return 0;
 }
 
-// off[SCNATTN_ROLLOUT_NOFF]: where the results live in the workspace, in 4-byte elements (order: include/scnattn.h)
-int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off) {
+// off[SCNATTN_ROLLOUT_NOFF]: where the results live in the workspace, in 4-byte elements (order: include/scnattn.h); the _f
+// form off[SCNATTN_ROLLOUT_NOFF_F], the nkeep records' offset behind them
+int rollout_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f, bool filtered,
+                   long* off) {
     SCN_TRY(check_beam(d, K, max_steps));
+    SCN_TRY(check_filter(f, filtered));
     SCN_ARG(off, "rollout_layout: offsets is NULL");
     RolloutWs b;
-    carve_rollout(*d, K, max_steps, want_alpha, layout_base(), b);
-    const void* p[SCNATTN_ROLLOUT_NOFF] = {b.s.open_rows, b.s.nsrc, b.s.nopen, b.s.length, b.s.sum_logp, b.s.token, b.s.logp,
-                                           b.alpha};
-    offsets_from(layout_base(), p, SCNATTN_ROLLOUT_NOFF, off);
+    carve_rollout(*d, K, max_steps, want_alpha, filtered, layout_base(), b);
+    const void* p[SCNATTN_ROLLOUT_NOFF_F] = {b.s.open_rows, b.s.nsrc, b.s.nopen, b.s.length, b.s.sum_logp, b.s.token, b.s.logp,
+                                             b.alpha, b.nkeep};
+    offsets_from(layout_base(), p, filtered ? SCNATTN_ROLLOUT_NOFF_F : SCNATTN_ROLLOUT_NOFF, off);
     return 0;
 }
 
-int rollout_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
-                 const float* enc, const float* tags, int start_token, float* ws) {
+int rollout_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
+                 bool filtered, const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws) {
     SCN_TRY(check_beam(dp, K, max_steps));
+    SCN_TRY(check_filter(f, filtered));
     const scnattn_dims& d = *dp;
     SCN_ARG(w && enc && tags && ws, "rollout_init: null argument");
     SCN_ARG(start_token >= 0 && start_token < d.V, "rollout_init: start token outside the vocabulary");
     SCN_ARG(aligned16(ws), "rollout_init: the workspace must be 16-byte aligned");
     RolloutWs b;
-    carve_rollout(d, K, max_steps, want_alpha, ws, b);
+    carve_rollout(d, K, max_steps, want_alpha, filtered, ws, b);
     SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));      // the records of closed rows: <pad> / 0.0
     SCN_TRY(rollout_state_init(st, d.B, K, b.s));
     SCN_TRY(decode_setup(st, d, K, w, enc, tags, start_token, b));
     return 0;
 }
 
-// Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.
-int rollout_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
-                  const float* enc, int end_token, float inv_temp, unsigned long long seed, unsigned draw, int greedy_first,
-                  int t0, int n_steps, float* ws) {
+// Steps t0 .. t0 + n_steps - 1 (0-based; clipped to max_steps).  A finished image's kernels are no-ops.  The _f form swaps
+// the pick for the filtered one: the same launches per step.
+int rollout_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
+                  bool filtered, const scnattn_params* w, const float* enc, int end_token, float inv_temp,
+                  unsigned long long seed, unsigned draw, int greedy_first, int t0, int n_steps, float* ws) {
     SCN_TRY(check_beam(dp, K, max_steps));
+    SCN_TRY(check_filter(f, filtered));
     const scnattn_dims& d = *dp;
     SCN_ARG(w && enc && ws, "rollout_steps: null argument");
     SCN_ARG(t0 >= 0 && n_steps >= 0, "rollout_steps: negative step");
@@ -425,13 +444,17 @@ int rollout_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, 
     SCN_ARG(end_token >= 0 && end_token < d.V, "rollout_steps: end token outside the vocabulary");
     const int N = d.B, P = d.P, M = d.M, V = d.V, R = N * K;
     RolloutWs b;
-    carve_rollout(d, K, max_steps, want_alpha, ws, b);
+    carve_rollout(d, K, max_steps, want_alpha, filtered, ws, b);
     const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
     for (int t = t0; t < t1; ++t) {
         const bool even = (t & 1) == 0;         // the state of step t sits in A for even t, in B for odd t
         SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, b.alpha ? b.alpha + (long)t * R * P : nullptr, even ? b.hA : b.hB,
                             even ? b.cA : b.cB, even ? b.hB : b.hA, even ? b.cB : b.cA));
-        SCN_TRY(rollout_pick(st, N, K, V, b.logits, V, inv_temp, seed, draw, t, greedy_first, end_token, b.s));
+        if (filtered)
+            SCN_TRY(rollout_pick_filtered(st, N, K, V, b.logits, V, inv_temp, seed, draw, t, greedy_first, end_token, f->top_k,
+                                          f->top_p, b.nkeep + (long)t * R, 0, b.s));
+        else
+            SCN_TRY(rollout_pick(st, N, K, V, b.logits, V, inv_temp, seed, draw, t, greedy_first, end_token, b.s));
         SCN_TRY(rollout_advance(st, N, K, M, V, b.s.token + (long)t * R, w->embedding_weight, b.emb, b.s.nopen, b.s.nsrc));
     }
     return 0;

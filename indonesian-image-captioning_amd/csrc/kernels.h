@@ -211,6 +211,15 @@ struct RolloutState {
 // (v >> 2, row, t, draw)); slot 0 of every image takes the plain arg-max when greedy_first != 0.  Contract: rollout.hip.
 int rollout_pick(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp, unsigned long long seed,
                  unsigned draw, int t, int greedy_first, int end_tok, const RolloutState& s);
+// The same pick inside the top-k / nucleus set of the row (include/scnattn.h: scnattn_sample_filter): the first
+// nkeep = min(L_k, L_p) words of the order (y descending, index ascending), logp under the renormalised kept set, and the
+// record nkeep_t[row] (0 for a closed row of an open image).  top_k 0 or >= V and top_p 1 mean off; both off launches
+// rollout_pick's kernel and leaves nkeep_t alone (it may then be null).  force_passes != 0 (tests): re-read the row from
+// global memory in every pass even when it fits the registers (V <= 10240).
+bool rollout_filter_ok(int top_k, float top_p);
+int rollout_pick_filtered(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp,
+                          unsigned long long seed, unsigned draw, int t, int greedy_first, int end_tok, int top_k, float top_p,
+                          int* nkeep_t, int force_passes, const RolloutState& s);
 // emb[row] = table[clamp(token_t[row])]; nsrc[n] = nopen[n] > 0 ? K : 0
 int rollout_advance(hipStream_t st, int N, int K, int M, int V, const int* token_t, const float* table, float* emb,
                     const int* nopen, int* nsrc);

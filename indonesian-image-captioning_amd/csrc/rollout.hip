@@ -16,6 +16,8 @@
 //                    A row of an image with nsrc[n] == 0 is neither read nor written; a closed row of an open image only
 //                    gets the records token = 0 (<pad>), logp = 0.0.  nsrc is read-only here, so no workgroup depends on
 //                    what another one does in the same launch.
+//   rollout_pick_filtered  the same pick inside the top-k / nucleus set of the row (further down): the cut by
+//                    bisection on the order-preserving integer image of y, counts and fp64 masses, then one keyed pass.
 //   rollout_advance  the next input embedding of every row (the token record clamped into the table) and, per image,
 //                    nsrc[n] = nopen[n] > 0 ? K : 0 for the attention kernels of the next step.
 // The arg-max slot skips the noise: key_v = y_v exactly.  Plain vector loads and stores; no kernel waits for another
@@ -159,6 +161,262 @@ __global__ __launch_bounds__(256) void rollout_state_init_kernel(int N, int K, R
     if (i == 0) s.open_rows[0] = s.R;
 }
 
+// ---- the filtered pick (top-k / nucleus; the contract: include/scnattn.h) ---------------------------------
+// The kept set is a prefix of the ORDER (y descending, index ascending), so it is described by two numbers: the image T of
+// the value at the cut and the index I of the last kept word among those equal to it.  With img() the order-preserving
+// unsigned image of y (-0 taken as +0), C(T) = #{v: img_v >= T} and A(T) = sum of e_v over the same words (fp64),
+//      enough(T) = C(T) >= L_k  or  A(T) >= top_p * A(0)
+// is monotone in T (an fp64 sum in a fixed order only grows when non-negative terms are inserted), so the largest T that
+// is enough is found bit by bit, 32 workgroup reductions, without sorting the row.  The words above T are then too few and
+// too light; those equal to T all carry the same e_T, and are taken in index order: j, the smallest count with
+// A_gt + j * e_T >= top_p * A(0), and the index of the (nkeep - C_gt)-th of them by bisection on the index.
+// EVERY sum is the same reduction: thread i adds its words (the groups of four q = i, i + 256, ..., words 4q .. 4q + 3) in
+// that order, a wave adds its lanes as a butterfly (all lanes end with the same bits), and the four waves are added
+// 0, 1, 2, 3.  No atomics on floating point.  A row of up to 10240 words stays in registers between the passes (as images
+// and terms: 80 registers per thread at V = 10000, where a copy in LDS cost a latency-bound loop per pass and four times
+// the time); LDS holds the reductions only.  Longer rows are re-read from global memory in every pass.
+__device__ __forceinline__ unsigned img_of(float y) {
+    const unsigned u = __float_as_uint(y == 0.f ? 0.f : y);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float y_of(unsigned img) {
+    return __uint_as_float((img & 0x80000000u) ? (img ^ 0x80000000u) : ~img);
+}
+
+struct Tally {
+    int a, b;           // two counts
+    double s;           // one mass
+};
+// red: 4 Tally of LDS.  Every thread returns the workgroup's total (the same bits in all of them).
+__device__ __forceinline__ Tally tally_all(Tally x, Tally* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        x.a += __shfl_xor(x.a, o, 64);
+        x.b += __shfl_xor(x.b, o, 64);
+        x.s += __shfl_xor(x.s, o, 64);
+    }
+    __syncthreads();                            // the previous round's readers are done with red
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    Tally r = red[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) { r.a += red[w].a; r.b += red[w].b; r.s += red[w].s; }
+    return r;
+}
+
+// NPT4 > 0: the row is HELD IN REGISTERS for all passes, NPT4 groups of four words per thread (thread i owns the groups
+// q = i, i + 256, ...: the words 4q .. 4q + 3, the group that shares one Philox call), as the image of y and the term e.
+// NPT4 == 0: every pass re-reads the logits from global memory and forms y and e again (one fp32 product, one expf: the same
+// bits every time), in the same ownership, so both forms add the same numbers in the same order.
+template <int NPT4, bool VEC>
+__global__ __launch_bounds__(256) void rollout_pick_filtered_kernel(int K, int V, const float* __restrict__ logits, long ld,
+                                                                    float inv_temp, unsigned k0, unsigned k1, unsigned draw,
+                                                                    int t, int greedy_first, int end_tok, int Lk, float top_p,
+                                                                    int* __restrict__ nkeep_t, RolloutState s) {
+    const int r = blockIdx.x, n = r / K, j = r - n * K;
+    if (s.nsrc[n] <= 0) return;                 // a closed image: uniform over the workgroup
+    int* token_t = s.token + (long)t * s.R;
+    float* logp_t = s.logp + (long)t * s.R;
+    if (s.length[r] != 0) {                     // a closed row of an open image
+        if (threadIdx.x == 0) { token_t[r] = 0; logp_t[r] = 0.f; nkeep_t[r] = 0; }
+        return;
+    }
+    __shared__ Tally red[4];
+    __shared__ unsigned redu[4];
+    __shared__ float sy[4];
+    const float* x = logits + (long)r * ld;
+    const int tid = threadIdx.x;
+    const bool use_p = top_p < 1.f;
+    const int groups = (V + 3) >> 2;
+    constexpr int NR = NPT4 > 0 ? NPT4 * 4 : 1;
+    unsigned ir[NR];                            // images; 0 for a slot beyond V (below every real number's image)
+    float er[NR];
+
+    // the maximum (as an image: exact, any order), and the row into registers
+    unsigned mx = 0u;
+    if constexpr (NPT4 > 0) {
+#pragma unroll
+        for (int g = 0; g < NPT4; ++g) {
+            const int v0 = (tid + 256 * g) * 4;
+            float y4[4] = {0.f, 0.f, 0.f, 0.f};
+            if (VEC && v0 + 3 < V) {
+                const f32x4 l = ld4(x + v0);
+                y4[0] = l[0]; y4[1] = l[1]; y4[2] = l[2]; y4[3] = l[3];
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (v0 + c < V) y4[c] = x[v0 + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                ir[4 * g + c] = v0 + c < V ? img_of(y4[c] * inv_temp) : 0u;
+                mx = max(mx, ir[4 * g + c]);
+            }
+        }
+    } else {
+        for (int q = tid; q < groups; q += 256)
+            for (int v = 4 * q; v < min(4 * q + 4, V); ++v) mx = max(mx, img_of(x[v] * inv_temp));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+    if ((tid & 63) == 0) redu[tid >> 6] = mx;
+    __syncthreads();
+    mx = max(max(redu[0], redu[1]), max(redu[2], redu[3]));
+    const float m = y_of(mx);
+
+    // e_v = expf(fl(y_v - m)), 0 for y_v = -inf
+    auto e_of = [&](float y) { return y == -INFINITY ? 0.f : expf(y - m); };
+    if constexpr (NPT4 > 0) {
+#pragma unroll
+        for (int i = 0; i < NR; ++i) er[i] = use_p && ir[i] != 0u ? e_of(y_of(ir[i])) : 0.f;
+    }
+    // f(v, image, e) for every word of this thread, in its fixed order
+    auto each = [&](auto f) {
+        if constexpr (NPT4 > 0) {
+#pragma unroll
+            for (int i = 0; i < NR; ++i) f((tid + 256 * (i >> 2)) * 4 + (i & 3), ir[i], er[i]);
+        } else {
+            for (int q = tid; q < groups; q += 256)
+                for (int v = 4 * q; v < min(4 * q + 4, V); ++v) {
+                    const float y = x[v] * inv_temp;
+                    f(v, img_of(y), use_p ? e_of(y) : 0.f);
+                }
+        }
+    };
+    // the tally of the words whose image is >= T
+    auto tally_ge = [&](unsigned T) {
+        Tally a = {0, 0, 0.0};
+        each([&](int v, unsigned im, float e) {
+            if (im >= T && v < V) {
+                a.a += 1;
+                a.s += (double)e;
+            }
+        });
+        return tally_all(a, red);
+    };
+    double need = 0.0;                          // top_p * the whole mass, in fp64
+    if (use_p) need = (double)top_p * tally_ge(0u).s;
+    unsigned T = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = T | (1u << bit);
+        if (cand > mx) continue;                // nothing up there: not enough (uniform)
+        const Tally c = tally_ge(cand);
+        if (c.a >= Lk || (use_p && c.s >= need)) T = cand;
+    }
+    // above the cut value (too few, too light) and equal to it
+    Tally g = {0, 0, 0.0};
+    each([&](int v, unsigned im, float e) {
+        if (v < V) {
+            if (im > T) {
+                g.a += 1;
+                g.s += (double)e;
+            } else if (im == T) {
+                g.b += 1;
+            }
+        }
+    });
+    g = tally_all(g, red);
+    const int c_gt = g.a, n_tie = g.b;
+    int jp = n_tie;
+    if (use_p) {
+        const double eT = (double)e_of(y_of(T));
+        const double q = (need - g.s) / eT;
+        jp = q >= (double)n_tie ? n_tie : (q >= 1.0 ? (int)ceil(q) : 1);      // NaN: 1
+        for (int i = 0; i < 4 && jp > 1 && g.s + (double)(jp - 1) * eT >= need; ++i) --jp;
+        for (int i = 0; i < 4 && jp < n_tie && g.s + (double)jp * eT < need; ++i) ++jp;
+    }
+    int nkeep = min(Lk, c_gt + jp);
+    nkeep = max(nkeep, min(c_gt + 1, V));       // never empty (a row with a NaN can confuse the counts; it stays in bounds)
+    const int c = nkeep - c_gt;                 // how many of the words equal to the cut value are kept: the first c
+    int last = V - 1;                           // the index of the c-th of them
+    if (c < n_tie) {
+        int lo = 0, hi = V - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            Tally a = {0, 0, 0.0};
+            each([&](int v, unsigned im, float) { a.a += im == T && v <= mid; });
+            a = tally_all(a, red);
+            if (a.a >= c) hi = mid; else lo = mid + 1;
+        }
+        last = lo;
+    }
+
+    // one pass over the kept words: the first key in the order and the kept mass
+    const bool noisy = !(greedy_first && j == 0);
+    float bk = -INFINITY, by = 0.f;
+    int bi = INT_MAX;
+    double sk = 0.0;
+    auto group = [&](int q, const unsigned* im4) {
+        const int v0 = q * 4;
+        bool keep[4], any = false;
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            const int v = v0 + cc;
+            keep[cc] = v < V && (im4[cc] > T || (im4[cc] == T && v <= last));
+            any |= keep[cc];
+        }
+        if (!any) return;
+        u32q b = {{0u, 0u, 0u, 0u}};
+        if (noisy) b = philox4x32_10((unsigned)q, (unsigned)r, (unsigned)t, draw, k0, k1);
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            if (keep[cc]) {
+                const float y = y_of(im4[cc]);
+                const float key = noisy ? y + gumbel(b.w[cc]) : y;
+                sk += (double)e_of(y);
+                if (key > bk || (key == bk && v0 + cc < bi)) { bk = key; by = y; bi = v0 + cc; }
+            }
+        }
+    };
+    if constexpr (NPT4 > 0) {
+#pragma unroll
+        for (int gq = 0; gq < NPT4; ++gq) group(tid + 256 * gq, ir + 4 * gq);
+    } else {
+        for (int q = tid; q < groups; q += 256) {
+            unsigned im4[4];
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) im4[cc] = 4 * q + cc < V ? img_of(x[4 * q + cc] * inv_temp) : 0u;
+            group(q, im4);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float bk2 = __shfl_xor(bk, o, 64), by2 = __shfl_xor(by, o, 64);
+        const int bi2 = __shfl_xor(bi, o, 64);
+        sk += __shfl_xor(sk, o, 64);
+        if (bk2 > bk || (bk2 == bk && bi2 < bi)) { bk = bk2; by = by2; bi = bi2; }
+    }
+    __syncthreads();                            // the last tally's readers are done with red
+    const int w = tid >> 6;
+    if ((tid & 63) == 0) {
+        red[w] = Tally{bi, __float_as_int(bk), sk};
+        sy[w] = by;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    bi = red[0].a; bk = __int_as_float(red[0].b); by = sy[0]; sk = red[0].s;
+#pragma unroll
+    for (int ww = 1; ww < 4; ++ww) {
+        const float bk2 = __int_as_float(red[ww].b);
+        const int bi2 = red[ww].a;
+        sk += red[ww].s;
+        if (bk2 > bk || (bk2 == bk && bi2 < bi)) { bk = bk2; by = sy[ww]; bi = bi2; }
+    }
+    const bool found = bi < V;                  // no first element (NaN): <pad>, and its logp is NaN
+    const int tok = found ? bi : 0;
+    // fp64 from the kept mass to the difference; ONE rounding to fp32
+    const float lp = found ? (float)((double)by - ((double)m + log(sk))) : __builtin_nanf("");
+    token_t[r] = tok;
+    logp_t[r] = lp;
+    nkeep_t[r] = nkeep;
+    s.sum_logp[r] += lp;
+    if (tok == end_tok) {
+        s.length[r] = t + 1;
+        atomicAdd(s.nopen + n, -1);
+        atomicAdd(s.open_rows, -1);
+    }
+}
+
 bool state_ok(const RolloutState& s, int N, int K) {
     return s.R == N * K && s.T >= 1 && s.open_rows && s.nsrc && s.nopen && s.length && s.sum_logp && s.token && s.logp;
 }
@@ -181,6 +439,45 @@ int rollout_pick(hipStream_t st, int N, int K, int V, const float* logits, long 
     else
         hipLaunchKernelGGL(rollout_pick_kernel<false>, dim3(N * K), dim3(256), 0, st, K, V, logits, ld, inv_temp, k0, k1, draw, t,
                            greedy_first, end_tok, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+bool rollout_filter_ok(int top_k, float top_p) { return top_k >= 0 && top_p > 0.f && top_p <= 1.f; }      // NaN: refused
+
+int rollout_pick_filtered(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp,
+                          unsigned long long seed, unsigned draw, int t, int greedy_first, int end_tok, int top_k, float top_p,
+                          int* nkeep_t, int force_passes, const RolloutState& s) {
+    SCN_ARG(rollout_filter_ok(top_k, top_p), "rollout_pick_filtered: need top_k >= 0 and 0 < top_p <= 1");
+    const bool k_on = top_k >= 1 && top_k < V, p_on = top_p < 1.f;
+    if (!k_on && !p_on)                         // the filter is off: the plain kernel and its bits; nkeep is not written
+        return rollout_pick(st, N, K, V, logits, ld, inv_temp, seed, draw, t, greedy_first, end_tok, s);
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= 1 && t >= 0, "rollout_pick_filtered: bad slot count / vocab_size / step");
+    SCN_ARG((long)N * K <= (1L << 20), "rollout_pick_filtered: too many rows (images x slots)");
+    SCN_ARG(inv_temp > 0.f && inv_temp < INFINITY, "rollout_pick_filtered: inv_temp must be positive and finite");
+    SCN_ARG(logits && ld >= V && state_ok(s, N, K), "rollout_pick_filtered: bad argument");
+    SCN_ARG(t < s.T, "rollout_pick_filtered: step beyond the records");
+    SCN_ARG(nkeep_t, "rollout_pick_filtered: the nkeep record is NULL");
+    const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(seed >> 32);
+    const bool vec = aligned16(logits) && ld % 4 == 0;
+    const int Lk = k_on ? top_k : V;
+    // a row of up to 10240 words (40 per thread) is held in registers, in the smallest of three sizes that takes it; a
+    // longer one (or force_passes) is re-read from global memory in every pass
+    const int groups = (V + 3) / 4, npt4 = force_passes || groups > 10 * 256 ? 0 : (groups + 255) / 256;
+    dim3 grid(N * K), block(256);
+#define L(NPT4)                                                                                                               \
+    do {                                                                                                                      \
+        if (vec) hipLaunchKernelGGL((rollout_pick_filtered_kernel<NPT4, true>), grid, block, 0, st, K, V, logits, ld, inv_temp, \
+                                    k0, k1, draw, t, greedy_first, end_tok, Lk, top_p, nkeep_t, s);                           \
+        else hipLaunchKernelGGL((rollout_pick_filtered_kernel<NPT4, false>), grid, block, 0, st, K, V, logits, ld, inv_temp,   \
+                                k0, k1, draw, t, greedy_first, end_tok, Lk, top_p, nkeep_t, s);                               \
+    } while (0)
+    if (npt4 == 0) L(0);
+    else if (npt4 <= 1) L(1);
+    else if (npt4 <= 3) L(3);
+    else L(10);
+#undef L
     SCN_LAUNCH_CHECK();
     return 0;
 }

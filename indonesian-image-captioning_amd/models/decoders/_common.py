@@ -291,8 +291,9 @@ def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=F
     return out
 
 
-def check_rollout_args(samples, temperature, greedy_first=False, who="rollout_batch"):
-    """The host-side refusals of a rollout: K = samples (+ 1 with greedy_first) slots per image in [1, 8], temperature > 0"""
+def check_rollout_args(samples, temperature, greedy_first=False, who="rollout_batch", top_k=0, top_p=1.0):
+    """The host-side refusals of a rollout: K = samples (+ 1 with greedy_first) slots per image in [1, 8], temperature > 0,
+    and the sample filter's: top_k an integer >= 0 (0: off), top_p in (0, 1] (1: off), NaN refused"""
     from scnattn import _lib
     samples = int(samples)
     K = samples + (1 if greedy_first else 0)
@@ -302,29 +303,33 @@ def check_rollout_args(samples, temperature, greedy_first=False, who="rollout_ba
     temperature = float(temperature)
     if not (temperature > 0.0 and temperature < float("inf")):
         raise ValueError("%s: temperature must be positive and finite (got %r)" % (who, temperature))
+    SF.sample_filter_struct(top_k, top_p, who)
     return K
 
 
 def rollout_batched(decoder, word_map, encoder_out, tag_out, use_attention, use_tags, samples=1, seed=0, draw=0,
-                    temperature=1.0, greedy_first=False):
+                    temperature=1.0, greedy_first=False, top_k=0, top_p=1.0):
     """Sampled captions for N images, the whole rollout on the device (csrc/rollout.hip, SF.rollout_run): encoder_out
     (N, h, w, E), tag_out (N, S).  K = samples (+ 1 with greedy_first: slot 0 of every image is then the arg-max caption)
     slots per image, rows R = N*K ordered n*K + j.  Every token is a draw from softmax(logits / temperature); the noise
     is a pure function of (seed, draw, row, step, word), so the same (seed, draw) repeats the captions and the next
     `draw` gives fresh ones.  No dropout, like the search; fp32 only.
+    top_k / top_p: truncated sampling (SF.rollout_run) -- every token is drawn from the top_k most likely words and / or
+    the nucleus holding top_p of the mass, and sum_logp is the log-likelihood under that truncated, renormalised
+    distribution.  The defaults (0, 1.0) are the full softmax and the plain kernels.
     Returns (caps (R, L) int64, caplens (R, 1) int64, sum_logp (R,)) ON THE DEVICE, in the form ``decoder.forward`` takes
     captions: caps = <start>, tokens ..., <end>, <pad> ...; caplens counts <start> and <end>, so decode_lengths =
     caplens - 1 is the number of sampled tokens and sum_logp their log-likelihood at this temperature.  A row that
     produced no <end> within the step limit is CUT OFF there: its caption is <start> and all `steps` tokens without an
     <end>, caplens = steps + 1 (decode_lengths = steps).  L = steps + 1."""
-    K = check_rollout_args(samples, temperature, greedy_first)
+    K = check_rollout_args(samples, temperature, greedy_first, top_k=top_k, top_p=top_p)
     from scnattn import _lib
     _lib.require_cuda(encoder_out, tag_out)
     V = len(word_map)
     dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
     start, end, pad = word_map[start_token], word_map[end_token], word_map[padding_token]
     res, steps = SF.rollout_run(dims, K, weights, enc, tag_out, start, end, seed, draw, inv_temp=1.0 / float(temperature),
-                                greedy_first=greedy_first)
+                                greedy_first=greedy_first, top_k=top_k, top_p=top_p)
     length = res["length"].to(torch.int64)
     n_tok = torch.where(length > 0, length, torch.full_like(length, steps))      # a cut-off row keeps every step
     R = length.numel()

@@ -71,9 +71,11 @@ class PureSCN(nn.Module):
                                            use_tags=True, options=options)
 
     def rollout_batch(self, word_map, encoder_out, tags=None, samples=1, seed=0, draw=0, temperature=1.0,
-                      greedy_first=False):
+                      greedy_first=False, top_k=0, top_p=1.0):
         """Sampled captions for self-critical training: encoder_out (N, h, w, E), tags (N, S) -> (caps (N*K, L) int64, caplens
         (N*K, 1) int64, sum_logp (N*K,)) on the device, K = samples (+ 1 with greedy_first), rows n*K + j, in the form
-        ``forward`` takes captions (_common.rollout_batched: the noise contract and what a cut-off row looks like)."""
+        ``forward`` takes captions (_common.rollout_batched: the noise contract, what a cut-off row looks like, and
+        top_k / top_p: truncated sampling, sum_logp then being the truncated distribution's)."""
         return _common.rollout_batched(self, word_map, encoder_out, tags, use_attention=False, use_tags=True, samples=samples,
-                                       seed=seed, draw=draw, temperature=temperature, greedy_first=greedy_first)
+                                       seed=seed, draw=draw, temperature=temperature, greedy_first=greedy_first,
+                                       top_k=top_k, top_p=top_p)

@@ -88,6 +88,10 @@ class SearchOpts(C.Structure):     # scnattn_search_options
                 ("banned", C.c_int32 * MAX_BANNED)]
 
 
+class SampleFilter(C.Structure):   # scnattn_sample_filter
+    _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
+
+
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
@@ -138,6 +142,14 @@ _SIGS = {
     "scnattn_rollout_pick": ([vp, i32, i32, i32, vp, i64, f32, C.c_uint64, C.c_uint32, i32, i32, i32, i32,
                               C.POINTER(vp)], i32),
     "scnattn_rollout_advance": ([vp, i32, i32, i32, i32, vp, vp, vp, vp, vp], i32),
+    "scnattn_rollout_workspace_f": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(SampleFilter), C.POINTER(sz)], i32),
+    "scnattn_rollout_layout_f": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(SampleFilter), C.POINTER(i64)], i32),
+    "scnattn_rollout_init_f": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(SampleFilter), C.POINTER(Params), vp, vp, i32,
+                                vp], i32),
+    "scnattn_rollout_steps_f": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(SampleFilter), C.POINTER(Params), vp, i32, f32,
+                                 C.c_uint64, C.c_uint32, i32, i32, i32, vp], i32),
+    "scnattn_rollout_pick_f": ([vp, i32, i32, i32, vp, i64, f32, C.c_uint64, C.c_uint32, i32, i32, i32, i32, C.POINTER(vp),
+                                C.POINTER(SampleFilter), vp, i32], i32),
     "scnattn_sgemm": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64], i32),
     "scnattn_sgemm_ws": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64,
                           vp, i64], i32),
@@ -259,6 +271,7 @@ _SIGS = {
 BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
 BEAM_NOFF_OPT = 14  # SCNATTN_BEAM_NOFF_OPT
 ROLLOUT_NOFF = 8    # SCNATTN_ROLLOUT_NOFF
+ROLLOUT_NOFF_F = 9  # SCNATTN_ROLLOUT_NOFF_F
 MAX_BEAM = 8
 MAX_ENSEMBLE = 4    # SCNATTN_MAX_ENSEMBLE
 RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM

@@ -409,8 +409,30 @@ _ROLLOUT_RESULTS = ("open_rows", "nsrc", "nopen", "length", "sum_logp", "token",
 _ROLLOUT_FLOAT = ("sum_logp", "logp", "alpha")
 
 
+def sample_filter_struct(top_k, top_p, who="rollout_run"):
+    """(top_k, top_p) -> scnattn_sample_filter after the header's refusals (ValueError), or None when both limits are at
+    their defaults (0 and 1.0): the plain entry points.  top_k >= the vocabulary is off too, but that is the library's to
+    see: it launches the plain kernel."""
+    import math
+    import operator
+    try:
+        top_k = operator.index(top_k)
+    except TypeError:
+        raise ValueError("%s: top_k must be an integer >= 0 (0: off; got %r)" % (who, top_k)) from None
+    if not 0 <= top_k <= 2 ** 31 - 1:
+        raise ValueError("%s: top_k must be an integer >= 0 (0: off; got %r)" % (who, top_k))
+    top_p = float(top_p)
+    if math.isnan(top_p) or not (0.0 < top_p <= 1.0):
+        raise ValueError("%s: top_p must be in (0, 1] (1: off; got %r)" % (who, top_p))
+    if C.c_float(top_p).value <= 0.0:
+        raise ValueError("%s: top_p %r vanishes in fp32" % (who, top_p))
+    if top_k == 0 and top_p == 1.0:
+        return None
+    return _lib.SampleFilter(top_k=top_k, top_p=top_p)
+
+
 def rollout_run(dims, K, weights, enc, tags, start, end, seed, draw, inv_temp=1.0, greedy_first=False,
-                max_steps=BEAM_MAX_STEPS, want_alpha=False, guard=0, chunk=BEAM_CHUNK):
+                max_steps=BEAM_MAX_STEPS, want_alpha=False, guard=0, chunk=BEAM_CHUNK, top_k=0, top_p=1.0, force_filtered=False):
     """K captions per image sampled from the decoder on the device (csrc/rollout.hip; the analogue of beam_search_run):
     every step picks one token per open row from softmax(logits * inv_temp) by the Gumbel arg-max, the noise being
     Philox4x32-10 of (seed, draw, row, step, word) -- the same (seed, draw) gives the same captions, another `draw` fresh
@@ -424,7 +446,16 @@ def rollout_run(dims, K, weights, enc, tags, start, end, seed, draw, inv_temp=1.
         sum_logp (R,)             the sum of the row's logp
         alpha (steps, R, P)       only with want_alpha (and attention), else None
         open_rows, nsrc, nopen    the counters (scnattn_rollout_layout)
+        nkeep (R, steps) int32    only with a filter: the size of the kept set the token was drawn from, 0 after <end>;
+                                  None without
+    top_k / top_p: TRUNCATED sampling (include/scnattn.h: scnattn_sample_filter) -- every token is drawn from the top_k most
+    likely words and / or the smallest set holding top_p of the mass, both measured on the full softmax, and logp /
+    sum_logp are those of the truncated, renormalised distribution.  The noise of a word does not depend on the filter.
+    The defaults (0, 1.0) call the plain entry points; force_filtered (tests) calls the _f ones even then.
     guard > 0 (tests): that many sentinel words behind the workspace, returned as results["guard"]."""
+    filt = sample_filter_struct(top_k, top_p)
+    if filt is None and force_filtered:
+        filt = _lib.SampleFilter(top_k=0, top_p=1.0)
     K = int(K)
     if not 1 <= K <= _lib.MAX_BEAM:
         raise ValueError("rollout_run: K must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, K))
@@ -442,7 +473,9 @@ def rollout_run(dims, K, weights, enc, tags, start, end, seed, draw, inv_temp=1.
     weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
     w = _params_struct(weights)
     N, wa = d.B, int(bool(want_alpha))
-    ws, off, nwords, t = _run_on_device("scnattn_rollout_%s", (C.byref(d), K, max_steps, wa), _lib.ROLLOUT_NOFF,
+    sfx, fl = ("", ()) if filt is None else ("_f", (C.byref(filt),))       # the filter after want_alpha
+    ws, off, nwords, t = _run_on_device("scnattn_rollout_%s" + sfx, (C.byref(d), K, max_steps, wa, *fl),
+                                        _lib.ROLLOUT_NOFF if filt is None else _lib.ROLLOUT_NOFF_F,
                                         (C.byref(w), ptr(enc), ptr(tags), int(start)),
                                         (C.byref(w), ptr(enc), int(end), inv_temp, int(seed), int(draw),
                                          int(bool(greedy_first))), stream_of(enc), dev, max_steps, chunk, guard)
@@ -459,6 +492,7 @@ def rollout_run(dims, K, weights, enc, tags, start, end, seed, draw, inv_temp=1.
         out[name] = src[off[i]:off[i] + sizes[name]]
     out["tokens"] = out.pop("token").view(t, R).t()
     out["logp"] = out["logp"].view(t, R).t()
+    out["nkeep"] = None if filt is None else wsi[off[_lib.ROLLOUT_NOFF]:off[_lib.ROLLOUT_NOFF] + t * R].view(t, R).t()
     if out["alpha"] is not None:
         out["alpha"] = out["alpha"].view(t, R, d.P)
     if guard:

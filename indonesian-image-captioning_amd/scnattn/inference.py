@@ -32,7 +32,8 @@ class Captioner:
     type a `DeviceBatchLoader` hands the same encoder: channels-last when the encoder asks for it, fp32 values
     (`image_dtype`; the fused stem reads fp32 images in both modes).  `dtype` bf16 runs the trunks under bf16 autocast, as
     `TrainStep` runs them; the decoder stays fp32.  `search_options`: a `models.decoders.SearchOptions` handed to
-    `sample_batch` (n-gram blocking, minimum length, banned tokens, length penalty); None: the reference's search."""
+    `sample_batch` (n-gram blocking, minimum length, banned tokens, length penalty); None: the reference's search.
+    `captioner.sample(images, samples=3, top_k=..., top_p=...)`: several sampled captions per image (below)."""
 
     def __init__(self, encoder, decoder, word_map, tagger=None, beam_size=5, dtype=torch.float32,
                  mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD, size=None, image_dtype=torch.float32,
@@ -70,21 +71,57 @@ class Captioner:
         return data.resize_normalize(images, self.lut, size=self.size, dtype=self.image_dtype,
                                      channels_last=self.channels_last)
 
-    @torch.no_grad()
-    def __call__(self, images, tag_count=0, overlays=False):
+    def _encode(self, images, want_tags):
+        """eval-mode trunks over the resized batch -> (encoder_out fp32, tags fp32 or None); the caller holds the device"""
         for m in (self.encoder, self.decoder, self.tagger):
             if m is not None and any(c.training for c in m.modules()):      # eval() itself walks and writes every module
                 m.eval()
+        batch = self.images_to_batch(images)
+        tags = None
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.dtype == torch.bfloat16):
+            encoder_out = self.encoder(batch)
+            if self.tagger is not None and want_tags:
+                tags = self.tagger(batch)
+        return encoder_out.float(), None if tags is None else tags.float()
+
+    @torch.no_grad()
+    def sample(self, images, samples=3, temperature=1.0, top_k=0, top_p=1.0, seed=0, draw=0, greedy_first=False):
+        """Several different captions per image by truncated sampling instead of one by search: the trunks and the batch
+        path of `__call__`, then ONE `decoder.rollout_batch` (the whole rollout on the device) and one download.
+        -> per image a list of `samples` (+ 1 with greedy_first: the arg-max caption first) records
+            tokens  <start>, the sampled words, <end> (absent from a caption that was cut off at the step limit)
+            words   the same without <start>, <end>, <pad>, through the reversed word map
+            logp    the caption's log-probability under the distribution it was drawn from (temperature and filter
+                    included)
+        top_k / top_p cut the tail of every step's softmax (0 / 1.0: off; `rollout_batch`); (seed, draw) repeats the
+        captions and the next `draw` gives fresh ones.  No alphas and no overlays."""
+        if not hasattr(self.decoder, "rollout_batch"):
+            raise ValueError("Captioner.sample: a %s cannot sample (no rollout_batch)" % type(self.decoder).__name__)
+        from models.decoders._common import check_rollout_args
+        K = check_rollout_args(samples, temperature, greedy_first, who="Captioner.sample", top_k=top_k, top_p=top_p)
         with torch.cuda.device(self.device):
-            batch = self.images_to_batch(images)
-            tags = None
-            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.dtype == torch.bfloat16):
-                encoder_out = self.encoder(batch)
-                if self.tagger is not None and (self.needs_tags or tag_count > 0):
-                    tags = self.tagger(batch)
-            encoder_out = encoder_out.float()
-            if tags is not None:
-                tags = tags.float()
+            encoder_out, tags = self._encode(images, self.needs_tags)
+            caps, caplens, sum_logp = self.decoder.rollout_batch(self.word_map, encoder_out, tags, samples=samples, seed=seed,
+                                                                 draw=draw, temperature=temperature,
+                                                                 greedy_first=greedy_first, top_k=top_k, top_p=top_p)
+            # one download: the captions, their lengths and the bits of sum_logp side by side
+            host = torch.cat([caps, caplens, sum_logp.view(torch.int32).to(torch.int64).unsqueeze(1)], dim=1).cpu()
+        L = caps.shape[1]
+        logp = host[:, L + 1].to(torch.int32).view(torch.float32)
+        out = []
+        for n in range(host.shape[0] // K):
+            recs = []
+            for r in range(n * K, (n + 1) * K):
+                seq = host[r, :int(host[r, L])].tolist()
+                recs.append({"tokens": seq, "words": [self.rev_word_map[w] for w in seq if w not in self.skip],
+                             "logp": float(logp[r])})
+            out.append(recs)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, images, tag_count=0, overlays=False):
+        with torch.cuda.device(self.device):
+            encoder_out, tags = self._encode(images, self.needs_tags or tag_count > 0)
             kw = {} if self.search_options is None else {"options": self.search_options}
             if self.needs_tags:
                 results = self.decoder.sample_batch(self.beam_size, self.word_map, encoder_out, tags, **kw)
