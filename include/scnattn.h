@@ -26,6 +26,9 @@ extern "C" {
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
+                               + diverse beam search: groups of beams, a Hamming penalty (scnattn_diversity, scnattn_beam_*_div,
+                               scnattn_ensemble_*_div, scnattn_beam_merge_groups, scnattn_beam_row_topk_groups; new symbols only, the
+                               version stays);
                                + truncated sampling: top-k / nucleus rollouts (scnattn_sample_filter, scnattn_rollout_*_f; new symbols only,
                                the version stays);
                                + search options: n-gram blocking, minimum length, banned tokens (scnattn_search_options, scnattn_beam_*_opt,
@@ -290,6 +293,71 @@ int scnattn_beam_row_topk_ens_opt(void* stream, int N, int K, int V, int M, cons
 int scnattn_beam_advance_opt(void* stream, int N, int K, int D, int M, int V, int t, int max_steps, const float* hs,
                              const float* cs, const int32_t* parent_t, const int32_t* token_t, const float* table,
                              const int32_t* hist_src, int32_t* hist_dst, float* hd, float* cd, float* emb);
+/* ---- DIVERSE beam search: groups of beams, a Hamming penalty (Vijayakumar et al. 2016; both searches above) --
+ * The reference has no such search; the semantics are this library's.  "The search order" is the order above: value
+ * descending, flat index ascending.  The K slots of an image are split into G = groups groups of Kg = K / G slots,
+ * 1 <= G, 1 <= Kg, G * Kg = K <= 8 <= V; penalty lambda >= 0, finite.  The slots of image n are the rows n*K + g*Kg + s.
+ *   Every group is the search above with beam size Kg: it starts from one live source (its slot 0, the <start> row), its kk
+ *   shrinks as its beams complete, it keeps its own completions in completion order (by step, within a step by rank) at
+ *   n*K + g*Kg .., its own running best (replaced only on a strictly greater score) and its own open-beam fallback, and it
+ *   finishes on its own.  A finished group is a no-op and penalises nobody.
+ *   At step t the groups of an image are handled in order g = 0 .. G-1.  c(g, v) is the number of picks of the groups h < g
+ *   at this step whose word is v -- all of their kk picks count, <end> picks like any other word.  Candidate (j, v) of group
+ *   g has the raw value r = score[j] + logp_j(v), the value of the search above with the same bits, and the selection value
+ *   a = fmaf(-lambda, (float)c(g, v), r) in fp32.  The group takes its top kk by (a descending, flat index j_in_group*V + v
+ *   ascending).
+ *   NOTHING OF THE PENALTY IS STORED: scores, comp_score and best_score hold raw values r, so scores stay sums of the
+ *   model's log-probabilities, as with the search options.  Slots are compacted in rank order of a; dead slots get a copy of
+ *   the group's slot 0.  parent[t][row] is a slot of the IMAGE (g*Kg + j), as is comp_parent, so _advance and _advance_opt
+ *   are used unchanged and with no_repeat_ngram the history follows the same parents.
+ *   Search options compose: the exclusions act in the row selection as above, and the candidate-count refusal uses
+ *   K = G * Kg.  A length penalty chooses among a group's finished beams on the host, per group.
+ *   G = 1 is the search above bit for bit, for any lambda: c == 0 and fmaf(-lambda, 0, r) == r.
+ * Why K candidates per row are enough: group g is penalised on at most g*Kg <= K - Kg distinct words, a penalty only moves a
+ * candidate down, and exclusions happen before the ranking; so whatever group g can take from a row lies within that row's
+ * unpenalised top Kg + g*Kg <= K in the search order.  The launches per step are exactly those of the search above.
+ *   _workspace_div / _layout_div / _init_div / _steps_div   the four calls of each search with `opt` (may be NULL: no
+ *       options) and `div` after max_steps (the ensemble: after alpha_member); K is the TOTAL G * Kg; the same opt / div
+ *       in all four.  _layout_div writes SCNATTN_BEAM_NOFF_OPT offsets, those of _layout_opt (13: -1 without options),
+ *       with these shapes: 1 nsrc, 2 kk, 3 ncomp, 4 best_idx, 5 best_score are [N*G], entry n*G + g; nsrc counts the live
+ *       slots g*Kg .. g*Kg + nsrc - 1 of the group; 0 open_images counts the images with an open group.
+ *       With G > 1 the attention kernels of a step take K live slots for an image while any of its groups is open and 0
+ *       afterwards: dead slots hold finite copies, so computing them is correct, only wasted (G = 1: nsrc, as above).
+ *   scnattn_beam_merge_groups   the merge alone, on the state arrays a _layout_div describes (state: the 12 pointers of
+ *       scnattn_beam_merge); Kg slots per group, K % Kg == 0.
+ *   scnattn_beam_row_topk_groups   _row_topk with the group liveness: nsrc int[N * K/Kg], row n*K + g*Kg + s is live when
+ *       s < nsrc[n * K/Kg + g]; every live row still gets K candidates; rows of dead slots are neither read nor written.
+ * Refused (-1): groups < 1, K % groups != 0, K outside [1, 8], a penalty that is negative, NaN or infinite, and whatever the
+ * searches above refuse. */
+typedef struct {
+    int32_t groups;
+    float penalty;
+} scnattn_diversity;
+int scnattn_beam_workspace_div(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                               const scnattn_diversity* div, size_t* bytes);
+int scnattn_beam_layout_div(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                            const scnattn_diversity* div, long* offsets);
+int scnattn_beam_init_div(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                          const scnattn_diversity* div, const scnattn_params* w, const float* enc, const float* tags,
+                          int start_token, float* ws);
+int scnattn_beam_steps_div(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                           const scnattn_diversity* div, const scnattn_params* w, const float* enc, int end_token, int t0,
+                           int n_steps, float* ws);
+int scnattn_ensemble_workspace_div(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                   const scnattn_search_options* opt, const scnattn_diversity* div, size_t* bytes);
+int scnattn_ensemble_layout_div(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                const scnattn_search_options* opt, const scnattn_diversity* div, long* offsets);
+int scnattn_ensemble_init_div(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                              const scnattn_search_options* opt, const scnattn_diversity* div, const scnattn_params* w,
+                              const float* enc, const float* const* tags, int start_token, float* ws);
+int scnattn_ensemble_steps_div(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                               const scnattn_search_options* opt, const scnattn_diversity* div, const scnattn_params* w,
+                               const float* enc, const float* member_w, int mode, int end_token, int t0, int n_steps,
+                               float* ws);
+int scnattn_beam_merge_groups(void* stream, int N, int K, int Kg, float penalty, int V, int end_token, int t,
+                              const float* candv, const int32_t* candi, void* const* state);
+int scnattn_beam_row_topk_groups(void* stream, int N, int K, int Kg, int V, const float* logits, long ld, const float* scores,
+                                 const int32_t* nsrc, float* outv, int32_t* outi, int force_passes);
 /* ---- sampled rollouts for self-critical training (csrc/rollout.hip, the driver beside the search's) ---------------------
  * The set-up and the decode step of the search above over the same N*K rows, but the K slots of an image are INDEPENDENT
  * captions: nothing is compacted, the state carries over slot for slot, and after fc one token per open row is picked:

@@ -36,16 +36,17 @@ int seq_bwd(hipStream_t st, const scnattn_dims* d, const scnattn_params* w, cons
             const float* saved, float* scratch, const float* dpreds, const float* dalphas, const scnattn_params* g,
             float* denc, float* dtags, const scnattn_pool* pool);
 // the one search driver (beam_search.cpp); o: the search options, null for a search without
-int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
-                     size_t* bytes);
-int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
-                  long* off);
-int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
-                int max_steps, const scnattn_params* w, const float* enc, const float* const* tags, int start_token,
-                float* ws);
-int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
-                 int max_steps, const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token,
-                 int t0, int n_steps, float* ws);
+// v: the diversity of a search in groups, null for a search without
+int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                     const scnattn_diversity* v, int K, int max_steps, size_t* bytes);
+int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                  const scnattn_diversity* v, int K, int max_steps, long* off);
+int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
+                const float* const* tags, int start_token, float* ws);
+int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                 const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
+                 const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws);
 // filtered: the _f form (f is then checked and the workspace holds the nkeep records); else f is ignored
 int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
                       bool filtered, size_t* bytes);
@@ -108,25 +109,27 @@ int scnattn_profile_collect(double* out6) {
     return profile_collect(out6);
 }
 
-// The sixteen search entry points over the one driver.  The single search is the one-member ensemble of weight 1 in mode 0
+// The search entry points over the one driver (sixteen here, the eight _div forms below).  The single search is the one-member ensemble of weight 1 in mode 0
 // that records its attention maps when it has any; the _opt forms are the calls whose options may not be NULL.
 static int alpha_of(const scnattn_dims* d) { return d && d->has_att ? 0 : -1; }
 static const float k_one[1] = {1.f};
 static int no_options() { SCN_ARG(false, "search options are NULL"); return -1; }
 
 int scnattn_beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes) {
-    return search_workspace(1, d, alpha_of(d), nullptr, K, max_steps, bytes);
+    return search_workspace(1, d, alpha_of(d), nullptr, nullptr, K, max_steps, bytes);
 }
 int scnattn_beam_layout(const scnattn_dims* d, int K, int max_steps, long* offsets) {
-    return search_layout(1, d, alpha_of(d), nullptr, K, max_steps, offsets);
+    return search_layout(1, d, alpha_of(d), nullptr, nullptr, K, max_steps, offsets);
 }
 int scnattn_beam_init(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                       const float* tags, int start_token, float* ws) {
-    return search_init(ST(stream), 1, d, alpha_of(d), nullptr, K, max_steps, w, enc, tags ? &tags : nullptr, start_token, ws);
+    return search_init(ST(stream), 1, d, alpha_of(d), nullptr, nullptr, K, max_steps, w, enc, tags ? &tags : nullptr,
+                       start_token, ws);
 }
 int scnattn_beam_steps(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                        int end_token, int t0, int n_steps, float* ws) {
-    return search_steps(ST(stream), 1, d, alpha_of(d), nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0, n_steps, ws);
+    return search_steps(ST(stream), 1, d, alpha_of(d), nullptr, nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0,
+                        n_steps, ws);
 }
 int scnattn_beam_attn_scores(void* stream, int N, int K, int P, int A, const float* att1, const float* att2, int nslab,
                              long slab_stride, long att2_ld, const float* dec_bias, const float* w, const float* b0,
@@ -159,19 +162,19 @@ int scnattn_beam_row_topk_ens(void* stream, int N, int K, int V, int M, const fl
     return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, nullptr, outv, outi, force_passes);
 }
 int scnattn_ensemble_workspace(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, size_t* bytes) {
-    return search_workspace(M, dims, alpha_member, nullptr, K, max_steps, bytes);
+    return search_workspace(M, dims, alpha_member, nullptr, nullptr, K, max_steps, bytes);
 }
 int scnattn_ensemble_layout(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, long* offsets) {
-    return search_layout(M, dims, alpha_member, nullptr, K, max_steps, offsets);
+    return search_layout(M, dims, alpha_member, nullptr, nullptr, K, max_steps, offsets);
 }
 int scnattn_ensemble_init(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                           const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
-    return search_init(ST(stream), M, dims, alpha_member, nullptr, K, max_steps, w, enc, tags, start_token, ws);
+    return search_init(ST(stream), M, dims, alpha_member, nullptr, nullptr, K, max_steps, w, enc, tags, start_token, ws);
 }
 int scnattn_ensemble_steps(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                            const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
                            int n_steps, float* ws) {
-    return search_steps(ST(stream), M, dims, alpha_member, nullptr, K, max_steps, w, enc, member_w, mode, end_token, t0,
+    return search_steps(ST(stream), M, dims, alpha_member, nullptr, nullptr, K, max_steps, w, enc, member_w, mode, end_token, t0,
                         n_steps, ws);
 }
 int scnattn_beam_merge(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
@@ -190,41 +193,109 @@ int scnattn_beam_advance(void* stream, int N, int K, int D, int M, int V, const 
 }
 
 int scnattn_beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, size_t* bytes) {
-    return opt ? search_workspace(1, d, alpha_of(d), opt, K, max_steps, bytes) : no_options();
+    return opt ? search_workspace(1, d, alpha_of(d), opt, nullptr, K, max_steps, bytes) : no_options();
 }
 int scnattn_beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, long* offsets) {
-    return opt ? search_layout(1, d, alpha_of(d), opt, K, max_steps, offsets) : no_options();
+    return opt ? search_layout(1, d, alpha_of(d), opt, nullptr, K, max_steps, offsets) : no_options();
 }
 int scnattn_beam_init_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                           const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws) {
-    return opt ? search_init(ST(stream), 1, d, alpha_of(d), opt, K, max_steps, w, enc, tags ? &tags : nullptr, start_token, ws)
+    return opt ? search_init(ST(stream), 1, d, alpha_of(d), opt, nullptr, K, max_steps, w, enc, tags ? &tags : nullptr,
+                             start_token, ws)
                : no_options();
 }
 int scnattn_beam_steps_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                            const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws) {
-    return opt ? search_steps(ST(stream), 1, d, alpha_of(d), opt, K, max_steps, w, enc, k_one, 0, end_token, t0, n_steps, ws)
+    return opt ? search_steps(ST(stream), 1, d, alpha_of(d), opt, nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0,
+                              n_steps, ws)
                : no_options();
 }
 int scnattn_ensemble_workspace_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                    const scnattn_search_options* opt, size_t* bytes) {
-    return opt ? search_workspace(M, dims, alpha_member, opt, K, max_steps, bytes) : no_options();
+    return opt ? search_workspace(M, dims, alpha_member, opt, nullptr, K, max_steps, bytes) : no_options();
 }
 int scnattn_ensemble_layout_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                 const scnattn_search_options* opt, long* offsets) {
-    return opt ? search_layout(M, dims, alpha_member, opt, K, max_steps, offsets) : no_options();
+    return opt ? search_layout(M, dims, alpha_member, opt, nullptr, K, max_steps, offsets) : no_options();
 }
 int scnattn_ensemble_init_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                               const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
                               const float* const* tags, int start_token, float* ws) {
-    return opt ? search_init(ST(stream), M, dims, alpha_member, opt, K, max_steps, w, enc, tags, start_token, ws) : no_options();
+    return opt ? search_init(ST(stream), M, dims, alpha_member, opt, nullptr, K, max_steps, w, enc, tags, start_token, ws)
+               : no_options();
 }
 int scnattn_ensemble_steps_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
                                const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws) {
-    return opt ? search_steps(ST(stream), M, dims, alpha_member, opt, K, max_steps, w, enc, member_w, mode, end_token, t0,
-                              n_steps, ws)
+    return opt ? search_steps(ST(stream), M, dims, alpha_member, opt, nullptr, K, max_steps, w, enc, member_w, mode, end_token,
+                              t0, n_steps, ws)
                : no_options();
 }
+// The _div forms: opt may be NULL, div may not.
+static int no_diversity() { SCN_ARG(false, "the diversity is NULL"); return -1; }
+
+int scnattn_beam_workspace_div(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                               const scnattn_diversity* div, size_t* bytes) {
+    return div ? search_workspace(1, d, alpha_of(d), opt, div, K, max_steps, bytes) : no_diversity();
+}
+int scnattn_beam_layout_div(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                            const scnattn_diversity* div, long* offsets) {
+    return div ? search_layout(1, d, alpha_of(d), opt, div, K, max_steps, offsets) : no_diversity();
+}
+int scnattn_beam_init_div(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                          const scnattn_diversity* div, const scnattn_params* w, const float* enc, const float* tags,
+                          int start_token, float* ws) {
+    return div ? search_init(ST(stream), 1, d, alpha_of(d), opt, div, K, max_steps, w, enc, tags ? &tags : nullptr,
+                             start_token, ws)
+               : no_diversity();
+}
+int scnattn_beam_steps_div(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                           const scnattn_diversity* div, const scnattn_params* w, const float* enc, int end_token, int t0,
+                           int n_steps, float* ws) {
+    return div ? search_steps(ST(stream), 1, d, alpha_of(d), opt, div, K, max_steps, w, enc, k_one, 0, end_token, t0,
+                              n_steps, ws)
+               : no_diversity();
+}
+int scnattn_ensemble_workspace_div(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                   const scnattn_search_options* opt, const scnattn_diversity* div, size_t* bytes) {
+    return div ? search_workspace(M, dims, alpha_member, opt, div, K, max_steps, bytes) : no_diversity();
+}
+int scnattn_ensemble_layout_div(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                const scnattn_search_options* opt, const scnattn_diversity* div, long* offsets) {
+    return div ? search_layout(M, dims, alpha_member, opt, div, K, max_steps, offsets) : no_diversity();
+}
+int scnattn_ensemble_init_div(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                              const scnattn_search_options* opt, const scnattn_diversity* div, const scnattn_params* w,
+                              const float* enc, const float* const* tags, int start_token, float* ws) {
+    return div ? search_init(ST(stream), M, dims, alpha_member, opt, div, K, max_steps, w, enc, tags, start_token, ws)
+               : no_diversity();
+}
+int scnattn_ensemble_steps_div(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                               const scnattn_search_options* opt, const scnattn_diversity* div, const scnattn_params* w,
+                               const float* enc, const float* member_w, int mode, int end_token, int t0, int n_steps,
+                               float* ws) {
+    return div ? search_steps(ST(stream), M, dims, alpha_member, opt, div, K, max_steps, w, enc, member_w, mode, end_token,
+                              t0, n_steps, ws)
+               : no_diversity();
+}
+int scnattn_beam_merge_groups(void* stream, int N, int K, int Kg, float penalty, int V, int end_token, int t,
+                              const float* candv, const int32_t* candi, void* const* state) {
+    if (!state) { set_error("scnattn_beam_merge_groups: state is NULL"); return -1; }
+    if (N <= 0 || K < 1 || K > SCN_MAX_BEAM) { set_error("scnattn_beam_merge_groups: bad N / beam size"); return -1; }
+    const BeamState s{N * K, (float*)state[6], (int*)state[1], (int*)state[2], (int*)state[3], (int*)state[4],
+                      (float*)state[5], (int*)state[0], (float*)state[7], (int*)state[8], (int*)state[9], (int*)state[10],
+                      (int*)state[11]};
+    return beam_merge_groups(ST(stream), N, K, Kg, penalty, V, end_token, t, candv, candi, s);
+}
+int scnattn_beam_row_topk_groups(void* stream, int N, int K, int Kg, int V, const float* logits, long ld, const float* scores,
+                                 const int32_t* nsrc, float* outv, int32_t* outi, int force_passes) {
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "scnattn_beam_row_topk_groups: need 1 <= beam size <= 8 <= vocab_size");
+    SCN_ARG(Kg >= 1 && K % Kg == 0, "scnattn_beam_row_topk_groups: the slots per group must divide the beam size");
+    SCN_ARG(logits && scores && nsrc && outv && outi && ld >= V, "scnattn_beam_row_topk_groups: bad argument");
+    return beam_row_topk_ens(ST(stream), N, K, V, 1, EnsRows{{logits}, {ld}, {1.f}}, 0, scores, nsrc, nullptr, outv, outi,
+                             force_passes, Kg);
+}
+
 // what step t of a search with `opt` excludes, for the selection kernel alone; the launcher checks the ranges
 static int excl_of(const scnattn_search_options* opt, int end_token, int t, const int32_t* hist, int max_steps, BeamExcl& x) {
     SCN_ARG(opt, "search options are NULL");

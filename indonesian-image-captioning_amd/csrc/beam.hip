@@ -12,6 +12,10 @@
 //                      with EXCLUSIONS (search options) banned words, <end> before min_length and words that
 //                      would repeat an n-gram of the row's history are not candidates (a bitmap in LDS)
 //   beam_merge         per image: the top kk of the nsrc x K row candidates, <end> picks recorded, the rest compacted
+//   beam_merge_groups  the same for a search in G groups of Kg slots (diverse beam search): the groups of an
+//                      image in order, each ranking its candidates after a penalty per word the groups before it picked at
+//                      this step; nsrc / kk / ncomp / best_* are then per (image, group) and the row selection decides
+//                      liveness per group (its Kg parameter)
 //   beam_advance       h / c gathered from the parent slot, next input embedding gathered from the table; with search
 //                      options (beam_advance_opt, the same kernel) also the per-beam word history int32 [N*K][max_steps],
 //                      gathered from the parent slot and extended
@@ -356,8 +360,9 @@ struct NoExcl {};       // what the kernel without exclusions takes in place of 
 // EXCL: the rounds skip the words of the row's bitmap (excl_fill); nothing else differs, so with an empty bitmap the outputs
 // are the bits of EXCL = false.  The staged and the unstaged path read the same bitmap.  Without EXCL neither the bitmap nor
 // the history takes LDS.
+// Kg: the slots per group (K % Kg == 0, nsrc is [N * K/Kg]); Kg = K: no groups, nsrc [N] and the live rows a prefix.
 template <bool STAGED, bool EXCL>
-__global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int V, int M, int mode, EnsRows e, unsigned vecmask,
+__global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int Kg, int V, int M, int mode, EnsRows e, unsigned vecmask,
                                                                 std::conditional_t<EXCL, BeamExcl, NoExcl> x,
                                                                 const float* __restrict__ scores,
                                                                 const int* __restrict__ nsrc, float* __restrict__ outv,
@@ -374,7 +379,8 @@ __global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int V, in
     const int tid = threadIdx.x;
     const long row = blockIdx.x;
     const int n = (int)(row / K), j = (int)(row - (long)n * K);
-    if (j >= nsrc[n]) return;
+    const int grp = j / Kg;
+    if (j - grp * Kg >= nsrc[n * (K / Kg) + grp]) return;
     const int groups = (V + 3) >> 2;
     const float* g[SCN_MAX_ENSEMBLE];
     float lse[SCN_MAX_ENSEMBLE];
@@ -487,6 +493,103 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(int K, int V, int end_to
     if (nopen == 0) atomicAdd(s.open_images, -1);
 }
 
+// The merge of a search in G = K / Kg groups: one wave per image walks the groups in order.  Group g owns the
+// slots g*Kg .. g*Kg + Kg - 1 of the image and entry n*G + g of nsrc / kk / ncomp / best_idx / best_score; its candidates
+// are the nsrc_g x K rows of the row selection (Kg * K <= 64 lanes).  A lane ranks its candidate by
+//   a = fmaf(-penalty, c, r),  r = the raw value, c = how many picks of the groups before it at this step carry its word
+// under (a descending, flat index j_in_group * V + word ascending); lane 0 then records the kk_g picks as beam_merge_kernel
+// does -- with r, not a: nothing of the penalty is stored -- and appends their words, <end> included, to the list in LDS
+// (at most K <= 8 words).  A finished group is skipped and penalises nobody.  G = 1: c == 0 and fmaf(-penalty, 0, r) == r,
+// so the ranks, and with them every store, are beam_merge_kernel's.
+// open_images counts the images with an open group; att_live[n] (when given) is K while image n has one, else 0.
+__global__ __launch_bounds__(64) void beam_merge_groups_kernel(int K, int Kg, float penalty, int V, int end_tok, int t,
+                                                               const float* __restrict__ candv,
+                                                               const int* __restrict__ candi, BeamState s) {
+    __shared__ float sv[8];
+    __shared__ int sj[8], sw[8];
+    __shared__ int pw[8], pc[8];    // the words picked so far at this step, with their counts
+    __shared__ int npw;
+    const int n = blockIdx.x, lane = threadIdx.x, G = K / Kg;
+    if (lane == 0) npw = 0;
+    __syncthreads();
+    int was_open = 0, still_open = 0;       // lane 0's
+    int* token_t = s.token + (long)t * s.R;
+    int* parent_t = s.parent + (long)t * s.R;
+    for (int g = 0; g < G; ++g) {
+        const int sg = n * G + g;
+        const int ns = min(s.nsrc[sg], Kg), k = min(s.kk[sg], Kg);
+        if (k <= 0) continue;               // a finished group: uniform over the wave
+        const int j = lane / K, r = lane - j * K;
+        const bool valid = j < ns;          // ns <= Kg, so lane < Kg * K <= 64
+        const long ci = ((long)n * K + g * Kg + (valid ? j : 0)) * K + r;
+        const float v = valid ? candv[ci] : -INFINITY;
+        const int w = valid ? candi[ci] : 0;
+        const int flat = valid ? j * V + w : INT_MAX;
+        int c = 0;
+        for (int i = 0; i < npw; ++i)
+            if (pw[i] == w) c = pc[i];
+        const float a = valid ? fmaf(-penalty, (float)c, v) : -INFINITY;
+        int rank = 0;
+        for (int l = 0; l < 64; ++l) {
+            const float oa = __shfl(a, l, 64);
+            const int of = __shfl(flat, l, 64);
+            if (of != INT_MAX && before(oa, of, a, flat)) ++rank;
+        }
+        if (valid && rank < k) { sv[rank] = v; sj[rank] = j; sw[rank] = w; }
+        __syncthreads();
+        if (lane == 0) {
+            // picks in rank order: <end> picks are recorded as completed, the rest compacted to the group's slots 0 ..
+            int nopen = 0, nc = s.ncomp[sg], bi = s.best_idx[sg];
+            float bs = s.best_score[sg];
+            int tok0 = 0, par0 = 0;
+            const long r0 = (long)n * K + g * Kg;
+            for (int q = 0; q < k; ++q) {
+                if (sw[q] == end_tok) {
+                    if (nc < Kg) {
+                        s.comp_score[r0 + nc] = sv[q];
+                        s.comp_step[r0 + nc] = t;
+                        s.comp_parent[r0 + nc] = g * Kg + sj[q];
+                        if (bi < 0 || sv[q] > bs) { bs = sv[q]; bi = nc; }     // strictly greater: index(max(...))
+                        ++nc;
+                    }
+                } else {
+                    if (nopen == 0) { tok0 = sw[q]; par0 = g * Kg + sj[q]; }
+                    token_t[r0 + nopen] = sw[q];
+                    parent_t[r0 + nopen] = g * Kg + sj[q];
+                    s.scores[r0 + nopen] = sv[q];
+                    ++nopen;
+                }
+                int at = 0;                 // every pick counts, <end> like any other word
+                while (at < npw && pw[at] != sw[q]) ++at;
+                if (at < npw) {
+                    ++pc[at];
+                } else if (npw < 8) {
+                    pw[npw] = sw[q];
+                    pc[npw] = 1;
+                    ++npw;
+                }
+            }
+            for (int d = nopen; d < Kg; ++d) {      // dead slots: a copy of the group's slot 0 (zeros when nothing is open)
+                token_t[r0 + d] = tok0;
+                parent_t[r0 + d] = par0;
+                s.scores[r0 + d] = 0.f;
+            }
+            s.ncomp[sg] = nc;
+            s.best_idx[sg] = bi;
+            s.best_score[sg] = bs;
+            s.nsrc[sg] = nopen;
+            s.kk[sg] = nopen;
+            was_open = 1;
+            still_open |= nopen > 0;
+        }
+        __syncthreads();                    // the list is complete before the next group counts in it
+    }
+    if (lane == 0 && was_open && !still_open) {
+        atomicAdd(s.open_images, -1);
+        if (s.att_live) s.att_live[n] = 0;
+    }
+}
+
 // h / c gathered from the parent slot, the next input embedding from the table.  With hist_d (search options): also the
 // row's history for step t+1, the parent slot's t words of hist_s, then this step's word.  A dead slot carries slot 0's
 // parent / token records, so it gets slot 0's history.
@@ -519,7 +622,8 @@ __global__ __launch_bounds__(256) void beam_expand_rows_kernel(long total, int K
     out[i] = in[(row / K) * W + (i - row * W)];
 }
 
-__global__ __launch_bounds__(256) void beam_state_init_kernel(int N, int K, BeamState s) {
+// G groups per image (1: no groups): the per-group arrays hold N*G entries, each group with K/G beams to fill
+__global__ __launch_bounds__(256) void beam_state_init_kernel(int N, int K, int G, BeamState s) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < s.R) {
         s.scores[i] = 0.f;
@@ -527,13 +631,14 @@ __global__ __launch_bounds__(256) void beam_state_init_kernel(int N, int K, Beam
         s.comp_step[i] = -1;
         s.comp_parent[i] = 0;
     }
-    if (i < N) {
+    if (i < N * G) {
         s.nsrc[i] = 1;          // the reference selects from scores[0] only at step 1
-        s.kk[i] = K;
+        s.kk[i] = K / G;
         s.ncomp[i] = 0;
         s.best_idx[i] = -1;
         s.best_score[i] = 0.f;
     }
+    if (i < N && s.att_live) s.att_live[i] = K;
     if (i == 0) s.open_images[0] = N;
 }
 
@@ -585,10 +690,12 @@ int beam_attn_context(hipStream_t st, int N, int K, int P, int E, const float* e
 
 // The one launcher of the selection; x: what the step excludes, null: nothing.
 int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes) {
+                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes, int Kg) {
     if (N <= 0) return 0;
     SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "beam_row_topk_ens: need 1 <= members <= 4");
     SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk_ens: need 1 <= beam size <= 8 and vocab_size >= beam size");
+    if (Kg == 0) Kg = K;
+    SCN_ARG(Kg >= 1 && K % Kg == 0, "beam_row_topk_ens: the slots per group must divide the beam size");
     SCN_ARG(mode == 0 || mode == 1, "beam_row_topk_ens: mode must be 0 (logprob) or 1 (prob)");
     SCN_ARG(scores && nsrc && outv && outi, "beam_row_topk_ens: null argument");
     if (x) {
@@ -617,9 +724,9 @@ int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows&
     const size_t lds = stage ? staged : fixed;
     dim3 grid(N * K), block(256);
 #define L(STAGED)                                                                                                             \
-    if (x) hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, true>), grid, block, lds, st, K, V, M, mode, e, vecmask, *x,   \
-                              scores, nsrc, outv, outi);                                                                      \
-    else   hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, false>), grid, block, lds, st, K, V, M, mode, e, vecmask,      \
+    if (x) hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, true>), grid, block, lds, st, K, Kg, V, M, mode, e, vecmask,   \
+                              *x, scores, nsrc, outv, outi);                                                                  \
+    else   hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, false>), grid, block, lds, st, K, Kg, V, M, mode, e, vecmask,  \
                               NoExcl{}, scores, nsrc, outv, outi);
     if (stage) { L(true) } else { L(false) }
 #undef L
@@ -645,6 +752,21 @@ int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const fl
                 s.open_images && s.comp_score && s.comp_step && s.comp_parent && s.token && s.parent,
             "beam_merge: bad argument");
     hipLaunchKernelGGL(beam_merge_kernel, dim3(N), dim3(64), 0, st, K, V, end_tok, t, candv, candi, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_merge_groups(hipStream_t st, int N, int K, int Kg, float penalty, int V, int end_tok, int t, const float* candv,
+                      const int* candi, const BeamState& s) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K && t >= 0, "beam_merge_groups: bad beam size / step");
+    SCN_ARG(Kg >= 1 && K % Kg == 0, "beam_merge_groups: the slots per group must divide the beam size");
+    SCN_ARG(penalty >= 0.f && penalty < INFINITY, "beam_merge_groups: the penalty must be finite and not negative");
+    SCN_ARG((long)K * V < INT_MAX, "beam_merge_groups: beam size x vocab_size overflows the flat index");
+    SCN_ARG(candv && candi && s.R == N * K && s.scores && s.nsrc && s.kk && s.ncomp && s.best_idx && s.best_score &&
+                s.open_images && s.comp_score && s.comp_step && s.comp_parent && s.token && s.parent,
+            "beam_merge_groups: bad argument");
+    hipLaunchKernelGGL(beam_merge_groups_kernel, dim3(N), dim3(64), 0, st, K, Kg, penalty, V, end_tok, t, candv, candi, s);
     SCN_LAUNCH_CHECK();
     return 0;
 }
@@ -683,9 +805,10 @@ int beam_expand_rows(hipStream_t st, int N, int K, int W, const float* in, float
     return 0;
 }
 
-int beam_state_init(hipStream_t st, int N, int K, const BeamState& s) {
+int beam_state_init(hipStream_t st, int N, int K, const BeamState& s, int G) {
     SCN_ARG(N > 0 && K >= 1 && K <= SCN_MAX_BEAM && s.R == N * K, "beam_state_init: bad argument");
-    hipLaunchKernelGGL(beam_state_init_kernel, dim3(cdiv(s.R > N ? s.R : N, 256)), dim3(256), 0, st, N, K, s);
+    SCN_ARG(G >= 1 && K % G == 0, "beam_state_init: the groups must divide the beam size");
+    hipLaunchKernelGGL(beam_state_init_kernel, dim3(cdiv(s.R > N ? s.R : N, 256)), dim3(256), 0, st, N, K, G, s);
     SCN_LAUNCH_CHECK();
     return 0;
 }

@@ -4,10 +4,11 @@
 // between chunks of steps and the token / parent / alpha records at the end.
 // fp32 only: option "decoder_bf16" is not looked at here.
 //
-// ONE driver (search_workspace / search_layout / search_init / search_steps) serves the sixteen entry points
-// scnattn_beam_*, scnattn_ensemble_* and their _opt forms (csrc/api.cpp): M decoders step under one search state
-// (DESIGN.md 5m), the single search being M = 1 with weight 1 in mode 0, and search options are a pointer
-// that is null without them.
+// ONE driver (search_workspace / search_layout / search_init / search_steps) serves the twenty-four entry points
+// scnattn_beam_*, scnattn_ensemble_* and their _opt and _div forms (csrc/api.cpp): M decoders step under one search state
+// (DESIGN.md 5m), the single search being M = 1 with weight 1 in mode 0; search options and the diversity
+// of a search in groups are pointers that are null without them.  With a diversity the selection takes the
+// group size, beam_merge_groups replaces beam_merge and the attention kernels take att_live: the same launches.
 //
 // Launches per step, all in search_steps: per member the decode part (decode_step; with attention skinny
 // h.[Wd^T|Wbeta^T|Ha], beam_attn_scores, beam_attn_context, skinny z.Wa[M:], skinny emb.Wa[:M], scn_mix_fwd, skinny gates,
@@ -49,6 +50,7 @@ struct SearchWs {
     int* candi;
     float* alpha;       // [T][R][P] of alpha_member, or null
     int* hist;          // [2][R][T] with search options, else null
+    int G;              // groups of a diverse search; 1 without: the per-group state arrays hold N*G entries
     size_t state_floats;
     StepWs m[SCN_MAX_ENSEMBLE];
 };
@@ -98,19 +100,23 @@ void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b, const
     b.gws = shared_gws ? shared_gws->gws : c.take(BEAM_GEMM_WS_FLOATS);
 }
 
-// In this order: the BeamState fields, alpha, the members' step state, candv / candi, the history -- all of which init
+// In this order: the BeamState fields, alpha, the members' step state, candv / candi, the history, att_live -- which init
 // zero-fills (state_floats) -- then the members' set-up results with the shared split-K scratch.
-size_t carve_search(int M, const scnattn_dims* d, int K, int T, int alpha_member, bool hist, float* base, SearchWs& b) {
+// div: a diverse search, whose per-group arrays hold N*G entries and which also keeps att_live [N] (behind the history).
+size_t carve_search(int M, const scnattn_dims* d, int K, int T, int alpha_member, bool hist, const scnattn_diversity* div,
+                    float* base, SearchWs& b) {
     Carver c(base);
     const int N = d[0].B, P = d[0].P;
     const long R = (long)N * K;
+    b.G = div ? div->groups : 1;
+    const long NG = (long)N * b.G;
     b.s.R = (int)R;
     b.s.scores = c.take(R);
-    b.s.nsrc = ints(c.take(N));
-    b.s.kk = ints(c.take(N));
-    b.s.ncomp = ints(c.take(N));
-    b.s.best_idx = ints(c.take(N));
-    b.s.best_score = c.take(N);
+    b.s.nsrc = ints(c.take(NG));
+    b.s.kk = ints(c.take(NG));
+    b.s.ncomp = ints(c.take(NG));
+    b.s.best_idx = ints(c.take(NG));
+    b.s.best_score = c.take(NG);
     b.s.open_images = ints(c.take(1));
     b.s.comp_score = c.take(R);
     b.s.comp_step = ints(c.take(R));
@@ -126,6 +132,7 @@ size_t carve_search(int M, const scnattn_dims* d, int K, int T, int alpha_member
     b.candv = c.take(sz(R, K));
     b.candi = ints(c.take(sz(R, K)));
     b.hist = hist ? ints(c.take(sz(2, R, T))) : nullptr;
+    b.s.att_live = div ? ints(c.take(N)) : nullptr;
     b.state_floats = c.off;
     for (int m = 0; m < M; ++m) {
         b.m[m].state_floats = b.state_floats;
@@ -156,6 +163,16 @@ int check_options(const scnattn_search_options* o, int V, int K, int T, int end_
     SCN_ARG((long)V - o->n_banned - 1 - (o->no_repeat_ngram >= 1 ? T : 0) >= K,
             "the options may leave a row fewer than beam_size candidates "
             "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) >= beam_size)");
+    return 0;
+}
+
+// The refusals of a diverse search (include/scnattn.h); K is the total G * Kg.
+int check_diversity(const scnattn_diversity* v, int K) {
+    SCN_ARG(v, "the diversity is NULL");
+    SCN_ARG(v->groups >= 1, "groups must be at least 1");
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM, "beam_size must be in [1, 8]");
+    SCN_ARG(K % v->groups == 0, "beam_size (the total over the groups) must be a multiple of groups");
+    SCN_ARG(v->penalty >= 0.f && v->penalty < INFINITY, "the diversity penalty must be finite and not negative");
     return 0;
 }
 
@@ -256,36 +273,39 @@ int decode_step(hipStream_t st, const scnattn_dims& d, int K, const scnattn_para
 }  // namespace
 
 // ---- the search: M decoders under ONE search state; o: the search options, null without ------------
-int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
-                     size_t* bytes) {
+int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                     const scnattn_diversity* v, int K, int max_steps, size_t* bytes) {
+    if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
     SCN_ARG(bytes, "search_workspace: bytes is NULL");
     SearchWs b;
-    *bytes = carve_search(M, d, K, max_steps, alpha_member, o != nullptr, nullptr, b);
+    *bytes = carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, nullptr, b);
     return 0;
 }
 
 // off[SCNATTN_BEAM_NOFF]: where the results live in the workspace, in 4-byte elements (order: include/scnattn.h); with
-// options off[SCNATTN_BEAM_NOFF_OPT], the history's offset behind them
-int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K, int max_steps,
-                  long* off) {
+// options or a diversity off[SCNATTN_BEAM_NOFF_OPT], the history's offset (-1 without options) behind them
+int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                  const scnattn_diversity* v, int K, int max_steps, long* off) {
+    if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
     SCN_ARG(off, "search_layout: offsets is NULL");
     SearchWs b;
-    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, layout_base(), b);
+    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, layout_base(), b);
     const void* p[SCNATTN_BEAM_NOFF_OPT] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
                                             b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
                                             b.s.parent, b.alpha, b.hist};
-    offsets_from(layout_base(), p, o ? SCNATTN_BEAM_NOFF_OPT : SCNATTN_BEAM_NOFF, off);
+    offsets_from(layout_base(), p, (o || v) ? SCNATTN_BEAM_NOFF_OPT : SCNATTN_BEAM_NOFF, off);
     return 0;
 }
 
 // The history int32 [2][R][max_steps] of a search with options is zero-filled with the rest of the state.
-int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
-                int max_steps, const scnattn_params* w, const float* enc, const float* const* tags, int start_token,
-                float* ws) {
+int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
+                const float* const* tags, int start_token, float* ws) {
+    if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
     SCN_ARG(w && enc && tags && ws, "search_init: null argument");
@@ -293,9 +313,9 @@ int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, 
     SCN_ARG(start_token >= 0 && start_token < d[0].V, "search_init: start token outside the vocabulary");
     SCN_ARG(aligned16(ws), "search_init: the workspace must be 16-byte aligned");
     SearchWs b;
-    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, ws, b);
+    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, ws, b);
     SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
-    SCN_TRY(beam_state_init(st, d[0].B, K, b.s));
+    SCN_TRY(beam_state_init(st, d[0].B, K, b.s, b.G));
     for (int m = 0; m < M; ++m) SCN_TRY(decode_setup(st, d[m], K, w + m, enc, tags[m], start_token, b.m[m]));
     return 0;
 }
@@ -304,9 +324,10 @@ int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, 
 // member, decode_step with that member's hA/cA -> hB/cB, then ONE selection over the M logits buffers, ONE beam_merge, and
 // per member beam_advance with its own table and state.  With options the selection takes what step t excludes, and one
 // history serves all members: step t reads buffer t & 1, the first member's advance writes buffer (t + 1) & 1.
-int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o, int K,
-                 int max_steps, const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token,
-                 int t0, int n_steps, float* ws) {
+int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
+                 const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
+                 const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws) {
+    if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) {    // only a search with options needs to know <end>: min_length keeps it out, and it may not be banned
         SCN_ARG(end_token >= 0, "search_steps: end token outside the vocabulary");
@@ -316,7 +337,11 @@ int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member,
     SCN_ARG(t0 >= 0 && n_steps >= 0, "search_steps: negative step");
     const int N = d[0].B, P = d[0].P, V = d[0].V, R = N * K, T = max_steps;
     SearchWs b;
-    carve_search(M, d, K, T, alpha_member, o != nullptr, ws, b);
+    carve_search(M, d, K, T, alpha_member, o != nullptr, v, ws, b);
+    const int Kg = K / b.G;
+    // what the attention kernels take as the image's live slots: in groups the live rows are no prefix of the image's slots,
+    // so K while any group is open; one group is the search without groups, its nsrc [N] the prefix length
+    const int* att_live = b.G > 1 ? b.s.att_live : b.s.nsrc;
     EnsRows rows{};
     for (int m = 0; m < M; ++m) {
         rows.p[m] = b.m[m].logits;
@@ -329,13 +354,16 @@ int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member,
         int* parent_t = b.s.parent + (long)t * R;
         for (int m = 0; m < M; ++m) {
             const StepWs& s = b.m[m];
-            SCN_TRY(decode_step(st, d[m], K, w + m, enc, s, b.s.nsrc, s.alpha ? s.alpha + (long)t * R * P : nullptr, s.hA, s.cA,
+            SCN_TRY(decode_step(st, d[m], K, w + m, enc, s, att_live, s.alpha ? s.alpha + (long)t * R * P : nullptr, s.hA, s.cA,
                                 s.hB, s.cB));
         }
         BeamExcl x{};
         if (o) x = step_excl(*o, t, T, R, end_token, b.hist);
-        SCN_TRY(beam_row_topk_ens(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, o ? &x : nullptr, b.candv, b.candi, 0));
-        SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
+        SCN_TRY(beam_row_topk_ens(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, o ? &x : nullptr, b.candv, b.candi, 0, Kg));
+        if (v)
+            SCN_TRY(beam_merge_groups(st, N, K, Kg, v->penalty, V, end_token, t, b.candv, b.candi, b.s));
+        else
+            SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));
         for (int m = 0; m < M; ++m) {
             const StepWs& s = b.m[m];
             if (o && m == 0)

@@ -148,6 +148,9 @@ struct BeamState {
     int* comp_parent;       // [R]    source slot that picked it
     int* token;             // [steps][R]  word of the beam that sits in this slot AFTER the step
     int* parent;            // [steps][R]  slot it came from
+    // The grouped search (beam_merge_groups): nsrc .. best_score are then [N*G], one entry per (image,
+    // group), and att_live [N] is what the attention kernels take for nsrc: K while any group of the image is open, else 0.
+    int* att_live = nullptr;
 };
 // e[n*K+j][p] for j < nsrc[n]; att2 = sum(slabs) + bd over rows n*K+j; rows of dead slots are left untouched
 int beam_attn_scores(hipStream_t st, int N, int K, int P, int A, const float* att1, Slabs att2, const float* bd,
@@ -178,14 +181,21 @@ struct BeamExcl {
 // x: the candidates left out of the K rounds (the log-sum-exp still runs over all V logits); null: none, which writes the
 // bits of an `x` that excludes nothing.  With x it refuses unless V - n_banned - 1 - (g >= 1 ? T : 0) >= K.
 // force_passes != 0 (tests): read the rows from global memory in every pass even when a row fits the LDS.
+// Kg: the slots per group of a grouped search (K % Kg == 0; nsrc is then [N * K/Kg] and row n*K + g*Kg + s is live when
+// s < nsrc[n * K/Kg + g]); Kg = K (or 0, the default) is the search without groups.  A live row runs K rounds either way.
 int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes);
+                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes, int Kg = 0);
 // The single decoder's selection, the top K of scores[row] + logits[row][v] - lse(row): beam_row_topk_ens with M = 1,
 // mode 0, w = 1, nothing excluded.
 int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
                   float* outv, int* outi, int force_passes);
 int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
                const BeamState& s);
+// The merge of a search in G = K / Kg groups of Kg slots (include/scnattn.h: "diverse beam search"): per image the groups in
+// order, group g ranking its nsrc_g x K candidates by fmaf(-penalty, c, value), c = the picks of groups h < g at this step
+// with the candidate's word; raw values are stored.  s.nsrc .. s.best_score are [N*G], s.att_live [N] may be null.
+int beam_merge_groups(hipStream_t st, int N, int K, int Kg, float penalty, int V, int end_tok, int t, const float* candv,
+                      const int* candi, const BeamState& s);
 // One kernel behind both: h / c of row n*K+s gathered from its parent slot, emb from the table; the _opt form also writes
 // the row's history for step t+1, the parent slot's first t entries of hist_s, then token_t[row] (hist_s != hist_d)
 int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,
@@ -194,7 +204,8 @@ int beam_advance_opt(hipStream_t st, int N, int K, int D, int M, int V, int t, i
                      const int* parent_t, const int* token_t, const float* table, const int* hist_s, int* hist_d, float* hd,
                      float* cd, float* emb);
 int beam_expand_rows(hipStream_t st, int N, int K, int W, const float* in, float* out);
-int beam_state_init(hipStream_t st, int N, int K, const BeamState& s);
+// G groups per image (1: the search without groups): every group starts from one live source, its slot 0, with K / G to fill
+int beam_state_init(hipStream_t st, int N, int K, const BeamState& s, int G = 1);
 
 // ---- rollout.hip: sampled rollouts (K independent slots per image, rows n*K + j, nothing compacted) ------------------
 struct RolloutState {

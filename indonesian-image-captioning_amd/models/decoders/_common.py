@@ -231,20 +231,70 @@ def beam_search_batched(decoder, beam_size, word_map, encoder_out, tag_out, use_
     return trace_back(res, steps, N, k, start, end, (hh, ww), use_attention, return_all, length_penalty=alpha)
 
 
+def check_groups_args(beam_size, groups, diversity, V, who="sample_groups"):
+    """The host-side refusals of a diverse search, before anything touches the GPU -> (beams per group, groups, total K,
+    penalty): beam_size (PER GROUP) and groups integers >= 1 with beam_size * groups in [1, 8] and <= vocab_size, a finite
+    penalty >= 0"""
+    import math
+    from scnattn import _lib
+    if int(beam_size) != beam_size or int(groups) != groups or beam_size < 1 or groups < 1:
+        raise ValueError("%s: beam_size and groups must be integers >= 1 (got %r, %r)" % (who, beam_size, groups))
+    kg, G = int(beam_size), int(groups)
+    K = kg * G
+    if K > _lib.MAX_BEAM:
+        raise ValueError("%s: beam_size x groups = %d beams per image exceeds %d" % (who, K, _lib.MAX_BEAM))
+    if V < K:
+        raise ValueError("%s: vocab_size %d is smaller than beam_size x groups = %d" % (who, V, K))
+    lam = float(diversity)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("%s: the diversity penalty must be finite and not negative (got %r)" % (who, diversity))
+    return kg, G, K, lam
+
+
+def beam_search_grouped(decoder, beam_size, groups, diversity, word_map, encoder_out, tag_out, use_attention, use_tags,
+                        return_all=False, options=None, with_scores=False):
+    """DIVERSE beam search (include/scnattn.h; Vijayakumar et al. 2016) for N images on the device: ``groups`` groups of
+    ``beam_size`` beams each, beam_size * groups <= 8.  Every group searches like ``beam_search_batched`` with beam_size
+    beams, but at each step a candidate pays ``diversity`` for every pick of an earlier group with the same word at that
+    step; returned scores are raw sums of log-probabilities.  Returns, per image, a list of ``groups`` results, each in
+    the form ``beam_search_batched`` returns for an image (``return_all`` / ``options`` as there; the length penalty
+    chooses per group).  groups == 1 is ``beam_search_batched`` bit for bit, whatever the penalty."""
+    V = len(word_map)
+    kg, G, K, lam = check_groups_args(beam_size, groups, diversity, V)
+    start, end = word_map[start_token], word_map[end_token]
+    dev_options, alpha = device_options(options)
+    if dev_options is not None:
+        dev_options.check(V, K, SF.BEAM_MAX_STEPS, end)       # the candidate-count rule takes the total K
+    from scnattn import _lib
+    _lib.require_cuda(encoder_out, tag_out)
+    N, hh, ww, E = encoder_out.shape
+    dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
+    res, steps = SF.beam_search_run(dims, K, weights, enc, tag_out, start, end, options=dev_options, groups=G, diversity=lam)
+    out = trace_back(res, steps, N, K, start, end, (hh, ww), use_attention, return_all, length_penalty=alpha, groups=G,
+                     with_scores=with_scores)
+    return out if G > 1 else [[x] for x in out]
+
+
 def pick_best(done_scores, lengths, length_penalty):
     """index of the first maximum of score / L**alpha over the beams, in the order given (Python floats)"""
     norm = [s / float(L) ** length_penalty for s, L in zip(done_scores, lengths)]
     return norm.index(max(norm))
 
 
-def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=False, length_penalty=0.0):
+def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=False, length_penalty=0.0, groups=1,
+               with_scores=False):
     """The results of a device search (SF.beam_search_run / SF.ensemble_search_run) -> the list of N results that
     ``beam_search_batched`` documents: the parent chains read off the token / parent records, the all-ones first alpha map
     (``use_attention``: the search kept maps), the fallback to the best open beam.
     ``length_penalty`` alpha != 0: the returned caption is the first maximum, in completion order (the open beams: slot
     order), of score / L**alpha with L = len(sequence) - 1, the decoded tokens with <end>; the (sequence, score) lists of
-    ``return_all`` keep raw scores.  alpha == 0: the device's best_idx decides, as without options."""
+    ``return_all`` keep raw scores.  alpha == 0: the device's best_idx decides, as without options.
+    ``groups`` > 1 (a diverse search; k is the TOTAL over the groups): the per-group records are read -- group g of image n
+    keeps its completions at n*k + g*kg .., its open beams in slots g*kg .., its counters at n*groups + g -- and the result
+    of an image is the list of its ``groups`` results, each in the form above.  ``with_scores``: each result is paired
+    with the raw score of the caption it returns."""
     hh, ww = map_hw
+    kg = k // groups
     token, parent = res["token"].tolist(), res["parent"].tolist()
     alpha = res["alpha"]
     ones = torch.ones(1, hh, ww)
@@ -267,28 +317,43 @@ def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=F
         maps = [ones] + [alpha[t, r].view(1, hh, ww) for t, r in rows]
         return torch.cat(maps).tolist()
 
-    out = []
-    for n in range(N):
+    def group(n, g):
+        """the result of group g of image n: its slots are g*kg .. g*kg + kg - 1 of the image"""
+        sg, s0 = n * groups + g, g * kg
         done = []       # (sequence, alpha rows, score) in completion order
-        for ci in range(int(res["ncomp"][n])):
-            r = n * k + ci
+        for ci in range(int(res["ncomp"][sg])):
+            r = n * k + s0 + ci
             t, src = int(res["comp_step"][r]), int(res["comp_parent"][r])
             words, rows = chain(n, t - 1, src)
             done.append((words + [end], rows + [(t, n * k + src)], float(res["comp_score"][r])))
         if done:
-            i = int(res["best_idx"][n])
+            i = int(res["best_idx"][sg])
         else:           # nothing reached <end> within the step limit: the best open beam (rank order: slot 0)
-            for s in range(int(res["nsrc"][n])):
+            for s in range(s0, s0 + int(res["nsrc"][sg])):
                 words, rows = chain(n, steps - 1, s)
                 done.append((words, rows, float(res["scores"][n * k + s])))
             scores = [x[2] for x in done]
             i = scores.index(max(scores))
         if length_penalty != 0.0:
             i = pick_best([x[2] for x in done], [len(x[0]) - 1 for x in done], length_penalty)
-        seq, rows, _ = done[i]
+        seq, rows, score = done[i]
         one = (seq, alphas_of(rows)) if use_attention else seq
-        out.append((one, [(s, sc) for s, _, sc in done]) if return_all else one)
-    return out
+        one = (one, [(s, sc) for s, _, sc in done]) if return_all else one
+        return (one, score) if with_scores else one
+
+    # The results are nested lists of plain numbers (an attention map per word: some 10 000 floats and 800 lists per
+    # caption) and hold no reference cycles; the collector, woken by every few hundred new lists to walk all of them again,
+    # made up most of this function's time once an image returns several captions.  It rests while they are built.
+    import gc
+    resting = gc.isenabled()
+    gc.disable()
+    try:
+        if groups == 1:
+            return [group(n, 0) for n in range(N)]
+        return [[group(n, g) for g in range(groups)] for n in range(N)]
+    finally:
+        if resting:
+            gc.enable()
 
 
 def check_rollout_args(samples, temperature, greedy_first=False, who="rollout_batch", top_k=0, top_p=1.0):

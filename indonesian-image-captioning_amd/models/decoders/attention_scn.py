@@ -89,6 +89,13 @@ class AttentionSCN(nn.Module):
         return _common.beam_search_batched(self, beam_size, word_map, encoder_out, tag_out, use_attention=True,
                                            use_tags=True, options=options)
 
+    def sample_groups(self, beam_size, groups, diversity, word_map, encoder_out, tag_out, options=None, **kw):
+        """Diverse beam search: ``groups`` groups of ``beam_size`` beams, a penalty ``diversity`` per word an earlier group
+        picked at the same step -> per image a list of ``groups`` results, each what ``sample_batch`` returns for an image
+        (_common.beam_search_grouped)."""
+        return _common.beam_search_grouped(self, beam_size, groups, diversity, word_map, encoder_out, tag_out,
+                                           use_attention=True, use_tags=True, options=options, **kw)
+
     def rollout_batch(self, word_map, encoder_out, tags=None, samples=1, seed=0, draw=0, temperature=1.0,
                       greedy_first=False, top_k=0, top_p=1.0):
         """Sampled captions for self-critical training: encoder_out (N, h, w, E), tags (N, S) -> (caps (N*K, L) int64, caplens

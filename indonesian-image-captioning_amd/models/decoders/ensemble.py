@@ -68,16 +68,32 @@ class DecoderEnsemble(nn.Module):
     def has_alphas(self):
         return self.alpha_member is not None
 
+    def sample_groups(self, beam_size, groups, diversity, word_map, encoder_out, tags=None, options=None, return_all=False,
+                      with_scores=False):
+        """Diverse beam search under the combined distribution (_common.beam_search_grouped): ``groups`` groups of
+        ``beam_size`` beams -> per image a list of ``groups`` results, each what ``sample_batch`` returns for an image."""
+        return self._search(beam_size, word_map, encoder_out, tags, return_all, options, groups=groups, diversity=diversity,
+                            with_scores=with_scores)
+
     def sample_batch(self, beam_size, word_map, encoder_out, tags=None, return_all=False, options=None):
         """encoder_out (N, h, w, E), tags (N, S) (may be None when no member uses tags) -> list of N results in the form
         ``_common.beam_search_batched`` returns them: the sequence with the leading <start>, paired with the attention maps
         of ``alpha_member`` (the all-ones first map included) when there is one; the best open beam where nothing
         completed; with ``return_all`` each result paired with the image's completed (sequence, score) list.
         ``options``: a ``SearchOptions`` as a single decoder's ``sample_batch`` takes it (None / all-default: untouched)."""
-        k = int(beam_size)
-        if not 1 <= k <= SF._lib.MAX_BEAM:
-            raise ValueError("sample_batch: beam_size must be in [1, %d] (got %d)" % (SF._lib.MAX_BEAM, k))
+        return self._search(int(beam_size), word_map, encoder_out, tags, return_all, options)
+
+    def _search(self, beam_size, word_map, encoder_out, tags, return_all, options, groups=None, diversity=0.0,
+                with_scores=False):
+        """groups None: sample_batch with beam_size beams; else sample_groups with beam_size beams in each of the groups"""
         V = len(word_map)
+        G, lam = 1, 0.0
+        if groups is None:
+            k = beam_size
+            if not 1 <= k <= SF._lib.MAX_BEAM:
+                raise ValueError("sample_batch: beam_size must be in [1, %d] (got %d)" % (SF._lib.MAX_BEAM, k))
+        else:
+            _, G, k, lam = _common.check_groups_args(beam_size, groups, diversity, V)     # k: the total over the groups
         if V != self.vocab_size:
             raise ValueError("sample_batch: the word map has %d words, the members' vocab_size is %d" % (V, self.vocab_size))
         if V < k:
@@ -98,5 +114,7 @@ class DecoderEnsemble(nn.Module):
             weights_list.append(weights)
             tags_list.append(tg)
         res, steps = SF.ensemble_search_run(dims_list, k, weights_list, enc, tags_list, self.member_weights, self.combine,
-                                            start, end, self.alpha_member, options=dev_options)
-        return _common.trace_back(res, steps, N, k, start, end, (hh, ww), self.has_alphas, return_all, length_penalty=alpha)
+                                            start, end, self.alpha_member, options=dev_options, groups=G, diversity=lam)
+        out = _common.trace_back(res, steps, N, k, start, end, (hh, ww), self.has_alphas, return_all, length_penalty=alpha,
+                                 groups=G, with_scores=with_scores)
+        return [[x] for x in out] if groups is not None and G == 1 else out

@@ -122,6 +122,13 @@ class PureAttention(nn.Module):
         return _common.beam_search_batched(self, beam_size, word_map, encoder_out, None, use_attention=True,
                                            use_tags=False, options=options)
 
+    def sample_groups(self, beam_size, groups, diversity, word_map, encoder_out, tags=None, options=None, **kw):
+        """Diverse beam search: ``groups`` groups of ``beam_size`` beams, a penalty ``diversity`` per word an earlier group
+        picked at the same step -> per image a list of ``groups`` results, each what ``sample_batch`` returns for an image
+        (_common.beam_search_grouped); `tags` is ignored (this decoder has none)."""
+        return _common.beam_search_grouped(self, beam_size, groups, diversity, word_map, encoder_out, None,
+                                           use_attention=True, use_tags=False, options=options, **kw)
+
     def rollout_batch(self, word_map, encoder_out, tags=None, samples=1, seed=0, draw=0, temperature=1.0,
                       greedy_first=False, top_k=0, top_p=1.0):
         """Sampled captions for self-critical training: encoder_out (N, h, w, E); `tags` is ignored (this decoder has none)

@@ -88,6 +88,10 @@ class SearchOpts(C.Structure):     # scnattn_search_options
                 ("banned", C.c_int32 * MAX_BANNED)]
 
 
+class Diversity(C.Structure):      # scnattn_diversity
+    _fields_ = [("groups", C.c_int32), ("penalty", C.c_float)]
+
+
 class SampleFilter(C.Structure):   # scnattn_sample_filter
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
 
@@ -134,6 +138,23 @@ _SIGS = {
     "scnattn_beam_row_topk_ens_opt": ([vp, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(f32), i32, vp, vp,
                                        C.POINTER(SearchOpts), i32, i32, vp, i32, vp, vp, i32], i32),
     "scnattn_beam_advance_opt": ([vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+    "scnattn_beam_workspace_div": ([C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity), C.POINTER(sz)],
+                                   i32),
+    "scnattn_beam_layout_div": ([C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity), C.POINTER(i64)], i32),
+    "scnattn_beam_init_div": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity), C.POINTER(Params),
+                               vp, vp, i32, vp], i32),
+    "scnattn_beam_steps_div": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity), C.POINTER(Params),
+                                vp, i32, i32, i32, vp], i32),
+    "scnattn_ensemble_workspace_div": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity),
+                                        C.POINTER(sz)], i32),
+    "scnattn_ensemble_layout_div": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity),
+                                     C.POINTER(i64)], i32),
+    "scnattn_ensemble_init_div": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity),
+                                   C.POINTER(Params), vp, C.POINTER(vp), i32, vp], i32),
+    "scnattn_ensemble_steps_div": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Diversity),
+                                    C.POINTER(Params), vp, C.POINTER(f32), i32, i32, i32, i32, vp], i32),
+    "scnattn_beam_merge_groups": ([vp, i32, i32, i32, f32, i32, i32, i32, vp, vp, C.POINTER(vp)], i32),
+    "scnattn_beam_row_topk_groups": ([vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, i32], i32),
     "scnattn_rollout_workspace": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(sz)], i32),
     "scnattn_rollout_layout": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(i64)], i32),
     "scnattn_rollout_init": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, vp, i32, vp], i32),

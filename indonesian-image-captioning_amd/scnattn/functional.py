@@ -274,8 +274,34 @@ def search_options_struct(options, vocab_size, beam_size, max_steps, end_token):
     return o
 
 
+def diversity_struct(groups, diversity, beam_size):
+    """(groups, diversity) of a search whose TOTAL beam size is beam_size -> scnattn_diversity, after its refusals
+    (ValueError): groups >= 1 dividing beam_size, a finite penalty >= 0"""
+    import math
+    if int(groups) != groups or groups < 1:
+        raise ValueError("groups must be an integer >= 1 (got %r)" % (groups,))
+    if beam_size % int(groups) != 0:
+        raise ValueError("beam_size %d (the total over the groups) is not a multiple of groups %d" % (beam_size, groups))
+    diversity = float(diversity)
+    if not (math.isfinite(diversity) and diversity >= 0.0):
+        raise ValueError("the diversity penalty must be finite and not negative (got %r)" % (diversity,))
+    return _lib.Diversity(groups=int(groups), penalty=diversity)
+
+
+def _search_form(options, groups, diversity, V, beam_size, max_steps, end_token):
+    """(suffix of the four calls, what they take behind max_steps / alpha_member, offsets): the plain calls, the _opt form
+    with options, and -- only when groups > 1 -- the _div form, whose options may be NULL"""
+    div = diversity_struct(groups, diversity, beam_size)
+    opt = None if options is None else search_options_struct(options, V, beam_size, max_steps, end_token)
+    if div.groups > 1:
+        return "_div", (C.byref(opt) if opt is not None else None, C.byref(div)), _lib.BEAM_NOFF_OPT
+    if opt is not None:
+        return "_opt", (C.byref(opt),), _lib.BEAM_NOFF_OPT
+    return "", (), _lib.BEAM_NOFF
+
+
 def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token, max_steps=BEAM_MAX_STEPS,
-                    chunk=BEAM_CHUNK, guard=0, options=None):
+                    chunk=BEAM_CHUNK, guard=0, options=None, groups=1, diversity=0.0):
     """The whole search of N images on the device.  dims: 12-tuple in scnattn_dims order with B = N (T, L unused);
     enc (N, P, E) as the caller has it (no copy per beam), tags (N, S) un-expanded; weights in PARAM_FIELDS order.
     Returns (results, steps): host tensors by the names of scnattn_beam_layout -- token / parent (steps, N*K),
@@ -283,39 +309,40 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
     behind the workspace, returned as results["guard"] (host int32).
     options: a models.decoders.SearchOptions runs the scnattn_beam_*_opt calls (its length_penalty is the caller's
     business: trace_back) and adds results["history"] (N*K, steps) int32, the words of the beam in every slot; None: the
-    plain search, and results["history"] is None."""
+    plain search, and results["history"] is None.
+    groups > 1: a DIVERSE search (include/scnattn.h; the scnattn_beam_*_div calls) in `groups` groups of beam_size / groups
+    slots with the penalty `diversity`; beam_size is the total.  nsrc / kk / ncomp / best_idx / best_score then hold
+    N * groups entries, entry n * groups + g.  groups == 1 takes today's entry points, whatever `diversity` says."""
     require_cuda(enc, tags, *weights)
     if not 1 <= beam_size <= _lib.MAX_BEAM:
         raise ValueError("beam_size must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, beam_size))
     d = Dims(*dims)
     if d.V < beam_size:
         raise ValueError("vocab_size %d is smaller than beam_size %d" % (d.V, beam_size))
-    # with options: the same four calls in their _opt form, the options struct after max_steps
-    sfx, opt = "", ()
-    if options is not None:
-        sfx, opt = "_opt", (C.byref(search_options_struct(options, d.V, beam_size, max_steps, end_token)),)
+    # with options: the same four calls in their _opt form, the options struct after max_steps; in groups: the _div form
+    sfx, opt, noff = _search_form(options, groups, diversity, d.V, beam_size, max_steps, end_token)
     dev = enc.device
     enc, tags = f32c(enc), f32c(tags)
     weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
     w = _params_struct(weights)
     K, N = beam_size, d.B
-    ws, off, nwords, t = _run_on_device("scnattn_beam_%s" + sfx, (C.byref(d), K, max_steps, *opt),
-                                        _lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF,
+    ws, off, nwords, t = _run_on_device("scnattn_beam_%s" + sfx, (C.byref(d), K, max_steps, *opt), noff,
                                         (C.byref(w), ptr(enc), ptr(tags), start_token), (C.byref(w), ptr(enc), end_token),
                                         stream_of(enc), dev, max_steps, chunk, guard)
-    return _beam_results(ws, off, N, K, d.P, t, nwords, guard, max_steps), t
+    return _beam_results(ws, off, N, K, d.P, t, nwords, guard, max_steps, groups=int(groups)), t
 
 
-def _beam_results(ws, off, N, K, P, t, nwords, guard, max_steps=BEAM_MAX_STEPS):
+def _beam_results(ws, off, N, K, P, t, nwords, guard, max_steps=BEAM_MAX_STEPS, groups=1):
     """the host tensors of a finished search (t steps ran), by the names of scnattn_beam_layout; "history" (N*K, t): the
-    current one of the two history buffers of a search with options (scnattn_beam_layout_opt), None without"""
+    current one of the two history buffers of a search with options (scnattn_beam_layout_opt), None without; the
+    per-group arrays of a search in groups hold N * groups entries"""
     wsi = ws.view(torch.int32)
-    R = N * K
+    R, NG = N * K, N * groups
     hist = None
-    if len(off) > _lib.BEAM_NOFF:
+    if len(off) > _lib.BEAM_NOFF and off[_lib.BEAM_NOFF] >= 0:
         cur = off[_lib.BEAM_NOFF] + (t & 1) * R * max_steps
         hist = wsi[cur:cur + R * max_steps].view(R, max_steps)[:, :t].cpu()
-    sizes = {"open_images": 1, "nsrc": N, "kk": N, "ncomp": N, "best_idx": N, "best_score": N, "scores": R,
+    sizes = {"open_images": 1, "nsrc": NG, "kk": NG, "ncomp": NG, "best_idx": NG, "best_score": NG, "scores": R,
              "comp_score": R, "comp_step": R, "comp_parent": R, "token": t * R, "parent": t * R, "alpha": t * R * P}
     out = {}
     for i, name in enumerate(_BEAM_RESULTS):
@@ -358,13 +385,13 @@ def normalise_member_weights(weights, M):
 
 
 def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, member_weights, mode, start, end, alpha_member,
-                        max_steps=BEAM_MAX_STEPS, chunk=BEAM_CHUNK, guard=0, options=None):
+                        max_steps=BEAM_MAX_STEPS, chunk=BEAM_CHUNK, guard=0, options=None, groups=1, diversity=0.0):
     """beam_search_run for an ensemble of M <= 4 decoders under one search state (csrc/beam_search.cpp:
     scnattn_ensemble_*): dims_list / weights_list / tags_list hold one entry per member, as beam_search_run takes them;
     enc (N, P, E) is shared.  member_weights: M positive numbers (None: equal), normalised here; mode: "logprob" / 0 (the
     weighted mean of the members' log-probabilities) or "prob" / 1 (the log of the weighted mean of their probabilities).
     alpha_member: the member whose attention maps are kept (-1 or None: none).  Returns (results, steps) exactly as
-    beam_search_run does; `guard` and `options` have the same meaning."""
+    beam_search_run does; `guard`, `options`, `groups` and `diversity` have the same meaning."""
     M = len(dims_list)
     if not 1 <= M <= _lib.MAX_ENSEMBLE:
         raise ValueError("an ensemble has 1 to %d members (got %d)" % (_lib.MAX_ENSEMBLE, M))
@@ -393,13 +420,12 @@ def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, memb
     tg = (C.c_void_p * M)(*[t.data_ptr() for t in tags_list])
     cw = (C.c_float * M)(*mw)
     K, N = beam_size, d[0].B
-    sfx, opt = "", ()       # with options: the _opt form of the four calls, the options struct after alpha_member
-    if options is not None:
-        sfx, opt = "_opt", (C.byref(search_options_struct(options, d[0].V, beam_size, max_steps, int(end))),)
-    ws, off, nwords, t = _run_on_device("scnattn_ensemble_%s" + sfx, (M, d, K, max_steps, alpha_member, *opt),
-                                        _lib.BEAM_NOFF_OPT if opt else _lib.BEAM_NOFF, (w, ptr(enc), tg, int(start)),
-                                        (w, ptr(enc), cw, mode, int(end)), stream_of(enc), dev, max_steps, chunk, guard)
-    return _beam_results(ws, off, N, K, d[0].P, t, nwords, guard, max_steps), t
+    # with options: the _opt form of the four calls, the options struct after alpha_member; in groups: the _div form
+    sfx, opt, noff = _search_form(options, groups, diversity, d[0].V, beam_size, max_steps, int(end))
+    ws, off, nwords, t = _run_on_device("scnattn_ensemble_%s" + sfx, (M, d, K, max_steps, alpha_member, *opt), noff,
+                                        (w, ptr(enc), tg, int(start)), (w, ptr(enc), cw, mode, int(end)), stream_of(enc),
+                                        dev, max_steps, chunk, guard)
+    return _beam_results(ws, off, N, K, d[0].P, t, nwords, guard, max_steps, groups=int(groups)), t
 
 
 # ----------------------------------------------------------------------------------------------

@@ -33,7 +33,8 @@ class Captioner:
     (`image_dtype`; the fused stem reads fp32 images in both modes).  `dtype` bf16 runs the trunks under bf16 autocast, as
     `TrainStep` runs them; the decoder stays fp32.  `search_options`: a `models.decoders.SearchOptions` handed to
     `sample_batch` (n-gram blocking, minimum length, banned tokens, length penalty); None: the reference's search.
-    `captioner.sample(images, samples=3, top_k=..., top_p=...)`: several sampled captions per image (below)."""
+    `captioner.sample(images, samples=3, top_k=..., top_p=...)`: several sampled captions per image (below);
+    `captioner.diverse(images, groups=3, beam_size=2, diversity=0.5)`: several captions per image by diverse beam search."""
 
     def __init__(self, encoder, decoder, word_map, tagger=None, beam_size=5, dtype=torch.float32,
                  mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD, size=None, image_dtype=torch.float32,
@@ -115,6 +116,36 @@ class Captioner:
                 seq = host[r, :int(host[r, L])].tolist()
                 recs.append({"tokens": seq, "words": [self.rev_word_map[w] for w in seq if w not in self.skip],
                              "logp": float(logp[r])})
+            out.append(recs)
+        return out
+
+    @torch.no_grad()
+    def diverse(self, images, groups=3, beam_size=2, diversity=0.5):
+        """Several different captions per image by DIVERSE beam search instead of sampling: the trunks and the batch path
+        of `__call__`, then ONE `decoder.sample_groups` (one search on the device, one download).  `groups` groups of
+        `beam_size` beams each (groups x beam_size <= 8); a group pays `diversity` for every word an earlier group picked at
+        the same step.  `search_options` are honoured.
+        -> per image a list of `groups` records
+            group   0 .. groups - 1
+            tokens  the group's caption as `__call__` returns it (<start>, the words, <end> unless cut off)
+            words   the same without <start>, <end>, <pad>, through the reversed word map
+            score   the caption's sum of log-probabilities (nothing of the penalty is in it)
+        groups = 1: the one record holds `__call__`'s caption."""
+        if not hasattr(self.decoder, "sample_groups"):
+            raise ValueError("Captioner.diverse: a %s has no sample_groups" % type(self.decoder).__name__)
+        from models.decoders._common import check_groups_args
+        check_groups_args(beam_size, groups, diversity, len(self.word_map), who="Captioner.diverse")
+        with torch.cuda.device(self.device):
+            encoder_out, tags = self._encode(images, self.needs_tags)
+            results = self.decoder.sample_groups(beam_size, groups, diversity, self.word_map, encoder_out, tags,
+                                                 options=self.search_options, with_scores=True)
+        out = []
+        for per_image in results:
+            recs = []
+            for g, (res, score) in enumerate(per_image):
+                seq = res[0] if self.has_alphas else res
+                recs.append({"group": g, "tokens": seq, "words": [self.rev_word_map[w] for w in seq if w not in self.skip],
+                             "score": score})
             out.append(recs)
         return out
 

@@ -11,7 +11,12 @@ the median is reported.  Prints one JSON line per side and one for the ratio.  N
     python tools/beam_bench.py --side batched --end-bias -30 [--no-repeat-ngram 3 --ban-unk] [--min-length N]
 
 One side alone; with --end-bias -30 nothing completes and every search runs all 51 steps, which makes the plain search
-and the search with options comparable per step."""
+and the search with options comparable per step.
+
+    python tools/beam_bench.py --side batched --end-bias -30 --beam 2 --groups 3 --diversity 0.5
+
+The diverse search: `--groups` groups of `--beam` beams each, to be set beside the plain search at the same
+total (`--beam 6`)."""
 import argparse
 import json
 import os
@@ -55,6 +60,8 @@ def side(args):
 
     def run():
         with torch.no_grad():
+            if args.side == "batched" and args.groups:     # the first group's caption stands for the image
+                return [r[0][0] for r in m.sample_groups(args.beam, args.groups, args.diversity, wm, enc, tags, **kw)]
             if args.side == "batched":
                 return [r[0] for r in m.sample_batch(args.beam, wm, enc, tags, **kw)]
             return [m.sample(args.beam, wm, enc[i:i + 1], tags[i:i + 1])[0] for i in range(args.images)]
@@ -71,7 +78,8 @@ def side(args):
         ms.append(a.elapsed_time(b))
     med = statistics.median(ms)
     lens = [len(s) for s in seqs]
-    print(json.dumps({"side": args.side, "images": args.images, "beam": args.beam, "median_ms": round(med, 3),
+    print(json.dumps({"side": args.side, "images": args.images, "beam": args.beam, "groups": args.groups,
+                      "diversity": args.diversity, "median_ms": round(med, 3),
                       "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "captions_per_s": round(args.images * 1e3 / med, 2),
                       "options": repr(kw.get("options")), "ms_per_step_of_longest": round(med / (max(lens) - 1), 4),
                       "steps_longest": max(lens) - 1, "lengths": sorted(lens), "digest": hash(tuple(map(tuple, seqs))) & 0xffffffff}))
@@ -89,6 +97,8 @@ def main():
     ap.add_argument("--no-repeat-ngram", type=int, default=0)      # search options (batched side only)
     ap.add_argument("--min-length", type=int, default=0)
     ap.add_argument("--ban-unk", action="store_true")
+    ap.add_argument("--groups", type=int, default=0)               # diverse search (batched side only):
+    ap.add_argument("--diversity", type=float, default=0.5)        # --groups groups of --beam beams; 0: the plain search
     ap.add_argument("--side", choices=["batched", "loop"])
     ap.add_argument("--out")
     args = ap.parse_args()
