@@ -26,6 +26,9 @@ extern "C" {
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
+                               + constrained beam search: required words, beam banks (scnattn_constraints, scnattn_beam_*_con,
+                               scnattn_ensemble_*_con, scnattn_beam_row_topk_con, scnattn_beam_row_topk_ens_con, scnattn_beam_merge_banks; new
+                               symbols only, the version stays);
                                + diverse beam search: groups of beams, a Hamming penalty (scnattn_diversity, scnattn_beam_*_div,
                                scnattn_ensemble_*_div, scnattn_beam_merge_groups, scnattn_beam_row_topk_groups; new symbols only, the
                                version stays);
@@ -358,6 +361,93 @@ int scnattn_beam_merge_groups(void* stream, int N, int K, int Kg, float penalty,
                               const float* candv, const int32_t* candi, void* const* state);
 int scnattn_beam_row_topk_groups(void* stream, int N, int K, int Kg, int V, const float* logits, long ld, const float* scores,
                                  const int32_t* nsrc, float* outv, int32_t* outi, int force_passes);
+/* ---- CONSTRAINED beam search: required words, beam banks (Anderson et al. 2017; Post & Vilar 2018) ----------
+ * The reference has no such search; the semantics are this library's.  "The search order" is the order above: value
+ * descending, flat index j*V + v ascending.
+ *   Per image n a list req[n] of C_n REQUIRED words, 0 <= C_n <= SCNATTN_MAX_REQUIRED = 4, distinct token ids in [0, V), C_n
+ *   free per image: int32 [N][4], the C_n words first, padded with -1.
+ *   STATE.  Every slot carries met, the bitmask of the image's required words that occur in its history (bit c: req[n][c]);
+ *   it starts at 0.  bank(slot) = popcount(met).  A child's mask is met(parent) | bit(c) when its word is req[n][c], else
+ *   met(parent).
+ *   ROW SELECTION of a live row (n, j) at step t.  The row's ORDINARY candidates are all words except what the options
+ *   exclude, the row's UNMET required words, and <end> unless the row has met all C_n words: a caption cannot finish with a
+ *   requirement open.  The kernel emits the row's top K ordinary candidates, as above, and separately 4 REQUIRED candidates:
+ *   entry c is (score[j] + c_v(req[n][c]), req[n][c]) when c < C_n, c is unmet in the row and the options do not exclude the
+ *   word (the n-gram rule can), else (-inf, -1).  The value is computed by the expression the K rounds use for that word, to
+ *   the bit.  NOTHING IS RENORMALISED: scores stay sums of the model's log-probabilities.
+ *   MERGE of image n.  An ordinary candidate of row j lies in bank popcount(met_j), a required one in bank popcount(met_j) + 1;
+ *   within a bank candidates are in the search order.  The kk picks are made ROUND-ROBIN over the banks: visit b = C_n,
+ *   C_n - 1, .., 0, then again from C_n; at each visit take the bank's best candidate not yet picked, if it has one; stop at
+ *   kk picks.  The picked set is then arranged in the search order, and in that order everything is as in _merge: <end> picks
+ *   are recorded as completed (the running best replaced only by a strictly greater score), the others compacted to slots
+ *   0 .. nopen-1 with their new met, dead slots get slot 0's copy.
+ *   Why K ordinary candidates per row are enough: a bank receives at most kk <= K picks, a row's ordinary candidates all lie
+ *   in ONE bank, and a bank's picks are a prefix of its order; so whatever is picked from a row lies within that row's top K
+ *   ordinary candidates, and its required candidates are all emitted.
+ *   STEP LIMIT.  An image with no completed beam after max_steps falls back to the open beam with the largest popcount(met),
+ *   ties to the higher score, then to the lower slot (C_n = 0: the fallback above); the caller reads scores / met.  Beams that
+ *   can no longer satisfy their requirements in the steps left are not pruned; the result reports what was met.
+ *   C_n = 0 for every image is the search above BIT FOR BIT (one bank, nothing extra excluded, the picks are the top kk), and
+ *   images are independent: an image with an empty list in a mixed batch gets exactly its plain result.
+ *   Search options compose (the exclusions are the union; a length penalty chooses among finished beams, all of which satisfy
+ *   the requirements), as does the ensemble (the selection kernel is shared).  Groups (_div) do NOT compose, and multi-word
+ *   phrases are out of scope.  The launches per step are those of the search above: the selection runs in its constrained
+ *   flavour and _merge_banks replaces _merge.
+ *   _workspace_con / _layout_con / _init_con / _steps_con   the four calls of each search with `opt` (may be NULL: no options)
+ *       and `con` after max_steps (the ensemble: after alpha_member); the same opt / con in all four.  con->required is a HOST
+ *       array that every call checks and _init_con copies into the workspace (it returns after the copy).  _layout_con writes
+ *       SCNATTN_BEAM_NOFF_CON offsets: those of _layout_opt (13: -1 without options), then 14 met int[N*K] (the masks of the
+ *       slots after the last step) and 15 the required table int[N][4].
+ *   scnattn_beam_row_topk_con / _row_topk_ens_con   the selection alone for step t: _row_topk_opt / _row_topk_ens_opt (opt
+ *       may be NULL) with required int[N][4] and met int[N*K] ON THE DEVICE and the outputs reqv f32 / reqi int [N*K][4].
+ *       Rows of dead slots are neither read nor written.
+ *   scnattn_beam_merge_banks   the merge alone, on the state arrays a _layout_con describes (state: the 12 pointers of
+ *       scnattn_beam_merge) with met int[N*K] and required int[N][4] on the device.
+ * Refused (-1): con NULL or without a table, n_images != B, a required word equal to <start> (checked by _init_con), <end>
+ * (_steps_con) or con->pad_token, a required word the options ban, a duplicate within an image, an id outside the
+ * vocabulary, a word behind a -1 of its row (more than 4 words cannot be stated), K outside [1, 8], unless
+ *       V - n_banned - 1 - (no_repeat_ngram >= 1 ? max_steps : 0) - 4 >= K,
+ * and whatever the searches above refuse. */
+#define SCNATTN_MAX_REQUIRED 4
+#define SCNATTN_BEAM_NOFF_CON 16
+typedef struct {
+    int32_t n_images;           /* must equal dims.B */
+    int32_t pad_token;          /* <pad>, refused as a required word; -1: not stated */
+    const int32_t* required;    /* HOST int32 [n_images][4]: the C_n words of image n, then -1 */
+} scnattn_constraints;
+int scnattn_beam_workspace_con(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                               const scnattn_constraints* con, size_t* bytes);
+int scnattn_beam_layout_con(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                            const scnattn_constraints* con, long* offsets);
+int scnattn_beam_init_con(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                          const scnattn_constraints* con, const scnattn_params* w, const float* enc, const float* tags,
+                          int start_token, float* ws);
+int scnattn_beam_steps_con(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                           const scnattn_constraints* con, const scnattn_params* w, const float* enc, int end_token, int t0,
+                           int n_steps, float* ws);
+int scnattn_ensemble_workspace_con(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                   const scnattn_search_options* opt, const scnattn_constraints* con, size_t* bytes);
+int scnattn_ensemble_layout_con(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                const scnattn_search_options* opt, const scnattn_constraints* con, long* offsets);
+int scnattn_ensemble_init_con(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                              const scnattn_search_options* opt, const scnattn_constraints* con, const scnattn_params* w,
+                              const float* enc, const float* const* tags, int start_token, float* ws);
+int scnattn_ensemble_steps_con(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                               const scnattn_search_options* opt, const scnattn_constraints* con, const scnattn_params* w,
+                               const float* enc, const float* member_w, int mode, int end_token, int t0, int n_steps,
+                               float* ws);
+int scnattn_beam_row_topk_con(void* stream, int N, int K, int V, const float* logits, long ld, const float* scores,
+                              const int32_t* nsrc, const scnattn_search_options* opt, int end_token, int t,
+                              const int32_t* hist, int max_steps, const int32_t* required, const int32_t* met, float* outv,
+                              int32_t* outi, float* reqv, int32_t* reqi, int force_passes);
+int scnattn_beam_row_topk_ens_con(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
+                                  const float* w, int mode, const float* scores, const int32_t* nsrc,
+                                  const scnattn_search_options* opt, int end_token, int t, const int32_t* hist,
+                                  int max_steps, const int32_t* required, const int32_t* met, float* outv, int32_t* outi,
+                                  float* reqv, int32_t* reqi, int force_passes);
+int scnattn_beam_merge_banks(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
+                             const float* reqv, const int32_t* reqi, const int32_t* required, int32_t* met,
+                             void* const* state);
 /* ---- sampled rollouts for self-critical training (csrc/rollout.hip, the driver beside the search's) ---------------------
  * The set-up and the decode step of the search above over the same N*K rows, but the K slots of an image are INDEPENDENT
  * captions: nothing is compacted, the state carries over slot for slot, and after fc one token per open row is picked:

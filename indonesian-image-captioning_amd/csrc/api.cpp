@@ -36,17 +36,17 @@ int seq_bwd(hipStream_t st, const scnattn_dims* d, const scnattn_params* w, cons
             const float* saved, float* scratch, const float* dpreds, const float* dalphas, const scnattn_params* g,
             float* denc, float* dtags, const scnattn_pool* pool);
 // the one search driver (beam_search.cpp); o: the search options, null for a search without
-// v: the diversity of a search in groups, null for a search without
+// v: the diversity of a search in groups, null for a search without; cn: the constraints of a constrained search, likewise
 int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                     const scnattn_diversity* v, int K, int max_steps, size_t* bytes);
+                     const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, size_t* bytes);
 int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                  const scnattn_diversity* v, int K, int max_steps, long* off);
+                  const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, long* off);
 int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
-                const float* const* tags, int start_token, float* ws);
+                const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, const scnattn_params* w,
+                const float* enc, const float* const* tags, int start_token, float* ws);
 int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                 const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
-                 const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws);
+                 const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, const scnattn_params* w,
+                 const float* enc, const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws);
 // filtered: the _f form (f is then checked and the workspace holds the nkeep records); else f is ignored
 int rollout_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
                       bool filtered, size_t* bytes);
@@ -109,26 +109,26 @@ int scnattn_profile_collect(double* out6) {
     return profile_collect(out6);
 }
 
-// The search entry points over the one driver (sixteen here, the eight _div forms below).  The single search is the one-member ensemble of weight 1 in mode 0
+// The search entry points over the one driver (sixteen here, the eight _div and the eight _con forms below).  The single search is the one-member ensemble of weight 1 in mode 0
 // that records its attention maps when it has any; the _opt forms are the calls whose options may not be NULL.
 static int alpha_of(const scnattn_dims* d) { return d && d->has_att ? 0 : -1; }
 static const float k_one[1] = {1.f};
 static int no_options() { SCN_ARG(false, "search options are NULL"); return -1; }
 
 int scnattn_beam_workspace(const scnattn_dims* d, int K, int max_steps, size_t* bytes) {
-    return search_workspace(1, d, alpha_of(d), nullptr, nullptr, K, max_steps, bytes);
+    return search_workspace(1, d, alpha_of(d), nullptr, nullptr, nullptr, K, max_steps, bytes);
 }
 int scnattn_beam_layout(const scnattn_dims* d, int K, int max_steps, long* offsets) {
-    return search_layout(1, d, alpha_of(d), nullptr, nullptr, K, max_steps, offsets);
+    return search_layout(1, d, alpha_of(d), nullptr, nullptr, nullptr, K, max_steps, offsets);
 }
 int scnattn_beam_init(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                       const float* tags, int start_token, float* ws) {
-    return search_init(ST(stream), 1, d, alpha_of(d), nullptr, nullptr, K, max_steps, w, enc, tags ? &tags : nullptr,
+    return search_init(ST(stream), 1, d, alpha_of(d), nullptr, nullptr, nullptr, K, max_steps, w, enc, tags ? &tags : nullptr,
                        start_token, ws);
 }
 int scnattn_beam_steps(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_params* w, const float* enc,
                        int end_token, int t0, int n_steps, float* ws) {
-    return search_steps(ST(stream), 1, d, alpha_of(d), nullptr, nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0,
+    return search_steps(ST(stream), 1, d, alpha_of(d), nullptr, nullptr, nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0,
                         n_steps, ws);
 }
 int scnattn_beam_attn_scores(void* stream, int N, int K, int P, int A, const float* att1, const float* att2, int nslab,
@@ -162,19 +162,19 @@ int scnattn_beam_row_topk_ens(void* stream, int N, int K, int V, int M, const fl
     return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, nullptr, outv, outi, force_passes);
 }
 int scnattn_ensemble_workspace(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, size_t* bytes) {
-    return search_workspace(M, dims, alpha_member, nullptr, nullptr, K, max_steps, bytes);
+    return search_workspace(M, dims, alpha_member, nullptr, nullptr, nullptr, K, max_steps, bytes);
 }
 int scnattn_ensemble_layout(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member, long* offsets) {
-    return search_layout(M, dims, alpha_member, nullptr, nullptr, K, max_steps, offsets);
+    return search_layout(M, dims, alpha_member, nullptr, nullptr, nullptr, K, max_steps, offsets);
 }
 int scnattn_ensemble_init(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                           const scnattn_params* w, const float* enc, const float* const* tags, int start_token, float* ws) {
-    return search_init(ST(stream), M, dims, alpha_member, nullptr, nullptr, K, max_steps, w, enc, tags, start_token, ws);
+    return search_init(ST(stream), M, dims, alpha_member, nullptr, nullptr, nullptr, K, max_steps, w, enc, tags, start_token, ws);
 }
 int scnattn_ensemble_steps(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                            const scnattn_params* w, const float* enc, const float* member_w, int mode, int end_token, int t0,
                            int n_steps, float* ws) {
-    return search_steps(ST(stream), M, dims, alpha_member, nullptr, nullptr, K, max_steps, w, enc, member_w, mode, end_token, t0,
+    return search_steps(ST(stream), M, dims, alpha_member, nullptr, nullptr, nullptr, K, max_steps, w, enc, member_w, mode, end_token, t0,
                         n_steps, ws);
 }
 int scnattn_beam_merge(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
@@ -193,41 +193,41 @@ int scnattn_beam_advance(void* stream, int N, int K, int D, int M, int V, const 
 }
 
 int scnattn_beam_workspace_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, size_t* bytes) {
-    return opt ? search_workspace(1, d, alpha_of(d), opt, nullptr, K, max_steps, bytes) : no_options();
+    return opt ? search_workspace(1, d, alpha_of(d), opt, nullptr, nullptr, K, max_steps, bytes) : no_options();
 }
 int scnattn_beam_layout_opt(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt, long* offsets) {
-    return opt ? search_layout(1, d, alpha_of(d), opt, nullptr, K, max_steps, offsets) : no_options();
+    return opt ? search_layout(1, d, alpha_of(d), opt, nullptr, nullptr, K, max_steps, offsets) : no_options();
 }
 int scnattn_beam_init_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                           const scnattn_params* w, const float* enc, const float* tags, int start_token, float* ws) {
-    return opt ? search_init(ST(stream), 1, d, alpha_of(d), opt, nullptr, K, max_steps, w, enc, tags ? &tags : nullptr,
+    return opt ? search_init(ST(stream), 1, d, alpha_of(d), opt, nullptr, nullptr, K, max_steps, w, enc, tags ? &tags : nullptr,
                              start_token, ws)
                : no_options();
 }
 int scnattn_beam_steps_opt(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                            const scnattn_params* w, const float* enc, int end_token, int t0, int n_steps, float* ws) {
-    return opt ? search_steps(ST(stream), 1, d, alpha_of(d), opt, nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0,
+    return opt ? search_steps(ST(stream), 1, d, alpha_of(d), opt, nullptr, nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0,
                               n_steps, ws)
                : no_options();
 }
 int scnattn_ensemble_workspace_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                    const scnattn_search_options* opt, size_t* bytes) {
-    return opt ? search_workspace(M, dims, alpha_member, opt, nullptr, K, max_steps, bytes) : no_options();
+    return opt ? search_workspace(M, dims, alpha_member, opt, nullptr, nullptr, K, max_steps, bytes) : no_options();
 }
 int scnattn_ensemble_layout_opt(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                 const scnattn_search_options* opt, long* offsets) {
-    return opt ? search_layout(M, dims, alpha_member, opt, nullptr, K, max_steps, offsets) : no_options();
+    return opt ? search_layout(M, dims, alpha_member, opt, nullptr, nullptr, K, max_steps, offsets) : no_options();
 }
 int scnattn_ensemble_init_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                               const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
                               const float* const* tags, int start_token, float* ws) {
-    return opt ? search_init(ST(stream), M, dims, alpha_member, opt, nullptr, K, max_steps, w, enc, tags, start_token, ws)
+    return opt ? search_init(ST(stream), M, dims, alpha_member, opt, nullptr, nullptr, K, max_steps, w, enc, tags, start_token, ws)
                : no_options();
 }
 int scnattn_ensemble_steps_opt(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                const scnattn_search_options* opt, const scnattn_params* w, const float* enc,
                                const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws) {
-    return opt ? search_steps(ST(stream), M, dims, alpha_member, opt, nullptr, K, max_steps, w, enc, member_w, mode, end_token,
+    return opt ? search_steps(ST(stream), M, dims, alpha_member, opt, nullptr, nullptr, K, max_steps, w, enc, member_w, mode, end_token,
                               t0, n_steps, ws)
                : no_options();
 }
@@ -236,45 +236,45 @@ static int no_diversity() { SCN_ARG(false, "the diversity is NULL"); return -1; 
 
 int scnattn_beam_workspace_div(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                                const scnattn_diversity* div, size_t* bytes) {
-    return div ? search_workspace(1, d, alpha_of(d), opt, div, K, max_steps, bytes) : no_diversity();
+    return div ? search_workspace(1, d, alpha_of(d), opt, div, nullptr, K, max_steps, bytes) : no_diversity();
 }
 int scnattn_beam_layout_div(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                             const scnattn_diversity* div, long* offsets) {
-    return div ? search_layout(1, d, alpha_of(d), opt, div, K, max_steps, offsets) : no_diversity();
+    return div ? search_layout(1, d, alpha_of(d), opt, div, nullptr, K, max_steps, offsets) : no_diversity();
 }
 int scnattn_beam_init_div(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                           const scnattn_diversity* div, const scnattn_params* w, const float* enc, const float* tags,
                           int start_token, float* ws) {
-    return div ? search_init(ST(stream), 1, d, alpha_of(d), opt, div, K, max_steps, w, enc, tags ? &tags : nullptr,
+    return div ? search_init(ST(stream), 1, d, alpha_of(d), opt, div, nullptr, K, max_steps, w, enc, tags ? &tags : nullptr,
                              start_token, ws)
                : no_diversity();
 }
 int scnattn_beam_steps_div(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
                            const scnattn_diversity* div, const scnattn_params* w, const float* enc, int end_token, int t0,
                            int n_steps, float* ws) {
-    return div ? search_steps(ST(stream), 1, d, alpha_of(d), opt, div, K, max_steps, w, enc, k_one, 0, end_token, t0,
+    return div ? search_steps(ST(stream), 1, d, alpha_of(d), opt, div, nullptr, K, max_steps, w, enc, k_one, 0, end_token, t0,
                               n_steps, ws)
                : no_diversity();
 }
 int scnattn_ensemble_workspace_div(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                    const scnattn_search_options* opt, const scnattn_diversity* div, size_t* bytes) {
-    return div ? search_workspace(M, dims, alpha_member, opt, div, K, max_steps, bytes) : no_diversity();
+    return div ? search_workspace(M, dims, alpha_member, opt, div, nullptr, K, max_steps, bytes) : no_diversity();
 }
 int scnattn_ensemble_layout_div(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                 const scnattn_search_options* opt, const scnattn_diversity* div, long* offsets) {
-    return div ? search_layout(M, dims, alpha_member, opt, div, K, max_steps, offsets) : no_diversity();
+    return div ? search_layout(M, dims, alpha_member, opt, div, nullptr, K, max_steps, offsets) : no_diversity();
 }
 int scnattn_ensemble_init_div(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                               const scnattn_search_options* opt, const scnattn_diversity* div, const scnattn_params* w,
                               const float* enc, const float* const* tags, int start_token, float* ws) {
-    return div ? search_init(ST(stream), M, dims, alpha_member, opt, div, K, max_steps, w, enc, tags, start_token, ws)
+    return div ? search_init(ST(stream), M, dims, alpha_member, opt, div, nullptr, K, max_steps, w, enc, tags, start_token, ws)
                : no_diversity();
 }
 int scnattn_ensemble_steps_div(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
                                const scnattn_search_options* opt, const scnattn_diversity* div, const scnattn_params* w,
                                const float* enc, const float* member_w, int mode, int end_token, int t0, int n_steps,
                                float* ws) {
-    return div ? search_steps(ST(stream), M, dims, alpha_member, opt, div, K, max_steps, w, enc, member_w, mode, end_token,
+    return div ? search_steps(ST(stream), M, dims, alpha_member, opt, div, nullptr, K, max_steps, w, enc, member_w, mode, end_token,
                               t0, n_steps, ws)
                : no_diversity();
 }
@@ -294,6 +294,65 @@ int scnattn_beam_row_topk_groups(void* stream, int N, int K, int Kg, int V, cons
     SCN_ARG(logits && scores && nsrc && outv && outi && ld >= V, "scnattn_beam_row_topk_groups: bad argument");
     return beam_row_topk_ens(ST(stream), N, K, V, 1, EnsRows{{logits}, {ld}, {1.f}}, 0, scores, nsrc, nullptr, outv, outi,
                              force_passes, Kg);
+}
+
+// The _con forms: opt may be NULL, con may not.
+static int no_constraints() { SCN_ARG(false, "the constraints are NULL"); return -1; }
+
+int scnattn_beam_workspace_con(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                               const scnattn_constraints* con, size_t* bytes) {
+    return con ? search_workspace(1, d, alpha_of(d), opt, nullptr, con, K, max_steps, bytes) : no_constraints();
+}
+int scnattn_beam_layout_con(const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                            const scnattn_constraints* con, long* offsets) {
+    return con ? search_layout(1, d, alpha_of(d), opt, nullptr, con, K, max_steps, offsets) : no_constraints();
+}
+int scnattn_beam_init_con(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                          const scnattn_constraints* con, const scnattn_params* w, const float* enc, const float* tags,
+                          int start_token, float* ws) {
+    return con ? search_init(ST(stream), 1, d, alpha_of(d), opt, nullptr, con, K, max_steps, w, enc, tags ? &tags : nullptr,
+                             start_token, ws)
+               : no_constraints();
+}
+int scnattn_beam_steps_con(void* stream, const scnattn_dims* d, int K, int max_steps, const scnattn_search_options* opt,
+                           const scnattn_constraints* con, const scnattn_params* w, const float* enc, int end_token, int t0,
+                           int n_steps, float* ws) {
+    return con ? search_steps(ST(stream), 1, d, alpha_of(d), opt, nullptr, con, K, max_steps, w, enc, k_one, 0, end_token, t0,
+                              n_steps, ws)
+               : no_constraints();
+}
+int scnattn_ensemble_workspace_con(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                   const scnattn_search_options* opt, const scnattn_constraints* con, size_t* bytes) {
+    return con ? search_workspace(M, dims, alpha_member, opt, nullptr, con, K, max_steps, bytes) : no_constraints();
+}
+int scnattn_ensemble_layout_con(int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                                const scnattn_search_options* opt, const scnattn_constraints* con, long* offsets) {
+    return con ? search_layout(M, dims, alpha_member, opt, nullptr, con, K, max_steps, offsets) : no_constraints();
+}
+int scnattn_ensemble_init_con(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                              const scnattn_search_options* opt, const scnattn_constraints* con, const scnattn_params* w,
+                              const float* enc, const float* const* tags, int start_token, float* ws) {
+    return con ? search_init(ST(stream), M, dims, alpha_member, opt, nullptr, con, K, max_steps, w, enc, tags, start_token, ws)
+               : no_constraints();
+}
+int scnattn_ensemble_steps_con(void* stream, int M, const scnattn_dims* dims, int K, int max_steps, int alpha_member,
+                               const scnattn_search_options* opt, const scnattn_constraints* con, const scnattn_params* w,
+                               const float* enc, const float* member_w, int mode, int end_token, int t0, int n_steps,
+                               float* ws) {
+    return con ? search_steps(ST(stream), M, dims, alpha_member, opt, nullptr, con, K, max_steps, w, enc, member_w, mode,
+                              end_token, t0, n_steps, ws)
+               : no_constraints();
+}
+int scnattn_beam_merge_banks(void* stream, int N, int K, int V, int end_token, int t, const float* candv, const int32_t* candi,
+                             const float* reqv, const int32_t* reqi, const int32_t* required, int32_t* met,
+                             void* const* state) {
+    if (!state) { set_error("scnattn_beam_merge_banks: state is NULL"); return -1; }
+    if (N <= 0 || K < 1 || K > SCN_MAX_BEAM) { set_error("scnattn_beam_merge_banks: bad N / beam size"); return -1; }
+    BeamState s{N * K, (float*)state[6], (int*)state[1], (int*)state[2], (int*)state[3], (int*)state[4],
+                (float*)state[5], (int*)state[0], (float*)state[7], (int*)state[8], (int*)state[9], (int*)state[10],
+                (int*)state[11]};
+    s.met = met;
+    return beam_merge_banks(ST(stream), N, K, V, end_token, t, candv, candi, reqv, reqi, required, s);
 }
 
 // what step t of a search with `opt` excludes, for the selection kernel alone; the launcher checks the ranges
@@ -334,6 +393,37 @@ int scnattn_beam_row_topk_ens_opt(void* stream, int N, int K, int V, int M, cons
     SCN_TRY(excl_of(opt, end_token, t, hist, max_steps, x));
     SCN_ARG(end_token < V, "end token outside the vocabulary");
     return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, &x, outv, outi, force_passes);
+}
+// the selection of a constrained search alone: opt may be NULL (nothing excluded); required / met on the device
+static int excl_con_of(const scnattn_search_options* opt, int end_token, int t, const int32_t* hist, int max_steps, BeamExcl& x) {
+    if (opt) return excl_of(opt, end_token, t, hist, max_steps, x);
+    x = BeamExcl{};
+    x.t = t;
+    x.T = max_steps;
+    x.end_excl = -1;
+    return 0;
+}
+int scnattn_beam_row_topk_con(void* stream, int N, int K, int V, const float* logits, long ld, const float* scores,
+                              const int32_t* nsrc, const scnattn_search_options* opt, int end_token, int t,
+                              const int32_t* hist, int max_steps, const int32_t* required, const int32_t* met, float* outv,
+                              int32_t* outi, float* reqv, int32_t* reqi, int force_passes) {
+    BeamExcl x;
+    SCN_TRY(excl_con_of(opt, end_token, t, hist, max_steps, x));
+    const EnsRows e{{logits}, {ld}, {1.f}};
+    const BeamCon c{required, met, end_token, reqv, reqi};
+    return beam_row_topk_ens(ST(stream), N, K, V, 1, e, 0, scores, nsrc, &x, outv, outi, force_passes, 0, &c);
+}
+int scnattn_beam_row_topk_ens_con(void* stream, int N, int K, int V, int M, const float* const* logits, const long* ld,
+                                  const float* w, int mode, const float* scores, const int32_t* nsrc,
+                                  const scnattn_search_options* opt, int end_token, int t, const int32_t* hist,
+                                  int max_steps, const int32_t* required, const int32_t* met, float* outv, int32_t* outi,
+                                  float* reqv, int32_t* reqi, int force_passes) {
+    EnsRows e;
+    SCN_TRY(rows_of(M, logits, ld, w, e));
+    BeamExcl x;
+    SCN_TRY(excl_con_of(opt, end_token, t, hist, max_steps, x));
+    const BeamCon c{required, met, end_token, reqv, reqi};
+    return beam_row_topk_ens(ST(stream), N, K, V, M, e, mode, scores, nsrc, &x, outv, outi, force_passes, 0, &c);
 }
 int scnattn_beam_advance_opt(void* stream, int N, int K, int D, int M, int V, int t, int max_steps, const float* hs,
                              const float* cs, const int32_t* parent_t, const int32_t* token_t, const float* table,

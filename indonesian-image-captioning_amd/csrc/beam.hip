@@ -16,6 +16,10 @@
 //                      image in order, each ranking its candidates after a penalty per word the groups before it picked at
 //                      this step; nsrc / kk / ncomp / best_* are then per (image, group) and the row selection decides
 //                      liveness per group (its Kg parameter)
+//   beam_merge_banks   the merge of a CONSTRAINED search: the selection (its CON flavour) also emits per row
+//                      the image's unmet required words as 4 candidates of their own; the nsrc x (K + 4) candidates fall
+//                      into banks by the number of required words met, the kk picks go round-robin over the banks, and the
+//                      per-slot mask `met` is written here, where the parent and the word are both known
 //   beam_advance       h / c gathered from the parent slot, next input embedding gathered from the table; with search
 //                      options (beam_advance_opt, the same kernel) also the per-beam word history int32 [N*K][max_steps],
 //                      gathered from the parent slot and extended
@@ -361,9 +365,15 @@ struct NoExcl {};       // what the kernel without exclusions takes in place of 
 // are the bits of EXCL = false.  The staged and the unstaged path read the same bitmap.  Without EXCL neither the bitmap nor
 // the history takes LDS.
 // Kg: the slots per group (K % Kg == 0, nsrc is [N * K/Kg]); Kg = K: no groups, nsrc [N] and the live rows a prefix.
-template <bool STAGED, bool EXCL>
+// CON (a constrained search; needs EXCL): once the options' bitmap is complete every thread notes which of
+// the image's required words the row may still offer (unmet in the row, not excluded by the options), then the unmet
+// required words -- and <end> while one is unmet -- are set in the bitmap as well, so the K rounds run over the row's
+// ORDINARY candidates; the 4 required candidates are written from the same expression the rounds use for a word (from buf
+// when STAGED, else from EnsGroup::combine: the same bits).  Without CON nothing of this is compiled.
+template <bool STAGED, bool EXCL, bool CON = false>
 __global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int Kg, int V, int M, int mode, EnsRows e, unsigned vecmask,
-                                                                std::conditional_t<EXCL, BeamExcl, NoExcl> x,
+                                                                std::conditional_t<CON, BeamExclCon,
+                                                                                   std::conditional_t<EXCL, BeamExcl, NoExcl>> x,
                                                                 const float* __restrict__ scores,
                                                                 const int* __restrict__ nsrc, float* __restrict__ outv,
                                                                 int* __restrict__ outi) {
@@ -394,6 +404,30 @@ __global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int Kg, i
         }
     }
     if constexpr (EXCL) excl_fill(x, row, V, bits, reinterpret_cast<int*>(sm + 16 + excl_bitmap_words(V)));
+    int rw[SCN_MAX_REQUIRED];                       // CON: the image's required words, and which of them the row may offer
+    unsigned offered = 0;
+    if constexpr (CON) {
+        const int met = x.c.met[row];
+        int full = 0;
+#pragma unroll
+        for (int c = 0; c < SCN_MAX_REQUIRED; ++c) {
+            rw[c] = x.c.req[n * SCN_MAX_REQUIRED + c];
+            if (rw[c] >= V) rw[c] = -1;
+            if (rw[c] >= 0) full |= 1 << c;
+        }
+        const int unmet = full & ~met;
+        __syncthreads();                            // the options' bitmap is complete
+#pragma unroll
+        for (int c = 0; c < SCN_MAX_REQUIRED; ++c)
+            if (((unmet >> c) & 1) && !excl_test(bits, rw[c])) offered |= 1u << c;
+        __syncthreads();                            // ... and read by everyone before the requirements enter it
+        if (tid == 0) {
+#pragma unroll
+            for (int c = 0; c < SCN_MAX_REQUIRED; ++c)
+                if ((unmet >> c) & 1) excl_set(bits, rw[c], V);
+            if (unmet) excl_set(bits, x.c.end_tok, V);      // a caption cannot finish with a requirement open
+        }
+    }
     if (STAGED) {
         for (int q = tid; q < groups; q += 256) {
             EnsGroup eg;
@@ -405,6 +439,29 @@ __global__ __launch_bounds__(256) void beam_row_topk_ens_kernel(int K, int Kg, i
     }
     if (STAGED || EXCL) __syncthreads();            // buf and the bitmap are complete; uniform over the workgroup
     const float sc = scores[row];
+    if constexpr (CON) {
+        // thread c: required candidate c, the value by the expression of the rounds below
+#pragma unroll
+        for (int c = 0; c < SCN_MAX_REQUIRED; ++c) {
+            if (tid != c) continue;
+            float val = -INFINITY;
+            int wi = -1;
+            if ((offered >> c) & 1u) {
+                wi = rw[c];
+                if (STAGED) {
+                    val = sc + buf[wi];
+                } else {
+                    EnsGroup eg;
+                    eg.load(M, g, wi >> 2, V, vecmask);
+#pragma unroll
+                    for (int cc = 0; cc < 4; ++cc)
+                        if (cc == (wi & 3)) val = sc + eg.combine(M, mode, cc, lse, e);
+                }
+            }
+            x.c.reqv[row * SCN_MAX_REQUIRED + c] = val;
+            x.c.reqi[row * SCN_MAX_REQUIRED + c] = wi;
+        }
+    }
     float pv = INFINITY;
     int pi = -1;
     for (int r = 0; r < K; ++r) {
@@ -590,6 +647,128 @@ __global__ __launch_bounds__(64) void beam_merge_groups_kernel(int K, int Kg, fl
     }
 }
 
+// The merge of a constrained search: two waves per image, one candidate per thread.  Row j of the image
+// brings K + 4 candidates: its K ordinary ones (bank popcount(met_j), the child keeps met_j) and its 4 required ones (entry
+// c with a word: bank popcount(met_j) + 1, the child's mask met_j | 1 << c).  A thread ranks its candidate among those of
+// its bank by counting through LDS and enters the bank's list when it is among the bank's first K; thread 0 then walks the
+// banks round-robin (C_n, C_n - 1, .., 0, and again) for kk picks, puts the picked set into the search order and records it
+// exactly as beam_merge_kernel does, with the children's masks.  Every thread has read its row's met before the first
+// barrier; thread 0 writes met after the second.  C_n = 0: one bank, nothing required, the stores of beam_merge_kernel.
+constexpr int BANK_W = SCN_MAX_BEAM + SCN_MAX_REQUIRED;     // candidates per row at K = 8
+constexpr int BANK_NC = SCN_MAX_BEAM * BANK_W;              // 96 candidates per image at most
+
+__global__ __launch_bounds__(128) void beam_merge_banks_kernel(int K, int V, int end_tok, int t, const float* __restrict__ candv,
+                                                               const int* __restrict__ candi, const float* __restrict__ reqv,
+                                                               const int* __restrict__ reqi, const int* __restrict__ req,
+                                                               BeamState s) {
+    __shared__ float cv[BANK_NC];
+    __shared__ int cf[BANK_NC], cb[BANK_NC], cm[BANK_NC];   // flat index (INT_MAX: no candidate), bank, the child's met
+    __shared__ int bl[SCN_MAX_REQUIRED + 1][SCN_MAX_BEAM];  // a bank's first K candidates in the search order (-1: none)
+    __shared__ int bp[SCN_MAX_REQUIRED + 1], pk[SCN_MAX_BEAM];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const int ns = min(s.nsrc[n], K), k = min(s.kk[n], K);
+    if (k <= 0) return;         // finished image: a no-op
+    const int W = K + SCN_MAX_REQUIRED, nc = K * W;
+    int C = 0;
+#pragma unroll
+    for (int c = 0; c < SCN_MAX_REQUIRED; ++c) C += req[n * SCN_MAX_REQUIRED + c] >= 0;
+    float v = -INFINITY;
+    int flat = INT_MAX, bank = 0;
+    if (tid < nc) {
+        const int j = tid / W, r = tid - j * W;
+        int cmet = 0;
+        if (j < ns) {
+            const long row = (long)n * K + j;
+            const int met = s.met[row] & ((1 << SCN_MAX_REQUIRED) - 1);
+            if (r < K) {
+                v = candv[row * K + r];
+                flat = j * V + candi[row * K + r];
+                bank = __popc(met);
+                cmet = met;
+            } else {
+                const int c = r - K, w = reqi[row * SCN_MAX_REQUIRED + c];
+                if (w >= 0) {
+                    v = reqv[row * SCN_MAX_REQUIRED + c];
+                    flat = j * V + w;
+                    bank = min(__popc(met) + 1, SCN_MAX_REQUIRED);
+                    cmet = met | (1 << c);
+                }
+            }
+        }
+        cv[tid] = v;
+        cf[tid] = flat;
+        cb[tid] = bank;
+        cm[tid] = cmet;
+    }
+    if (tid < (SCN_MAX_REQUIRED + 1) * SCN_MAX_BEAM) (&bl[0][0])[tid] = -1;
+    if (tid <= SCN_MAX_REQUIRED) bp[tid] = 0;
+    __syncthreads();
+    if (flat != INT_MAX) {
+        int rank = 0;
+        for (int l = 0; l < nc; ++l)
+            if (cf[l] != INT_MAX && cb[l] == bank && before(cv[l], cf[l], v, flat)) ++rank;
+        if (rank < K) bl[bank][rank] = tid;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    int np = 0;
+    for (bool any = true; any && np < k;) {         // round-robin over the banks, the highest first
+        any = false;
+        for (int b = C; b >= 0 && np < k; --b) {
+            const int at = bp[b];
+            if (at < K && bl[b][at] >= 0) {
+                pk[np++] = bl[b][at];
+                bp[b] = at + 1;
+                any = true;
+            }
+        }
+    }
+    for (int a = 1; a < np; ++a) {                  // the picked set in the search order
+        const int i = pk[a];
+        int q = a;
+        while (q > 0 && before(cv[i], cf[i], cv[pk[q - 1]], cf[pk[q - 1]])) { pk[q] = pk[q - 1]; --q; }
+        pk[q] = i;
+    }
+    // picks in that order: <end> picks are recorded as completed, the rest compacted to slots 0 .. nopen-1
+    int nopen = 0, ncp = s.ncomp[n], bi = s.best_idx[n];
+    float bs = s.best_score[n];
+    int tok0 = 0, par0 = 0, met0 = 0;
+    const long r0 = (long)n * K;
+    int* token_t = s.token + (long)t * s.R;
+    int* parent_t = s.parent + (long)t * s.R;
+    for (int q = 0; q < np; ++q) {
+        const int i = pk[q], j = i / W, w = cf[i] - j * V;
+        if (w == end_tok) {
+            if (ncp < K) {
+                s.comp_score[r0 + ncp] = cv[i];
+                s.comp_step[r0 + ncp] = t;
+                s.comp_parent[r0 + ncp] = j;
+                if (bi < 0 || cv[i] > bs) { bs = cv[i]; bi = ncp; }     // strictly greater: index(max(...))
+                ++ncp;
+            }
+        } else {
+            if (nopen == 0) { tok0 = w; par0 = j; met0 = cm[i]; }
+            token_t[r0 + nopen] = w;
+            parent_t[r0 + nopen] = j;
+            s.scores[r0 + nopen] = cv[i];
+            s.met[r0 + nopen] = cm[i];
+            ++nopen;
+        }
+    }
+    for (int d = nopen; d < K; ++d) {       // dead slots: a copy of slot 0 (zeros when nothing is open)
+        token_t[r0 + d] = tok0;
+        parent_t[r0 + d] = par0;
+        s.scores[r0 + d] = 0.f;
+        s.met[r0 + d] = met0;
+    }
+    s.ncomp[n] = ncp;
+    s.best_idx[n] = bi;
+    s.best_score[n] = bs;
+    s.nsrc[n] = nopen;
+    s.kk[n] = nopen;
+    if (nopen == 0) atomicAdd(s.open_images, -1);
+}
+
 // h / c gathered from the parent slot, the next input embedding from the table.  With hist_d (search options): also the
 // row's history for step t+1, the parent slot's t words of hist_s, then this step's word.  A dead slot carries slot 0's
 // parent / token records, so it gets slot 0's history.
@@ -690,7 +869,8 @@ int beam_attn_context(hipStream_t st, int N, int K, int P, int E, const float* e
 
 // The one launcher of the selection; x: what the step excludes, null: nothing.
 int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes, int Kg) {
+                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes, int Kg,
+                      const BeamCon* cn) {
     if (N <= 0) return 0;
     SCN_ARG(M >= 1 && M <= SCN_MAX_ENSEMBLE, "beam_row_topk_ens: need 1 <= members <= 4");
     SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K, "beam_row_topk_ens: need 1 <= beam size <= 8 and vocab_size >= beam size");
@@ -710,6 +890,15 @@ int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows&
                 "beam_row_topk_ens: the options may leave a row fewer than beam_size candidates "
                 "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) >= beam_size)");
     }
+    if (cn) {
+        SCN_ARG(x, "beam_row_topk_ens: the constraints need the exclusions (which may exclude nothing)");
+        SCN_ARG(Kg == K, "beam_row_topk_ens: constraints and groups do not compose");
+        SCN_ARG(cn->req && cn->met && cn->reqv && cn->reqi, "beam_row_topk_ens: null constraint operand");
+        SCN_ARG(cn->end_tok >= 0 && cn->end_tok < V, "beam_row_topk_ens: the end token lies outside the vocabulary");
+        SCN_ARG((long)V - x->n_banned - 1 - (x->g >= 1 ? x->T : 0) - SCN_MAX_REQUIRED >= K,
+                "beam_row_topk_ens: options and required words may leave a row fewer than beam_size candidates "
+                "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) - 4 >= beam_size)");
+    }
     unsigned vecmask = 0;
     for (int m = 0; m < M; ++m) {
         SCN_ARG(e.p[m] && e.ld[m] >= V, "beam_row_topk_ens: a member's logits are null or its leading dimension < vocab_size");
@@ -724,6 +913,13 @@ int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows&
     const size_t lds = stage ? staged : fixed;
     dim3 grid(N * K), block(256);
 #define L(STAGED)                                                                                                             \
+    if (cn) {                                                                                                                 \
+        BeamExclCon xc;                                                                                                       \
+        static_cast<BeamExcl&>(xc) = *x;                                                                                      \
+        xc.c = *cn;                                                                                                           \
+        hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, true, true>), grid, block, lds, st, K, Kg, V, M, mode, e,        \
+                           vecmask, xc, scores, nsrc, outv, outi);                                                            \
+    } else                                                                                                                    \
     if (x) hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, true>), grid, block, lds, st, K, Kg, V, M, mode, e, vecmask,   \
                               *x, scores, nsrc, outv, outi);                                                                  \
     else   hipLaunchKernelGGL((beam_row_topk_ens_kernel<STAGED, false>), grid, block, lds, st, K, Kg, V, M, mode, e, vecmask,  \
@@ -752,6 +948,19 @@ int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const fl
                 s.open_images && s.comp_score && s.comp_step && s.comp_parent && s.token && s.parent,
             "beam_merge: bad argument");
     hipLaunchKernelGGL(beam_merge_kernel, dim3(N), dim3(64), 0, st, K, V, end_tok, t, candv, candi, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int beam_merge_banks(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
+                     const float* reqv, const int* reqi, const int* req, const BeamState& s) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= K && t >= 0, "beam_merge_banks: bad beam size / step");
+    SCN_ARG((long)K * V < INT_MAX, "beam_merge_banks: beam size x vocab_size overflows the flat index");
+    SCN_ARG(candv && candi && reqv && reqi && req && s.R == N * K && s.scores && s.nsrc && s.kk && s.ncomp && s.best_idx &&
+                s.best_score && s.open_images && s.comp_score && s.comp_step && s.comp_parent && s.token && s.parent && s.met,
+            "beam_merge_banks: bad argument");
+    hipLaunchKernelGGL(beam_merge_banks_kernel, dim3(N), dim3(128), 0, st, K, V, end_tok, t, candv, candi, reqv, reqi, req, s);
     SCN_LAUNCH_CHECK();
     return 0;
 }

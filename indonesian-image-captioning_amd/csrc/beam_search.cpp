@@ -4,11 +4,13 @@
 // between chunks of steps and the token / parent / alpha records at the end.
 // fp32 only: option "decoder_bf16" is not looked at here.
 //
-// ONE driver (search_workspace / search_layout / search_init / search_steps) serves the twenty-four entry points
-// scnattn_beam_*, scnattn_ensemble_* and their _opt and _div forms (csrc/api.cpp): M decoders step under one search state
-// (DESIGN.md 5m), the single search being M = 1 with weight 1 in mode 0; search options and the diversity
-// of a search in groups are pointers that are null without them.  With a diversity the selection takes the
-// group size, beam_merge_groups replaces beam_merge and the attention kernels take att_live: the same launches.
+// ONE driver (search_workspace / search_layout / search_init / search_steps) serves the thirty-two entry points
+// scnattn_beam_*, scnattn_ensemble_* and their _opt, _div and _con forms (csrc/api.cpp): M decoders step under one search
+// state, the single search being M = 1 with weight 1 in mode 0; search options, the diversity
+// of a search in groups and the constraints of a constrained search are pointers that are null
+// without them.  With a diversity the selection takes the group size, beam_merge_groups replaces beam_merge and the
+// attention kernels take att_live; with constraints the selection runs in its constrained flavour and beam_merge_banks
+// replaces beam_merge: the same launches.
 //
 // Launches per step, all in search_steps: per member the decode part (decode_step; with attention skinny
 // h.[Wd^T|Wbeta^T|Ha], beam_attn_scores, beam_attn_context, skinny z.Wa[M:], skinny emb.Wa[:M], scn_mix_fwd, skinny gates,
@@ -51,6 +53,10 @@ struct SearchWs {
     float* alpha;       // [T][R][P] of alpha_member, or null
     int* hist;          // [2][R][T] with search options, else null
     int G;              // groups of a diverse search; 1 without: the per-group state arrays hold N*G entries
+    // a constrained search, else null: the required candidates [R][4] of the step, the table int [N][4]
+    // (s.met [R] is the per-slot mask)
+    float* reqv;
+    int *reqi, *req;
     size_t state_floats;
     StepWs m[SCN_MAX_ENSEMBLE];
 };
@@ -103,8 +109,9 @@ void carve_step_setup(Carver& c, const scnattn_dims& d, long R, StepWs& b, const
 // In this order: the BeamState fields, alpha, the members' step state, candv / candi, the history, att_live -- which init
 // zero-fills (state_floats) -- then the members' set-up results with the shared split-K scratch.
 // div: a diverse search, whose per-group arrays hold N*G entries and which also keeps att_live [N] (behind the history).
+// con: a constrained search, which keeps met, the required candidates and the table behind those.
 size_t carve_search(int M, const scnattn_dims* d, int K, int T, int alpha_member, bool hist, const scnattn_diversity* div,
-                    float* base, SearchWs& b) {
+                    bool con, float* base, SearchWs& b) {
     Carver c(base);
     const int N = d[0].B, P = d[0].P;
     const long R = (long)N * K;
@@ -133,6 +140,10 @@ size_t carve_search(int M, const scnattn_dims* d, int K, int T, int alpha_member
     b.candi = ints(c.take(sz(R, K)));
     b.hist = hist ? ints(c.take(sz(2, R, T))) : nullptr;
     b.s.att_live = div ? ints(c.take(N)) : nullptr;
+    b.s.met = con ? ints(c.take(R)) : nullptr;
+    b.reqv = con ? c.take(sz(R, SCN_MAX_REQUIRED)) : nullptr;
+    b.reqi = con ? ints(c.take(sz(R, SCN_MAX_REQUIRED))) : nullptr;
+    b.req = con ? ints(c.take(sz(N, SCN_MAX_REQUIRED))) : nullptr;
     b.state_floats = c.off;
     for (int m = 0; m < M; ++m) {
         b.m[m].state_floats = b.state_floats;
@@ -166,6 +177,36 @@ int check_options(const scnattn_search_options* o, int V, int K, int T, int end_
     return 0;
 }
 
+// The refusals of a constrained search (include/scnattn.h); o: the options, null without; start / end < 0: not known to this
+// call.  Reads the HOST table of the constraints.
+int check_constraints(const scnattn_constraints* c, const scnattn_search_options* o, const scnattn_diversity* v, int N, int V,
+                      int K, int T, int start_token, int end_token) {
+    SCN_ARG(c && c->required, "the constraints (or their table of required words) are NULL");
+    SCN_ARG(!v, "constraints and groups do not compose: a search takes required words or a diversity, not both");
+    SCN_ARG(c->n_images == N, "the constraints must hold one row of required words per image");
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM, "beam_size must be in [1, 8]");
+    for (int n = 0; n < N; ++n) {
+        const int32_t* r = c->required + (long)n * SCN_MAX_REQUIRED;
+        bool ended = false;
+        for (int i = 0; i < SCN_MAX_REQUIRED; ++i) {
+            if (r[i] == -1) { ended = true; continue; }
+            SCN_ARG(!ended, "a required word stands behind a -1 of its row (the words first, then the padding)");
+            SCN_ARG(r[i] >= 0 && r[i] < V, "a required word lies outside the vocabulary");
+            SCN_ARG(r[i] != start_token && r[i] != end_token && r[i] != c->pad_token,
+                    "<start>, <end> and <pad> may not be required");
+            for (int q = 0; q < i; ++q) SCN_ARG(r[q] != r[i], "a required word occurs twice in an image's list");
+            if (o)
+                for (int q = 0; q < o->n_banned && q < SCN_MAX_BANNED; ++q)
+                    SCN_ARG(o->banned[q] != r[i], "a required word is banned by the options");
+        }
+    }
+    const int nb = o ? o->n_banned : 0, g = o ? o->no_repeat_ngram : 0;
+    SCN_ARG((long)V - nb - 1 - (g >= 1 ? T : 0) - SCN_MAX_REQUIRED >= K,
+            "options and required words may leave a row fewer than beam_size candidates "
+            "(need vocab_size - banned - 1 - (no_repeat_ngram ? max_steps : 0) - 4 >= beam_size)");
+    return 0;
+}
+
 // The refusals of a diverse search (include/scnattn.h); K is the total G * Kg.
 int check_diversity(const scnattn_diversity* v, int K) {
     SCN_ARG(v, "the diversity is NULL");
@@ -177,15 +218,18 @@ int check_diversity(const scnattn_diversity* v, int K) {
 }
 
 // what step t excludes; hist: the [2][R][T] buffers, step t reads buffer t & 1 and its advance writes the other
-BeamExcl step_excl(const scnattn_search_options& o, int t, int T, long R, int end_token, const int* hist) {
+// o null (a constrained search without options): nothing is excluded
+BeamExcl step_excl(const scnattn_search_options* o, int t, int T, long R, int end_token, const int* hist) {
     BeamExcl x{};
     x.t = t;
     x.T = T;
-    x.g = o.no_repeat_ngram;
-    x.end_excl = t < o.min_length ? end_token : -1;
-    x.n_banned = o.n_banned;
+    x.end_excl = -1;
+    if (!o) return x;
+    x.g = o->no_repeat_ngram;
+    x.end_excl = t < o->min_length ? end_token : -1;
+    x.n_banned = o->n_banned;
     x.hist = hist + (long)(t & 1) * R * T;
-    for (int i = 0; i < o.n_banned; ++i) x.banned[i] = o.banned[i];
+    for (int i = 0; i < o->n_banned; ++i) x.banned[i] = o->banned[i];
     return x;
 }
 
@@ -274,47 +318,60 @@ int decode_step(hipStream_t st, const scnattn_dims& d, int K, const scnattn_para
 
 // ---- the search: M decoders under ONE search state; o: the search options, null without ------------
 int search_workspace(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                     const scnattn_diversity* v, int K, int max_steps, size_t* bytes) {
+                     const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, size_t* bytes) {
     if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    if (cn) SCN_TRY(check_constraints(cn, o, v, d[0].B, d[0].V, K, max_steps, -1, -1));
     SCN_ARG(bytes, "search_workspace: bytes is NULL");
     SearchWs b;
-    *bytes = carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, nullptr, b);
+    *bytes = carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, cn != nullptr, nullptr, b);
     return 0;
 }
 
 // off[SCNATTN_BEAM_NOFF]: where the results live in the workspace, in 4-byte elements (order: include/scnattn.h); with
-// options or a diversity off[SCNATTN_BEAM_NOFF_OPT], the history's offset (-1 without options) behind them
+// options or a diversity off[SCNATTN_BEAM_NOFF_OPT], the history's offset (-1 without options) behind them; with
+// constraints off[SCNATTN_BEAM_NOFF_CON], met and the required table behind that
 int search_layout(int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                  const scnattn_diversity* v, int K, int max_steps, long* off) {
+                  const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, long* off) {
     if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    if (cn) SCN_TRY(check_constraints(cn, o, v, d[0].B, d[0].V, K, max_steps, -1, -1));
     SCN_ARG(off, "search_layout: offsets is NULL");
     SearchWs b;
-    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, layout_base(), b);
-    const void* p[SCNATTN_BEAM_NOFF_OPT] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
+    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, cn != nullptr, layout_base(), b);
+    const void* p[SCNATTN_BEAM_NOFF_CON] = {b.s.open_images, b.s.nsrc, b.s.kk, b.s.ncomp, b.s.best_idx, b.s.best_score,
                                             b.s.scores, b.s.comp_score, b.s.comp_step, b.s.comp_parent, b.s.token,
-                                            b.s.parent, b.alpha, b.hist};
-    offsets_from(layout_base(), p, (o || v) ? SCNATTN_BEAM_NOFF_OPT : SCNATTN_BEAM_NOFF, off);
+                                            b.s.parent, b.alpha, b.hist, b.s.met, b.req};
+    offsets_from(layout_base(), p, cn ? SCNATTN_BEAM_NOFF_CON : (o || v) ? SCNATTN_BEAM_NOFF_OPT : SCNATTN_BEAM_NOFF, off);
     return 0;
 }
 
 // The history int32 [2][R][max_steps] of a search with options is zero-filled with the rest of the state.
+// The required table of a constrained search is copied from the host behind that fill, and the call waits for the copy: the
+// device never reads the caller's array (the four calls do, for their checks).
 int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
-                const float* const* tags, int start_token, float* ws) {
+                const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, const scnattn_params* w,
+                const float* enc, const float* const* tags, int start_token, float* ws) {
     if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) SCN_TRY(check_options(o, d[0].V, K, max_steps, -1));
+    if (cn) {
+        SCN_ARG(start_token >= 0, "search_init: start token outside the vocabulary");
+        SCN_TRY(check_constraints(cn, o, v, d[0].B, d[0].V, K, max_steps, start_token, -1));
+    }
     SCN_ARG(w && enc && tags && ws, "search_init: null argument");
     for (int m = 0; m < M; ++m) SCN_ARG(tags[m], "search_init: a member's tags are NULL");
     SCN_ARG(start_token >= 0 && start_token < d[0].V, "search_init: start token outside the vocabulary");
     SCN_ARG(aligned16(ws), "search_init: the workspace must be 16-byte aligned");
     SearchWs b;
-    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, ws, b);
+    carve_search(M, d, K, max_steps, alpha_member, o != nullptr, v, cn != nullptr, ws, b);
     SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));
+    if (cn) {
+        SCN_HIP(hipMemcpyAsync(b.req, cn->required, sz(d[0].B, SCN_MAX_REQUIRED) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        SCN_HIP(hipStreamSynchronize(st));
+    }
     SCN_TRY(beam_state_init(st, d[0].B, K, b.s, b.G));
     for (int m = 0; m < M; ++m) SCN_TRY(decode_setup(st, d[m], K, w + m, enc, tags[m], start_token, b.m[m]));
     return 0;
@@ -324,21 +381,27 @@ int search_init(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, 
 // member, decode_step with that member's hA/cA -> hB/cB, then ONE selection over the M logits buffers, ONE beam_merge, and
 // per member beam_advance with its own table and state.  With options the selection takes what step t excludes, and one
 // history serves all members: step t reads buffer t & 1, the first member's advance writes buffer (t + 1) & 1.
+// With constraints the selection also takes them (and exclusions that may be empty) and beam_merge_banks replaces beam_merge.
 int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member, const scnattn_search_options* o,
-                 const scnattn_diversity* v, int K, int max_steps, const scnattn_params* w, const float* enc,
-                 const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws) {
+                 const scnattn_diversity* v, const scnattn_constraints* cn, int K, int max_steps, const scnattn_params* w,
+                 const float* enc, const float* member_w, int mode, int end_token, int t0, int n_steps, float* ws) {
     if (v) SCN_TRY(check_diversity(v, K));
     SCN_TRY(check_search(M, d, K, max_steps, alpha_member));
     if (o) {    // only a search with options needs to know <end>: min_length keeps it out, and it may not be banned
         SCN_ARG(end_token >= 0, "search_steps: end token outside the vocabulary");
         SCN_TRY(check_options(o, d[0].V, K, max_steps, end_token));
     }
+    if (cn) {   // a caption may not end with a requirement open, and <end> may not be required
+        SCN_ARG(end_token >= 0 && end_token < d[0].V, "search_steps: end token outside the vocabulary");
+        SCN_TRY(check_constraints(cn, o, v, d[0].B, d[0].V, K, max_steps, -1, end_token));
+    }
     SCN_ARG(w && enc && member_w && ws, "search_steps: null argument");
     SCN_ARG(t0 >= 0 && n_steps >= 0, "search_steps: negative step");
     const int N = d[0].B, P = d[0].P, V = d[0].V, R = N * K, T = max_steps;
     SearchWs b;
-    carve_search(M, d, K, T, alpha_member, o != nullptr, v, ws, b);
+    carve_search(M, d, K, T, alpha_member, o != nullptr, v, cn != nullptr, ws, b);
     const int Kg = K / b.G;
+    const BeamCon bc{b.req, b.s.met, end_token, b.reqv, b.reqi};
     // what the attention kernels take as the image's live slots: in groups the live rows are no prefix of the image's slots,
     // so K while any group is open; one group is the search without groups, its nsrc [N] the prefix length
     const int* att_live = b.G > 1 ? b.s.att_live : b.s.nsrc;
@@ -358,9 +421,12 @@ int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member,
                                 s.hB, s.cB));
         }
         BeamExcl x{};
-        if (o) x = step_excl(*o, t, T, R, end_token, b.hist);
-        SCN_TRY(beam_row_topk_ens(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, o ? &x : nullptr, b.candv, b.candi, 0, Kg));
-        if (v)
+        if (o || cn) x = step_excl(o, t, T, R, end_token, b.hist);
+        SCN_TRY(beam_row_topk_ens(st, N, K, V, M, rows, mode, b.s.scores, b.s.nsrc, (o || cn) ? &x : nullptr, b.candv, b.candi, 0,
+                                  Kg, cn ? &bc : nullptr));
+        if (cn)
+            SCN_TRY(beam_merge_banks(st, N, K, V, end_token, t, b.candv, b.candi, b.reqv, b.reqi, b.req, b.s));
+        else if (v)
             SCN_TRY(beam_merge_groups(st, N, K, Kg, v->penalty, V, end_token, t, b.candv, b.candi, b.s));
         else
             SCN_TRY(beam_merge(st, N, K, V, end_token, t, b.candv, b.candi, b.s));

@@ -151,6 +151,9 @@ struct BeamState {
     // The grouped search (beam_merge_groups): nsrc .. best_score are then [N*G], one entry per (image,
     // group), and att_live [N] is what the attention kernels take for nsrc: K while any group of the image is open, else 0.
     int* att_live = nullptr;
+    // The constrained search (beam_merge_banks): met [R], per slot the bitmask of the image's required words
+    // that occur in the slot's history.
+    int* met = nullptr;
 };
 // e[n*K+j][p] for j < nsrc[n]; att2 = sum(slabs) + bd over rows n*K+j; rows of dead slots are left untouched
 int beam_attn_scores(hipStream_t st, int N, int K, int P, int A, const float* att1, Slabs att2, const float* bd,
@@ -175,6 +178,22 @@ struct BeamExcl {
     const int* hist;        // [N*K][T] (may be null when g == 0)
     int banned[SCN_MAX_BANNED];
 };
+// ---- the CONSTRAINTS: words a caption must contain ------------------------------------------------------
+#define SCN_MAX_REQUIRED 4
+// What the selection of a constrained search takes beside the exclusions: per live row the image's unmet required words
+// leave the K rounds, as does <end> = end_tok while a requirement is open, and the row's 4 REQUIRED candidates go to
+// reqv / reqi [N*K][4]: entry c is (scores[row] + c_v(req[n][c]), req[n][c]) when the word exists, is unmet in the row and is
+// not excluded by the options, else (-inf, -1).  Everything on the device.
+struct BeamCon {
+    const int* req;         // [N][4] the required words of image n, padded with -1
+    const int* met;         // [N*K]  bit c: the slot's history holds req[n][c]
+    int end_tok;
+    float* reqv;            // [N*K][4]
+    int* reqi;              // [N*K][4]
+};
+struct BeamExclCon : BeamExcl {
+    BeamCon c;
+};
 // THE selection (one kernel template, one launcher).  outv / outi [N*K][K]: per live row the top K of scores[row] + c_v,
 // best first, with l_mv = logits_m[row][v] - lse_m(row) and
 // mode 0: c_v = sum_m w_m l_mv;  mode 1: c_v = a_v + log(sum_m w_m exp(l_mv - a_v)), a_v = max_m l_mv.
@@ -183,8 +202,11 @@ struct BeamExcl {
 // force_passes != 0 (tests): read the rows from global memory in every pass even when a row fits the LDS.
 // Kg: the slots per group of a grouped search (K % Kg == 0; nsrc is then [N * K/Kg] and row n*K + g*Kg + s is live when
 // s < nsrc[n * K/Kg + g]); Kg = K (or 0, the default) is the search without groups.  A live row runs K rounds either way.
+// cn: the constraints of a constrained search (needs x, which may exclude nothing, and no groups); null: none.  With cn the
+// candidate-count refusal asks for SCN_MAX_REQUIRED more words.
 int beam_row_topk_ens(hipStream_t st, int N, int K, int V, int M, const EnsRows& e, int mode, const float* scores,
-                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes, int Kg = 0);
+                      const int* nsrc, const BeamExcl* x, float* outv, int* outi, int force_passes, int Kg = 0,
+                      const BeamCon* cn = nullptr);
 // The single decoder's selection, the top K of scores[row] + logits[row][v] - lse(row): beam_row_topk_ens with M = 1,
 // mode 0, w = 1, nothing excluded.
 int beam_row_topk(hipStream_t st, int N, int K, int V, const float* logits, long ld, const float* scores, const int* nsrc,
@@ -196,6 +218,12 @@ int beam_merge(hipStream_t st, int N, int K, int V, int end_tok, int t, const fl
 // with the candidate's word; raw values are stored.  s.nsrc .. s.best_score are [N*G], s.att_live [N] may be null.
 int beam_merge_groups(hipStream_t st, int N, int K, int Kg, float penalty, int V, int end_tok, int t, const float* candv,
                       const int* candi, const BeamState& s);
+// The merge of a constrained search (include/scnattn.h: "CONSTRAINED beam search"): per image the nsrc x (K + 4) ordinary
+// and required candidates of the selection fall into banks by the number of required words their beam would have met, the
+// kk picks go round-robin over the banks C_n .. 0, and the picked set is recorded in the search order as beam_merge does,
+// with the new s.met.  req [N][4] on the device.
+int beam_merge_banks(hipStream_t st, int N, int K, int V, int end_tok, int t, const float* candv, const int* candi,
+                     const float* reqv, const int* reqi, const int* req, const BeamState& s);
 // One kernel behind both: h / c of row n*K+s gathered from its parent slot, emb from the table; the _opt form also writes
 // the row's history for step t+1, the parent slot's first t entries of hist_s, then token_t[row] (hist_s != hist_d)
 int beam_advance(hipStream_t st, int N, int K, int D, int M, int V, const float* hs, const float* cs, const int* parent_t,

@@ -275,6 +275,58 @@ def beam_search_grouped(decoder, beam_size, groups, diversity, word_map, encoder
     return out if G > 1 else [[x] for x in out]
 
 
+def check_required_args(required, N, word_map, beam_size, options=None, who="sample_constrained"):
+    """The host-side refusals of a constrained search, before anything touches the GPU (ValueError) -> the lists as lists
+    of ints: one sequence per image, at most 4 distinct token ids of the vocabulary each, none of them <start>, <end>,
+    <pad> or banned by ``options``; beam_size in [1, 8]; the candidate-count rule with 4 more words"""
+    if isinstance(required, (str, bytes)) or not hasattr(required, "__len__"):
+        raise ValueError("%s: required must hold one sequence of token ids per image" % who)
+    lists = []
+    for r in required:
+        if isinstance(r, torch.Tensor):
+            r = r.tolist()
+        if isinstance(r, (str, bytes)) or not hasattr(r, "__iter__"):
+            raise ValueError("%s: required must hold one sequence of token ids per image (got %r)" % (who, r))
+        lists.append(list(r))
+    try:
+        SF.required_table(lists, N, len(word_map), beam_size, SF.BEAM_MAX_STEPS, word_map[start_token], word_map[end_token],
+                          word_map.get(padding_token, -1), options)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (who, e)) from None
+    return [[int(w) for w in r] for r in lists]
+
+
+def beam_search_constrained(decoder, beam_size, required, word_map, encoder_out, tag_out, use_attention, use_tags,
+                            return_all=False, options=None, with_scores=False, with_met=False):
+    """CONSTRAINED beam search (include/scnattn.h; Anderson et al. 2017, Post & Vilar 2018) for N images on the device:
+    ``required[n]`` holds at most 4 token ids the caption of image n must contain.  The beams of an image are kept in banks
+    by the number of required words they have met and every step fills the banks round-robin; <end> is a candidate only for
+    a beam that has met them all, so every completed caption satisfies its list.  Returns per image what
+    ``beam_search_batched`` returns (``return_all`` / ``options`` as there); ``with_scores``: (result, raw score);
+    ``with_met``: (result, raw score, bitmask of the required words the returned caption contains) -- the mask is
+    incomplete only when nothing completed within the step limit.  Empty lists: ``beam_search_batched`` bit for bit."""
+    from scnattn import _lib
+    k = beam_size
+    if int(k) != k or not 1 <= k <= _lib.MAX_BEAM:
+        raise ValueError("sample_constrained: beam_size must be an integer in [1, %d] (got %r)" % (_lib.MAX_BEAM, k))
+    k = int(k)
+    V = len(word_map)
+    if V < k:
+        raise ValueError("sample_constrained: vocab_size %d is smaller than beam_size %d" % (V, k))
+    start, end = word_map[start_token], word_map[end_token]
+    dev_options, alpha = device_options(options)
+    if dev_options is not None:
+        dev_options.check(V, k, SF.BEAM_MAX_STEPS, end)       # before anything touches the GPU
+    lists = check_required_args(required, encoder_out.shape[0], word_map, k, dev_options)
+    _lib.require_cuda(encoder_out, tag_out)
+    N, hh, ww, E = encoder_out.shape
+    dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
+    res, steps = SF.beam_search_run(dims, k, weights, enc, tag_out, start, end, options=dev_options, required=lists,
+                                    pad_token=word_map.get(padding_token, -1))
+    return trace_back(res, steps, N, k, start, end, (hh, ww), use_attention, return_all, length_penalty=alpha,
+                      with_scores=with_scores, with_met=with_met)
+
+
 def pick_best(done_scores, lengths, length_penalty):
     """index of the first maximum of score / L**alpha over the beams, in the order given (Python floats)"""
     norm = [s / float(L) ** length_penalty for s, L in zip(done_scores, lengths)]
@@ -282,7 +334,7 @@ def pick_best(done_scores, lengths, length_penalty):
 
 
 def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=False, length_penalty=0.0, groups=1,
-               with_scores=False):
+               with_scores=False, with_met=False):
     """The results of a device search (SF.beam_search_run / SF.ensemble_search_run) -> the list of N results that
     ``beam_search_batched`` documents: the parent chains read off the token / parent records, the all-ones first alpha map
     (``use_attention``: the search kept maps), the fallback to the best open beam.
@@ -292,9 +344,16 @@ def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=F
     ``groups`` > 1 (a diverse search; k is the TOTAL over the groups): the per-group records are read -- group g of image n
     keeps its completions at n*k + g*kg .., its open beams in slots g*kg .., its counters at n*groups + g -- and the result
     of an image is the list of its ``groups`` results, each in the form above.  ``with_scores``: each result is paired
-    with the raw score of the caption it returns."""
+    with the raw score of the caption it returns.
+    A CONSTRAINED search (res["met"] is not None; include/scnattn.h): every completed beam has met all the image's required
+    words; the fallback takes the open beams with the largest popcount(met) and chooses among THOSE as above (the higher
+    score, then the lower slot; with alpha != 0 the length-normalised score) -- with no required words that is the fallback
+    above.  ``with_met``: each result becomes (result, score, met_mask), met_mask the bitmask (bit c: the image's c-th
+    required word) of what the returned caption contains."""
     hh, ww = map_hw
     kg = k // groups
+    met = res["met"].tolist() if res.get("met") is not None else None
+    full = [sum(1 << c for c, w in enumerate(row) if w >= 0) for row in res["required"].tolist()] if met is not None else None
     token, parent = res["token"].tolist(), res["parent"].tolist()
     alpha = res["alpha"]
     ones = torch.ones(1, hh, ww)
@@ -326,19 +385,29 @@ def trace_back(res, steps, N, k, start, end, map_hw, use_attention, return_all=F
             t, src = int(res["comp_step"][r]), int(res["comp_parent"][r])
             words, rows = chain(n, t - 1, src)
             done.append((words + [end], rows + [(t, n * k + src)], float(res["comp_score"][r])))
+        pool = None     # the beams the choice is among (indices into done); None: all of them
+        masks = None
         if done:
             i = int(res["best_idx"][sg])
         else:           # nothing reached <end> within the step limit: the best open beam (rank order: slot 0)
             for s in range(s0, s0 + int(res["nsrc"][sg])):
                 words, rows = chain(n, steps - 1, s)
                 done.append((words, rows, float(res["scores"][n * k + s])))
-            scores = [x[2] for x in done]
-            i = scores.index(max(scores))
+            pool = list(range(len(done)))
+            if met is not None:     # a constrained search: first the beams that met the most required words
+                masks = [met[n * k + s0 + q] for q in pool]
+                most = max(bin(m).count("1") for m in masks)
+                pool = [q for q in pool if bin(masks[q]).count("1") == most]
+            scores = [done[q][2] for q in pool]
+            i = pool[scores.index(max(scores))]
         if length_penalty != 0.0:
-            i = pick_best([x[2] for x in done], [len(x[0]) - 1 for x in done], length_penalty)
+            among = pool if pool is not None else list(range(len(done)))
+            i = among[pick_best([done[q][2] for q in among], [len(done[q][0]) - 1 for q in among], length_penalty)]
         seq, rows, score = done[i]
         one = (seq, alphas_of(rows)) if use_attention else seq
         one = (one, [(s, sc) for s, _, sc in done]) if return_all else one
+        if with_met:
+            return one, score, (0 if met is None else masks[i] if masks is not None else full[n])
         return (one, score) if with_scores else one
 
     # The results are nested lists of plain numbers (an attention map per word: some 10 000 floats and 800 lists per

@@ -75,6 +75,15 @@ class DecoderEnsemble(nn.Module):
         return self._search(beam_size, word_map, encoder_out, tags, return_all, options, groups=groups, diversity=diversity,
                             with_scores=with_scores)
 
+    def sample_constrained(self, beam_size, required, word_map, encoder_out, tags=None, options=None, with_scores=False,
+                           return_all=False, with_met=False):
+        """Constrained beam search under the combined distribution (_common.beam_search_constrained): ``required[n]`` holds
+        at most 4 token ids the caption of image n must contain -> per image what ``sample_batch`` returns."""
+        if int(beam_size) != beam_size:
+            raise ValueError("sample_constrained: beam_size must be an integer (got %r)" % (beam_size,))
+        return self._search(int(beam_size), word_map, encoder_out, tags, return_all, options, with_scores=with_scores,
+                            required=required, with_met=with_met)
+
     def sample_batch(self, beam_size, word_map, encoder_out, tags=None, return_all=False, options=None):
         """encoder_out (N, h, w, E), tags (N, S) (may be None when no member uses tags) -> list of N results in the form
         ``_common.beam_search_batched`` returns them: the sequence with the leading <start>, paired with the attention maps
@@ -84,8 +93,9 @@ class DecoderEnsemble(nn.Module):
         return self._search(int(beam_size), word_map, encoder_out, tags, return_all, options)
 
     def _search(self, beam_size, word_map, encoder_out, tags, return_all, options, groups=None, diversity=0.0,
-                with_scores=False):
-        """groups None: sample_batch with beam_size beams; else sample_groups with beam_size beams in each of the groups"""
+                with_scores=False, required=None, with_met=False):
+        """groups None: sample_batch with beam_size beams; else sample_groups with beam_size beams in each of the groups;
+        required (groups None): sample_constrained"""
         V = len(word_map)
         G, lam = 1, 0.0
         if groups is None:
@@ -104,6 +114,9 @@ class DecoderEnsemble(nn.Module):
         dev_options, alpha = _common.device_options(options)
         if dev_options is not None:
             dev_options.check(V, k, SF.BEAM_MAX_STEPS, end)       # before anything touches the GPU
+        pad = word_map.get(_common.padding_token, -1)
+        if required is not None:
+            required = _common.check_required_args(required, encoder_out.shape[0], word_map, k, dev_options)
         SF._lib.require_cuda(encoder_out, tags)
         N, hh, ww, _ = encoder_out.shape
         dims_list, weights_list, tags_list = [], [], []
@@ -114,7 +127,8 @@ class DecoderEnsemble(nn.Module):
             weights_list.append(weights)
             tags_list.append(tg)
         res, steps = SF.ensemble_search_run(dims_list, k, weights_list, enc, tags_list, self.member_weights, self.combine,
-                                            start, end, self.alpha_member, options=dev_options, groups=G, diversity=lam)
+                                            start, end, self.alpha_member, options=dev_options, groups=G, diversity=lam,
+                                            required=required, pad_token=pad)
         out = _common.trace_back(res, steps, N, k, start, end, (hh, ww), self.has_alphas, return_all, length_penalty=alpha,
-                                 groups=G, with_scores=with_scores)
+                                 groups=G, with_scores=with_scores, with_met=with_met)
         return [[x] for x in out] if groups is not None and G == 1 else out

@@ -77,6 +77,13 @@ class PureSCN(nn.Module):
         return _common.beam_search_grouped(self, beam_size, groups, diversity, word_map, encoder_out, tag_out,
                                            use_attention=False, use_tags=True, options=options, **kw)
 
+    def sample_constrained(self, beam_size, required, word_map, encoder_out, tags, options=None, with_scores=False, **kw):
+        """CONSTRAINED beam search: ``required[n]`` holds at most 4 token ids the caption of image n must contain -> per
+        image what ``sample_batch`` returns (with_scores: paired with its raw score); every completed caption contains its
+        words, empty lists give ``sample_batch`` bit for bit (_common.beam_search_constrained)."""
+        return _common.beam_search_constrained(self, beam_size, required, word_map, encoder_out, tags, use_attention=False,
+                                               use_tags=True, options=options, with_scores=with_scores, **kw)
+
     def rollout_batch(self, word_map, encoder_out, tags=None, samples=1, seed=0, draw=0, temperature=1.0,
                       greedy_first=False, top_k=0, top_p=1.0):
         """Sampled captions for self-critical training: encoder_out (N, h, w, E), tags (N, S) -> (caps (N*K, L) int64, caplens

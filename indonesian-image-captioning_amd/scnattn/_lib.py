@@ -92,6 +92,13 @@ class Diversity(C.Structure):      # scnattn_diversity
     _fields_ = [("groups", C.c_int32), ("penalty", C.c_float)]
 
 
+MAX_REQUIRED = 4                   # SCNATTN_MAX_REQUIRED
+
+
+class Constraints(C.Structure):    # scnattn_constraints; `required` points at a HOST int32 [n_images][4] the caller keeps alive
+    _fields_ = [("n_images", C.c_int32), ("pad_token", C.c_int32), ("required", C.c_void_p)]
+
+
 class SampleFilter(C.Structure):   # scnattn_sample_filter
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
 
@@ -155,6 +162,27 @@ _SIGS = {
                                     C.POINTER(Params), vp, C.POINTER(f32), i32, i32, i32, i32, vp], i32),
     "scnattn_beam_merge_groups": ([vp, i32, i32, i32, f32, i32, i32, i32, vp, vp, C.POINTER(vp)], i32),
     "scnattn_beam_row_topk_groups": ([vp, i32, i32, i32, i32, vp, i64, vp, vp, vp, vp, i32], i32),
+    "scnattn_beam_workspace_con": ([C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints), C.POINTER(sz)],
+                                   i32),
+    "scnattn_beam_layout_con": ([C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints), C.POINTER(i64)],
+                                i32),
+    "scnattn_beam_init_con": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints),
+                               C.POINTER(Params), vp, vp, i32, vp], i32),
+    "scnattn_beam_steps_con": ([vp, C.POINTER(Dims), i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints),
+                                C.POINTER(Params), vp, i32, i32, i32, vp], i32),
+    "scnattn_ensemble_workspace_con": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints),
+                                        C.POINTER(sz)], i32),
+    "scnattn_ensemble_layout_con": ([i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints),
+                                     C.POINTER(i64)], i32),
+    "scnattn_ensemble_init_con": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints),
+                                   C.POINTER(Params), vp, C.POINTER(vp), i32, vp], i32),
+    "scnattn_ensemble_steps_con": ([vp, i32, C.POINTER(Dims), i32, i32, i32, C.POINTER(SearchOpts), C.POINTER(Constraints),
+                                    C.POINTER(Params), vp, C.POINTER(f32), i32, i32, i32, i32, vp], i32),
+    "scnattn_beam_row_topk_con": ([vp, i32, i32, i32, vp, i64, vp, vp, C.POINTER(SearchOpts), i32, i32, vp, i32, vp, vp, vp,
+                                   vp, vp, vp, i32], i32),
+    "scnattn_beam_row_topk_ens_con": ([vp, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(f32), i32, vp, vp,
+                                       C.POINTER(SearchOpts), i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32], i32),
+    "scnattn_beam_merge_banks": ([vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)], i32),
     "scnattn_rollout_workspace": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(sz)], i32),
     "scnattn_rollout_layout": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(i64)], i32),
     "scnattn_rollout_init": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, vp, i32, vp], i32),
@@ -291,6 +319,7 @@ _SIGS = {
 
 BEAM_NOFF = 13      # SCNATTN_BEAM_NOFF
 BEAM_NOFF_OPT = 14  # SCNATTN_BEAM_NOFF_OPT
+BEAM_NOFF_CON = 16  # SCNATTN_BEAM_NOFF_CON
 ROLLOUT_NOFF = 8    # SCNATTN_ROLLOUT_NOFF
 ROLLOUT_NOFF_F = 9  # SCNATTN_ROLLOUT_NOFF_F
 MAX_BEAM = 8

@@ -288,11 +288,55 @@ def diversity_struct(groups, diversity, beam_size):
     return _lib.Diversity(groups=int(groups), penalty=diversity)
 
 
-def _search_form(options, groups, diversity, V, beam_size, max_steps, end_token):
-    """(suffix of the four calls, what they take behind max_steps / alpha_member, offsets): the plain calls, the _opt form
-    with options, and -- only when groups > 1 -- the _div form, whose options may be NULL"""
+def required_table(required, N, V, beam_size, max_steps, start_token, end_token, pad_token=-1, options=None):
+    """The refusals of a constrained search (include/scnattn.h; ValueError) -> the int32 table [N][4] as a ctypes array:
+    `required` holds per image a sequence of at most 4 distinct token ids in [0, V), none of them <start>, <end>, <pad> or
+    banned by `options`; beam_size in [1, 8]; and every row must still offer beam_size ordinary candidates:
+    V - banned - 1 - (no_repeat_ngram ? max_steps : 0) - 4 >= beam_size."""
+    if not 1 <= beam_size <= _lib.MAX_BEAM:
+        raise ValueError("beam_size must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, beam_size))
+    required = [list(r) for r in required]
+    if len(required) != N:
+        raise ValueError("required: %d lists for %d images" % (len(required), N))
+    banned = set(options.banned_tokens) if options is not None else set()
+    ngram = options.no_repeat_ngram if options is not None else 0
+    tab = (C.c_int32 * (N * _lib.MAX_REQUIRED))(*([-1] * (N * _lib.MAX_REQUIRED)))
+    for n, words in enumerate(required):
+        if len(words) > _lib.MAX_REQUIRED:
+            raise ValueError("required: image %d has %d words, at most %d" % (n, len(words), _lib.MAX_REQUIRED))
+        for i, w in enumerate(words):
+            if isinstance(w, bool) or int(w) != w:
+                raise ValueError("required: image %d: %r is not a token id" % (n, w))
+            w = int(w)
+            if not 0 <= w < V:
+                raise ValueError("required: image %d: token %d lies outside the vocabulary" % (n, w))
+            if w in (start_token, end_token, pad_token):
+                raise ValueError("required: image %d: <start>, <end> and <pad> may not be required (token %d)" % (n, w))
+            if w in banned:
+                raise ValueError("required: image %d: token %d is banned by the search options" % (n, w))
+            if w in [int(x) for x in words[:i]]:
+                raise ValueError("required: image %d: token %d occurs twice" % (n, w))
+            tab[n * _lib.MAX_REQUIRED + i] = w
+    if V - len(banned) - 1 - (max_steps if ngram >= 1 else 0) - _lib.MAX_REQUIRED < beam_size:
+        raise ValueError("options and required words may leave a beam fewer than beam_size candidates (need vocab_size - "
+                         "banned - 1 - (no_repeat_ngram ? max_steps : 0) - %d >= beam_size)" % _lib.MAX_REQUIRED)
+    return tab
+
+
+def _search_form(options, groups, diversity, V, beam_size, max_steps, end_token, required=None, N=0, start_token=-1,
+                 pad_token=-1):
+    """(suffix of the four calls, what they take behind max_steps / alpha_member, offsets): the plain
+    calls, the _opt form with options, only when groups > 1 the _div form, whose options may be NULL, and with `required`
+    (a list per image, empty lists included) the _con form, likewise -- which groups > 1 may not join"""
     div = diversity_struct(groups, diversity, beam_size)
     opt = None if options is None else search_options_struct(options, V, beam_size, max_steps, end_token)
+    if required is not None:
+        if div.groups > 1:
+            raise ValueError("required words and groups do not compose: a search takes one or the other")
+        tab = required_table(required, N, V, beam_size, max_steps, start_token, end_token, pad_token, options)
+        con = _lib.Constraints(n_images=N, pad_token=pad_token, required=C.addressof(tab))
+        con._table = tab        # the host table lives as long as the struct
+        return "_con", (C.byref(opt) if opt is not None else None, C.byref(con)), _lib.BEAM_NOFF_CON
     if div.groups > 1:
         return "_div", (C.byref(opt) if opt is not None else None, C.byref(div)), _lib.BEAM_NOFF_OPT
     if opt is not None:
@@ -301,7 +345,7 @@ def _search_form(options, groups, diversity, V, beam_size, max_steps, end_token)
 
 
 def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token, max_steps=BEAM_MAX_STEPS,
-                    chunk=BEAM_CHUNK, guard=0, options=None, groups=1, diversity=0.0):
+                    chunk=BEAM_CHUNK, guard=0, options=None, groups=1, diversity=0.0, required=None, pad_token=-1):
     """The whole search of N images on the device.  dims: 12-tuple in scnattn_dims order with B = N (T, L unused);
     enc (N, P, E) as the caller has it (no copy per beam), tags (N, S) un-expanded; weights in PARAM_FIELDS order.
     Returns (results, steps): host tensors by the names of scnattn_beam_layout -- token / parent (steps, N*K),
@@ -312,7 +356,10 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
     plain search, and results["history"] is None.
     groups > 1: a DIVERSE search (include/scnattn.h; the scnattn_beam_*_div calls) in `groups` groups of beam_size / groups
     slots with the penalty `diversity`; beam_size is the total.  nsrc / kk / ncomp / best_idx / best_score then hold
-    N * groups entries, entry n * groups + g.  groups == 1 takes today's entry points, whatever `diversity` says."""
+    N * groups entries, entry n * groups + g.  groups == 1 takes today's entry points, whatever `diversity` says.
+    required: per image a sequence of at most 4 token ids -> a CONSTRAINED search (include/scnattn.h; the scnattn_beam_*_con
+    calls, also when every list is empty); results["met"] (N*K,) int32 then holds the masks of the slots after the last step
+    and results["required"] the table (N, 4); None: no constraints, and the results have neither entry."""
     require_cuda(enc, tags, *weights)
     if not 1 <= beam_size <= _lib.MAX_BEAM:
         raise ValueError("beam_size must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, beam_size))
@@ -320,7 +367,8 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
     if d.V < beam_size:
         raise ValueError("vocab_size %d is smaller than beam_size %d" % (d.V, beam_size))
     # with options: the same four calls in their _opt form, the options struct after max_steps; in groups: the _div form
-    sfx, opt, noff = _search_form(options, groups, diversity, d.V, beam_size, max_steps, end_token)
+    sfx, opt, noff = _search_form(options, groups, diversity, d.V, beam_size, max_steps, end_token, required, d.B,
+                                  start_token, pad_token)
     dev = enc.device
     enc, tags = f32c(enc), f32c(tags)
     weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
@@ -335,9 +383,14 @@ def beam_search_run(dims, beam_size, weights, enc, tags, start_token, end_token,
 def _beam_results(ws, off, N, K, P, t, nwords, guard, max_steps=BEAM_MAX_STEPS, groups=1):
     """the host tensors of a finished search (t steps ran), by the names of scnattn_beam_layout; "history" (N*K, t): the
     current one of the two history buffers of a search with options (scnattn_beam_layout_opt), None without; the
-    per-group arrays of a search in groups hold N * groups entries"""
+    per-group arrays of a search in groups hold N * groups entries; "met" (N*K,) and "required" (N, 4) of a constrained
+    search (scnattn_beam_layout_con), absent without"""
     wsi = ws.view(torch.int32)
     R, NG = N * K, N * groups
+    met = req = None
+    if len(off) >= _lib.BEAM_NOFF_CON:
+        met = wsi[off[_lib.BEAM_NOFF_OPT]:off[_lib.BEAM_NOFF_OPT] + R].cpu()
+        req = wsi[off[_lib.BEAM_NOFF_OPT + 1]:off[_lib.BEAM_NOFF_OPT + 1] + N * _lib.MAX_REQUIRED].view(N, _lib.MAX_REQUIRED).cpu()
     hist = None
     if len(off) > _lib.BEAM_NOFF and off[_lib.BEAM_NOFF] >= 0:
         cur = off[_lib.BEAM_NOFF] + (t & 1) * R * max_steps
@@ -355,6 +408,8 @@ def _beam_results(ws, off, N, K, P, t, nwords, guard, max_steps=BEAM_MAX_STEPS, 
     if out["alpha"] is not None:
         out["alpha"] = out["alpha"].view(t, R, P)
     out["history"] = hist
+    if met is not None:         # only a constrained search has these entries
+        out["met"], out["required"] = met, req
     if guard:
         out["guard"] = wsi[nwords:].cpu()
     return out
@@ -385,13 +440,14 @@ def normalise_member_weights(weights, M):
 
 
 def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, member_weights, mode, start, end, alpha_member,
-                        max_steps=BEAM_MAX_STEPS, chunk=BEAM_CHUNK, guard=0, options=None, groups=1, diversity=0.0):
+                        max_steps=BEAM_MAX_STEPS, chunk=BEAM_CHUNK, guard=0, options=None, groups=1, diversity=0.0,
+                        required=None, pad_token=-1):
     """beam_search_run for an ensemble of M <= 4 decoders under one search state (csrc/beam_search.cpp:
     scnattn_ensemble_*): dims_list / weights_list / tags_list hold one entry per member, as beam_search_run takes them;
     enc (N, P, E) is shared.  member_weights: M positive numbers (None: equal), normalised here; mode: "logprob" / 0 (the
     weighted mean of the members' log-probabilities) or "prob" / 1 (the log of the weighted mean of their probabilities).
     alpha_member: the member whose attention maps are kept (-1 or None: none).  Returns (results, steps) exactly as
-    beam_search_run does; `guard`, `options`, `groups` and `diversity` have the same meaning."""
+    beam_search_run does; `guard`, `options`, `groups`, `diversity`, `required` and `pad_token` have the same meaning."""
     M = len(dims_list)
     if not 1 <= M <= _lib.MAX_ENSEMBLE:
         raise ValueError("an ensemble has 1 to %d members (got %d)" % (_lib.MAX_ENSEMBLE, M))
@@ -421,7 +477,8 @@ def ensemble_search_run(dims_list, beam_size, weights_list, enc, tags_list, memb
     cw = (C.c_float * M)(*mw)
     K, N = beam_size, d[0].B
     # with options: the _opt form of the four calls, the options struct after alpha_member; in groups: the _div form
-    sfx, opt, noff = _search_form(options, groups, diversity, d[0].V, beam_size, max_steps, int(end))
+    sfx, opt, noff = _search_form(options, groups, diversity, d[0].V, beam_size, max_steps, int(end), required, d[0].B,
+                                  int(start), pad_token)
     ws, off, nwords, t = _run_on_device("scnattn_ensemble_%s" + sfx, (M, d, K, max_steps, alpha_member, *opt), noff,
                                         (w, ptr(enc), tg, int(start)), (w, ptr(enc), cw, mode, int(end)), stream_of(enc),
                                         dev, max_steps, chunk, guard)

@@ -150,6 +150,52 @@ class Captioner:
         return out
 
     @torch.no_grad()
+    def constrained(self, images, words):
+        """Captions that must CONTAIN given words (constrained beam search, `decoder.sample_constrained`): the trunks and
+        the batch path of `__call__`, then one search on the device with `beam_size` beams.  `words`: one list of strings
+        for all images, or one list per image (at most 4 distinct words each, an empty list: no requirement); a word is
+        looked up in the word map and a missing one raises ValueError.  `search_options` are honoured.
+        -> one record per image
+            tokens     the caption as `__call__` returns it
+            words      the same without <start>, <end>, <pad>, through the reversed word map
+            alphas     the attention maps as `__call__` returns them (None without attention)
+            score      the caption's sum of log-probabilities
+            missing    the required words absent from the caption (only a caption cut off at the step limit can lack any)
+            satisfied  not missing"""
+        if not hasattr(self.decoder, "sample_constrained"):
+            raise ValueError("Captioner.constrained: a %s has no sample_constrained" % type(self.decoder).__name__)
+        images = list(images)
+        words = list(words)
+        if all(isinstance(w, str) for w in words):
+            words = [words] * len(images)
+        if len(words) != len(images):
+            raise ValueError("Captioner.constrained: %d word lists for %d images" % (len(words), len(images)))
+        required = []
+        for per_image in words:
+            if isinstance(per_image, str):
+                raise ValueError("Captioner.constrained: words is one list of strings, or one list of strings per image")
+            ids = []
+            for w in per_image:
+                if w not in self.word_map:
+                    raise ValueError("Captioner.constrained: %r is not in the word map" % (w,))
+                ids.append(self.word_map[w])
+            required.append(ids)
+        from models.decoders._common import check_required_args, device_options
+        check_required_args(required, len(images), self.word_map, self.beam_size, device_options(self.search_options)[0],
+                            who="Captioner.constrained")
+        with torch.cuda.device(self.device):
+            encoder_out, tags = self._encode(images, self.needs_tags)
+            results = self.decoder.sample_constrained(self.beam_size, required, self.word_map, encoder_out, tags,
+                                                      options=self.search_options, with_scores=True)
+        records = []
+        for (res, score), per_image, ids in zip(results, words, required):
+            seq, alphas = res if self.has_alphas else (res, None)
+            missing = [w for w, i in zip(per_image, ids) if i not in seq]
+            records.append({"tokens": seq, "words": [self.rev_word_map[w] for w in seq if w not in self.skip],
+                            "alphas": alphas, "score": score, "satisfied": not missing, "missing": missing})
+        return records
+
+    @torch.no_grad()
     def __call__(self, images, tag_count=0, overlays=False):
         with torch.cuda.device(self.device):
             encoder_out, tags = self._encode(images, self.needs_tags or tag_count > 0)
