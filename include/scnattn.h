@@ -25,6 +25,8 @@ extern "C" {
 
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
+                               + scoring given captions: teacher-forced log-probabilities, rank and arg-max per token (scnattn_rollout_*_sc,
+                               scnattn_rollout_score; new symbols only, the version stays);
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
                                + constrained beam search: required words, beam banks (scnattn_constraints, scnattn_beam_*_con,
                                scnattn_ensemble_*_con, scnattn_beam_row_topk_con, scnattn_beam_row_topk_ens_con, scnattn_beam_merge_banks; new
@@ -546,6 +548,55 @@ int scnattn_rollout_steps_f(void* stream, const scnattn_dims* d, int K, int max_
 int scnattn_rollout_pick_f(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, uint64_t seed,
                            uint32_t draw, int t, int greedy_first, int end_token, int max_steps, void* const* state,
                            const scnattn_sample_filter* filter, int32_t* nkeep_t, int force_passes);
+/* ---- SCORING given captions: teacher-forced log-probabilities (csrc/rollout.hip: rollout_score) -----------
+ * The reference has none of this; the semantics are this library's.  The rollout's chain with the pick TOLD its token: row
+ * r = n*K + j carries ntok[r] given tokens, target[t][r] at step t, and K captions of one image share the image-side set-up.
+ *   OPEN AND CLOSED   a row is open at step t iff t < ntok[r].  A row of an image with nsrc[n] == 0 is neither read nor
+ *                written.  A closed row of an open image gets the records token = 0, logp = 0.0, rank = 0, best = 0.
+ *   QUANTITIES   y_v = fl(logits[row][v] * inv_temp), the fp32 number _pick forms, and the ORDER of the project (y
+ *                descending, index ascending, compared as fp32 numbers, so -0 == +0).  A y of -0 is TAKEN AS +0 in the
+ *                arithmetic below too (the kernel works on the order-preserving image of y, as the filtered pick does), so
+ *                a row whose one finite logit is -0 gives logp = +0.0 like any other.
+ *                  token = target                 so _advance works unchanged
+ *                  best  = the first word of the ORDER (the lowest index among the maxima)
+ *                  rank  = the number of words strictly before the target in the ORDER: those with a larger y and those
+ *                          with an equal y and a lower index.  rank == 0 <=> best == target.
+ *   logp         the arithmetic of the filtered pick with everything kept: m = max y; e_v = expf(fl(y_v - m)) in fp32, a
+ *                -inf logit has e_v = 0 exactly; S = the fp64 sum of the e_v in one fixed order (thread i of 256 adds its
+ *                groups of four words q = i, i + 256, ..., words 4q .. 4q + 3; lanes are then added as a butterfly, then
+ *                the waves 0..3);  logp = (double)y_target - ((double)m + log(S)), rounded ONCE to fp32.  A -inf target
+ *                gives -inf, a row with one finite logit +0.0.  sum_logp accumulates the fp32 records in fp32, as _pick
+ *                does.  No floating-point atomics: the same inputs give the same bits, for any chunking of the steps.
+ *   CLOSING      when t + 1 == ntok[r] the row closes: nopen[n] -= 1 and open_rows -= 1, as _pick closes a row on <end>.
+ *                <end> itself is NOT special here: it is a token like any other, and a caption without <end> is scored as
+ *                given.
+ *   ODD INPUTS   a target outside [0, V) gives logp = NaN and rank = V (best is still the row's), writes only its own
+ *                records, and _advance clamps the token.  A row that holds a NaN is OUTSIDE this contract; it still
+ *                writes only its own records.
+ * K in [1, 8], max_steps as for the search, inv_temp > 0 and finite, the start token inside the vocabulary; a refusal
+ * returns -1 before anything is launched.  want_alpha as in the rollout: the maps are the attention of the given caption.
+ * fp32 only; dense encoder_out only.
+ *   _workspace_sc / _layout_sc   _layout_sc writes SCNATTN_ROLLOUT_NOFF_SC offsets: the 8 of scnattn_rollout_layout (3 length
+ *       now holds ntok), then 8 rank int[max_steps][N*K], 9 best int[max_steps][N*K], 10 target int[max_steps][N*K].
+ *   _init_sc   the captions as device pointers: targets int32 [N*K][ld_tok] row-major with ld_tok >= max_steps (the first
+ *       max_steps entries of a row are read), ntok int32 [N*K], each in [0, max_steps] (clamped into it).  One kernel copies
+ *       the captions into the workspace step-major and sets nopen[n] = #{j: ntok > 0}, nsrc[n] = nopen[n] > 0 ? K : 0,
+ *       open_rows = sum of nopen, sum_logp = 0; then the set-up of _init.  Ragged input is allowed: a slot with ntok == 0 is
+ *       empty, and an image whose slots are all empty is closed from the start.
+ *   _steps_sc  steps t0 .. t0+n_steps-1 (clipped to max_steps): the search's decode part, _score, _advance -- the launches
+ *       of a rollout step; chunks and the open_rows counter as in the rollout.
+ *   scnattn_rollout_score   the kernel alone for step t (state: the seven pointers 0..6 of scnattn_rollout_layout, 3 holding
+ *       ntok); target_t / rank_t / best_t int[N*K] are the given tokens and the records of that step. */
+#define SCNATTN_ROLLOUT_NOFF_SC 11
+int scnattn_rollout_workspace_sc(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
+int scnattn_rollout_layout_sc(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* offsets);
+int scnattn_rollout_init_sc(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                            const float* enc, const float* tags, int start_token, const int32_t* targets, long ld_tok,
+                            const int32_t* ntok, float* ws);
+int scnattn_rollout_steps_sc(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                             const float* enc, float inv_temp, int t0, int n_steps, float* ws);
+int scnattn_rollout_score(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, int t, int max_steps,
+                          void* const* state, const int32_t* target_t, int32_t* rank_t, int32_t* best_t);
 /* The kernels of a step (csrc/beam.hip), one launch each; nsrc int[N] on the device.
  *   _attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0 for j < nsrc[n] (other rows untouched)
  *   _attn_context  alpha_out [N*K][P], awe [N*K][E] (either may be NULL), z = sigmoid(gpre + gate_bias) * awe (gpre NULL: awe)

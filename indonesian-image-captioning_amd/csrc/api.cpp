@@ -57,6 +57,14 @@ int rollout_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, in
 int rollout_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_sample_filter* f,
                   bool filtered, const scnattn_params* w, const float* enc, int end_token, float inv_temp,
                   unsigned long long seed, unsigned draw, int greedy_first, int t0, int n_steps, float* ws);
+// scoring given captions: the _sc form of the rollout driver
+int score_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
+int score_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off);
+int score_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+               const float* enc, const float* tags, int start_token, const int* targets, long ld_tok, const int* ntok,
+               float* ws);
+int score_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                const float* enc, float inv_temp, int t0, int n_steps, float* ws);
 
 int pool_desc(const scnattn_pool* p, PoolDesc& out) {
     out = PoolDesc{0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -492,6 +500,27 @@ int scnattn_rollout_pick_f(void* stream, int N, int K, int V, const float* logit
 int scnattn_rollout_advance(void* stream, int N, int K, int M, int V, const int32_t* token_t, const float* table, float* emb,
                             const int32_t* nopen, int32_t* nsrc) {
     return rollout_advance(ST(stream), N, K, M, V, token_t, table, emb, nopen, nsrc);
+}
+int scnattn_rollout_workspace_sc(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
+    return score_workspace(d, K, max_steps, want_alpha, bytes);
+}
+int scnattn_rollout_layout_sc(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* offsets) {
+    return score_layout(d, K, max_steps, want_alpha, offsets);
+}
+int scnattn_rollout_init_sc(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                            const float* enc, const float* tags, int start_token, const int32_t* targets, long ld_tok,
+                            const int32_t* ntok, float* ws) {
+    return score_init(ST(stream), d, K, max_steps, want_alpha, w, enc, tags, start_token, targets, ld_tok, ntok, ws);
+}
+int scnattn_rollout_steps_sc(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                             const float* enc, float inv_temp, int t0, int n_steps, float* ws) {
+    return score_steps(ST(stream), d, K, max_steps, want_alpha, w, enc, inv_temp, t0, n_steps, ws);
+}
+int scnattn_rollout_score(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, int t, int max_steps,
+                          void* const* state, const int32_t* target_t, int32_t* rank_t, int32_t* best_t) {
+    RolloutState s;
+    SCN_TRY(rollout_state_of("scnattn_rollout_score", N, K, max_steps, state, s));
+    return rollout_score(ST(stream), N, K, V, logits, ld, inv_temp, t, target_t, rank_t, best_t, s);
 }
 
 int scnattn_seq_workspace(const scnattn_dims* d, const scnattn_pool* pool, size_t* saved_bytes, size_t* scratch_bytes) {

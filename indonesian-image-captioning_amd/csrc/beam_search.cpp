@@ -64,6 +64,7 @@ struct SearchWs {
 struct RolloutWs : StepWs {
     RolloutState s;
     int* nkeep;             // [T][R] words kept by the sample filter (the _f form of the driver), else null
+    int *rank, *best, *target;      // [T][R] each: the records and the given tokens of a scoring run (_sc), else null
 };
 
 inline int* ints(float* p) { return reinterpret_cast<int*>(p); }
@@ -452,7 +453,9 @@ int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member,
 namespace {
 
 // filtered: the _f form of the four calls, whose workspace also holds the nkeep records (behind alpha, zero-filled by init)
-size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, bool filtered, float* base, RolloutWs& b) {
+// scored: the _sc form, which keeps rank, best and the given tokens there instead
+size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, bool filtered, float* base, RolloutWs& b,
+                     bool scored = false) {
     Carver c(base);
     const int N = d.B, P = d.P;
     const long R = (long)N * K;
@@ -467,6 +470,9 @@ size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, bool f
     b.s.logp = c.take(sz(T, R));
     b.alpha = (d.has_att && want_alpha) ? c.take(sz(T, R, P)) : nullptr;
     b.nkeep = filtered ? ints(c.take(sz(T, R))) : nullptr;
+    b.rank = scored ? ints(c.take(sz(T, R))) : nullptr;
+    b.best = scored ? ints(c.take(sz(T, R))) : nullptr;
+    b.target = scored ? ints(c.take(sz(T, R))) : nullptr;
     carve_step_state(c, d, R, b);
     b.state_floats = c.off;
     carve_step_setup(c, d, R, b);
@@ -550,6 +556,69 @@ int rollout_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, 
         else
             SCN_TRY(rollout_pick(st, N, K, V, b.logits, V, inv_temp, seed, draw, t, greedy_first, end_token, b.s));
         SCN_TRY(rollout_advance(st, N, K, M, V, b.s.token + (long)t * R, w->embedding_weight, b.emb, b.s.nopen, b.s.nsrc));
+    }
+    return 0;
+}
+
+// ---- scoring given captions (the _sc form; include/scnattn.h) --------------------------------------------------------------
+// The rollout's chain with the pick replaced by rollout_score, which is told the token: the same launches per step.  The
+// workspace is the plain rollout's with three more records behind alpha; `length` holds ntok.
+int score_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_ARG(bytes, "rollout_workspace_sc: bytes is NULL");
+    RolloutWs b;
+    *bytes = carve_rollout(*d, K, max_steps, want_alpha, false, nullptr, b, true);
+    return 0;
+}
+
+// off[SCNATTN_ROLLOUT_NOFF_SC]: the 8 of rollout_layout, then rank, best, target
+int score_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_ARG(off, "rollout_layout_sc: offsets is NULL");
+    RolloutWs b;
+    carve_rollout(*d, K, max_steps, want_alpha, false, layout_base(), b, true);
+    const void* p[SCNATTN_ROLLOUT_NOFF_SC] = {b.s.open_rows, b.s.nsrc, b.s.nopen, b.s.length, b.s.sum_logp, b.s.token, b.s.logp,
+                                              b.alpha, b.rank, b.best, b.target};
+    offsets_from(layout_base(), p, SCNATTN_ROLLOUT_NOFF_SC, off);
+    return 0;
+}
+
+int score_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
+               const float* enc, const float* tags, int start_token, const int* targets, long ld_tok, const int* ntok,
+               float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    const scnattn_dims& d = *dp;
+    SCN_ARG(w && enc && tags && ws, "rollout_init_sc: null argument");
+    SCN_ARG(targets && ntok, "rollout_init_sc: the captions are NULL");
+    SCN_ARG(ld_tok >= max_steps, "rollout_init_sc: ld_tok must be at least max_steps");
+    SCN_ARG(start_token >= 0 && start_token < d.V, "rollout_init_sc: start token outside the vocabulary");
+    SCN_ARG(aligned16(ws), "rollout_init_sc: the workspace must be 16-byte aligned");
+    RolloutWs b;
+    carve_rollout(d, K, max_steps, want_alpha, false, ws, b, true);
+    SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));      // the records of closed rows: zeros
+    SCN_TRY(rollout_score_init(st, d.B, K, targets, ld_tok, ntok, b.target, b.s));
+    SCN_TRY(decode_setup(st, d, K, w, enc, tags, start_token, b));
+    return 0;
+}
+
+int score_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                const float* enc, float inv_temp, int t0, int n_steps, float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    const scnattn_dims& d = *dp;
+    SCN_ARG(w && enc && ws, "rollout_steps_sc: null argument");
+    SCN_ARG(t0 >= 0 && n_steps >= 0, "rollout_steps_sc: negative step");
+    SCN_ARG(inv_temp > 0.f && inv_temp < INFINITY, "rollout_steps_sc: inv_temp must be positive and finite");
+    const int N = d.B, P = d.P, M = d.M, V = d.V, R = N * K;
+    RolloutWs b;
+    carve_rollout(d, K, max_steps, want_alpha, false, ws, b, true);
+    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
+    for (int t = t0; t < t1; ++t) {
+        const bool even = (t & 1) == 0;         // the state of step t sits in A for even t, in B for odd t
+        const long o = (long)t * R;
+        SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, b.alpha ? b.alpha + o * P : nullptr, even ? b.hA : b.hB,
+                            even ? b.cA : b.cB, even ? b.hB : b.hA, even ? b.cB : b.cA));
+        SCN_TRY(rollout_score(st, N, K, V, b.logits, V, inv_temp, t, b.target + o, b.rank + o, b.best + o, b.s));
+        SCN_TRY(rollout_advance(st, N, K, M, V, b.s.token + o, w->embedding_weight, b.emb, b.s.nopen, b.s.nsrc));
     }
     return 0;
 }

@@ -263,6 +263,16 @@ int rollout_pick_filtered(hipStream_t st, int N, int K, int V, const float* logi
 int rollout_advance(hipStream_t st, int N, int K, int M, int V, const int* token_t, const float* table, float* emb,
                     const int* nopen, int* nsrc);
 int rollout_state_init(hipStream_t st, int N, int K, const RolloutState& s);
+// SCORING given captions (include/scnattn.h: teacher-forced log-probabilities): the pick with the token told.  s.length
+// holds ntok, the number of given tokens of the row; a row is open at step t iff t < ntok.  Per open row: token = the
+// target, logp under softmax(logits * inv_temp) (fp32 terms, fp64 sum in tally order, one rounding), rank = words strictly
+// before the target in the ORDER, best = the first word of the ORDER; the row closes at t + 1 == ntok.
+int rollout_score(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp, int t,
+                  const int* target_t, int* rank_t, int* best_t, const RolloutState& s);
+// The state of a scoring run from the captions: target_ws [T][R] = targets [R][ld_tok] transposed, s.length = ntok clamped
+// into [0, T], nopen / nsrc / open_rows counted from it, sum_logp = 0.  One launch.
+int rollout_score_init(hipStream_t st, int N, int K, const int* targets, long ld_tok, const int* ntok, int* target_ws,
+                       const RolloutState& s);
 
 // ---- scn_cell.hip ----------------------------------------------------------------------------
 int scn_mix_fwd(hipStream_t st, int rows, int F4, Slabs pz, const float* ex, Slabs ph, const float* qx,

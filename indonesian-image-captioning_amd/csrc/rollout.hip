@@ -18,6 +18,8 @@
 //                    what another one does in the same launch.
 //   rollout_pick_filtered  the same pick inside the top-k / nucleus set of the row (further down): the cut by
 //                    bisection on the order-preserving integer image of y, counts and fp64 masses, then one keyed pass.
+//   rollout_score    the pick TOLD its token (scoring given captions; further down): the token's
+//                    log-probability, its rank in the row and the row's first word, the row closing after its last given token.
 //   rollout_advance  the next input embedding of every row (the token record clamped into the table) and, per image,
 //                    nsrc[n] = nopen[n] > 0 ? K : 0 for the attention kernels of the next step.
 // The arg-max slot skips the noise: key_v = y_v exactly.  Plain vector loads and stores; no kernel waits for another
@@ -417,6 +419,142 @@ __global__ __launch_bounds__(256) void rollout_pick_filtered_kernel(int K, int V
     }
 }
 
+// ---- scoring given captions (teacher forcing; the contract: include/scnattn.h) ------------------------------
+// The pick with the token told: s.length holds ntok, and a row is open at step t iff t < ntok[r].  Two passes over the row,
+// which the fc product has just left in L2, in the ownership of the filtered pick (thread i: the groups of four q = i,
+// i + 256, ...):
+//   1. the first word of the ORDER as one 64-bit maximum: the image of y above the complemented index, so that among equal
+//      images the lower index is the larger number.  Its upper half is the image of m = max y.
+//   2. rank (the words strictly before the target in the ORDER, an exact count on images) and S = sum of e_v (fp64), in one
+//      tally_all.
+// y is taken back from its image in both passes, so -0 counts as +0 everywhere.  There is one form for every V: no row is
+// held in registers, hence no second set of bits to keep equal.
+template <bool VEC>
+__device__ __forceinline__ void load_group(const float* x, int v0, int V, float* e) {
+    if (VEC && v0 + 3 < V) {
+        const f32x4 l = ld4(x + v0);
+        e[0] = l[0]; e[1] = l[1]; e[2] = l[2]; e[3] = l[3];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = v0 + c < V ? x[v0 + c] : 0.f;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void rollout_score_kernel(int K, int V, const float* __restrict__ logits, long ld,
+                                                            float inv_temp, int t, const int* __restrict__ target_t,
+                                                            int* __restrict__ rank_t, int* __restrict__ best_t,
+                                                            RolloutState s) {
+    const int r = blockIdx.x, n = r / K;
+    if (s.nsrc[n] <= 0) return;                 // a closed image: uniform over the workgroup
+    int* token_t = s.token + (long)t * s.R;
+    float* logp_t = s.logp + (long)t * s.R;
+    const int ntok = s.length[r];
+    if (t >= ntok) {                            // a closed row of an open image
+        if (threadIdx.x == 0) { token_t[r] = 0; logp_t[r] = 0.f; rank_t[r] = 0; best_t[r] = 0; }
+        return;
+    }
+    __shared__ Tally red[4];
+    __shared__ unsigned long long redk[4];
+    const float* x = logits + (long)r * ld;
+    const int tid = threadIdx.x;
+    const int groups = (V + 3) >> 2;
+    const int tgt = target_t[r];
+    const bool inside = tgt >= 0 && tgt < V;
+    const unsigned it = inside ? img_of(x[tgt] * inv_temp) : 0u;
+
+    unsigned long long top = 0ull;              // below every real word: an index is < 2^31, so ~index is not 0
+    for (int q = tid; q < groups; q += 256) {
+        const int v0 = q * 4;
+        float e[4];
+        load_group<VEC>(x, v0, V, e);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (v0 + c < V) {
+                const unsigned long long k = ((unsigned long long)img_of(e[c] * inv_temp) << 32) | (unsigned)~(v0 + c);
+                top = k > top ? k : top;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned hi = (unsigned)__shfl_xor((int)(top >> 32), o, 64), lo = (unsigned)__shfl_xor((int)top, o, 64);
+        const unsigned long long k = ((unsigned long long)hi << 32) | lo;
+        top = k > top ? k : top;
+    }
+    if ((tid & 63) == 0) redk[tid >> 6] = top;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) top = redk[w] > top ? redk[w] : top;
+    const unsigned mx = (unsigned)(top >> 32);
+    const int best = (int)~(unsigned)top;
+    const float m = y_of(mx);
+
+    Tally a = {0, 0, 0.0};
+    for (int q = tid; q < groups; q += 256) {
+        const int v0 = q * 4;
+        float e[4];
+        load_group<VEC>(x, v0, V, e);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int v = v0 + c;
+            if (v < V) {
+                const unsigned im = img_of(e[c] * inv_temp);
+                const float y = y_of(im);
+                a.a += im > it || (im == it && v < tgt);
+                a.s += (double)(y == -INFINITY ? 0.f : expf(y - m));
+            }
+        }
+    }
+    a = tally_all(a, red);
+    if (tid != 0) return;
+    // fp64 from the mass to the difference; ONE rounding to fp32
+    const float lp = inside ? (float)((double)y_of(it) - ((double)m + log(a.s))) : __builtin_nanf("");
+    token_t[r] = tgt;
+    logp_t[r] = lp;
+    rank_t[r] = inside ? a.a : V;
+    best_t[r] = best;
+    s.sum_logp[r] += lp;
+    if (t + 1 == ntok) {
+        atomicAdd(s.nopen + n, -1);
+        atomicAdd(s.open_rows, -1);
+    }
+}
+
+// target_ws [T][R] from targets [R][ld_tok]; ntok clamped into [0, T]; the counters counted from it (every thread that
+// needs a count reads the caller's ntok itself: no workgroup waits for another)
+__global__ __launch_bounds__(256) void rollout_score_init_kernel(int N, int K, const int* __restrict__ targets, long ld_tok,
+                                                                 const int* __restrict__ ntok, int* __restrict__ target_ws,
+                                                                 RolloutState s) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int R = s.R, T = s.T;
+    auto len = [&](int r) { return min(max(ntok[r], 0), T); };
+    if (i < (long)R * T) {
+        const int r = (int)(i / T), t = (int)(i - (long)r * T);
+        target_ws[(long)t * R + r] = targets[r * ld_tok + t];
+    }
+    if (i < R) {
+        s.length[i] = len((int)i);
+        s.sum_logp[i] = 0.f;
+    }
+    if (i < N) {
+        int c = 0;
+        for (int j = 0; j < K; ++j) c += len((int)i * K + j) > 0;
+        s.nopen[i] = c;
+        s.nsrc[i] = c > 0 ? K : 0;
+    }
+    if (blockIdx.x == 0) {                      // open_rows: an integer count, so any order gives the same number
+        __shared__ int cnt[4];
+        int c = 0;
+        for (int r = threadIdx.x; r < R; r += 256) c += len(r) > 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) s.open_rows[0] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    }
+}
+
 bool state_ok(const RolloutState& s, int N, int K) {
     return s.R == N * K && s.T >= 1 && s.open_rows && s.nsrc && s.nopen && s.length && s.sum_logp && s.token && s.logp;
 }
@@ -495,6 +633,35 @@ int rollout_advance(hipStream_t st, int N, int K, int M, int V, const int* token
 int rollout_state_init(hipStream_t st, int N, int K, const RolloutState& s) {
     SCN_ARG(N > 0 && K >= 1 && K <= SCN_MAX_BEAM && state_ok(s, N, K), "rollout_state_init: bad argument");
     hipLaunchKernelGGL(rollout_state_init_kernel, dim3(cdiv(s.R, 256)), dim3(256), 0, st, N, K, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int rollout_score(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp, int t,
+                  const int* target_t, int* rank_t, int* best_t, const RolloutState& s) {
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= 1 && t >= 0, "rollout_score: bad slot count / vocab_size / step");
+    SCN_ARG((long)N * K <= (1L << 20), "rollout_score: too many rows (images x slots)");
+    SCN_ARG(inv_temp > 0.f && inv_temp < INFINITY, "rollout_score: inv_temp must be positive and finite");
+    SCN_ARG(logits && ld >= V && state_ok(s, N, K), "rollout_score: bad argument");
+    SCN_ARG(t < s.T, "rollout_score: step beyond the records");
+    SCN_ARG(target_t && rank_t && best_t, "rollout_score: a target / rank / best record is NULL");
+    if (aligned16(logits) && ld % 4 == 0)
+        hipLaunchKernelGGL(rollout_score_kernel<true>, dim3(N * K), dim3(256), 0, st, K, V, logits, ld, inv_temp, t, target_t,
+                           rank_t, best_t, s);
+    else
+        hipLaunchKernelGGL(rollout_score_kernel<false>, dim3(N * K), dim3(256), 0, st, K, V, logits, ld, inv_temp, t, target_t,
+                           rank_t, best_t, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int rollout_score_init(hipStream_t st, int N, int K, const int* targets, long ld_tok, const int* ntok, int* target_ws,
+                       const RolloutState& s) {
+    SCN_ARG(N > 0 && K >= 1 && K <= SCN_MAX_BEAM && state_ok(s, N, K), "rollout_score_init: bad argument");
+    SCN_ARG(targets && ntok && target_ws && ld_tok >= s.T, "rollout_score_init: null captions, or ld_tok below max_steps");
+    hipLaunchKernelGGL(rollout_score_init_kernel, dim3(cdiv((long)s.R * s.T, 256)), dim3(256), 0, st, N, K, targets, ld_tok,
+                       ntok, target_ws, s);
     SCN_LAUNCH_CHECK();
     return 0;
 }

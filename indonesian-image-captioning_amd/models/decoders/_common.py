@@ -472,3 +472,107 @@ def rollout_batched(decoder, word_map, encoder_out, tag_out, use_attention, use_
     caps[:, 0] = start
     caps[:, 1:] = torch.where(pos < n_tok.unsqueeze(1), res["tokens"].to(torch.int64), caps[:, 1:])
     return caps, (n_tok + 1).unsqueeze(1), res["sum_logp"].clone()
+
+
+SCORE_MAX_PER_IMAGE = 8       # captions of one image in one call: the K of the driver (scnattn._lib.MAX_BEAM)
+
+
+def check_score_args(word_map, n_images, caps, caplens, per_image, temperature=1.0, who="score_batch"):
+    """The refusals of ``score_batched`` (ValueError), on whatever device the captions live: per_image in [1, 8], caps
+    (n_images * per_image, L) with caplens one per row, a positive finite temperature; then, on the data, caplens - 1 <= 51,
+    <start> in front of every non-empty row, and every scored token inside the vocabulary.  The data checks are three
+    flags computed where the captions are and read with ONE download (one synchronisation when that is the GPU).
+    -> (per_image, ntok (R,) int64 on the captions' device)"""
+    import operator
+    try:
+        per_image = operator.index(per_image)
+    except TypeError:
+        raise ValueError("%s: per_image must be an integer in [1, %d] (got %r)" % (who, SCORE_MAX_PER_IMAGE, per_image)) from None
+    if not 1 <= per_image <= SCORE_MAX_PER_IMAGE:
+        raise ValueError("%s: per_image must be in [1, %d] (got %d)" % (who, SCORE_MAX_PER_IMAGE, per_image))
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature < float("inf")):
+        raise ValueError("%s: temperature must be positive and finite (got %r)" % (who, temperature))
+    R = n_images * per_image
+    if caps.dim() != 2 or caps.shape[0] != R or caps.shape[1] < 1 or caplens.numel() != R:
+        raise ValueError("%s: %d images x %d captions need caps (%d, L) and caplens (%d, 1) (got %s and %s)"
+                         % (who, n_images, per_image, R, R, tuple(caps.shape), tuple(caplens.shape)))
+    if caps.dtype.is_floating_point or caplens.dtype.is_floating_point:
+        raise ValueError("%s: caps and caplens must be integer tensors" % who)
+    V, L = len(word_map), caps.shape[1]
+    ntok = (caplens.reshape(-1).to(torch.int64) - 1).clamp_min(0)
+    tgt = caps[:, 1:].to(torch.int64)
+    given = torch.arange(L - 1, device=caps.device).unsqueeze(0) < ntok.unsqueeze(1)
+    too_long = (ntok > min(SF.BEAM_MAX_STEPS, L - 1)).any()
+    no_start = ((caps[:, 0] != word_map[start_token]) & (ntok > 0)).any()
+    outside = (((tgt < 0) | (tgt >= V)) & given).any()
+    too_long, no_start, outside = torch.stack([too_long, no_start, outside]).tolist()
+    if too_long:
+        raise ValueError("%s: a caption has more than %d tokens after <start> (caplens - 1), or more than caps holds"
+                         % (who, SF.BEAM_MAX_STEPS))
+    if no_start:
+        raise ValueError("%s: a non-empty caption does not begin with <start>" % who)
+    if outside:
+        raise ValueError("%s: a caption holds a token outside the vocabulary of %d words" % (who, V))
+    return per_image, ntok
+
+
+def score_batched(decoder, word_map, encoder_out, tag_out, use_attention, use_tags, caps, caplens, per_image,
+                  temperature=1.0, want_alpha=False):
+    """The log-probabilities of GIVEN captions, teacher-forced on the device (csrc/rollout.hip: rollout_score,
+    SF.score_run): encoder_out (N, h, w, E), tag_out (N, S); caps (N*per_image, L) and caplens (N*per_image, 1) in the form
+    ``forward`` takes and ``rollout_batch`` returns them, row n*per_image + j belonging to image n.  The scored tokens are
+    caps[:, 1:caplens] (ntok = caplens - 1 of them); <end> is a token like any other, so a caption without one is scored
+    as given.  caplens <= 1 marks an EMPTY slot (ragged input: fewer than per_image captions for an image); its records are
+    zeros.  The per_image captions of an image share the image-side set-up, and no (rows, T, V) scores exist anywhere.
+    No dropout, like the search; fp32 only.
+    The arguments are checked before anything touches the GPU (check_score_args; ValueError); the checks that need the
+    captions' values cost ONE synchronisation when the captions are on the device.
+    Returns a dict ON THE DEVICE:
+        logp (R, L-1)        log softmax(logits / temperature) at every given token, 0.0 beyond ntok
+        sum_logp (R,)        their fp32 sum: the caption's log-likelihood
+        n_tokens (R,) int32  ntok
+        rank (R, L-1) int32  how many words the model ranks before the given one (0: it is the model's own word)
+        best (R, L-1) int32  the model's own word at that position, given the caption so far
+        alpha (R, L-1, P)    with want_alpha and attention: the attention maps of the given caption; else None"""
+    from scnattn import _lib
+    N = encoder_out.shape[0]
+    per_image, ntok = check_score_args(word_map, N, caps, caplens, per_image, temperature)
+    _lib.require_cuda(encoder_out, tag_out, caps, caplens)
+    V = len(word_map)
+    dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
+    R, L = caps.shape
+    T = SF.BEAM_MAX_STEPS
+    targets = torch.zeros(R, T, dtype=torch.int32, device=caps.device)
+    n = min(L - 1, T)
+    targets[:, :n] = caps[:, 1:1 + n]
+    res, steps = SF.score_run(dims, per_image, weights, enc, tag_out, word_map[start_token], targets, ntok.to(torch.int32),
+                              inv_temp=1.0 / float(temperature), want_alpha=want_alpha)
+
+    def padded(x):          # (R, steps, ...) -> (R, L - 1, ...), zeros beyond the longest caption
+        out = torch.zeros((R, L - 1) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
+        out[:, :steps] = x
+        return out
+
+    alpha = res["alpha"]
+    return dict(logp=padded(res["logp"]), sum_logp=res["sum_logp"].clone(), n_tokens=res["ntok"].clone(),
+                rank=padded(res["rank"]), best=padded(res["best"]),
+                alpha=None if alpha is None else padded(alpha.transpose(0, 1)))
+
+
+def score_matrix(decoder, word_map, encoder_out, tags, caps, caplens, temperature=1.0):
+    """Every one of Q captions against every one of N images -> (N, Q) log-likelihoods on the device (image-caption
+    retrieval; recall@k stays with the caller).  caps (Q, L), caplens (Q, 1).  A loop of ``score_batch`` calls, 8 captions
+    at a time, every image scoring the same 8."""
+    N, Q = encoder_out.shape[0], caps.shape[0]
+    if caps.dim() != 2 or caplens.numel() != Q:
+        raise ValueError("score_matrix: caps must be (Q, L) and caplens (Q, 1) (got %s and %s)"
+                         % (tuple(caps.shape), tuple(caplens.shape)))
+    caplens = caplens.reshape(Q, 1)
+    out = []
+    for q0 in range(0, Q, SCORE_MAX_PER_IMAGE):
+        k = min(SCORE_MAX_PER_IMAGE, Q - q0)
+        res = decoder.score_batch(word_map, encoder_out, tags, caps[q0:q0 + k].repeat(N, 1), caplens[q0:q0 + k].repeat(N, 1),
+                                  per_image=k, temperature=temperature)
+        out.append(res["sum_logp"].view(N, k))
+    return torch.cat(out, dim=1) if out else torch.zeros(N, 0, device=encoder_out.device)

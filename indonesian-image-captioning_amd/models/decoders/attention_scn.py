@@ -113,6 +113,17 @@ class AttentionSCN(nn.Module):
                                        seed=seed, draw=draw, temperature=temperature, greedy_first=greedy_first,
                                        top_k=top_k, top_p=top_p)
 
+    def score_batch(self, word_map, encoder_out, tags, caps, caplens, per_image, temperature=1.0, want_alpha=False):
+        """The log-probabilities of GIVEN captions, teacher-forced on the device: caps (N*per_image, L), caplens
+        (N*per_image, 1) as ``forward`` takes them, rows n*per_image + j -> dict(logp, sum_logp, n_tokens, rank, best,
+        alpha) on the device (_common.score_batched: the checks, empty slots, what each record is)."""
+        return _common.score_batched(self, word_map, encoder_out, tags, use_attention=True, use_tags=True, caps=caps,
+                                     caplens=caplens, per_image=per_image, temperature=temperature, want_alpha=want_alpha)
+
+    def score_matrix(self, word_map, encoder_out, tags, caps, caplens, temperature=1.0):
+        """Q captions against N images -> (N, Q) log-likelihoods on the device (_common.score_matrix)"""
+        return _common.score_matrix(self, word_map, encoder_out, tags, caps, caplens, temperature=temperature)
+
 
 _KEY_OF_FIELD = {
     "attention_encoder_att_weight": "attention.encoder_att.weight",

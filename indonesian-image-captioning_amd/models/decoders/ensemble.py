@@ -132,3 +132,43 @@ class DecoderEnsemble(nn.Module):
         out = _common.trace_back(res, steps, N, k, start, end, (hh, ww), self.has_alphas, return_all, length_penalty=alpha,
                                  groups=G, with_scores=with_scores, with_met=with_met)
         return [[x] for x in out] if groups is not None and G == 1 else out
+
+    def score_batch(self, word_map, encoder_out, tags, caps, caplens, per_image, temperature=1.0, want_alpha=False):
+        """The log-probabilities of GIVEN captions under the COMBINED distribution: every member's ``score_batch`` (the
+        same arguments and refusals, `_common.score_batched`), then ``combine_logp`` on the device -- for every token
+        exactly the score the ensemble search accumulates for it.  sum_logp is the fp32 sum of the combined records.
+        rank and best are None for more than one member (they would need the combined row); alpha is that of
+        ``alpha_member``.  A one-member ensemble returns the decoder's result bit for bit."""
+        if len(word_map) != self.vocab_size:
+            raise ValueError("score_batch: the word map has %d words, the members' vocab_size is %d"
+                             % (len(word_map), self.vocab_size))
+        if self.needs_tags and tags is None:
+            raise ValueError("score_batch: a member of the ensemble uses tags and none were given")
+        res = [dec.score_batch(word_map, encoder_out, tags, caps, caplens, per_image, temperature=temperature,
+                               want_alpha=want_alpha and i == self.alpha_member)
+               for i, dec in enumerate(self.decoders)]
+        if len(res) == 1:
+            return res[0]
+        logp = combine_logp([r["logp"] for r in res], self.member_weights, COMBINE.index(self.combine))
+        return dict(logp=logp, sum_logp=logp.sum(dim=1), n_tokens=res[0]["n_tokens"], rank=None, best=None,
+                    alpha=None if self.alpha_member is None else res[self.alpha_member]["alpha"])
+
+
+def combine_logp(logps, w, mode):
+    """The header's ensemble formula taken at ONE word: logps the members' log-probabilities of it (tensors of one
+    shape), w their weights -> mode 0 ("logprob"): sum_m w_m l_m, summed in member order; mode 1 ("prob"):
+    a + log sum_m w_m exp(l_m - a) with a = max_m l_m.  In the dtype of `logps`, on their device.  A position where every
+    member holds -inf gives -inf in both modes."""
+    if mode == 0:
+        c = w[0] * logps[0]
+        for wm, l in zip(w[1:], logps[1:]):
+            c = c + wm * l
+        return c
+    a = logps[0]
+    for l in logps[1:]:
+        a = torch.maximum(a, l)
+    safe = torch.where(torch.isinf(a), torch.zeros_like(a), a)       # a = -inf: exp(l - a) would be NaN
+    s = w[0] * torch.exp(logps[0] - safe)
+    for wm, l in zip(w[1:], logps[1:]):
+        s = s + wm * torch.exp(l - safe)
+    return a + torch.log(s)

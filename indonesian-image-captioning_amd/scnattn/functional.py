@@ -584,6 +584,79 @@ def rollout_run(dims, K, weights, enc, tags, start, end, seed, draw, inv_temp=1.
 
 
 # ----------------------------------------------------------------------------------------------
+# scoring given captions (include/scnattn.h: scnattn_rollout_*_sc)
+# ----------------------------------------------------------------------------------------------
+_SCORE_RESULTS = ("open_rows", "nsrc", "nopen", "ntok", "sum_logp", "token", "logp", "alpha", "rank", "best", "target")
+_SCORE_FLOAT = ("sum_logp", "logp", "alpha")
+
+
+def score_run(dims, K, weights, enc, tags, start, targets, ntok, inv_temp=1.0, max_steps=BEAM_MAX_STEPS, want_alpha=False,
+              guard=0, chunk=BEAM_CHUNK):
+    """The log-probabilities of GIVEN captions under the decoder, teacher-forced on the device (csrc/rollout.hip:
+    rollout_score; the analogue of rollout_run with the pick told its token).  K captions per image, rows n*K + j:
+    targets (R, >= max_steps) int32 on the device, row r holding ntok[r] tokens (what follows <start>); ntok (R,) int32 on
+    the device, each in [0, max_steps]; 0 marks an empty slot, and an image whose slots are all empty is closed from the
+    start.  dims / weights / enc / tags as for beam_search_run.  Returns (results, steps); the results stay ON THE DEVICE
+    (views of the workspace); the open-row counter is downloaded between chunks and the longest ntok once at the end, so
+    steps is the length of the longest caption:
+        logp (R, steps)           log softmax(logits * inv_temp) at the given token, 0.0 at and beyond ntok
+        rank (R, steps) int32     the words strictly before the given one in the order (value descending, index ascending)
+        best (R, steps) int32     the model's own first word at that position
+        tokens (R, steps) int32   the given tokens as recorded, 0 beyond ntok
+        sum_logp (R,)             the fp32 sum of the row's logp
+        ntok (R,) int32           as given (clamped into [0, max_steps])
+        alpha (steps, R, P)       only with want_alpha (and attention), else None: the attention of the given caption
+        open_rows, nsrc, nopen    the counters (scnattn_rollout_layout)
+    guard > 0 (tests): that many sentinel words behind the workspace, returned as results["guard"]."""
+    K = int(K)
+    if not 1 <= K <= _lib.MAX_BEAM:
+        raise ValueError("score_run: K must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, K))
+    inv_temp = float(inv_temp)
+    if not (inv_temp > 0.0 and inv_temp < float("inf")):
+        raise ValueError("score_run: inv_temp must be positive and finite (got %r)" % inv_temp)
+    d = Dims(*dims)
+    if not 0 <= int(start) < d.V:
+        raise ValueError("score_run: start token outside the vocabulary")
+    N = d.B
+    R = N * K
+    if targets.dtype != torch.int32 or ntok.dtype != torch.int32:
+        raise ValueError("score_run: targets and ntok must be int32")
+    if targets.dim() != 2 or targets.shape[0] != R or targets.shape[1] < max_steps or ntok.numel() != R:
+        raise ValueError("score_run: targets must be (%d, >= %d) and ntok (%d,) (got %s and %s)"
+                         % (R, max_steps, R, tuple(targets.shape), tuple(ntok.shape)))
+    require_cuda(enc, tags, targets, ntok, *weights)
+    dev = enc.device
+    enc, tags = f32c(enc), f32c(tags)
+    targets, ntok = targets.contiguous(), ntok.contiguous()
+    weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
+    w = _params_struct(weights)
+    wa = int(bool(want_alpha))
+    ws, off, nwords, t = _run_on_device("scnattn_rollout_%s_sc", (C.byref(d), K, max_steps, wa), _lib.ROLLOUT_NOFF_SC,
+                                        (C.byref(w), ptr(enc), ptr(tags), int(start), ptr(targets), targets.shape[1],
+                                         ptr(ntok)),
+                                        (C.byref(w), ptr(enc), inv_temp), stream_of(enc), dev, max_steps, chunk, guard)
+    wsi = ws.view(torch.int32)
+    # the steps of the last chunk beyond the longest caption were no-ops: leave them out (one more 4-byte download)
+    t = min(t, int(wsi[off[3]:off[3] + R].max()))
+    sizes = {"open_rows": 1, "nsrc": N, "nopen": N, "ntok": R, "sum_logp": R, "alpha": t * R * d.P}
+    out = {}
+    for i, name in enumerate(_SCORE_RESULTS):
+        if off[i] < 0:
+            out[name] = None
+            continue
+        src = ws if name in _SCORE_FLOAT else wsi
+        out[name] = src[off[i]:off[i] + sizes.get(name, t * R)]
+    out["tokens"] = out.pop("token")
+    for name in ("tokens", "logp", "rank", "best", "target"):
+        out[name] = out[name].view(t, R).t()
+    if out["alpha"] is not None:
+        out["alpha"] = out["alpha"].view(t, R, d.P)
+    if guard:
+        out["guard"] = wsi[nwords:]
+    return out, t
+
+
+# ----------------------------------------------------------------------------------------------
 # stand-alone SCN cell (any batch size), split exactly where the reference splits it:
 #   scn_input      = SCNCell.forward's x side      (models/scn_cell.py:64-91)
 #   scn_recurrent  = SCNCell.recurrent_step        (models/scn_cell.py:112-154)

@@ -15,6 +15,16 @@ from . import data, viz
 from ._lib import require_cuda
 
 _SPECIAL = ("<start>", "<end>", "<pad>")        # utils/token.py; dropped from the sentence (inference.py:156-157)
+SCORE_MAX_TOKENS = 51       # the step limit of the device drivers (scnattn.functional.BEAM_MAX_STEPS)
+
+
+def rerank_order(records, length_penalty=0.0):
+    """records of `Captioner.score` (each with "score" and "tokens" = <start> + the scored tokens) -> the same records
+    sorted by score / n_tokens**length_penalty, largest first; equal keys keep their input order (a stable sort)."""
+    length_penalty = float(length_penalty)
+    if length_penalty != length_penalty or length_penalty in (float("inf"), float("-inf")):
+        raise ValueError("rerank: length_penalty must be finite (got %r)" % (length_penalty,))
+    return sorted(records, key=lambda r: -(r["score"] / float(len(r["tokens"]) - 1) ** length_penalty))
 
 
 class Captioner:
@@ -194,6 +204,91 @@ class Captioner:
             records.append({"tokens": seq, "words": [self.rev_word_map[w] for w in seq if w not in self.skip],
                             "alphas": alphas, "score": score, "satisfied": not missing, "missing": missing})
         return records
+
+    def caption_tokens(self, caption):
+        """One given caption -> its token ids with <start> in front.  A list of token ids is taken as given (a leading
+        <start> is not doubled; nothing is appended: a caption without <end> is scored without one).  A list of WORDS is a
+        sentence: words outside the map become <unk>, and <end> is appended unless the sentence already ends with it."""
+        caption = list(caption)
+        start, end = self.word_map["<start>"], self.word_map["<end>"]
+        if caption and all(isinstance(w, str) for w in caption):
+            if "<unk>" not in self.word_map and any(w not in self.word_map for w in caption):
+                raise ValueError("Captioner.score: a word is outside the word map, which has no <unk>")
+            ids = [self.word_map.get(w, self.word_map.get("<unk>")) for w in caption]
+            if ids[-1] != end:
+                ids.append(end)
+        else:
+            if any(isinstance(w, (str, bool)) or int(w) != w for w in caption):
+                raise ValueError("Captioner.score: a caption is a list of token ids or a list of words")
+            ids = [int(w) for w in caption]
+        if ids and ids[0] == start:
+            ids = ids[1:]
+        if not ids:
+            raise ValueError("Captioner.score: an empty caption")
+        if not all(0 <= w < len(self.word_map) for w in ids):
+            raise ValueError("Captioner.score: a token id outside the vocabulary")
+        if len(ids) > SCORE_MAX_TOKENS:
+            raise ValueError("Captioner.score: a caption of %d tokens (at most %d)" % (len(ids), SCORE_MAX_TOKENS))
+        return [start] + ids
+
+    @torch.no_grad()
+    def score(self, images, captions, temperature=1.0):
+        """How likely does the model find THESE captions for these images: teacher-forced log-probabilities on the device
+        (`decoder.score_batch`).  `captions`: per image a list of captions, each a list of token ids or of words
+        (`caption_tokens`).  ONE pass of the trunks; the decoder scores 8 captions per image and call, so an image with
+        more takes several calls over the same encoder output.  -> per image a list of records, in input order:
+            tokens     <start> and the scored tokens
+            words      the same without <start>, <end>, <pad>, through the reversed word map
+            logp       per scored token its log-probability
+            score      their sum, the caption's log-likelihood
+            per_token  score / n_tokens
+            rank       per scored token how many words the model ranks before it (0: the model's own choice); None under
+                       an ensemble of several members"""
+        if not hasattr(self.decoder, "score_batch"):
+            raise ValueError("Captioner.score: a %s cannot score (no score_batch)" % type(self.decoder).__name__)
+        images = list(images)
+        captions = [list(c) for c in captions]
+        if len(captions) != len(images):
+            raise ValueError("Captioner.score: %d caption lists for %d images" % (len(captions), len(images)))
+        seqs = [[self.caption_tokens(c) for c in per_image] for per_image in captions]
+        N = len(images)
+        most = max([len(s) for s in seqs] or [0])
+        out = [[] for _ in range(N)]
+        if most == 0:
+            return out
+        L = max(len(s) for per_image in seqs for s in per_image)
+        pad = self.word_map["<pad>"]
+        with torch.cuda.device(self.device):
+            encoder_out, tags = self._encode(images, self.needs_tags)
+            for c0 in range(0, most, 8):
+                K = min(8, most - c0)
+                caps = torch.full((N * K, L), pad, dtype=torch.int64)
+                caplens = torch.zeros(N * K, 1, dtype=torch.int64)         # 0: an empty slot
+                for n, per_image in enumerate(seqs):
+                    for j, s in enumerate(per_image[c0:c0 + K]):
+                        caps[n * K + j, :len(s)] = torch.tensor(s)
+                        caplens[n * K + j, 0] = len(s)
+                res = self.decoder.score_batch(self.word_map, encoder_out, tags, caps.to(self.device),
+                                               caplens.to(self.device), per_image=K, temperature=temperature)
+                # one download per call: the bits of logp and sum_logp beside the ranks
+                rank = res["rank"] if res["rank"] is not None else torch.full_like(res["logp"], -1, dtype=torch.int32)
+                host = torch.cat([res["logp"].view(torch.int32), rank, res["sum_logp"].view(torch.int32).unsqueeze(1)],
+                                 dim=1).cpu()
+                logp, ranks = host[:, :L - 1].view(torch.float32), host[:, L - 1:2 * (L - 1)]
+                total = host[:, -1:].contiguous().view(torch.float32)
+                for n, per_image in enumerate(seqs):
+                    for j, s in enumerate(per_image[c0:c0 + K]):
+                        r, nt = n * K + j, len(s) - 1
+                        out[n].append({"tokens": s, "words": [self.rev_word_map[w] for w in s if w not in self.skip],
+                                       "logp": logp[r, :nt].tolist(), "score": float(total[r, 0]),
+                                       "per_token": float(total[r, 0]) / nt,
+                                       "rank": None if res["rank"] is None else ranks[r, :nt].tolist()})
+        return out
+
+    def rerank(self, images, captions, length_penalty=0.0, temperature=1.0):
+        """`score`, then per image the records sorted by score / n_tokens**length_penalty, best first (`rerank_order`:
+        the form `SearchOptions.length_penalty` uses; ties keep the input order)."""
+        return [rerank_order(recs, length_penalty) for recs in self.score(images, captions, temperature=temperature)]
 
     @torch.no_grad()
     def __call__(self, images, tag_count=0, overlays=False):

@@ -544,6 +544,66 @@ def evaluate_captions(batches, encoder, encoder_tagger, decoder, word_map, beam_
     return scorer.score((hyp, torch.cat(hyp_lens)), skip_hyp=special)
 
 
+def evaluate_likelihood(encoder, decoder, loader, word_map, tagger=None):
+    """How likely does the model find the split's own references: corpus perplexity and teacher-forced accuracy from
+    `decoder.score_batch` (the whole scoring on the device).  `loader` yields (imgs, allcaps) or (imgs, allcaps, allcaplens):
+    allcaps (N, per_image, L) int holds ALL references of every image (5 in the reference's data), each <start>, the words,
+    <end>, <pad> ...; allcaplens (N, per_image) counts <start> and <end> (absent: up to and including the first <end>, else
+    every token before the padding); a length <= 1 marks a missing reference.  More than 8 references per image are scored
+    8 at a time over the same encoder output.  ONE download per batch: the bits of logp beside rank and n_tokens.
+    Returns dict:
+        perplexity   exp(-sum logp / sum n_tokens), summed in fp64 from the fp32 logp records
+        top1, top5   percent of the reference tokens that the model ranks first / among its first five (rank < 1, < 5)
+        mean_rank    the mean of rank over the reference tokens (0: every token was the model's own choice)
+        n_tokens, n_captions, sum_logp   the totals behind them
+    top1, top5 and mean_rank are None under an ensemble of several members, whose score_batch has no rank."""
+    import math
+    decoder.eval()
+    encoder.eval()
+    if hasattr(tagger, "eval"):
+        tagger.eval()
+    needs_tags = not isinstance(decoder, PureAttention) and getattr(decoder, "needs_tags", True)
+    if needs_tags and tagger is None:
+        raise ValueError("evaluate_likelihood: a %s decoder needs a tagger" % type(decoder).__name__)
+    end, pad = word_map['<end>'], word_map['<pad>']
+    total_lp, n_tok, n_cap, top1, top5, rank_sum, ranked = 0.0, 0, 0, 0, 0, 0, True
+    with torch.no_grad():
+        for batch in loader:
+            imgs, allcaps = batch[0], batch[1]
+            N, Q, L = allcaps.shape
+            if len(batch) > 2:
+                lens = batch[2].reshape(N, Q).to(torch.int64)
+            else:
+                is_end = allcaps == end
+                first_end = torch.where(is_end.any(2), is_end.to(torch.int64).argmax(2) + 1, (allcaps != pad).sum(2))
+                lens = first_end
+            encoder_out = encoder(imgs)
+            tags = tagger(imgs) if needs_tags else None
+            parts = []
+            for q0 in range(0, Q, 8):
+                k = min(8, Q - q0)
+                res = decoder.score_batch(word_map, encoder_out, tags, allcaps[:, q0:q0 + k].reshape(N * k, L),
+                                          lens[:, q0:q0 + k].reshape(N * k, 1), per_image=k)
+                ranked = ranked and res["rank"] is not None
+                rank = res["rank"] if res["rank"] is not None else torch.zeros_like(res["logp"], dtype=torch.int32)
+                parts.append(torch.cat([res["logp"].view(torch.int32), rank, res["n_tokens"].unsqueeze(1)], dim=1))
+            host = torch.cat(parts).cpu()                   # the one download of the batch
+            nt = host[:, -1].to(torch.int64)
+            given = torch.arange(L - 1).unsqueeze(0) < nt.unsqueeze(1)
+            logp, rank = host[:, :L - 1].view(torch.float32), host[:, L - 1:2 * (L - 1)]
+            total_lp += float(logp.double()[given].sum())
+            n_tok += int(nt.sum())
+            n_cap += int((nt > 0).sum())
+            top1 += int((rank[given] < 1).sum())
+            top5 += int((rank[given] < 5).sum())
+            rank_sum += int(rank[given].to(torch.int64).sum())
+    if n_tok == 0:
+        raise ValueError("evaluate_likelihood: no reference tokens")
+    return {"perplexity": math.exp(-total_lp / n_tok), "top1": 100.0 * top1 / n_tok if ranked else None,
+            "top5": 100.0 * top5 / n_tok if ranked else None, "mean_rank": rank_sum / n_tok if ranked else None,
+            "n_tokens": n_tok, "n_captions": n_cap, "sum_logp": total_lp}
+
+
 TAGGER_DEFAULTS = dict(semantic_size=1000, dropout=0.15, batch_size=32, encoder_lr=1e-4, grad_clip=5.0, image_size=256)
 
 
