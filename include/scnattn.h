@@ -1199,7 +1199,15 @@ int scnattn_wgrad16_rows(void* stream, int R, int Cin, int Cout, const void* dy,
  * Backward: weight gradients with a non-null dw[i] are written there (fp32, the parameter's layout); with side_stream they run
  * on it, forked from `stream` by events (the caller joins it and keeps save / tmp / x alive until then).  dx_out receives the
  * gradient of the block input: for an identity block it is dres (accumulated in place); with a downsample the caller adds
- * dxd_out (the [N*Ho*Wo][Cin] gradient through downsample.0) into the strided rows of dx_out itself. */
+ * dxd_out (the [N*Ho*Wo][Cin] gradient through downsample.0) into the strided rows of dx_out itself.  dx_out / dxd_out
+ * receive NULL when need_dx == 0, dxd_out also for an identity block.
+ * Scratch, in floats (Rin = N*Hi*Wi, Rout = N*Ho*Wo, ld = scnattn_cgemm_stat_ld):
+ *   part, bnpart: 2 * max(p * ld(Rin), 4p * ld(Rout)) each (scnattn/block.py part_floats).  bnpart_floats is checked: the
+ *                 forward call needs 2 * 4p * ld(Rout) of it with a downsample (nothing without), the backward call all of
+ *                 it.  part has no size field: the caller guarantees it (forward only).
+ *   ws (side_ws): the split workspace scnattn_cgemm16 / scnattn_wgrad16_* are given; their policies size the split to it.
+ * Every refusal -- geometry (p, Cin multiples of 64; even maps at stride 2; an identity block keeps its shape), a null
+ * buffer or parameter, a bnpart that is too small -- returns -1 before anything is launched: nothing is written. */
 typedef struct scnattn_block16 {
     int N, Cin, Hi, Wi, p, stride, has_down, pad;
     const float* gamma[4]; const float* beta[4]; float* run_mean[4]; float* run_var[4]; const float* shift[4];

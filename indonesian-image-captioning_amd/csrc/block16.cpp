@@ -41,6 +41,31 @@ int carve(const scnattn_block16* b, Carve& c) {
     return 0;
 }
 
+// floats of `part` / `bnpart` a block's partials need at most (scnattn/block.py part_floats): p channels over the input rows
+// or 4p channels over the output rows, [2][C][stat_ld(R)] each; a reduce pass never uses more chunks than 64-row tiles
+long partial_floats(const scnattn_block16* b, const Carve& c) {
+    const long in = (long)b->p * scnattn_cgemm_stat_ld((int)c.Rin), out = c.C4 * scnattn_cgemm_stat_ld((int)c.Rout);
+    return 2 * (in > out ? in : out);
+}
+
+// every refusal that can be read off the struct, in front of the first launch: a refused call writes nothing
+int check_fwd(const scnattn_block16* b, const Carve& c) {
+    SCN_ARG(b->x && b->save && b->stats && b->ws && b->part && b->bnpart, "block16_fwd: null buffer");
+    for (int i = 0; i < (b->has_down ? 4 : 3); ++i)
+        SCN_ARG(b->gamma[i] && b->beta[i] && b->w[i], "block16_fwd: null parameter");
+    SCN_ARG(!b->has_down || 2L * c.C4 * scnattn_cgemm_stat_ld((int)c.Rout) <= b->bnpart_floats,
+            "block16_fwd: bnpart too small for the downsample's partials");
+    return 0;
+}
+
+int check_bwd(const scnattn_block16* b, const Carve& c) {
+    SCN_ARG(b->x && b->save && b->stats && b->ws && b->bnpart && b->dout && b->tmp && b->dgb, "block16_bwd: null buffer");
+    for (int i = 0; i < (b->has_down ? 4 : 3); ++i)
+        SCN_ARG(b->gamma[i] && b->beta[i] && b->wt[i], "block16_bwd: null parameter");
+    SCN_ARG(partial_floats(b, c) <= b->bnpart_floats, "block16_bwd: bnpart too small for the block's partials");
+    return 0;
+}
+
 inline char* at16(void* base, long elems) { return static_cast<char*>(base) + 2 * elems; }
 inline const char* at16(const void* base, long elems) { return static_cast<const char*>(base) + 2 * elems; }
 
@@ -87,7 +112,7 @@ int scnattn_block16_fwd(void* st, const scnattn_block16* b) {
     scn::t_plan_out = nullptr;  // many launches per call: not plannable (include/scnattn.h, scnattn_plan_next)
     Carve c;
     SCN_TRY(carve(b, c));
-    SCN_ARG(b->x && b->save && b->stats && b->ws && b->part && b->bnpart, "block16_fwd: null buffer");
+    SCN_TRY(check_fwd(b, c));
     const int p = b->p, C4 = (int)c.C4, Cin = b->Cin, s = b->stride;
     const int Ho = (b->Hi - 1) / s + 1, Wo = (b->Wi - 1) / s + 1;
     const int Rin = (int)c.Rin, Rout = (int)c.Rout;
@@ -129,7 +154,7 @@ int scnattn_block16_bwd(void* st, const scnattn_block16* b, void** dx_out, void*
     scn::t_plan_out = nullptr;  // many launches per call: not plannable (include/scnattn.h, scnattn_plan_next)
     Carve c;
     SCN_TRY(carve(b, c));
-    SCN_ARG(b->x && b->save && b->stats && b->ws && b->bnpart && b->dout && b->tmp && b->dgb, "block16_bwd: null buffer");
+    SCN_TRY(check_bwd(b, c));
     const int p = b->p, C4 = (int)c.C4, Cin = b->Cin, s = b->stride;
     const int Ho = (b->Hi - 1) / s + 1, Wo = (b->Wi - 1) / s + 1;
     const int Rin = (int)c.Rin, Rout = (int)c.Rout;
@@ -171,7 +196,6 @@ int scnattn_block16_bwd(void* st, const scnattn_block16* b, void** dx_out, void*
         e.emean = mean(i); e.einvstd = istd(i); e.egamma = b->gamma[i]; e.ebeta = b->beta[i];
         return e;
     };
-    SCN_ARG(2L * p * scnattn_cgemm_stat_ld(Rin) <= b->bnpart_floats, "block16_bwd: bnpart too small for the mask epilogue's partials");
     {
         const scnattn_conv_extra e2 = mask_ex(1, S(c.z2), p);
         SCN_TRY(scnattn_cgemm16(st, Rout, p, C4, T(c.dz3), C4, b->wt[2], C4, 0.f, T(c.dz2), p, 1, b->ws, b->ws_floats, &e2));

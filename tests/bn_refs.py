@@ -369,16 +369,18 @@ def judge_slots(kernel, ok, got, t1, t2, slot, nslot):
     ok(kernel, "slots", got, want, (cnt + 8) * U * torch.stack([sums(t1.abs()), sums(t2.abs())]), K_SLOT)
 
 
-def judge_finalize(kernel, ok, s1, s2, shift, R, out, I, eps=EPS, k=None):
-    """mean / invstd / run_mean / run_var / ss of `out` (None: not written) from the partials s1, s2 [C][n] that were summed"""
+def judge_finalize(kernel, ok, s1, s2, shift, R, out, I, eps=EPS, k=None, momentum=MOM, s=None):
+    """mean / invstd / run_mean / run_var / ss of `out` (None: not written) from the partials s1, s2 [C][n] that were summed.
+    s: the dict of stats_of_partials from a caller whose partials are not stored (tests/block16_refs.py derives mean, var,
+    m1, bm1, bvar from the exact product and the slot bounds); s1, s2 are not read then."""
     k = RSQRT_ULP if k is None else k
-    s = stats_of_partials(s1, s2, shift, R)
+    s = stats_of_partials(s1, s2, shift, R) if s is None else s
     ok(kernel, "mean", out["mean"], s["mean"], s["bm1"] + 2 * U * s["mean"].abs(), K_FIN)
     e = float(np.float32(eps))
     lo = torch.rsqrt(s["var_raw"] + s["bvar"] + e) * (1 - k * U)
     hi = torch.rsqrt((s["var_raw"] - s["bvar"]).clamp_min(0.0) + e) * (1 + k * U)
     ok(kernel, "invstd", out["invstd"], (lo + hi) / 2, (hi - lo) / 2, K_FIN)
-    om, m = mom_pair()
+    om, m = mom_pair(momentum)
     mean, invstd = out["mean"].double(), out["invstd"].double()
     if out.get("run_mean") is not None:
         old = I["run_mean"].double()
