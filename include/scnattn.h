@@ -27,6 +27,8 @@ extern "C" {
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
                                + scoring given captions: teacher-forced log-probabilities, rank and arg-max per token (scnattn_rollout_*_sc,
                                scnattn_rollout_score; new symbols only, the version stays);
+                               + scheduled sampling: gold and sampled input words mixed by a coin (scnattn_rollout_*_ss,
+                               scnattn_rollout_pick_mixed; new symbols only, the version stays);
                                + the caption metrics in the loss pass (scnattn_caption_loss_metrics_fwd; new symbol only, the version stays);
                                + constrained beam search: required words, beam banks (scnattn_constraints, scnattn_beam_*_con,
                                scnattn_ensemble_*_con, scnattn_beam_row_topk_con, scnattn_beam_row_topk_ens_con, scnattn_beam_merge_banks; new
@@ -597,6 +599,55 @@ int scnattn_rollout_steps_sc(void* stream, const scnattn_dims* d, int K, int max
                              const float* enc, float inv_temp, int t0, int n_steps, float* ws);
 int scnattn_rollout_score(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, int t, int max_steps,
                           void* const* state, const int32_t* target_t, int32_t* rank_t, int32_t* best_t);
+/* ---- SCHEDULED SAMPLING: gold and sampled input words mixed by a coin (csrc/rollout.hip: rollout_pick_mixed)
+ * The reference has none of this; the semantics are this library's.  The scoring chain above with a pick that is TOLD the
+ * gold word and flips a coin (Bengio et al. 2015): row r = n*K + j carries nmix[r] gold words, gold[t][r] at step t, and
+ * token[t][r] -- the gold word or the model's own sample -- is the decoder's input at step t + 1.
+ *   OPEN AND CLOSED   a row is open at step t iff t < nmix[r].  A row of an image with nsrc[n] == 0 is neither read nor
+ *                written.  A closed row of an open image gets the records token = 0, sample = -1, logp = 0.0, replaced = 0.
+ *   THE COIN     bits = word 0 of Philox4x32-10 with the rollout's key (seed & 0xffffffff, seed >> 32) and counter
+ *                (0xFFFFFFFF, row, t, draw).  The first counter word of a word's noise is v >> 2 < 2^30, so the coin never
+ *                shares a counter with it.  u = ((bits >> 9) + 0.5) * 2^-23 (exact in fp32, inside (0, 1));
+ *                replaced = u < prob, compared in fp32.  prob == 0 never replaces, prob == 1 always does.  The decision
+ *                depends on (seed, draw, row, t) alone -- not on V, N, K, prob's other rows or the chunking of the steps.
+ *   NOT REPLACED the row's logits are not read.  token = gold, sample = -1, logp = 0.0, replaced = 0.
+ *   REPLACED     the pick is _pick's, in its arithmetic and with its noise (counter (v >> 2, row, t, draw)):
+ *                y_v = fl(logits[row][v] * inv_temp), key_v = fl(y_v + g_v), the first key under the TIE RULE, and
+ *                logp = y_token - logsumexp(y) from the same pass.  greedy != 0: EVERY row takes the arg-max (key_v = y_v;
+ *                there is no greedy_first here).  token = sample = the pick, logp, replaced = 1, and sum_logp[row] += logp
+ *                in fp32.  At prob == 1 and greedy == 0 the tokens are _pick's for the same logits, (seed, draw, t) and K,
+ *                bit for bit.
+ *   CLOSING      when t + 1 == nmix[r] the row closes: nopen[n] -= 1 and open_rows -= 1, as _score closes a row.  <end> is
+ *                NOT special: a sampled <end> becomes an input like any other word, and the gold length alone governs
+ *                the row.
+ *   ODD INPUTS   a gold word outside [0, V) is recorded as given; _advance clamps it.  A replaced row that holds a NaN is
+ *                outside this contract, as in _pick; it still writes only its own records.
+ * K in [1, 8], max_steps as for the search, inv_temp > 0 and finite, prob in [0, 1] (NaN refused), the start token inside
+ * the vocabulary; a refusal returns -1 before anything is launched.  want_alpha as in the rollout: the maps are the attention
+ * over the mixed inputs.  fp32 only; dense encoder_out only.
+ *   _workspace_ss / _layout_ss   _layout_ss writes SCNATTN_ROLLOUT_NOFF_SS offsets: the 8 of scnattn_rollout_layout (3 length
+ *       now holds nmix), then 8 sample int[max_steps][N*K], 9 replaced int[max_steps][N*K], 10 gold int[max_steps][N*K].
+ *   _init_ss   the gold words as device pointers: gold int32 [N*K][ld_tok] row-major with ld_tok >= max_steps (the first
+ *       max_steps entries of a row are read), nmix int32 [N*K], each in [0, max_steps] (clamped into it).  The kernel of
+ *       _init_sc copies the words into the workspace step-major and sets the counters from nmix as it does from ntok; then
+ *       the set-up of _init.  A slot with nmix == 0 is empty, and an image whose slots are all empty is closed from the
+ *       start: nothing but the zero-fill of _init_ss touches its records.
+ *   _steps_ss  steps t0 .. t0+n_steps-1 (clipped to max_steps): the search's decode part, _pick_mixed, _advance -- the
+ *       launches of a rollout step; chunks and the open_rows counter as in the rollout.
+ *   scnattn_rollout_pick_mixed   the kernel alone for step t (state: the seven pointers 0..6 of scnattn_rollout_layout, 3
+ *       holding nmix); gold_t / sample_t / replaced_t int[N*K] are the gold words and the records of that step. */
+#define SCNATTN_ROLLOUT_NOFF_SS 11
+int scnattn_rollout_workspace_ss(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
+int scnattn_rollout_layout_ss(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* offsets);
+int scnattn_rollout_init_ss(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                            const float* enc, const float* tags, int start_token, const int32_t* gold, long ld_tok,
+                            const int32_t* nmix, float* ws);
+int scnattn_rollout_steps_ss(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                             const float* enc, float inv_temp, float prob, uint64_t seed, uint32_t draw, int greedy, int t0,
+                             int n_steps, float* ws);
+int scnattn_rollout_pick_mixed(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, float prob,
+                               uint64_t seed, uint32_t draw, int t, int greedy, int max_steps, void* const* state,
+                               const int32_t* gold_t, int32_t* sample_t, int32_t* replaced_t);
 /* The kernels of a step (csrc/beam.hip), one launch each; nsrc int[N] on the device.
  *   _attn_scores   e[n*K+j][p] = w . relu(att1[n][p][:] + att2[n*K+j][:]) + b0 for j < nsrc[n] (other rows untouched)
  *   _attn_context  alpha_out [N*K][P], awe [N*K][E] (either may be NULL), z = sigmoid(gpre + gate_bias) * awe (gpre NULL: awe)

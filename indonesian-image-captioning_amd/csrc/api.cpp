@@ -65,6 +65,14 @@ int score_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int 
                float* ws);
 int score_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
                 const float* enc, float inv_temp, int t0, int n_steps, float* ws);
+// scheduled sampling: the _ss form of the rollout driver
+int mix_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes);
+int mix_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off);
+int mix_init(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+             const float* enc, const float* tags, int start_token, const int* gold, long ld_tok, const int* nmix, float* ws);
+int mix_steps(hipStream_t st, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+              const float* enc, float inv_temp, float prob, unsigned long long seed, unsigned draw, int greedy, int t0,
+              int n_steps, float* ws);
 
 int pool_desc(const scnattn_pool* p, PoolDesc& out) {
     out = PoolDesc{0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -521,6 +529,30 @@ int scnattn_rollout_score(void* stream, int N, int K, int V, const float* logits
     RolloutState s;
     SCN_TRY(rollout_state_of("scnattn_rollout_score", N, K, max_steps, state, s));
     return rollout_score(ST(stream), N, K, V, logits, ld, inv_temp, t, target_t, rank_t, best_t, s);
+}
+int scnattn_rollout_workspace_ss(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
+    return mix_workspace(d, K, max_steps, want_alpha, bytes);
+}
+int scnattn_rollout_layout_ss(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* offsets) {
+    return mix_layout(d, K, max_steps, want_alpha, offsets);
+}
+int scnattn_rollout_init_ss(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                            const float* enc, const float* tags, int start_token, const int32_t* gold, long ld_tok,
+                            const int32_t* nmix, float* ws) {
+    return mix_init(ST(stream), d, K, max_steps, want_alpha, w, enc, tags, start_token, gold, ld_tok, nmix, ws);
+}
+int scnattn_rollout_steps_ss(void* stream, const scnattn_dims* d, int K, int max_steps, int want_alpha, const scnattn_params* w,
+                             const float* enc, float inv_temp, float prob, uint64_t seed, uint32_t draw, int greedy, int t0,
+                             int n_steps, float* ws) {
+    return mix_steps(ST(stream), d, K, max_steps, want_alpha, w, enc, inv_temp, prob, seed, draw, greedy, t0, n_steps, ws);
+}
+int scnattn_rollout_pick_mixed(void* stream, int N, int K, int V, const float* logits, long ld, float inv_temp, float prob,
+                               uint64_t seed, uint32_t draw, int t, int greedy, int max_steps, void* const* state,
+                               const int32_t* gold_t, int32_t* sample_t, int32_t* replaced_t) {
+    RolloutState s;
+    SCN_TRY(rollout_state_of("scnattn_rollout_pick_mixed", N, K, max_steps, state, s));
+    return rollout_pick_mixed(ST(stream), N, K, V, logits, ld, inv_temp, prob, seed, draw, t, greedy, gold_t, sample_t,
+                              replaced_t, s);
 }
 
 int scnattn_seq_workspace(const scnattn_dims* d, const scnattn_pool* pool, size_t* saved_bytes, size_t* scratch_bytes) {

@@ -65,6 +65,7 @@ struct RolloutWs : StepWs {
     RolloutState s;
     int* nkeep;             // [T][R] words kept by the sample filter (the _f form of the driver), else null
     int *rank, *best, *target;      // [T][R] each: the records and the given tokens of a scoring run (_sc), else null
+    int *sample, *replaced, *gold;  // [T][R] each: the records and the gold words of a scheduled-sampling run (_ss), else null
 };
 
 inline int* ints(float* p) { return reinterpret_cast<int*>(p); }
@@ -453,9 +454,10 @@ int search_steps(hipStream_t st, int M, const scnattn_dims* d, int alpha_member,
 namespace {
 
 // filtered: the _f form of the four calls, whose workspace also holds the nkeep records (behind alpha, zero-filled by init)
-// scored: the _sc form, which keeps rank, best and the given tokens there instead
+// scored: the _sc form, which keeps rank, best and the given tokens there instead; mixed: the _ss form, with sample,
+// replaced and the gold words
 size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, bool filtered, float* base, RolloutWs& b,
-                     bool scored = false) {
+                     bool scored = false, bool mixed = false) {
     Carver c(base);
     const int N = d.B, P = d.P;
     const long R = (long)N * K;
@@ -473,6 +475,9 @@ size_t carve_rollout(const scnattn_dims& d, int K, int T, int want_alpha, bool f
     b.rank = scored ? ints(c.take(sz(T, R))) : nullptr;
     b.best = scored ? ints(c.take(sz(T, R))) : nullptr;
     b.target = scored ? ints(c.take(sz(T, R))) : nullptr;
+    b.sample = mixed ? ints(c.take(sz(T, R))) : nullptr;
+    b.replaced = mixed ? ints(c.take(sz(T, R))) : nullptr;
+    b.gold = mixed ? ints(c.take(sz(T, R))) : nullptr;
     carve_step_state(c, d, R, b);
     b.state_floats = c.off;
     carve_step_setup(c, d, R, b);
@@ -618,6 +623,71 @@ int score_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, in
         SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, b.alpha ? b.alpha + o * P : nullptr, even ? b.hA : b.hB,
                             even ? b.cA : b.cB, even ? b.hB : b.hA, even ? b.cB : b.cA));
         SCN_TRY(rollout_score(st, N, K, V, b.logits, V, inv_temp, t, b.target + o, b.rank + o, b.best + o, b.s));
+        SCN_TRY(rollout_advance(st, N, K, M, V, b.s.token + o, w->embedding_weight, b.emb, b.s.nopen, b.s.nsrc));
+    }
+    return 0;
+}
+
+// ---- scheduled sampling (the _ss form; include/scnattn.h) -------------------------------------------------------------------
+// The scoring chain with the pick replaced by rollout_pick_mixed, which is told the gold word and flips a coin: the same
+// launches per step.  The workspace is the plain rollout's with three more records behind alpha; `length` holds nmix.
+int mix_workspace(const scnattn_dims* d, int K, int max_steps, int want_alpha, size_t* bytes) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_ARG(bytes, "rollout_workspace_ss: bytes is NULL");
+    RolloutWs b;
+    *bytes = carve_rollout(*d, K, max_steps, want_alpha, false, nullptr, b, false, true);
+    return 0;
+}
+
+// off[SCNATTN_ROLLOUT_NOFF_SS]: the 8 of rollout_layout, then sample, replaced, gold
+int mix_layout(const scnattn_dims* d, int K, int max_steps, int want_alpha, long* off) {
+    SCN_TRY(check_beam(d, K, max_steps));
+    SCN_ARG(off, "rollout_layout_ss: offsets is NULL");
+    RolloutWs b;
+    carve_rollout(*d, K, max_steps, want_alpha, false, layout_base(), b, false, true);
+    const void* p[SCNATTN_ROLLOUT_NOFF_SS] = {b.s.open_rows, b.s.nsrc, b.s.nopen, b.s.length, b.s.sum_logp, b.s.token, b.s.logp,
+                                              b.alpha, b.sample, b.replaced, b.gold};
+    offsets_from(layout_base(), p, SCNATTN_ROLLOUT_NOFF_SS, off);
+    return 0;
+}
+
+int mix_init(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
+             const float* enc, const float* tags, int start_token, const int* gold, long ld_tok, const int* nmix, float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    const scnattn_dims& d = *dp;
+    SCN_ARG(w && enc && tags && ws, "rollout_init_ss: null argument");
+    SCN_ARG(gold && nmix, "rollout_init_ss: the captions are NULL");
+    SCN_ARG(ld_tok >= max_steps, "rollout_init_ss: ld_tok must be at least max_steps");
+    SCN_ARG(start_token >= 0 && start_token < d.V, "rollout_init_ss: start token outside the vocabulary");
+    SCN_ARG(aligned16(ws), "rollout_init_ss: the workspace must be 16-byte aligned");
+    RolloutWs b;
+    carve_rollout(d, K, max_steps, want_alpha, false, ws, b, false, true);
+    SCN_HIP(hipMemsetAsync(ws, 0, b.state_floats * sizeof(float), st));      // the records of rows no kernel visits: zeros
+    SCN_TRY(rollout_score_init(st, d.B, K, gold, ld_tok, nmix, b.gold, b.s));
+    SCN_TRY(decode_setup(st, d, K, w, enc, tags, start_token, b));
+    return 0;
+}
+
+int mix_steps(hipStream_t st, const scnattn_dims* dp, int K, int max_steps, int want_alpha, const scnattn_params* w,
+              const float* enc, float inv_temp, float prob, unsigned long long seed, unsigned draw, int greedy, int t0,
+              int n_steps, float* ws) {
+    SCN_TRY(check_beam(dp, K, max_steps));
+    const scnattn_dims& d = *dp;
+    SCN_ARG(w && enc && ws, "rollout_steps_ss: null argument");
+    SCN_ARG(t0 >= 0 && n_steps >= 0, "rollout_steps_ss: negative step");
+    SCN_ARG(inv_temp > 0.f && inv_temp < INFINITY, "rollout_steps_ss: inv_temp must be positive and finite");
+    SCN_ARG(rollout_prob_ok(prob), "rollout_steps_ss: prob must be in [0, 1]");
+    const int N = d.B, P = d.P, M = d.M, V = d.V, R = N * K;
+    RolloutWs b;
+    carve_rollout(d, K, max_steps, want_alpha, false, ws, b, false, true);
+    const int t1 = t0 + n_steps < max_steps ? t0 + n_steps : max_steps;
+    for (int t = t0; t < t1; ++t) {
+        const bool even = (t & 1) == 0;         // the state of step t sits in A for even t, in B for odd t
+        const long o = (long)t * R;
+        SCN_TRY(decode_step(st, d, K, w, enc, b, b.s.nsrc, b.alpha ? b.alpha + o * P : nullptr, even ? b.hA : b.hB,
+                            even ? b.cA : b.cB, even ? b.hB : b.hA, even ? b.cB : b.cA));
+        SCN_TRY(rollout_pick_mixed(st, N, K, V, b.logits, V, inv_temp, prob, seed, draw, t, greedy, b.gold + o, b.sample + o,
+                                   b.replaced + o, b.s));
         SCN_TRY(rollout_advance(st, N, K, M, V, b.s.token + o, w->embedding_weight, b.emb, b.s.nopen, b.s.nsrc));
     }
     return 0;

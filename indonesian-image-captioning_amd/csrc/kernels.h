@@ -273,6 +273,15 @@ int rollout_score(hipStream_t st, int N, int K, int V, const float* logits, long
 // into [0, T], nopen / nsrc / open_rows counted from it, sum_logp = 0.  One launch.
 int rollout_score_init(hipStream_t st, int N, int K, const int* targets, long ld_tok, const int* ntok, int* target_ws,
                        const RolloutState& s);
+// SCHEDULED SAMPLING (include/scnattn.h: the _ss form): the pick told the gold word, behind a coin.  s.length holds nmix; a
+// row is open at step t iff t < nmix.  Per open row u = the uniform of word 0 of Philox with counter (0xFFFFFFFF, row, t,
+// draw); u < prob: rollout_pick's pick (every row the arg-max when greedy != 0), token = sample = the pick, its logp,
+// replaced = 1, sum_logp += logp; else token = gold, sample = -1, logp = 0.0, replaced = 0 and the logits are not read.  The
+// row closes at t + 1 == nmix; <end> is not special.  The state of a run comes from rollout_score_init (gold for targets).
+bool rollout_prob_ok(float prob);
+int rollout_pick_mixed(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp, float prob,
+                       unsigned long long seed, unsigned draw, int t, int greedy, const int* gold_t, int* sample_t,
+                       int* replaced_t, const RolloutState& s);
 
 // ---- scn_cell.hip ----------------------------------------------------------------------------
 int scn_mix_fwd(hipStream_t st, int rows, int F4, Slabs pz, const float* ex, Slabs ph, const float* qx,

@@ -20,6 +20,8 @@
 //                    bisection on the order-preserving integer image of y, counts and fp64 masses, then one keyed pass.
 //   rollout_score    the pick TOLD its token (scoring given captions; further down): the token's
 //                    log-probability, its rank in the row and the row's first word, the row closing after its last given token.
+//   rollout_pick_mixed  scheduled sampling (further down): a coin per (row, step) decides between the gold word
+//                    it is told and rollout_pick's own pick; the gold length alone closes the row.
 //   rollout_advance  the next input embedding of every row (the token record clamped into the table) and, per image,
 //                    nsrc[n] = nopen[n] > 0 ? K : 0 for the attention kernels of the next step.
 // The arg-max slot skips the noise: key_v = y_v exactly.  Plain vector loads and stores; no kernel waits for another
@@ -77,21 +79,12 @@ struct Pick {
     }
 };
 
+// The pick of row r at step t, by the whole workgroup in ONE pass over x[0 .. V): the row's Pick is complete in thread 0
+// alone, and only for thread 0 does this return true.  Every thread of the workgroup must call it (it synchronises).
 template <bool VEC>
-__global__ __launch_bounds__(256) void rollout_pick_kernel(int K, int V, const float* __restrict__ logits, long ld,
-                                                           float inv_temp, unsigned k0, unsigned k1, unsigned draw, int t,
-                                                           int greedy_first, int end_tok, RolloutState s) {
-    const int r = blockIdx.x, n = r / K, j = r - n * K;
-    if (s.nsrc[n] <= 0) return;                 // a closed image: uniform over the workgroup
-    int* token_t = s.token + (long)t * s.R;
-    float* logp_t = s.logp + (long)t * s.R;
-    if (s.length[r] != 0) {                     // a closed row of an open image
-        if (threadIdx.x == 0) { token_t[r] = 0; logp_t[r] = 0.f; }
-        return;
-    }
-    const bool noisy = !(greedy_first && j == 0);
-    const float* x = logits + (long)r * ld;
-    Pick p = {-INFINITY, 0.f, -INFINITY, 0.f, INT_MAX};
+__device__ __forceinline__ bool pick_row(const float* __restrict__ x, int V, float inv_temp, bool noisy, int r, int t,
+                                         unsigned draw, unsigned k0, unsigned k1, Pick& p) {
+    p = Pick{-INFINITY, 0.f, -INFINITY, 0.f, INT_MAX};
     const int groups = (V + 3) >> 2;
     for (int q = threadIdx.x; q < groups; q += 256) {
         const int v0 = q * 4;
@@ -122,11 +115,28 @@ __global__ __launch_bounds__(256) void rollout_pick_kernel(int K, int V, const f
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { sm[w] = p.m; ss[w] = p.s; sk[w] = p.bk; sy[w] = p.by; si[w] = p.bi; }
     __syncthreads();
-    if (threadIdx.x != 0) return;
+    if (threadIdx.x != 0) return false;
     p = Pick{sm[0], ss[0], sk[0], sy[0], si[0]};
     p.merge(sm[1], ss[1], sk[1], sy[1], si[1]);
     p.merge(sm[2], ss[2], sk[2], sy[2], si[2]);
     p.merge(sm[3], ss[3], sk[3], sy[3], si[3]);
+    return true;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void rollout_pick_kernel(int K, int V, const float* __restrict__ logits, long ld,
+                                                           float inv_temp, unsigned k0, unsigned k1, unsigned draw, int t,
+                                                           int greedy_first, int end_tok, RolloutState s) {
+    const int r = blockIdx.x, n = r / K, j = r - n * K;
+    if (s.nsrc[n] <= 0) return;                 // a closed image: uniform over the workgroup
+    int* token_t = s.token + (long)t * s.R;
+    float* logp_t = s.logp + (long)t * s.R;
+    if (s.length[r] != 0) {                     // a closed row of an open image
+        if (threadIdx.x == 0) { token_t[r] = 0; logp_t[r] = 0.f; }
+        return;
+    }
+    Pick p;
+    if (!pick_row<VEC>(logits + (long)r * ld, V, inv_temp, !(greedy_first && j == 0), r, t, draw, k0, k1, p)) return;
     const bool found = p.bi < V;                // a row of NaN alone has no first element: <pad>, and its logp is NaN
     const int tok = found ? p.bi : 0;
     const float lp = found ? p.by - (p.m + logf(p.s)) : __builtin_nanf("");
@@ -555,6 +565,51 @@ __global__ __launch_bounds__(256) void rollout_score_init_kernel(int N, int K, c
     }
 }
 
+// ---- scheduled sampling: the pick told the gold word, behind a coin (the contract: include/scnattn.h) ---------
+// s.length holds nmix, and a row is open at step t iff t < nmix[r], as in rollout_score.  The coin is word 0 of the Philox
+// call with the counter (0xFFFFFFFF, r, t, draw): a word's noise has v >> 2 < 2^30 there, so the two never meet.  Every
+// thread computes the same coin, so the branch is uniform over the workgroup, and a row that keeps its gold word does not
+// read its logits at all.  A replaced row is pick_row, the arithmetic and the noise of rollout_pick.
+template <bool VEC>
+__global__ __launch_bounds__(256) void rollout_pick_mixed_kernel(int K, int V, const float* __restrict__ logits, long ld,
+                                                                 float inv_temp, float prob, unsigned k0, unsigned k1,
+                                                                 unsigned draw, int t, int greedy,
+                                                                 const int* __restrict__ gold_t, int* __restrict__ sample_t,
+                                                                 int* __restrict__ replaced_t, RolloutState s) {
+    const int r = blockIdx.x, n = r / K;
+    if (s.nsrc[n] <= 0) return;                 // a closed image: uniform over the workgroup
+    int* token_t = s.token + (long)t * s.R;
+    float* logp_t = s.logp + (long)t * s.R;
+    const int nmix = s.length[r];
+    if (t >= nmix) {                            // a closed row of an open image
+        if (threadIdx.x == 0) { token_t[r] = 0; sample_t[r] = -1; logp_t[r] = 0.f; replaced_t[r] = 0; }
+        return;
+    }
+    const unsigned bits = philox4x32_10(0xFFFFFFFFu, (unsigned)r, (unsigned)t, draw, k0, k1).w[0];
+    const float u = ((float)(bits >> 9) + 0.5f) * 0x1p-23f;      // 24 significant bits: exact
+    int tok = gold_t[r], smp = -1, rep = 0;
+    float lp = 0.f;
+    if (u < prob) {
+        Pick p;
+        if (!pick_row<VEC>(logits + (long)r * ld, V, inv_temp, !greedy, r, t, draw, k0, k1, p)) return;
+        const bool found = p.bi < V;            // a row of NaN alone has no first element: <pad>, and its logp is NaN
+        tok = smp = found ? p.bi : 0;
+        lp = found ? p.by - (p.m + logf(p.s)) : __builtin_nanf("");
+        rep = 1;
+        s.sum_logp[r] += lp;
+    } else if (threadIdx.x != 0) {
+        return;
+    }
+    token_t[r] = tok;
+    sample_t[r] = smp;
+    logp_t[r] = lp;
+    replaced_t[r] = rep;
+    if (t + 1 == nmix) {
+        atomicAdd(s.nopen + n, -1);
+        atomicAdd(s.open_rows, -1);
+    }
+}
+
 bool state_ok(const RolloutState& s, int N, int K) {
     return s.R == N * K && s.T >= 1 && s.open_rows && s.nsrc && s.nopen && s.length && s.sum_logp && s.token && s.logp;
 }
@@ -652,6 +707,30 @@ int rollout_score(hipStream_t st, int N, int K, int V, const float* logits, long
     else
         hipLaunchKernelGGL(rollout_score_kernel<false>, dim3(N * K), dim3(256), 0, st, K, V, logits, ld, inv_temp, t, target_t,
                            rank_t, best_t, s);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+bool rollout_prob_ok(float prob) { return prob >= 0.f && prob <= 1.f; }      // NaN: refused
+
+int rollout_pick_mixed(hipStream_t st, int N, int K, int V, const float* logits, long ld, float inv_temp, float prob,
+                       unsigned long long seed, unsigned draw, int t, int greedy, const int* gold_t, int* sample_t,
+                       int* replaced_t, const RolloutState& s) {
+    SCN_ARG(rollout_prob_ok(prob), "rollout_pick_mixed: prob must be in [0, 1]");
+    SCN_ARG(inv_temp > 0.f && inv_temp < INFINITY, "rollout_pick_mixed: inv_temp must be positive and finite");
+    if (N <= 0) return 0;
+    SCN_ARG(K >= 1 && K <= SCN_MAX_BEAM && V >= 1 && t >= 0, "rollout_pick_mixed: bad slot count / vocab_size / step");
+    SCN_ARG((long)N * K <= (1L << 20), "rollout_pick_mixed: too many rows (images x slots)");
+    SCN_ARG(logits && ld >= V && state_ok(s, N, K), "rollout_pick_mixed: bad argument");
+    SCN_ARG(t < s.T, "rollout_pick_mixed: step beyond the records");
+    SCN_ARG(gold_t && sample_t && replaced_t, "rollout_pick_mixed: a gold / sample / replaced record is NULL");
+    const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(seed >> 32);
+    if (aligned16(logits) && ld % 4 == 0)
+        hipLaunchKernelGGL(rollout_pick_mixed_kernel<true>, dim3(N * K), dim3(256), 0, st, K, V, logits, ld, inv_temp, prob, k0,
+                           k1, draw, t, greedy, gold_t, sample_t, replaced_t, s);
+    else
+        hipLaunchKernelGGL(rollout_pick_mixed_kernel<false>, dim3(N * K), dim3(256), 0, st, K, V, logits, ld, inv_temp, prob, k0,
+                           k1, draw, t, greedy, gold_t, sample_t, replaced_t, s);
     SCN_LAUNCH_CHECK();
     return 0;
 }

@@ -560,6 +560,58 @@ def score_batched(decoder, word_map, encoder_out, tag_out, use_attention, use_ta
                 alpha=None if alpha is None else padded(alpha.transpose(0, 1)))
 
 
+def check_mix_args(word_map, n_images, caps, caplens, per_image, prob, temperature=1.0, who="mix_batch"):
+    """The refusals of ``mix_batched`` (ValueError): those of check_score_args, plus prob in [0, 1] (NaN refused).
+    -> (per_image, nmix (R,) int64 on the captions' device, prob as the fp32 number the kernel compares with)"""
+    prob = SF.mix_prob(prob, who)
+    per_image, ntok = check_score_args(word_map, n_images, caps, caplens, per_image, temperature, who)
+    return per_image, (ntok - 1).clamp_min(0), prob
+
+
+def mix_batched(decoder, word_map, encoder_out, tag_out, use_attention, use_tags, caps, caplens, prob, per_image=1, seed=0,
+                draw=0, temperature=1.0, greedy=False):
+    """SCHEDULED SAMPLING (Bengio et al. 2015): the decoder's INPUT words for a teacher-forced pass, a share `prob` of them
+    the model's own samples, mixed on the device (csrc/rollout.hip: rollout_pick_mixed, SF.mix_run).  encoder_out
+    (N, h, w, E), tag_out (N, S); caps (N*per_image, L) and caplens (N*per_image, 1) in the form ``forward`` takes, row
+    n*per_image + j belonging to image n.  ``forward`` embeds the positions 0 .. caplens - 2, so only the inputs at the
+    positions 1 .. caplens - 2 can be replaced (nmix = max(caplens - 2, 0) of them); the last gold word is never an input
+    and is never touched, and the TARGETS of the loss stay the caller's caps.  The word at position t + 1 is replaced when
+    the coin of (seed, draw, row, t) falls below prob, by a draw from softmax(logits / temperature) after the mixed inputs
+    0 .. t -- rollout_batch's pick with its noise -- or, with greedy, by the arg-max.  <end> is a word like any other.  No
+    dropout, like the rollout; fp32 only.  The arguments are checked before anything touches the GPU (check_mix_args).
+    Returns a dict ON THE DEVICE:
+        inputs (R, L) int64       <start>, the mixed words, then caps unchanged from position caplens - 1 on
+        replaced (R, L) bool      where inputs holds a sample
+        sample (R, L-1) int32     the sample taken at step t (for position t + 1), -1 where none was
+        logp (R, L-1)             its log-probability at this temperature, 0.0 elsewhere
+        sum_logp (R,)             the fp32 sum of the row's logp
+        n_replaced (R,) int32     how many inputs of the row were replaced"""
+    from scnattn import _lib
+    N = encoder_out.shape[0]
+    per_image, nmix, prob = check_mix_args(word_map, N, caps, caplens, per_image, prob, temperature)
+    _lib.require_cuda(encoder_out, tag_out, caps, caplens)
+    V = len(word_map)
+    dims, weights, enc, tag_out = _search_operands(decoder, V, encoder_out, tag_out, use_attention, use_tags)
+    R, L = caps.shape
+    T = SF.BEAM_MAX_STEPS
+    gold = torch.zeros(R, T, dtype=torch.int32, device=caps.device)
+    n = min(L - 1, T)
+    gold[:, :n] = caps[:, 1:1 + n]
+    res, steps = SF.mix_run(dims, per_image, weights, enc, tag_out, word_map[start_token], gold, nmix.to(torch.int32), prob,
+                            seed, draw, inv_temp=1.0 / float(temperature), greedy=greedy)
+    rep = res["replaced"] != 0
+    inputs = caps.to(torch.int64).clone()
+    inputs[:, 1:1 + steps] = torch.where(rep, res["tokens"].to(torch.int64), inputs[:, 1:1 + steps])
+    replaced = torch.zeros(R, L, dtype=torch.bool, device=caps.device)
+    replaced[:, 1:1 + steps] = rep
+    sample = torch.full((R, L - 1), -1, dtype=torch.int32, device=caps.device)
+    sample[:, :steps] = torch.where(rep, res["sample"], sample[:, :steps])
+    logp = torch.zeros(R, L - 1, dtype=torch.float32, device=caps.device)
+    logp[:, :steps] = res["logp"]
+    return dict(inputs=inputs, replaced=replaced, sample=sample, logp=logp, sum_logp=res["sum_logp"].clone(),
+                n_replaced=rep.sum(dim=1, dtype=torch.int32))
+
+
 def score_matrix(decoder, word_map, encoder_out, tags, caps, caplens, temperature=1.0):
     """Every one of Q captions against every one of N images -> (N, Q) log-likelihoods on the device (image-caption
     retrieval; recall@k stays with the caller).  caps (Q, L), caplens (Q, 1).  A loop of ``score_batch`` calls, 8 captions

@@ -124,6 +124,15 @@ class AttentionSCN(nn.Module):
         """Q captions against N images -> (N, Q) log-likelihoods on the device (_common.score_matrix)"""
         return _common.score_matrix(self, word_map, encoder_out, tags, caps, caplens, temperature=temperature)
 
+    def mix_batch(self, word_map, encoder_out, tags, caps, caplens, prob, per_image=1, seed=0, draw=0, temperature=1.0,
+                  greedy=False):
+        """Scheduled sampling: the input words of a teacher-forced pass over caps (N*per_image, L), caplens (N*per_image, 1),
+        a share `prob` of them the model's own samples -> dict(inputs, replaced, sample, logp, sum_logp, n_replaced) on the
+        device (_common.mix_batched: which positions can be replaced, the coin and the noise)."""
+        return _common.mix_batched(self, word_map, encoder_out, tags, use_attention=True, use_tags=True, caps=caps,
+                                   caplens=caplens, prob=prob, per_image=per_image, seed=seed, draw=draw,
+                                   temperature=temperature, greedy=greedy)
+
 
 _KEY_OF_FIELD = {
     "attention_encoder_att_weight": "attention.encoder_att.weight",

@@ -204,6 +204,13 @@ _SIGS = {
     "scnattn_rollout_init_sc": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, vp, i32, vp, i64, vp, vp], i32),
     "scnattn_rollout_steps_sc": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, f32, i32, i32, vp], i32),
     "scnattn_rollout_score": ([vp, i32, i32, i32, vp, i64, f32, i32, i32, C.POINTER(vp), vp, vp, vp], i32),
+    "scnattn_rollout_workspace_ss": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(sz)], i32),
+    "scnattn_rollout_layout_ss": ([C.POINTER(Dims), i32, i32, i32, C.POINTER(i64)], i32),
+    "scnattn_rollout_init_ss": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, vp, i32, vp, i64, vp, vp], i32),
+    "scnattn_rollout_steps_ss": ([vp, C.POINTER(Dims), i32, i32, i32, C.POINTER(Params), vp, f32, f32, C.c_uint64, C.c_uint32,
+                                  i32, i32, i32, vp], i32),
+    "scnattn_rollout_pick_mixed": ([vp, i32, i32, i32, vp, i64, f32, f32, C.c_uint64, C.c_uint32, i32, i32, i32,
+                                    C.POINTER(vp), vp, vp, vp], i32),
     "scnattn_sgemm": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64], i32),
     "scnattn_sgemm_ws": ([vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, i64, f32, vp, i64, vp, vp, i32, i64, i64, i64,
                           vp, i64], i32),
@@ -328,6 +335,7 @@ BEAM_NOFF_CON = 16  # SCNATTN_BEAM_NOFF_CON
 ROLLOUT_NOFF = 8    # SCNATTN_ROLLOUT_NOFF
 ROLLOUT_NOFF_F = 9  # SCNATTN_ROLLOUT_NOFF_F
 ROLLOUT_NOFF_SC = 11  # SCNATTN_ROLLOUT_NOFF_SC
+ROLLOUT_NOFF_SS = 11  # SCNATTN_ROLLOUT_NOFF_SS
 MAX_BEAM = 8
 MAX_ENSEMBLE = 4    # SCNATTN_MAX_ENSEMBLE
 RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM

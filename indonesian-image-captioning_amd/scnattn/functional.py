@@ -657,6 +657,94 @@ def score_run(dims, K, weights, enc, tags, start, targets, ntok, inv_temp=1.0, m
 
 
 # ----------------------------------------------------------------------------------------------
+# scheduled sampling (include/scnattn.h: scnattn_rollout_*_ss)
+# ----------------------------------------------------------------------------------------------
+_MIX_RESULTS = ("open_rows", "nsrc", "nopen", "nmix", "sum_logp", "token", "logp", "alpha", "sample", "replaced", "gold")
+_MIX_FLOAT = ("sum_logp", "logp", "alpha")
+
+
+def mix_prob(prob, who="mix_run"):
+    """the replacement probability as the fp32 number the kernel compares with: in [0, 1], NaN refused (ValueError)"""
+    import math
+    prob = float(prob)
+    if math.isnan(prob) or not 0.0 <= prob <= 1.0:
+        raise ValueError("%s: prob must be in [0, 1] (got %r)" % (who, prob))
+    return C.c_float(prob).value
+
+
+def mix_run(dims, K, weights, enc, tags, start, gold, nmix, prob, seed, draw, inv_temp=1.0, greedy=False,
+            max_steps=BEAM_MAX_STEPS, want_alpha=False, guard=0, chunk=BEAM_CHUNK):
+    """SCHEDULED SAMPLING on the device (csrc/rollout.hip: rollout_pick_mixed; the analogue of score_run with a coin): the
+    decoder walks the GOLD words of K captions per image, rows n*K + j, and at every step a coin of (seed, draw, row, step)
+    replaces the gold word with the model's own sample with probability `prob`; what was chosen is the next step's input.
+    gold (R, >= max_steps) int32 on the device, row r holding nmix[r] words (what follows <start>); nmix (R,) int32 on the
+    device, each in [0, max_steps]; 0 marks an empty slot.  A sample is rollout_run's pick with its noise (greedy: the
+    arg-max in every row); <end> is a word like any other and the gold length alone ends a row.  dims / weights / enc / tags
+    as for beam_search_run.  Returns (results, steps); the results stay ON THE DEVICE (views of the workspace); the open-row
+    counter is downloaded between chunks and the longest nmix once at the end, so steps is the longest row:
+        tokens (R, steps) int32    the word chosen at step t, the input of step t + 1: gold or the sample; 0 beyond nmix
+        replaced (R, steps) int32  1 where the sample was taken
+        sample (R, steps) int32    the sample where one was taken, else -1 (0 at the steps after the image's last row
+                                   closed, which no kernel visits)
+        logp (R, steps)            the sample's log-probability under softmax(logits * inv_temp), 0.0 elsewhere
+        sum_logp (R,)              the fp32 sum of the row's logp
+        gold (R, steps) int32      the gold words as given
+        nmix (R,) int32            as given (clamped into [0, max_steps])
+        alpha (steps, R, P)        only with want_alpha (and attention), else None: the attention over the mixed inputs
+        open_rows, nsrc, nopen     the counters (scnattn_rollout_layout)
+    guard > 0 (tests): that many sentinel words behind the workspace, returned as results["guard"]."""
+    K = int(K)
+    if not 1 <= K <= _lib.MAX_BEAM:
+        raise ValueError("mix_run: K must be in [1, %d] (got %d)" % (_lib.MAX_BEAM, K))
+    inv_temp = float(inv_temp)
+    if not (inv_temp > 0.0 and inv_temp < float("inf")):
+        raise ValueError("mix_run: inv_temp must be positive and finite (got %r)" % inv_temp)
+    prob = mix_prob(prob)
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(draw) < 2 ** 32:
+        raise ValueError("mix_run: seed must fit 64 bits and draw 32 bits, both unsigned")
+    d = Dims(*dims)
+    if not 0 <= int(start) < d.V:
+        raise ValueError("mix_run: start token outside the vocabulary")
+    N = d.B
+    R = N * K
+    if gold.dtype != torch.int32 or nmix.dtype != torch.int32:
+        raise ValueError("mix_run: gold and nmix must be int32")
+    if gold.dim() != 2 or gold.shape[0] != R or gold.shape[1] < max_steps or nmix.numel() != R:
+        raise ValueError("mix_run: gold must be (%d, >= %d) and nmix (%d,) (got %s and %s)"
+                         % (R, max_steps, R, tuple(gold.shape), tuple(nmix.shape)))
+    require_cuda(enc, tags, gold, nmix, *weights)
+    dev = enc.device
+    enc, tags = f32c(enc), f32c(tags)
+    gold, nmix = gold.contiguous(), nmix.contiguous()
+    weights = tuple(None if w is None else f32c(w.detach()) for w in weights)
+    w = _params_struct(weights)
+    wa = int(bool(want_alpha))
+    ws, off, nwords, t = _run_on_device("scnattn_rollout_%s_ss", (C.byref(d), K, max_steps, wa), _lib.ROLLOUT_NOFF_SS,
+                                        (C.byref(w), ptr(enc), ptr(tags), int(start), ptr(gold), gold.shape[1], ptr(nmix)),
+                                        (C.byref(w), ptr(enc), inv_temp, prob, int(seed), int(draw), int(bool(greedy))),
+                                        stream_of(enc), dev, max_steps, chunk, guard)
+    wsi = ws.view(torch.int32)
+    # the steps of the last chunk beyond the longest row were no-ops: leave them out (one more 4-byte download)
+    t = min(t, int(wsi[off[3]:off[3] + R].max()))
+    sizes = {"open_rows": 1, "nsrc": N, "nopen": N, "nmix": R, "sum_logp": R, "alpha": t * R * d.P}
+    out = {}
+    for i, name in enumerate(_MIX_RESULTS):
+        if off[i] < 0:
+            out[name] = None
+            continue
+        src = ws if name in _MIX_FLOAT else wsi
+        out[name] = src[off[i]:off[i] + sizes.get(name, t * R)]
+    out["tokens"] = out.pop("token")
+    for name in ("tokens", "logp", "sample", "replaced", "gold"):
+        out[name] = out[name].view(t, R).t()
+    if out["alpha"] is not None:
+        out["alpha"] = out["alpha"].view(t, R, d.P)
+    if guard:
+        out["guard"] = wsi[nwords:]
+    return out, t
+
+
+# ----------------------------------------------------------------------------------------------
 # stand-alone SCN cell (any batch size), split exactly where the reference splits it:
 #   scn_input      = SCNCell.forward's x side      (models/scn_cell.py:64-91)
 #   scn_recurrent  = SCNCell.recurrent_step        (models/scn_cell.py:112-154)

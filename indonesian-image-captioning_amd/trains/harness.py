@@ -70,10 +70,24 @@ class TrainStep:
     def __init__(self, kind="attention_scn", fine_tune_encoder=True, device="cuda", seed=1234, encoder=True,
                  bucket_mb=32, graph_encoder=False, tagger=False, force_reduce=False, encoder_dtype="f32",
                  decoder_dtype="f32", tagger_overlap=True,
-                 fused_loss=True, pooled_attention=True, metrics=False, **overrides):
+                 fused_loss=True, pooled_attention=True, metrics=False, scheduled_sampling=0.0, ss_temperature=1.0,
+                 ss_greedy=False, ss_seed=None, word_map=None, **overrides):
         self.cfg = dict(DEFAULTS)
         self.cfg.update(overrides)
         self.kind = kind
+        # scheduled sampling (Bengio et al. 2015): with probability `scheduled_sampling` an input word of the decoder is the
+        # model's own sample (decoder.mix_batch, at ss_temperature; ss_greedy: its arg-max) instead of the gold word; the
+        # targets stay the gold words.  0.0: the step below does not touch any of it.  The coin and the noise are keyed by
+        # (ss_seed, the number of steps so far); `last_mix` keeps inputs / replaced / n_replaced of the last mixed step on
+        # the device.  word_map: where <start> sits (default: synthetic_batch's convention).
+        from models.decoders._common import check_rollout_args
+        check_rollout_args(1, ss_temperature, who="TrainStep")
+        self.ss_temperature, self.ss_greedy = float(ss_temperature), bool(ss_greedy)
+        self.ss_seed = int(seed if ss_seed is None else ss_seed)
+        self.set_sampling_prob(scheduled_sampling)
+        self.word_map = word_map if word_map is not None else SyntheticWordMap(self.cfg["vocab_size"])
+        self.steps_done = 0
+        self.last_mix = None
         self.fused_loss = fused_loss
         # metrics=True: the loss pass also counts the step's top-5 / top-1 hits (trains/attention_scn.py:255-257) and leaves
         # them in `last_metrics` on the device; the loss, its gradient and the update keep their bits.  topk_percent() syncs.
@@ -159,6 +173,11 @@ class TrainStep:
             loss = loss + self.cfg["alpha_c"] * ((1. - alphas.sum(dim=1)) ** 2).mean()
         return loss
 
+    def set_sampling_prob(self, p):
+        """the share of input words replaced by the model's own samples from the next step on (scheduled_sampling_prob
+        gives the usual staircase); 0.0 is the plain teacher-forced step"""
+        self.sampling_prob = SF.mix_prob(p, "TrainStep.set_sampling_prob")
+
     def step(self, imgs, tags, caps, caplens, encoder_out=None, prepool=None, drop_in=False, caplens_host=None):
         """`drop_in=True` is the reference's literal call sequence (trains/attention_scn.py:213-216):
         `encoder_out = encoder(imgs)` materialises the (B,14,14,2048) map, `decoder(encoder_out, ...)` receives only
@@ -166,6 +185,10 @@ class TrainStep:
         explicitly and skips the pooling kernel and its 51 MB write.  `caplens_host`: the caption lengths as a CPU tensor
         when the caller has them on the host anyway (a loader does): the decoder then needs no device synchronisation
         to learn its loop bounds (models/decoders/_common.py::sort_by_length); ignored for `drop_in`."""
+        mixing = self.sampling_prob > 0.0
+        if mixing and self.encoder is None and encoder_out is None:
+            raise ValueError("TrainStep.step: scheduled sampling mixes on the dense encoder_out; a prepool map alone is not "
+                             "enough (hand encoder_out over: the map attached to it is still used by forward)")
         tag_event = None
         if self.tagger is not None and self.tagger_overlap and imgs.is_cuda and self.encoder is not None:
             # The frozen tagger's forward pass shares nothing with the caption encoder's: it runs on the side stream
@@ -186,7 +209,7 @@ class TrainStep:
             ev[0].record()
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.encoder_bf16):
             if self.encoder is not None:
-                if self.pooled_attention and not self.graphed and not drop_in:
+                if self.pooled_attention and not self.graphed and not drop_in and not mixing:
                     prepool = self.encoder(imgs, pooled=False)     # the decoder works on the 8x8 source map
                     encoder_out = None
                 else:
@@ -204,22 +227,38 @@ class TrainStep:
         if tag_event is not None:
             torch.cuda.current_stream(imgs.device).wait_event(tag_event)
             tags.record_stream(torch.cuda.current_stream(imgs.device))
+        inputs, pool_size = caps, self.encoder.enc_image_size if self.encoder is not None else 14
+        if mixing:
+            # the SCST step's feature route: the mix runs on the dense map, forward on the pre-pool map attached to it
+            from models.decoders._common import attached_prepool
+            with torch.no_grad():
+                mix = self.decoder.mix_batch(self.word_map, encoder_out.detach(), tags, caps, caplens, self.sampling_prob,
+                                             seed=self.ss_seed, draw=self.steps_done, temperature=self.ss_temperature,
+                                             greedy=self.ss_greedy)
+            inputs = mix["inputs"]
+            self.last_mix = dict(inputs=inputs, replaced=mix["replaced"], n_replaced=mix["n_replaced"])
+            prepool = attached_prepool(encoder_out)
+            if self.encoder is None:
+                pool_size = encoder_out.shape[1]
+            if prepool is not None:
+                encoder_out = None
         if self.kind == "attention_scn":
             scores, caps_sorted, decode_lengths, alphas, sort_ind = self.decoder(
-                encoder_out, tags, caps, caplens, prepool=prepool,
-                pool_size=self.encoder.enc_image_size if self.encoder is not None else 14,
+                encoder_out, tags, inputs, caplens, prepool=prepool, pool_size=pool_size,
                 caplens_host=None if drop_in else caplens_host)
         elif self.kind == "pure_scn":
             scores, caps_sorted, decode_lengths, sort_ind = self.decoder(
-                encoder_out, tags, caps, caplens, prepool=prepool,
-                pool_size=self.encoder.enc_image_size if self.encoder is not None else 14,
+                encoder_out, tags, inputs, caplens, prepool=prepool, pool_size=pool_size,
                 caplens_host=None if drop_in else caplens_host)
             alphas = None
         else:
             scores, caps_sorted, decode_lengths, alphas, sort_ind = self.decoder(
-                encoder_out, caps, caplens, prepool=prepool,
-                pool_size=self.encoder.enc_image_size if self.encoder is not None else 14,
+                encoder_out, inputs, caplens, prepool=prepool, pool_size=pool_size,
                 caplens_host=None if drop_in else caplens_host)
+        if mixing:      # the decoder read the mixed words; the loss (and the metrics) are taken against the gold ones
+            assert torch.equal(caps_sorted, inputs[sort_ind]), "forward did not return the captions it was given"
+            caps_sorted = caps[sort_ind]
+        self.steps_done += 1
         dl_dev = (caplens.reshape(-1)[sort_ind] - 1).to(torch.int32) if self.fused_loss else None
         loss = self.loss_fn(scores, caps_sorted, decode_lengths, alphas, dl_dev)
         self.decoder_optimizer.zero_grad()
@@ -249,6 +288,16 @@ class TrainStep:
         if self.last_metrics is None:
             raise RuntimeError("TrainStep.topk_percent: no step has run with metrics=True")
         return topk_percent(self.last_metrics[1], self.last_metrics[2])
+
+
+def scheduled_sampling_prob(epoch, start=0, every=5, increase=0.05, max_prob=0.25):
+    """The usual staircase of the replacement probability (a host function): 0 before epoch `start`, then `increase` more
+    every `every` epochs, capped at max_prob: min(max_prob, increase * ((epoch - start) // every + 1))."""
+    if every < 1:
+        raise ValueError("scheduled_sampling_prob: every must be at least 1 (got %r)" % (every,))
+    if epoch < start:
+        return 0.0
+    return min(float(max_prob), increase * ((epoch - start) // every + 1))
 
 
 class SyntheticWordMap:
@@ -298,6 +347,9 @@ class SCSTTrainStep(TrainStep):
             raise ValueError("SCSTTrainStep: scorer must be a CaptionScorer (score_rows gives the rewards)")
         if kw.get("metrics"):
             raise ValueError("SCSTTrainStep: metrics=True belongs to the cross-entropy step")
+        if kw.get("scheduled_sampling"):
+            raise ValueError("SCSTTrainStep: scheduled_sampling belongs to the cross-entropy step (this one already trains on "
+                             "its own samples)")
         super().__init__(seed=seed, **kw)
         self.scorer, self.samples, self.baseline, self.temperature = scorer, int(samples), baseline, float(temperature)
         self.word_map = word_map if word_map is not None else SyntheticWordMap(self.cfg["vocab_size"])
