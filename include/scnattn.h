@@ -25,6 +25,9 @@ extern "C" {
 
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
+                               + tagger evaluation: per-image / per-tag average precision, hits@k, tp/fp/fn per threshold
+                               (scnattn_tag_store_size, scnattn_tag_rows, scnattn_tag_cols, scnattn_tag_finalize; new symbols only, the
+                               version stays);
                                + scoring given captions: teacher-forced log-probabilities, rank and arg-max per token (scnattn_rollout_*_sc,
                                scnattn_rollout_score; new symbols only, the version stays);
                                + scheduled sampling: gold and sampled input words mixed by a coin (scnattn_rollout_*_ss,
@@ -1022,6 +1025,55 @@ int scnattn_text_cider(void* stream, int N, int R, const int32_t* hyp, int Lh, c
                        int Lr, const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref,
                        int n_skip_ref, const int64_t* table_keys, const int32_t* table_df, const long* table_off, long n_images,
                        double* score, double* mean, int32_t* flag);
+/* ---- tagger evaluation over tag probabilities (csrc/tagmetrics.hip; new symbols only, the version stays): ranking and
+ * per-class measures next to the reference's binary_accuracy, which an all-zero tagger passes at about 99 % ----------------
+ * Inputs: probs fp32 [B][S] (row stride ld_probs >= S), targets fp32 or uint8 [B][S] (row stride ld_targets >= S, in
+ * elements), on the device.  An entry is POSITIVE iff target >= 0.5 (binary_accuracy's convention; for uint8: non-zero).
+ * Scores must be finite and in [0, 1]: any other value sets *flag (int32 on the device; the calls only ever set it, the caller
+ * clears it) and the results are then unspecified.  Every comparison is an IEEE fp32 comparison of the stored values.
+ * AVERAGE PRECISION, tie-invariant counting form: for scores s with labels t and m >= 1 positives
+ *        AP = (1/m) * sum over positive i of TP(i) / N(i),   N(i) = #{j : s_j >= s_i},   TP(i) = #{j positive : s_j >= s_i}.
+ *   Both counts are exact integers, each quotient is one fp64 division, the sum is fp64 in ascending i, then one division by
+ *   m.  The value does not depend on how ties are ordered: sklearn's average_precision_score of a column, and (0 < m < S)
+ *   label_ranking_average_precision_score of a row.  m = 0 gives AP = 0 and the row / tag is left out of every mean.
+ * PER IMAGE (row): AP, npos, and hits@k for nk <= SCNATTN_TAG_MAX_K values of k (HOST array, each >= 1, clamped to S): the
+ *   number of positives among the top k, where entry i is in the top k iff #{j : s_j > s_i} + #{j < i : s_j == s_i} < k (ties
+ *   go to the lower index).  precision@k = hits / k (the clamped k), recall@k = hits / npos.
+ * PER TAG (column) over the n images stored: AP, npos, and for nt <= SCNATTN_TAG_MAX_THRESHOLDS thresholds (HOST fp32 array)
+ *   the counts tp, fp, fn with the prediction p >= threshold; agree = #{(p >= 0.5) == positive}.
+ *   scnattn_tag_store_size  bytes of the tag-major store of the caller: scores fp32 [S][cap], labels uint8 [S][cap].
+ *   scnattn_tag_rows        one batch: writes row_ap fp64 [cap], row_npos int32 [cap], row_hits int32 [cap][nk] at rows
+ *        row0 .. row0 + B - 1 and appends the batch to the store at the same columns.  Never synchronises.
+ *   scnattn_tag_cols        over store columns 0 .. n - 1: col_ap fp64 [S], col_npos int32 [S], col_counts int32 [S][nt][3]
+ *        (tp, fp, fn), col_agree int32 [S].
+ *   scnattn_tag_finalize    summary fp64 [SCNATTN_TAG_SUMMARY_LEN]:
+ *        [0] mean AP over the tags with a positive;  [1] mean AP over the images with a positive;
+ *        [2 + q] mean precision@k_q and [6 + q] mean recall@k_q over the images with a positive, q < nk;
+ *        [10 + 6 t ..] per threshold t < nt: micro P, R, F1 from the counts summed over tags, then macro P, R, F1 = means of
+ *        the per-tag values over the tags with a positive; P = tp / (tp + fp), R = tp / (tp + fn), F1 = 2 tp / (2 tp + fp +
+ *        fn), a 0 / 0 quotient counts as 0 (sklearn's zero_division = 0);
+ *        [58] binary_accuracy = 100 * agree / (n * S);  [59] n;  [60] images without a positive;  [61] tags without a
+ *        positive;  [62] *flag;  the rest 0.  A mean over nothing is NaN.  Every mean is summed in index order.
+ * Every floating-point sum has one fixed order and there is no floating-point atomic: results are the same bits from run to
+ * run and however the same images, in the same order, are split into batches.  Micro-averaged AP over all n * S entries is
+ * not computed (in counting form it costs #positives * n * S).  Refused with -1 before anything is launched: a null pointer,
+ * S outside 1..SCNATTN_TAG_MAX_S, cap outside 1..SCNATTN_TAG_MAX_IMAGES, row0 + B > cap or n > cap, n < 1, a leading
+ * dimension below S, more than 4 values of k or one below 1, more than 8 thresholds. */
+#define SCNATTN_TAG_MAX_S 4096
+#define SCNATTN_TAG_MAX_K 4
+#define SCNATTN_TAG_MAX_THRESHOLDS 8
+#define SCNATTN_TAG_MAX_IMAGES 1073741824L
+#define SCNATTN_TAG_SUMMARY_LEN 64
+int scnattn_tag_store_size(int S, long cap, size_t* score_bytes, size_t* label_bytes);
+int scnattn_tag_rows(void* stream, int B, int S, const float* probs, long ld_probs, const void* targets, int targets_u8,
+                     long ld_targets, long row0, long cap, const int32_t* ks, int nk, float* store_scores, uint8_t* store_labels,
+                     double* row_ap, int32_t* row_npos, int32_t* row_hits, int32_t* flag);
+int scnattn_tag_cols(void* stream, int S, long n, long cap, const float* store_scores, const uint8_t* store_labels,
+                     const float* thresholds, int nt, double* col_ap, int32_t* col_npos, int32_t* col_counts,
+                     int32_t* col_agree);
+int scnattn_tag_finalize(void* stream, int S, long n, const int32_t* ks, int nk, int nt, const double* row_ap,
+                         const int32_t* row_npos, const int32_t* row_hits, const double* col_ap, const int32_t* col_npos,
+                         const int32_t* col_counts, const int32_t* col_agree, const int32_t* flag, double* summary);
 /* Fused BatchNorm2d (+ residual) (+ ReLU) on channels-last maps viewed as [R = N*H*W, C] (C % 4 == 0):
  * the `bn -> relu` / `bn -> (+identity) -> relu` groups of torchvision's Bottleneck behind
  * models/encoders/caption.py:17-22.  `partial` needs scnattn_bn_workspace_floats(C) floats.

@@ -1233,6 +1233,30 @@ int scnattn_text_cider(void* stream, int N, int R, const int32_t* hyp, int Lh, c
                       table_keys, table_df, table_off, n_images, score, mean, flag);
 }
 
+int scnattn_tag_store_size(int S, long cap, size_t* score_bytes, size_t* label_bytes) {
+    return tag_store_size(S, cap, score_bytes, label_bytes);
+}
+
+int scnattn_tag_rows(void* stream, int B, int S, const float* probs, long ld_probs, const void* targets, int targets_u8,
+                     long ld_targets, long row0, long cap, const int32_t* ks, int nk, float* store_scores, uint8_t* store_labels,
+                     double* row_ap, int32_t* row_npos, int32_t* row_hits, int32_t* flag) {
+    return tag_rows(ST(stream), B, S, probs, ld_probs, targets, targets_u8, ld_targets, row0, cap, ks, nk, store_scores,
+                    store_labels, row_ap, row_npos, row_hits, flag);
+}
+
+int scnattn_tag_cols(void* stream, int S, long n, long cap, const float* store_scores, const uint8_t* store_labels,
+                     const float* thresholds, int nt, double* col_ap, int32_t* col_npos, int32_t* col_counts,
+                     int32_t* col_agree) {
+    return tag_cols(ST(stream), S, n, cap, store_scores, store_labels, thresholds, nt, col_ap, col_npos, col_counts, col_agree);
+}
+
+int scnattn_tag_finalize(void* stream, int S, long n, const int32_t* ks, int nk, int nt, const double* row_ap,
+                         const int32_t* row_npos, const int32_t* row_hits, const double* col_ap, const int32_t* col_npos,
+                         const int32_t* col_counts, const int32_t* col_agree, const int32_t* flag, double* summary) {
+    return tag_finalize(ST(stream), S, n, ks, nk, nt, row_ap, row_npos, row_hits, col_ap, col_npos, col_counts, col_agree, flag,
+                        summary);
+}
+
 long scnattn_resize_table_ints(int in_size, int out_size) {
     const long n = resize_table_ints(in_size, out_size);
     if (n < 0) set_error("scnattn_resize_table_ints: size outside 1..SCNATTN_RESIZE_MAX_DIM");

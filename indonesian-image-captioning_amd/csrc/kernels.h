@@ -375,6 +375,16 @@ int text_cider(hipStream_t st, int N, int R, const int32_t* hyp, int Lh, const i
                const int32_t* ref_len, const int32_t* skip_hyp, int n_skip_hyp, const int32_t* skip_ref, int n_skip_ref,
                const int64_t* table_keys, const int32_t* table_df, const long* table_off, long n_images, double* score,
                double* mean, int32_t* flag);
+// tagmetrics.hip: tagger evaluation (per-image / per-tag AP in counting form, hits@k, tp/fp/fn, summary); layouts in include/scnattn.h
+int tag_store_size(int S, long cap, size_t* score_bytes, size_t* label_bytes);
+int tag_rows(hipStream_t st, int B, int S, const float* probs, long ld_probs, const void* targets, int targets_u8, long ld_targets,
+             long row0, long cap, const int32_t* ks, int nk, float* store_scores, uint8_t* store_labels, double* row_ap,
+             int32_t* row_npos, int32_t* row_hits, int32_t* flag);
+int tag_cols(hipStream_t st, int S, long n, long cap, const float* store_scores, const uint8_t* store_labels,
+             const float* thresholds, int nt, double* col_ap, int32_t* col_npos, int32_t* col_counts, int32_t* col_agree);
+int tag_finalize(hipStream_t st, int S, long n, const int32_t* ks, int nk, int nt, const double* row_ap, const int32_t* row_npos,
+                 const int32_t* row_hits, const double* col_ap, const int32_t* col_npos, const int32_t* col_counts,
+                 const int32_t* col_agree, const int32_t* flag, double* summary);
 int pool_permute_fwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* x,
                      long sxb, long sxc, long sxh, long sxw, float* y);
 int pool_permute_bwd(hipStream_t st, int B, int C, int Hin, int Win, int Ho, int Wo, const float* dy,

@@ -315,6 +315,10 @@ _SIGS = {
     "scnattn_text_lcs": ([vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp], i32),
     "scnattn_text_ref_keys": ([vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp], i32),
     "scnattn_text_cider": ([vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp], i32),
+    "scnattn_tag_store_size": ([i32, i64, C.POINTER(sz), C.POINTER(sz)], i32),
+    "scnattn_tag_rows": ([vp, i32, i32, vp, i64, vp, i32, i64, i64, i64, C.POINTER(C.c_int32), i32, vp, vp, vp, vp, vp, vp], i32),
+    "scnattn_tag_cols": ([vp, i32, i64, i64, vp, vp, C.POINTER(C.c_float), i32, vp, vp, vp, vp], i32),
+    "scnattn_tag_finalize": ([vp, i32, i64, C.POINTER(C.c_int32), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
     "scnattn_bn_workspace_floats": ([i32], i32),
     "scnattn_bn_stats": ([vp, i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp], i32),
     "scnattn_bn_apply": ([vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp], i32),
@@ -341,6 +345,8 @@ MAX_ENSEMBLE = 4    # SCNATTN_MAX_ENSEMBLE
 RESIZE_MAX_DIM = 16384      # SCNATTN_RESIZE_MAX_DIM
 OVERLAY_MAX_MAP, OVERLAY_MAX_OUT = 32, 1024      # SCNATTN_OVERLAY_MAX_MAP, SCNATTN_OVERLAY_MAX_OUT
 TEXT_MAX_LEN, TEXT_MAX_REFS, TEXT_CIDER_MAX_TOKEN = 128, 32, 65534      # SCNATTN_TEXT_MAX_LEN, _MAX_REFS, _CIDER_MAX_TOKEN
+# SCNATTN_TAG_MAX_S, _MAX_K, _MAX_THRESHOLDS, _MAX_IMAGES, _SUMMARY_LEN
+TAG_MAX_S, TAG_MAX_K, TAG_MAX_THRESHOLDS, TAG_MAX_IMAGES, TAG_SUMMARY_LEN = 4096, 4, 8, 1 << 30, 64
 
 EXPORTS = tuple(_SIGS) + ("scnattn_last_error",)
 

@@ -710,17 +710,42 @@ class TaggerTrainStep:
         return loss, agree
 
 
-def validate_tagger(batches, encoder, losses=None):
+def validate_tagger(batches, encoder, losses=None, scorer=None):
     """The reference's tagger validate() (trains/tagger.py:195-250): eval mode, no_grad, one unweighted `update(val)` per
     batch for loss and accuracy (= agree / (B * S) * 100, binary_accuracy); returns the accuracy meter.  `batches` yields
-    (imgs, tags) on the device; `losses`: an AverageMeter that receives the per-batch losses."""
+    (imgs, tags) on the device; `losses`: an AverageMeter that receives the per-batch losses.  `scorer`: a
+    scnattn.tagmetrics.TagScorer that receives every batch's probabilities and tags (one launch each, no synchronisation);
+    its result() then holds tag mAP, precision / recall at k and per-tag F1 of the pass."""
     from utils.metric import AverageMeter
     encoder.eval()
     losses = AverageMeter() if losses is None else losses
     accs = AverageMeter()
     with torch.no_grad():
         for imgs, tags in batches:
-            _, loss, agree = encoder.tag_loss(imgs, tags)
+            probs, loss, agree = encoder.tag_loss(imgs, tags)
+            if scorer is not None:
+                scorer.update(probs, tags)
             losses.update(loss.item())
             accs.update(agree.item() / tags.numel() * 100.0)
     return accs
+
+
+def evaluate_tagger(batches, encoder, ks=(1, 5, 10, 20), thresholds=(0.5,), capacity=None):
+    """The reference's eval_tagger.py at any batch size, with the measures binary_accuracy cannot give: eval mode, no_grad,
+    `encoder(imgs)` of every batch into a TagScorer, one download at the end.  `batches` yields (imgs, tags) on the device.
+    `capacity`: the number of images (e.g. len(dataset)), so that a loader can be streamed; without it `batches` is made a
+    list first and counted.  Returns TagScorer.result()."""
+    from scnattn.tagmetrics import TagScorer
+    if capacity is None:
+        batches = list(batches)
+        capacity = sum(int(tags.shape[0]) for _, tags in batches)
+    encoder.eval()
+    scorer = None
+    with torch.no_grad():
+        for imgs, tags in batches:
+            if scorer is None:
+                scorer = TagScorer(encoder.semantic_size, capacity, ks=ks, thresholds=thresholds, device=tags.device)
+            scorer.update(encoder(imgs), tags)
+    if scorer is None:
+        raise ValueError("evaluate_tagger: no batches")
+    return scorer.result()
