@@ -25,6 +25,8 @@ extern "C" {
 
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
+                               + image augmentation in the input assembly: crop, flip, colour jitter (scnattn_augment_config,
+                               scnattn_u8_mean_grey, scnattn_augment_draw, scnattn_u8_gather_augment; new symbols only, the version stays);
                                + tagger evaluation: per-image / per-tag average precision, hits@k, tp/fp/fn per threshold
                                (scnattn_tag_store_size, scnattn_tag_rows, scnattn_tag_cols, scnattn_tag_finalize; new symbols only, the
                                version stays);
@@ -897,6 +899,57 @@ int scnattn_bce_bwd(void* stream, int B, int S, const float* probs, long ldp, co
  * A row index outside [0, n_src) yields a NaN image instead of a fault. */
 int scnattn_u8_gather_normalize(void* stream, const uint8_t* src, long n_src, const int64_t* idx, long n_out, int C,
                                 long HW, const float* lut, void* dst, int dst_bf16, int channels_last);
+/* Image augmentation in the same gather: random resized crop, horizontal flip, colour jitter.  The reference has none (it
+ * feeds Normalize only) and torchvision's differ; the semantics below are this library's own.  Images are C = 3 planes
+ * [N][3][H][W]; the output has the size of the source.
+ *   scnattn_u8_mean_grey    per source image the exact integer byte sums SR, SG, SB of its planes (sums: int64 [N][3], or
+ *                           NULL) and grey[i] = (0.299 SR + 0.587 SG + 0.114 SB) / (255 HW), formed in fp64 and rounded once
+ *                           to fp32.  Once over a resident dataset, or per staged batch.
+ *   scnattn_augment_draw    params[i] = (x0, y0, w, h, flip, bright, contr, sat), fp32 [n][8], a function of (seed, epoch,
+ *                           sid[i]) alone.  Uniforms u_k = (word_k >> 8) * 2^-24 of Philox4x32-10 with key (seed &
+ *                           0xffffffff, seed >> 32) and counter (q, sid & 0xffffffff, sid >> 32, epoch): q = 0 gives u0 area,
+ *                           u1 aspect, u2 x offset, u3 y offset; q = 1 gives u4 flip, u5 brightness, u6 contrast, u7
+ *                           saturation.
+ *                             a = scale_lo + u0 (scale_hi - scale_lo)      r = exp(log ratio_lo + u1 (log ratio_hi - log ratio_lo))
+ *                             w = min(W, W sqrt(a r))                      h = min(H, H sqrt(a / r))
+ *                             x0 = u2 (W - w)     y0 = u3 (H - h)          flip = u4 < flip_p ? 1 : 0
+ *                             bright / contr / sat = 1 + (2 u - 1) strength
+ *                           No rejection loop, no integer rounding of the rectangle.  Evaluated in fp64 on the fp32 values of
+ *                           cfg, each result rounded once to fp32.  Requires 0 < scale_lo <= scale_hi <= 1, 0 < ratio_lo <=
+ *                           ratio_hi, flip_p and the strengths in [0, 1], epoch >= 0.
+ *   scnattn_u8_gather_augment   row i of the output is image idx[i] (NULL: i) of src seen through params[i].  For output
+ *                           pixel (oy, ox):
+ *                             1. mirror: ox' = flip != 0 ? W - 1 - ox : ox
+ *                             2. sx = clamp(x0 + (ox' + 0.5) (w / W) - 0.5, 0, W - 1), sy likewise from (y0, h, H, oy): the
+ *                                half-pixel convention with border clamp of grid_sample(align_corners=False,
+ *                                padding_mode="border"); magnification is >= 1 for a drawn record, so there is no antialias filter
+ *                             3. v_c = bilinear blend of the four bytes around (sy, sx) (the right / lower neighbour index
+ *                                clamped to the border), divided by 255
+ *                             4. brightness: v_c = clamp(bright v_c, 0, 1)
+ *                             5. contrast: m = min(1, bright grey[row]); v_c = clamp(contr v_c + (1 - contr) m, 0, 1); skipped
+ *                                when grey is NULL.  grey is scnattn_u8_mean_grey of src (N entries): the mean of the SOURCE
+ *                                image, not of the crop
+ *                             6. saturation: g = 0.299 v_R + 0.587 v_G + 0.114 v_B; v_c = clamp(sat v_c + (1 - sat) g, 0, 1)
+ *                             7. dst = (v_c - mean[c]) / std[c], fp32 or bf16 (round to nearest even), [n][3][H][W] or,
+ *                                channels_last, [n][H][W][3]
+ *                           fp32 arithmetic in that order.  mean, std: HOST arrays of 3 floats.  A row index outside [0, N)
+ *                           yields a NaN image.  The coordinates are clamped whatever a record holds (NaN counts as 0), so a
+ *                           hand-made table never reads outside its image.  The record (W, H crop, 0 flip, 1, 1, 1) is the
+ *                           identity: ((byte / 255) - mean) / std with three roundings.
+ * 1 <= H, W <= 16384.  Every refusal returns -1 before anything is launched. */
+typedef struct scnattn_augment_config {
+    float scale_lo, scale_hi;      /* crop area as a fraction of the image */
+    float ratio_lo, ratio_hi;      /* aspect change of the crop, log-uniform */
+    float flip_p;                  /* probability of the mirror */
+    float brightness, contrast, saturation;      /* strengths: each factor is uniform in [1 - s, 1 + s] */
+} scnattn_augment_config;
+#define SCNATTN_AUGMENT_NPARAM 8
+int scnattn_u8_mean_grey(void* stream, const uint8_t* src, long N, long HW, int64_t* sums, float* grey);
+int scnattn_augment_draw(void* stream, long n, const int64_t* sid, int epoch, uint64_t seed, const scnattn_augment_config* cfg,
+                         int H, int W, float* params);
+int scnattn_u8_gather_augment(void* stream, const uint8_t* src, long N, const int64_t* idx, long n, int H, int W,
+                              const float* params, const float* grey, const float* mean, const float* std, void* dst,
+                              int dst_bf16, int channels_last);
 /* Image resize of the inference path: replaces the host-side `scipy.misc.imresize(img, (OH, OW))` of inference.py:33-38
  * and utils/dataset.py:368-373, i.e. `PIL.Image.resize((OW, OH), BILINEAR)` on the uint8 image, the grey -> three planes
  * replication before it and the `transpose(2, 0, 1)` after it -- bit for bit: Pillow's 8-bit resize is integer

@@ -1172,6 +1172,22 @@ int scnattn_u8_gather_normalize(void* stream, const uint8_t* src, long n_src, co
                                channels_last);
 }
 
+int scnattn_u8_mean_grey(void* stream, const uint8_t* src, long N, long HW, int64_t* sums, float* grey) {
+    return u8_mean_grey(ST(stream), src, N, HW, (long long*)sums, grey);
+}
+
+int scnattn_augment_draw(void* stream, long n, const int64_t* sid, int epoch, uint64_t seed, const scnattn_augment_config* cfg,
+                         int H, int W, float* params) {
+    return augment_draw(ST(stream), n, (const long long*)sid, epoch, (unsigned long long)seed, cfg, H, W, params);
+}
+
+int scnattn_u8_gather_augment(void* stream, const uint8_t* src, long N, const int64_t* idx, long n, int H, int W,
+                              const float* params, const float* grey, const float* mean, const float* std, void* dst,
+                              int dst_bf16, int channels_last) {
+    return u8_gather_augment(ST(stream), src, N, (const long long*)idx, n, H, W, params, grey, mean, std, dst, dst_bf16,
+                             channels_last);
+}
+
 int scnattn_u8_resize_bilinear(void* stream, const uint8_t* src, long src_bytes, const scnattn_image_desc* desc_host,
                                const scnattn_image_desc* desc_dev, int N, const int32_t* taps, long taps_len, int OH,
                                int OW, const float* lut, void* dst, int dst_kind, int channels_last) {

@@ -344,6 +344,14 @@ int bce_bwd(hipStream_t st, int B, int S, const float* probs, long ldp, const fl
 // data.hip: uint8 image rows (gathered by index) -> normalised fp32/bf16 batch, NCHW or channels-last
 int u8_gather_normalize(hipStream_t st, const uint8_t* src, long n_src, const long long* idx, long n_out, int C,
                         long HW, const float* lut, void* dst, int dst_bf16, int channels_last);
+// augment.hip: the same gather with a random resized crop, flip and colour jitter per sample (record of 8 floats from
+// augment_draw or from the caller), the per-image mean grey its contrast step reads; semantics in include/scnattn.h
+int u8_mean_grey(hipStream_t st, const uint8_t* src, long N, long HW, long long* sums, float* grey);
+int augment_draw(hipStream_t st, long n, const long long* sid, int epoch, unsigned long long seed,
+                 const scnattn_augment_config* cfg, int H, int W, float* params);
+int u8_gather_augment(hipStream_t st, const uint8_t* src, long n_src, const long long* idx, long n_out, int H, int W,
+                      const float* params, const float* grey, const float* mean, const float* std, void* dst, int dst_bf16,
+                      int channels_last);
 // resize.hip: a packed batch of decoded uint8 images -> Pillow's bilinear resize, as uint8 rows or normalised
 int u8_resize_bilinear(hipStream_t st, const uint8_t* src, long src_bytes, const struct scnattn_image_desc* desc_host,
                        const struct scnattn_image_desc* desc_dev, int N, const int* taps, long taps_len, int OH, int OW,

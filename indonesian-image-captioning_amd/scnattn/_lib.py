@@ -103,6 +103,14 @@ class SampleFilter(C.Structure):   # scnattn_sample_filter
     _fields_ = [("top_k", C.c_int32), ("top_p", C.c_float)]
 
 
+class AugmentConfig(C.Structure):  # scnattn_augment_config
+    _fields_ = [(k, C.c_float) for k in ("scale_lo", "scale_hi", "ratio_lo", "ratio_hi", "flip_p", "brightness", "contrast",
+                                         "saturation")]
+
+
+AUGMENT_NPARAM = 8                 # SCNATTN_AUGMENT_NPARAM
+
+
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
@@ -304,6 +312,10 @@ _SIGS = {
     "scnattn_bce_fwd": ([vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp], i32),
     "scnattn_bce_bwd": ([vp, i32, i32, vp, i64, vp, i64, vp, vp, i64], i32),
     "scnattn_u8_gather_normalize": ([vp, vp, i64, vp, i64, i32, i64, vp, vp, i32, i32], i32),
+    "scnattn_u8_mean_grey": ([vp, vp, i64, i64, vp, vp], i32),
+    "scnattn_augment_draw": ([vp, i64, vp, i32, C.c_uint64, C.POINTER(AugmentConfig), i32, i32, vp], i32),
+    "scnattn_u8_gather_augment": ([vp, vp, i64, vp, i64, i32, i32, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp,
+                                   i32, i32], i32),
     "scnattn_resize_table_ints": ([i32, i32], i64),
     "scnattn_u8_resize_bilinear": ([vp, vp, i64, vp, vp, i32, vp, i64, i32, i32, vp, vp, i32, i32], i32),
     "scnattn_u8_resize_taps": ([vp, vp, i64, vp, vp, i32, vp, vp, i64, i32, i32, vp, vp, i32, i32], i32),

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import h5lite
+from .augment import gather_augment, mean_grey
 from ._lib import RESIZE_MAX_DIM, ImageDesc, call, ptr, require_cuda, stream_of
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)      # trains/attention_scn.py:121-122
@@ -312,7 +313,7 @@ class DeviceBatchLoader:
 
     def __init__(self, data_folder, data_name, split, batch_size, device, cpi=5, shuffle=True, seed=0, rank=0,
                  world=1, dtype=torch.float32, channels_last=True, mean=IMAGENET_MEAN, std=IMAGENET_STD,
-                 resident=None, hbm_budget_bytes=64 << 30, prefetch=2, drop_last=False):
+                 resident=None, hbm_budget_bytes=64 << 30, prefetch=2, drop_last=False, augment=None):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceBatchLoader produces batches on an MI355X device; there is no CPU fallback "
@@ -330,6 +331,18 @@ class DeviceBatchLoader:
         nbytes = self.files.imgs.nbytes
         self.resident = (nbytes <= hbm_budget_bytes) if resident is None else bool(resident)
         self.imgs_dev = self._upload() if self.resident else None
+        # augment: a scnattn.augment.Augment -- crop, flip and colour jitter inside the gather (two launches per batch
+        # instead of one); None, or one whose every draw is the identity, leaves the plain kernel in place
+        if augment is not None and split != "TRAIN":
+            raise ValueError("augment is for the TRAIN split only (got %s): validation sees the images as they are" % split)
+        self.augment = None if augment is None or augment.is_identity else augment
+        self.grey = None
+        if self.augment is not None:
+            if self.files.imgs.shape[1] != 3:
+                raise ValueError("augment needs images of 3 planes, found %d" % self.files.imgs.shape[1])
+            self.norm = (None, None) if mean is None else (tuple(mean), tuple(std))
+            if self.resident and self.augment.contrast != 0.0:
+                self.grey = mean_grey(self.imgs_dev)              # once: the contrast step reads the SOURCE image's mean
 
     # ---- one-off upload of the uint8 dataset ---------------------------------------------------------------
     def _upload(self, chunk_rows=256):
@@ -361,6 +374,14 @@ class DeviceBatchLoader:
         n = -(-len(self.files) // self.world) if self.world > 1 else len(self.files)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
+    def _images(self, src, rows, n, sel, grey):
+        """the batch of `n` images: rows `rows` of src (None: the first n), augmented as samples `sel` when asked for"""
+        if self.augment is None:
+            return gather_normalize(src, rows, self.lut, n_out=n, dtype=self.dtype, channels_last=self.channels_last)
+        params = self.augment.draw(sel, self.epoch, src.shape[2], src.shape[3])
+        return gather_augment(src, rows, params, self.norm[0], self.norm[1], grey=grey, dtype=self.dtype,
+                              channels_last=self.channels_last)
+
     def _tuple(self, imgs, sel):
         caps = self.caps_dev.index_select(0, sel)
         caplens = self.caplens_dev.index_select(0, sel).unsqueeze(1)          # LongTensor([caplen]) per sample
@@ -380,8 +401,7 @@ class DeviceBatchLoader:
             for b in range(nb):
                 sl = slice(b * self.batch_size, min((b + 1) * self.batch_size, len(order)))
                 sel = order_dev[sl]
-                imgs = gather_normalize(self.imgs_dev, img_rows[sl].contiguous(), self.lut, dtype=self.dtype,
-                                        channels_last=self.channels_last)
+                imgs = self._images(self.imgs_dev, img_rows[sl].contiguous(), None, sel, self.grey)
                 yield self._tuple(imgs, sel)
             return
         yield from self._iter_staged(order, nb)
@@ -435,12 +455,19 @@ class DeviceBatchLoader:
                 b, s, n, ev = item
                 cur = torch.cuda.current_stream(self.device)
                 cur.wait_event(ev)
-                imgs = gather_normalize(staged[s], None, self.lut, n_out=n, dtype=self.dtype,
-                                        channels_last=self.channels_last)
+                sel = None
+                if self.augment is None:
+                    imgs = self._images(staged[s], None, n, None, None)
+                else:                                             # the draw needs the sample ids before the gather
+                    sel = torch.from_numpy(order[b * B:b * B + n]).to(self.device, non_blocking=True)
+                    # the grey table of this staged batch: the same values as the resident table's rows
+                    grey = mean_grey(staged[s][:n]) if self.augment.contrast != 0.0 else None
+                    imgs = self._images(staged[s][:n], None, n, sel, grey)
                 rel = torch.cuda.Event()
                 rel.record(cur)
                 released[s] = rel
-                sel = torch.from_numpy(order[b * B:b * B + n]).to(self.device, non_blocking=True)
+                if sel is None:
+                    sel = torch.from_numpy(order[b * B:b * B + n]).to(self.device, non_blocking=True)
                 yield self._tuple(imgs, sel)
         finally:
             stop.set()
