@@ -25,6 +25,8 @@ extern "C" {
 
 #define SCNATTN_VERSION 109 /* 0.1.9: - the scnattn_seq_bwd_streams entry point: decoder weight gradients on a second stream were not faster; - option dec_tail: the cell
                                kernels inside the skinny launches were slower; DESIGN.md keeps the numbers;
+                               + tagger losses for rare tags on the logits: positive weights, focal, asymmetric (scnattn_tag_loss_options,
+                               scnattn_tagloss_fwd, scnattn_tagloss_bwd; new symbols only, the version stays);
                                + image augmentation in the input assembly: crop, flip, colour jitter (scnattn_augment_config,
                                scnattn_u8_mean_grey, scnattn_augment_draw, scnattn_u8_gather_augment; new symbols only, the version stays);
                                + tagger evaluation: per-image / per-tag average precision, hits@k, tp/fp/fn per threshold
@@ -889,6 +891,41 @@ int scnattn_bce_fwd(void* stream, int B, int S, const float* z, long ldz, const 
                     long ldp, float* rows, float* out);
 int scnattn_bce_bwd(void* stream, int B, int S, const float* probs, long ldp, const float* targets, long ldt,
                     const float* grad_loss, float* dz, long lddz);
+/* Tagger losses for rare tags: the per-tag positive weight, the focal loss (Lin et al. 2017) and the asymmetric loss (Ridnik
+ * et al. 2021) as ONE family of element-wise terms ON THE LOGITS, in the place of bce_fwd / bce_bwd.  The reference has none
+ * (it trains under nn.BCELoss only); the semantics below are this library's own.
+ * For a logit z, a target t in [0, 1] and a tag weight w_s >= 0 (pos_weight[s]; 1 when pos_weight is NULL), with
+ * p = sigmoid(z), q = 1 - p and sp(x) = max(x, 0) + log1p(exp(-|x|))  (sp(z) = -log q, sp(-z) = -log p):
+ *   term(z, t) = t * w_s * Lpos(z) + (1 - t) * Lneg(z)
+ *   Lpos = (1 - p)^gamma_pos * (-log p)     = exp(-gamma_pos * sp(z)) * sp(-z)
+ *   Lneg = p^gamma_neg * (-log(1 - p))      = exp(-gamma_neg * sp(-z)) * sp(z)                          margin = 0
+ *   Lneg = p_m^gamma_neg * (-log1p(-p_m)),  p_m = max(p - margin, 0),  0^0 := 1                         margin > 0
+ *   out[0] = sum(term) / (B * S)            (BCELoss's normaliser, so that the losses stay comparable)
+ * and the derivative by the logit (q is formed as exp(-|z|) / (1 + exp(-|z|)) or 1 / (1 + exp(-|z|)), never as 1 - p):
+ *   dLpos/dz = -exp(-gamma_pos * sp(z)) * (gamma_pos * p * sp(-z) + q)
+ *   dLneg/dz =  exp(-gamma_neg * sp(-z)) * (gamma_neg * q * sp(z) + p)                                  margin = 0
+ *   dLneg/dz =  [p > margin] * (gamma_neg * p_m^(gamma_neg - 1) * (-log1p(-p_m)) + p_m^gamma_neg / (1 - p_m)) * p * q
+ *   dz       = grad_loss[0] / (B * S) * (t * w_s * dLpos/dz + (1 - t) * dLneg/dz)
+ * Nothing is clamped at -100: at z = -120, t = 1 the term is w_s * 120 and dz = -w_s * grad_loss / (B * S), where the BCE
+ * pair above has gradient 0.  (w, 0, 0, 0) is BCEWithLogitsLoss(pos_weight = w); gamma_pos = gamma_neg, margin 0 is the focal
+ * loss with its alpha balance carried by w; (0, 4, 0.05) is the asymmetric loss's published default.
+ *   tagloss_fwd   probs and out[1] (the agreement count) hold the bits bce_fwd writes for the same z and targets; rows:
+ *                 workspace of 2*B floats (row sums, row counts); out[0] as above
+ *   tagloss_bwd   reads the LOGITS, not the stored probs (a saturated p has lost what the gradient needs); grad_loss is the
+ *                 DEVICE scalar d/d loss
+ * Rows on 16-byte accesses when S % 4 == 0 and every base pointer (pos_weight included) and leading dimension allow it, the
+ * scalar form otherwise.  Fixed summation order (bit-reproducible).  Refused with -1 before anything is launched: gamma_pos
+ * or gamma_neg outside [0, 16] or not finite; margin outside [0, 1); margin > 0 together with 0 < gamma_neg < 1 (the gradient
+ * is unbounded at p -> margin+); a null pointer other than pos_weight; B or S < 1, B*S > 2^24, a leading dimension below S. */
+typedef struct scnattn_tag_loss_options {
+    float gamma_pos, gamma_neg, margin;
+} scnattn_tag_loss_options;
+int scnattn_tagloss_fwd(void* stream, int B, int S, const float* z, long ldz, const float* targets, long ldt,
+                        const float* pos_weight, const scnattn_tag_loss_options* opt, float* probs, long ldp, float* rows,
+                        float* out);
+int scnattn_tagloss_bwd(void* stream, int B, int S, const float* z, long ldz, const float* targets, long ldt,
+                        const float* pos_weight, const scnattn_tag_loss_options* opt, const float* grad_loss, float* dz,
+                        long lddz);
 /* Input assembly: replaces the per-sample host arithmetic of datasets/caption.py:51-53
  * (`torch.FloatTensor(imgs[i // cpi] / 255.)` + torchvision Normalize, trains/attention_scn.py:121-126).
  * src: n_src uint8 images [n_src][C][HW] in HBM (a staged batch or the whole dataset); idx: n_out int64

@@ -1166,6 +1166,18 @@ int scnattn_bce_bwd(void* stream, int B, int S, const float* probs, long ldp, co
     return bce_bwd(ST(stream), B, S, probs, ldp, targets, ldt, grad_loss, dz, lddz);
 }
 
+int scnattn_tagloss_fwd(void* stream, int B, int S, const float* z, long ldz, const float* targets, long ldt,
+                        const float* pos_weight, const scnattn_tag_loss_options* opt, float* probs, long ldp, float* rows,
+                        float* out) {
+    return tagloss_fwd(ST(stream), B, S, z, ldz, targets, ldt, pos_weight, opt, probs, ldp, rows, out);
+}
+
+int scnattn_tagloss_bwd(void* stream, int B, int S, const float* z, long ldz, const float* targets, long ldt,
+                        const float* pos_weight, const scnattn_tag_loss_options* opt, const float* grad_loss, float* dz,
+                        long lddz) {
+    return tagloss_bwd(ST(stream), B, S, z, ldz, targets, ldt, pos_weight, opt, grad_loss, dz, lddz);
+}
+
 int scnattn_u8_gather_normalize(void* stream, const uint8_t* src, long n_src, const int64_t* idx, long n_out, int C,
                                 long HW, const float* lut, void* dst, int dst_bf16, int channels_last) {
     return u8_gather_normalize(ST(stream), src, n_src, (const long long*)idx, n_out, C, HW, lut, dst, dst_bf16,

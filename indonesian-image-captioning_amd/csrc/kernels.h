@@ -341,6 +341,11 @@ int bce_fwd(hipStream_t st, int B, int S, const float* z, long ldz, const float*
             float* rows, float* out);
 int bce_bwd(hipStream_t st, int B, int S, const float* probs, long ldp, const float* t, long ldt, const float* g, float* dz,
             long lddz);
+// the weighted / focal / asymmetric family on the logits (include/scnattn.h: "Tagger losses for rare tags"), w: [S] or null
+int tagloss_fwd(hipStream_t st, int B, int S, const float* z, long ldz, const float* t, long ldt, const float* w,
+                const scnattn_tag_loss_options* opt, float* probs, long ldp, float* rows, float* out);
+int tagloss_bwd(hipStream_t st, int B, int S, const float* z, long ldz, const float* t, long ldt, const float* w,
+                const scnattn_tag_loss_options* opt, const float* g, float* dz, long lddz);
 // data.hip: uint8 image rows (gathered by index) -> normalised fp32/bf16 batch, NCHW or channels-last
 int u8_gather_normalize(hipStream_t st, const uint8_t* src, long n_src, const long long* idx, long n_out, int C,
                         long HW, const float* lut, void* dst, int dst_bf16, int channels_last);

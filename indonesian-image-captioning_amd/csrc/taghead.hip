@@ -7,7 +7,9 @@
 // The loss is the reference's function of the ROUNDED fp32 probability, quirks included: both logarithms are clamped
 // at -100 BEFORE they meet t or 1 - t (0 * -inf would be NaN), and the gradient is BCELoss's (p - t) / max(p(1-p), 1e-12)
 // times the sigmoid's p(1-p) -- exactly 0 where p saturated to 0 or 1, not the p - t of the logits form.
-// All four are bound by HBM or by their launch: the pool reads the map once (16.8 MB at B=32, 8x8, C=2048, half of that
+// tagloss_fwd / tagloss_bwd put the weighted, focal and asymmetric terms ON THE LOGITS in the place of the BCE pair
+// (include/scnattn.h: "Tagger losses for rare tags"): the same decomposition, probabilities and count, another term.
+// All are bound by HBM or by their launch: the pool reads the map once (16.8 MB at B=32, 8x8, C=2048, half of that
 // in bf16), one workgroup per image and 256 columns (256 workgroups there), whose pixel groups meet once in LDS in group
 // order.  Every sum has a fixed order; no atomics.
 // bf16 == 2 (tag_pool_fwd): the mean of a bf16 map is rounded to bf16 (nearest even) before the mask, as
@@ -212,6 +214,130 @@ __global__ __launch_bounds__(256) void bce_bwd_kernel(int S, const float* __rest
     }
 }
 
+// ---- the weighted / focal / asymmetric family on the logits (include/scnattn.h: "Tagger losses for rare tags") ----------------
+// FORM is uniform per launch and picked on the host: 0 both gammas 0 and no margin (BCE with logits, weighted), 1 a gamma,
+// no margin (focal), 2 a margin (asymmetric).  HASW: pos_weight is given.  No branch on the options inside the element loop
+// but gamma_neg == 0 under a margin, which is uniform over the launch (0^0 := 1).
+struct TagLossOpt { float gp, gn, m; };
+
+// sp(z) = -log(1 - p), sp(-z) = -log p, p and q = 1 - p from one expf, one log1pf and one division; q is never a difference.
+// The three element functions round every operation once (no contraction into fma): they evaluate the header's expressions
+// as a plain fp32 evaluation does, which is what their per-element test measures them against.
+struct LogitParts { float spz, spn, p, q; };
+__device__ __forceinline__ LogitParts logit_parts(float z) {
+#pragma clang fp contract(off)
+    const float e = expf(-fabsf(z)), l = log1pf(e), r = 1.f / (1.f + e);
+    const bool pos = z >= 0.f;
+    return {fmaxf(z, 0.f) + l, fmaxf(-z, 0.f) + l, pos ? r : e * r, pos ? e * r : r};
+}
+
+// p: the stored probability sigmoidf_(z), which the margin is taken from
+template <int FORM>
+__device__ __forceinline__ float tagloss_term(float z, float p, float t, float w, const TagLossOpt o) {
+#pragma clang fp contract(off)
+    const LogitParts a = logit_parts(z);
+    float lp = a.spn, ln = a.spz;
+    if (FORM != 0) lp *= expf(-o.gp * a.spz);
+    if (FORM == 1) ln *= expf(-o.gn * a.spn);
+    if (FORM == 2) {
+        const float pm = fmaxf(p - o.m, 0.f);
+        const float pw = o.gn == 0.f ? 1.f : (pm > 0.f ? expf((o.gn - 1.f) * logf(pm)) * pm : 0.f);
+        ln = pw * -log1pf(-pm);
+    }
+    return t * w * lp + (1.f - t) * ln;
+}
+
+template <int FORM>
+__device__ __forceinline__ float tagloss_grad(float z, float t, float w, const TagLossOpt o, float scale) {
+#pragma clang fp contract(off)
+    const LogitParts a = logit_parts(z);
+    float dp = -a.q, dn = a.p;
+    if (FORM != 0) dp = -expf(-o.gp * a.spz) * (o.gp * a.p * a.spn + a.q);
+    if (FORM == 1) dn = expf(-o.gn * a.spn) * (o.gn * a.q * a.spz + a.p);
+    if (FORM == 2) {
+        const float p = sigmoidf_(z), pm = p - o.m;
+        dn = 0.f;
+        if (pm > 0.f) {
+            float pw1 = 0.f, pw = 1.f;          // p_m^(gamma - 1) and p_m^gamma; gamma_neg is 0 or >= 1 here
+            if (o.gn != 0.f) { pw1 = expf((o.gn - 1.f) * logf(pm)); pw = pw1 * pm; }
+            dn = (o.gn * pw1 * -log1pf(-pm) + pw / (1.f - pm)) * p * a.q;
+        }
+    }
+    return scale * (t * w * dp + (1.f - t) * dn);
+}
+
+// bce_fwd_kernel's decomposition, probabilities and count; the term alone differs
+template <bool VEC, bool HASW, int FORM>
+__global__ __launch_bounds__(256) void tagloss_fwd_kernel(int S, const float* __restrict__ z, long ldz, const float* __restrict__ t,
+                                                          long ldt, const float* __restrict__ w, TagLossOpt o,
+                                                          float* __restrict__ probs, long ldp, float* __restrict__ row_sum,
+                                                          float* __restrict__ row_agree) {
+    const int b = blockIdx.x;
+    const float* zr = z + (long)b * ldz;
+    const float* tr = t + (long)b * ldt;
+    float* pr = probs + (long)b * ldp;
+    float acc = 0.f;
+    int n = 0;
+    if (VEC) {
+        for (int s = threadIdx.x * 4; s < S; s += 1024) {
+            const f32x4 zv = ld4(zr + s), tv = ld4(tr + s);
+            f32x4 wv = {1.f, 1.f, 1.f, 1.f};
+            if (HASW) wv = ld4(w + s);
+            f32x4 pv;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                pv[j] = sigmoidf_(zv[j]);
+                acc += tagloss_term<FORM>(zv[j], pv[j], tv[j], wv[j], o);
+                n += (pv[j] >= 0.5f) == (tv[j] >= 0.5f) ? 1 : 0;
+            }
+            *reinterpret_cast<f32x4*>(pr + s) = pv;
+        }
+    } else {
+        for (int s = threadIdx.x; s < S; s += 256) {
+            const float zz = zr[s], p = sigmoidf_(zz), tt = tr[s];
+            pr[s] = p;
+            acc += tagloss_term<FORM>(zz, p, tt, HASW ? w[s] : 1.f, o);
+            n += (p >= 0.5f) == (tt >= 0.5f) ? 1 : 0;
+        }
+    }
+    acc = wave_sum(acc);
+#pragma unroll
+    for (int o_ = 32; o_ > 0; o_ >>= 1) n += __shfl_xor(n, o_, 64);
+    __shared__ float pa[4];
+    __shared__ int pn[4];
+    if ((threadIdx.x & 63) == 0) { pa[threadIdx.x >> 6] = acc; pn[threadIdx.x >> 6] = n; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        row_sum[b] = (pa[0] + pa[1]) + (pa[2] + pa[3]);
+        row_agree[b] = (float)((pn[0] + pn[1]) + (pn[2] + pn[3]));
+    }
+}
+
+template <bool VEC, bool HASW, int FORM>
+__global__ __launch_bounds__(256) void tagloss_bwd_kernel(int S, const float* __restrict__ z, long ldz, const float* __restrict__ t,
+                                                          long ldt, const float* __restrict__ w, TagLossOpt o,
+                                                          const float* __restrict__ g, float count, float* __restrict__ dz,
+                                                          long lddz) {
+    const int b = blockIdx.x;
+    const float* zr = z + (long)b * ldz;
+    const float* tr = t + (long)b * ldt;
+    float* dr = dz + (long)b * lddz;
+    const float scale = g[0] / count;
+    if (VEC) {
+        for (int s = threadIdx.x * 4; s < S; s += 1024) {
+            const f32x4 zv = ld4(zr + s), tv = ld4(tr + s);
+            f32x4 wv = {1.f, 1.f, 1.f, 1.f};
+            if (HASW) wv = ld4(w + s);
+            f32x4 d;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[j] = tagloss_grad<FORM>(zv[j], tv[j], wv[j], o, scale);
+            *reinterpret_cast<f32x4*>(dr + s) = d;
+        }
+    } else {
+        for (int s = threadIdx.x; s < S; s += 256) dr[s] = tagloss_grad<FORM>(zr[s], tr[s], HASW ? w[s] : 1.f, o, scale);
+    }
+}
+
 inline bool rows16(const void* p, long ld) { return aligned16(p) && ld % 4 == 0; }
 
 template <typename T>
@@ -293,5 +419,66 @@ int bce_bwd(hipStream_t st, int B, int S, const float* probs, long ldp, const fl
     SCN_LAUNCH_CHECK();
     return 0;
 }
+
+// the refusals of the options (the comparisons are false for a NaN) and the kernel form they select
+static int tagloss_form(const scnattn_tag_loss_options* o, TagLossOpt& k) {
+    SCN_ARG(o, "tagloss: the options are NULL");
+    SCN_ARG(o->gamma_pos >= 0.f && o->gamma_pos <= 16.f && o->gamma_neg >= 0.f && o->gamma_neg <= 16.f,
+            "tagloss: gamma_pos and gamma_neg must be finite and in [0, 16]");
+    SCN_ARG(o->margin >= 0.f && o->margin < 1.f, "tagloss: the margin must be in [0, 1)");
+    SCN_ARG(!(o->margin > 0.f && o->gamma_neg > 0.f && o->gamma_neg < 1.f),
+            "tagloss: a margin with 0 < gamma_neg < 1 has an unbounded gradient at p -> margin");
+    k = TagLossOpt{o->gamma_pos, o->gamma_neg, o->margin};
+    return o->margin > 0.f ? 2 : (o->gamma_pos != 0.f || o->gamma_neg != 0.f) ? 1 : 0;
+}
+
+#define SCN_TAGLOSS_FORMS(KERNEL, VEC, HASW, ...)                                                                          \
+    do {                                                                                                                  \
+        if (form == 0) hipLaunchKernelGGL((KERNEL<VEC, HASW, 0>), dim3(B), dim3(256), 0, st, __VA_ARGS__);                \
+        else if (form == 1) hipLaunchKernelGGL((KERNEL<VEC, HASW, 1>), dim3(B), dim3(256), 0, st, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((KERNEL<VEC, HASW, 2>), dim3(B), dim3(256), 0, st, __VA_ARGS__);                          \
+    } while (0)
+#define SCN_TAGLOSS_LAUNCH(KERNEL, ...)                                                                                    \
+    do {                                                                                                                  \
+        if (vec && w) SCN_TAGLOSS_FORMS(KERNEL, true, true, __VA_ARGS__);                                                 \
+        else if (vec) SCN_TAGLOSS_FORMS(KERNEL, true, false, __VA_ARGS__);                                                \
+        else if (w) SCN_TAGLOSS_FORMS(KERNEL, false, true, __VA_ARGS__);                                                  \
+        else SCN_TAGLOSS_FORMS(KERNEL, false, false, __VA_ARGS__);                                                        \
+    } while (0)
+
+int tagloss_fwd(hipStream_t st, int B, int S, const float* z, long ldz, const float* t, long ldt, const float* w,
+                const scnattn_tag_loss_options* opt, float* probs, long ldp, float* rows, float* out) {
+    SCN_ARG(B > 0 && S > 0, "tagloss_fwd: bad shape");
+    SCN_ARG((long)B * S <= (1L << 24), "tagloss_fwd: B*S above 2^24 (the agreement count is kept as a float)");
+    SCN_ARG(z && t && probs && rows && out, "tagloss_fwd: null argument");
+    SCN_ARG(ldz >= S && ldt >= S && ldp >= S, "tagloss_fwd: leading dimension below the width");
+    TagLossOpt k;
+    const int form = tagloss_form(opt, k);
+    if (form < 0) return -1;
+    const bool vec = S % 4 == 0 && rows16(z, ldz) && rows16(t, ldt) && rows16(probs, ldp) && (!w || aligned16(w));
+    SCN_TAGLOSS_LAUNCH(tagloss_fwd_kernel, S, z, ldz, t, ldt, w, k, probs, ldp, rows, rows + B);
+    SCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bce_finalize_kernel, dim3(1), dim3(256), 0, st, B, rows, rows + B, (float)((long)B * S), out);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+
+int tagloss_bwd(hipStream_t st, int B, int S, const float* z, long ldz, const float* t, long ldt, const float* w,
+                const scnattn_tag_loss_options* opt, const float* g, float* dz, long lddz) {
+    SCN_ARG(B > 0 && S > 0, "tagloss_bwd: bad shape");
+    SCN_ARG((long)B * S <= (1L << 24), "tagloss_bwd: B*S above 2^24");
+    SCN_ARG(z && t && g && dz, "tagloss_bwd: null argument");
+    SCN_ARG(ldz >= S && ldt >= S && lddz >= S, "tagloss_bwd: leading dimension below the width");
+    TagLossOpt k;
+    const int form = tagloss_form(opt, k);
+    if (form < 0) return -1;
+    const bool vec = S % 4 == 0 && rows16(z, ldz) && rows16(t, ldt) && rows16(dz, lddz) && (!w || aligned16(w));
+    const float count = (float)((long)B * S);
+    SCN_TAGLOSS_LAUNCH(tagloss_bwd_kernel, S, z, ldz, t, ldt, w, k, g, count, dz, lddz);
+    SCN_LAUNCH_CHECK();
+    return 0;
+}
+#undef SCN_TAGLOSS_LAUNCH
+#undef SCN_TAGLOSS_FORMS
 
 }  // namespace scn

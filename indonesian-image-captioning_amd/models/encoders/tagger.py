@@ -42,11 +42,12 @@ class EncoderTagger(nn.Module):
         out = SF.linear(out, self.linear.weight, self.linear.bias)
         return self.sigmoid(out)
 
-    def tag_loss(self, images, targets):
+    def tag_loss(self, images, targets, loss=None):
         """One call for the train step and validation of trains/tagger.py:161-163,176: (probs, loss, agree) with
         probs = forward(images), loss = nn.BCELoss()(probs, targets) and agree = binary_accuracy's count of
         (probs >= 0.5) == (targets >= 0.5), the last two as 0-d device tensors.  The trunk is the one `forward` runs; pool,
-        dropout mask, sigmoid, loss and count run on csrc/taghead.hip (scnattn.functional.tag_head_loss)."""
+        dropout mask, sigmoid, loss and count run on csrc/taghead.hip (scnattn.functional.tag_head_loss).  `loss`: a
+        scnattn.functional.TagLoss in the place of nn.BCELoss (weights, focal, asymmetric); probs and agree stay what they are."""
         SF.require_cuda(images, targets)
         if self.channels_last and not stem_usable(self.resnet, images):
             images = images.contiguous(memory_format=torch.channels_last)
@@ -70,7 +71,8 @@ class EncoderTagger(nn.Module):
         if self.training:       # the module's own draw, pre-scaled by 1 / (1 - p); honours a replaced dropout module
             ks = self.dropout(torch.ones(x4.shape[0], x4.shape[1], device=x4.device))
         # a bf16 map (bf16 autocast): forward()'s pool hands its mean on in bf16; the step trains the function forward() evaluates
-        return SF.tag_head_loss(x4, ks, self.linear.weight, self.linear.bias, targets, pooled_bf16=x4.dtype == torch.bfloat16)
+        return SF.tag_head_loss(x4, ks, self.linear.weight, self.linear.bias, targets, pooled_bf16=x4.dtype == torch.bfloat16,
+                                loss=loss)
 
     def fine_tune(self, fine_tune=True):
         for p in self.resnet.parameters():

@@ -111,6 +111,10 @@ class AugmentConfig(C.Structure):  # scnattn_augment_config
 AUGMENT_NPARAM = 8                 # SCNATTN_AUGMENT_NPARAM
 
 
+class TagLossOpts(C.Structure):    # scnattn_tag_loss_options
+    _fields_ = [(k, C.c_float) for k in ("gamma_pos", "gamma_neg", "margin")]
+
+
 _SIGS = {
     "scnattn_version": ([], i32),
     "scnattn_set_option": ([C.c_char_p, i32], i32),
@@ -311,6 +315,8 @@ _SIGS = {
     "scnattn_tag_pool_bwd": ([vp, i32, i32, i32, vp, i64, vp, i64, vp, i32, i64, i64, i64], i32),
     "scnattn_bce_fwd": ([vp, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp], i32),
     "scnattn_bce_bwd": ([vp, i32, i32, vp, i64, vp, i64, vp, vp, i64], i32),
+    "scnattn_tagloss_fwd": ([vp, i32, i32, vp, i64, vp, i64, vp, C.POINTER(TagLossOpts), vp, i64, vp, vp], i32),
+    "scnattn_tagloss_bwd": ([vp, i32, i32, vp, i64, vp, i64, vp, C.POINTER(TagLossOpts), vp, vp, i64], i32),
     "scnattn_u8_gather_normalize": ([vp, vp, i64, vp, i64, i32, i64, vp, vp, i32, i32], i32),
     "scnattn_u8_mean_grey": ([vp, vp, i64, i64, vp, vp], i32),
     "scnattn_augment_draw": ([vp, i64, vp, i32, C.c_uint64, C.POINTER(AugmentConfig), i32, i32, vp], i32),

@@ -995,7 +995,8 @@ def pool_permute(x, out_size):
 
 
 # ----------------------------------------------------------------------------------------------
-# tagger head: global average pool (+ dropout mask) -> Linear -> Sigmoid -> BCELoss + binary accuracy  (csrc/taghead.hip)
+# tagger head: global average pool (+ dropout mask) -> Linear -> Sigmoid -> BCELoss + binary accuracy  (csrc/taghead.hip);
+# TagLoss: positive weights, focal and asymmetric terms on the logits in the place of BCELoss
 # ----------------------------------------------------------------------------------------------
 def _pixel_strides(x4):
     """(sb, sp, sc) of a (B, C, H, W) map read as x[b, q, c], q = h * W + w; None when the pixels have no common stride."""
@@ -1008,13 +1009,83 @@ def _pixel_strides(x4):
     return None
 
 
+class TagLoss:
+    """A tagger loss for rare tags (include/scnattn.h: "Tagger losses for rare tags"): per element of the logits
+        t w_s (1 - p)^gamma_pos (-log p) + (1 - t) p_m^gamma_neg (-log(1 - p_m)),   p_m = max(p - margin, 0),
+    averaged over B * S like nn.BCELoss.  `pos_weight`: float32 tensor [S] of weights >= 0 on the device, or None (all 1).
+    Immutable; the constructor refuses what the library refuses (ValueError).  TagLoss() is the identity: tag_head_loss then
+    runs the reference's BCELoss path."""
+    __slots__ = ("pos_weight", "gamma_pos", "gamma_neg", "margin")
+
+    def __init__(self, pos_weight=None, gamma_pos=0.0, gamma_neg=0.0, margin=0.0):
+        gp, gn, m = float(gamma_pos), float(gamma_neg), float(margin)
+        if not (0.0 <= gp <= 16.0 and 0.0 <= gn <= 16.0):        # false for a NaN
+            raise ValueError("TagLoss: gamma_pos and gamma_neg must be finite and in [0, 16] (got %r, %r)" % (gamma_pos, gamma_neg))
+        if not 0.0 <= m < 1.0:
+            raise ValueError("TagLoss: margin must be in [0, 1) (got %r)" % (margin,))
+        if m > 0.0 and 0.0 < gn < 1.0:
+            raise ValueError("TagLoss: a margin with 0 < gamma_neg < 1 has an unbounded gradient at p -> margin")
+        if pos_weight is not None:
+            if not torch.is_tensor(pos_weight) or pos_weight.dtype != torch.float32 or pos_weight.dim() != 1:
+                raise ValueError("TagLoss: pos_weight must be a float32 tensor [S]")
+            pos_weight = pos_weight.detach().contiguous()
+            if not bool((pos_weight >= 0).all()) or not bool(torch.isfinite(pos_weight).all()):
+                raise ValueError("TagLoss: pos_weight must be finite and >= 0")
+        for k, v in zip(self.__slots__, (pos_weight, gp, gn, m)):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, k, v):
+        raise AttributeError("TagLoss is immutable")
+
+    def __repr__(self):
+        return "TagLoss(pos_weight=%s, gamma_pos=%g, gamma_neg=%g, margin=%g)" % (
+            "None" if self.pos_weight is None else "[%d]" % self.pos_weight.numel(), self.gamma_pos, self.gamma_neg, self.margin)
+
+    @property
+    def is_identity(self):
+        return self.pos_weight is None and self.gamma_pos == 0.0 and self.gamma_neg == 0.0 and self.margin == 0.0
+
+    def struct(self):
+        return _lib.TagLossOpts(self.gamma_pos, self.gamma_neg, self.margin)
+
+    @classmethod
+    def asl(cls, gamma_neg=4.0, gamma_pos=0.0, margin=0.05):
+        """the asymmetric loss (Ridnik et al. 2021) with its published defaults"""
+        return cls(None, gamma_pos, gamma_neg, margin)
+
+    @classmethod
+    def focal(cls, gamma=2.0, pos_weight=None):
+        """the focal loss (Lin et al. 2017); its alpha balance is carried by pos_weight"""
+        return cls(pos_weight, gamma, gamma, 0.0)
+
+    @classmethod
+    def balanced(cls, targets, power=0.5, cap=100.0, **kw):
+        """w_s = clamp(((N - n_s) / max(n_s, 1))^power, 1, cap) from the positives n_s = #(t >= 0.5) of the [N, S] target
+        matrix `targets`; **kw: gamma_pos, gamma_neg, margin.  Plain torch: it runs once per training run."""
+        n = (targets >= 0.5).sum(dim=0).double()
+        w = ((targets.shape[0] - n) / n.clamp_min(1.0)).pow(power).clamp(1.0, cap)
+        return cls(w.float(), **kw)
+
+
+def prior_bias(targets, smooth=1.0):
+    """log((n_s + smooth) / (N - n_s + smooth)) [S] from the positives n_s = #(t >= 0.5) of the [N, S] matrix `targets`: the
+    RetinaNet initialisation of the head's bias (sigmoid(bias) = the tag's prior), which keeps the first steps of a focal run
+    from being swamped by the negatives"""
+    n = (targets >= 0.5).sum(dim=0).double()
+    return torch.log((n + smooth) / (targets.shape[0] - n + smooth)).float()
+
+
 class _TagHeadLoss(torch.autograd.Function):
     """probs = sigmoid(linear(mean_pixels(x4) * ks)), loss = BCELoss()(probs, targets), agree = #((probs >= .5) == (targets >= .5)).
-    The two reductions and the element-wise chain are the kernels of csrc/taghead.hip, the three products stay on the GEMM."""
+    The two reductions and the element-wise chain are the kernels of csrc/taghead.hip, the three products stay on the GEMM.
+    `loss`: None or an identity TagLoss for that path; any other TagLoss puts scnattn_tagloss_fwd / _bwd in the place of the
+    BCE pair and keeps the logits instead of the probabilities for the backward pass."""
 
     @staticmethod
-    def forward(ctx, x4, ks, W, b, targets, pooled_bf16=False):
-        require_cuda(x4, ks, W, b, targets)
+    def forward(ctx, x4, ks, W, b, targets, pooled_bf16=False, loss=None):
+        if loss is not None and loss.is_identity:
+            loss = None
+        require_cuda(x4, ks, W, b, targets, None if loss is None else loss.pos_weight)
         if x4.dtype not in (torch.float32, torch.bfloat16):
             x4 = x4.float()
         if _pixel_strides(x4) is None:
@@ -1035,8 +1106,16 @@ class _TagHeadLoss(torch.autograd.Function):
         probs = torch.empty((Bn, S), **f32)
         rows = torch.empty(2 * Bn, **f32)
         out = torch.empty(2, **f32)
-        call("scnattn_bce_fwd", st, Bn, S, ptr(z), S, ptr(targets), S, ptr(probs), S, ptr(rows), ptr(out))
-        ctx.save_for_backward(xd, ks, W, probs, targets)
+        if loss is None:
+            call("scnattn_bce_fwd", st, Bn, S, ptr(z), S, ptr(targets), S, ptr(probs), S, ptr(rows), ptr(out))
+            ctx.save_for_backward(xd, ks, W, probs, targets)
+        else:
+            if loss.pos_weight is not None and loss.pos_weight.numel() != S:
+                raise ValueError("tag_head_loss: pos_weight has %d weights for %d tags" % (loss.pos_weight.numel(), S))
+            call("scnattn_tagloss_fwd", st, Bn, S, ptr(z), S, ptr(targets), S, ptr(loss.pos_weight), C.byref(loss.struct()),
+                 ptr(probs), S, ptr(rows), ptr(out))
+            ctx.save_for_backward(xd, ks, W, z, targets)
+        ctx.loss = loss
         ctx.map = (x4.dtype, H, Wd)
         ctx.has_bias = b is not None
         loss, agree = out[0], out[1]
@@ -1047,15 +1126,19 @@ class _TagHeadLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _dprobs, dloss, _dagree):
         if dloss is None:
-            return None, None, None, None, None, None
-        xd, ks, W, probs, targets = ctx.saved_tensors
+            return None, None, None, None, None, None, None
+        xd, ks, W, probs, targets = ctx.saved_tensors          # `probs` holds the logits under a TagLoss
         dtype, H, Wd = ctx.map
         Bn, Cn = xd.shape
         S = W.shape[0]
         need = ctx.needs_input_grad          # (x4, ks, W, b, targets)
         st = stream_of(xd)
         dz = torch.empty((Bn, S), device=xd.device, dtype=torch.float32)
-        call("scnattn_bce_bwd", st, Bn, S, ptr(probs), S, ptr(targets), S, ptr(f32c(dloss).reshape(1)), ptr(dz), S)
+        if ctx.loss is None:
+            call("scnattn_bce_bwd", st, Bn, S, ptr(probs), S, ptr(targets), S, ptr(f32c(dloss).reshape(1)), ptr(dz), S)
+        else:
+            call("scnattn_tagloss_bwd", st, Bn, S, ptr(probs), S, ptr(targets), S, ptr(ctx.loss.pos_weight),
+                 C.byref(ctx.loss.struct()), ptr(f32c(dloss).reshape(1)), ptr(dz), S)
         dW = gemm(dz, xd, ta=True) if need[2] else None
         db = colsum(dz) if (ctx.has_bias and need[3]) else None
         dx = None
@@ -1066,16 +1149,20 @@ class _TagHeadLoss(torch.autograd.Function):
             sb, sp, sc = _pixel_strides(dx)
             call("scnattn_tag_pool_bwd", st, Bn, H * Wd, Cn, ptr(dxd), Cn, ptr(ks), Cn, ptr(dx),
                  1 if dtype == torch.bfloat16 else 0, sb, sp, sc)
-        return dx, None, dW, db, None, None
+        return dx, None, dW, db, None, None, None
 
 
-def tag_head_loss(x4, ks, W, b, targets, pooled_bf16=False):
+def tag_head_loss(x4, ks, W, b, targets, pooled_bf16=False, loss=None):
     """The tagger's head and loss on the (B, C, H, W) trunk map `x4` (fp32 or bf16, any strides): returns (probs (B, S),
     loss, agree), loss and agree 0-d device tensors.  `ks`: pre-scaled dropout keep mask (B, C) or None.  Gradients flow
     from `loss` to x4 (its own dtype, channels-last), W and b; probs and agree carry none.  `pooled_bf16` (bf16 maps only): round
     the pooled mean to bf16 as nn.AdaptiveAvgPool2d does on a bf16 map, i.e. compute what EncoderTagger.forward computes under
-    bf16 autocast; off, the mean keeps its fp32 accumulation."""
-    return _TagHeadLoss.apply(x4, ks, W, b, targets, pooled_bf16)
+    bf16 autocast; off, the mean keeps its fp32 accumulation.  `loss`: a TagLoss (weighted, focal or asymmetric terms on the
+    logits); None or the identity TagLoss() is the reference's BCELoss, bit for bit the path without the argument.  probs and
+    agree do not depend on it."""
+    if loss is not None and not isinstance(loss, TagLoss):
+        raise TypeError("tag_head_loss: loss must be a TagLoss or None")
+    return _TagHeadLoss.apply(x4, ks, W, b, targets, pooled_bf16, loss)
 
 
 # ----------------------------------------------------------------------------------------------

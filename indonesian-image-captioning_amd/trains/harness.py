@@ -666,10 +666,13 @@ class TaggerTrainStep:
         trunk fwd -> pool, dropout mask, Linear, Sigmoid, BCELoss and agreement count (EncoderTagger.tag_loss)
         -> zero_grad -> backward (+ bucketed all-reduce when world > 1) -> clamp +-5 -> Adam
     and returns (loss, agree) on the device: `loss.item()` and `agree / tags.numel() * 100` (binary_accuracy) are the
-    caller's syncs, as in TrainStep.  `encoder`: an EncoderTagger to train instead of a fresh one (a checkpoint's)."""
+    caller's syncs, as in TrainStep.  `encoder`: an EncoderTagger to train instead of a fresh one (a checkpoint's).
+    `loss`: a scnattn.functional.TagLoss in the place of BCELoss (positive weights, focal, asymmetric: the answers to rare
+    tags); None is the reference's loss, bit for bit.  `prior_bias_from`: an [N, S] target matrix whose tag frequencies
+    initialise linear.bias (scnattn.functional.prior_bias) -- for an untrained head; it overwrites the bias of `encoder`."""
 
     def __init__(self, fine_tune_encoder=False, device="cuda", seed=1234, encoder_dtype="f32", bucket_mb=32,
-                 force_reduce=False, encoder=None, **overrides):
+                 force_reduce=False, encoder=None, loss=None, prior_bias_from=None, **overrides):
         unknown = set(overrides) - set(TAGGER_DEFAULTS)
         if unknown:
             raise TypeError("TaggerTrainStep: unknown setting(s) %s" % ", ".join(sorted(unknown)))
@@ -683,6 +686,12 @@ class TaggerTrainStep:
             encoder = EncoderTagger(semantic_size=self.cfg["semantic_size"], dropout=self.cfg["dropout"], channels_last=True)
         self.encoder = encoder.to(self.device)
         self.encoder.fine_tune(fine_tune_encoder)
+        if loss is not None and not isinstance(loss, SF.TagLoss):
+            raise TypeError("TaggerTrainStep: loss must be a scnattn.functional.TagLoss or None")
+        self.loss = loss
+        if prior_bias_from is not None:
+            with torch.no_grad():
+                self.encoder.linear.bias.copy_(SF.prior_bias(prior_bias_from).to(self.device))
         self.optimizer = FusedClampAdam(filter(lambda p: p.requires_grad, self.encoder.parameters()),
                                         lr=self.cfg["encoder_lr"], grad_clip=self.cfg["grad_clip"])
         self.reducers = [GradReducer(self.optimizer.flat, max(bucket_mb << 20, 4096))]
@@ -695,7 +704,7 @@ class TaggerTrainStep:
 
     def step(self, imgs, tags):
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.encoder_bf16):
-            self.probs, loss, agree = self.encoder.tag_loss(imgs, tags)
+            self.probs, loss, agree = self.encoder.tag_loss(imgs, tags, loss=self.loss)
         self.optimizer.zero_grad()
         for r in self.reducers:
             r.reset()
@@ -710,22 +719,23 @@ class TaggerTrainStep:
         return loss, agree
 
 
-def validate_tagger(batches, encoder, losses=None, scorer=None):
+def validate_tagger(batches, encoder, losses=None, scorer=None, loss=None):
     """The reference's tagger validate() (trains/tagger.py:195-250): eval mode, no_grad, one unweighted `update(val)` per
     batch for loss and accuracy (= agree / (B * S) * 100, binary_accuracy); returns the accuracy meter.  `batches` yields
     (imgs, tags) on the device; `losses`: an AverageMeter that receives the per-batch losses.  `scorer`: a
     scnattn.tagmetrics.TagScorer that receives every batch's probabilities and tags (one launch each, no synchronisation);
-    its result() then holds tag mAP, precision / recall at k and per-tag F1 of the pass."""
+    its result() then holds tag mAP, precision / recall at k and per-tag F1 of the pass.  `loss`: the TagLoss the tagger is
+    trained under, so that `losses` reports the validation loss of that loss; the accuracy does not depend on it."""
     from utils.metric import AverageMeter
     encoder.eval()
     losses = AverageMeter() if losses is None else losses
     accs = AverageMeter()
     with torch.no_grad():
         for imgs, tags in batches:
-            probs, loss, agree = encoder.tag_loss(imgs, tags)
+            probs, batch_loss, agree = encoder.tag_loss(imgs, tags, loss=loss)
             if scorer is not None:
                 scorer.update(probs, tags)
-            losses.update(loss.item())
+            losses.update(batch_loss.item())
             accs.update(agree.item() / tags.numel() * 100.0)
     return accs
 
